@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the EKF/EKS hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (forward EKF kernel, pinv grid, backward EKS kernel, scenario-scoring tail) over
 BASELINE.json's headline sweep: SIAlphaModelEKFOptControlled over 300 regions x 250 NPI-cost weights x (400 observed +
@@ -15,7 +15,10 @@ every pass each rank's per-chain Pareto coordinates (J0, J1) -- 16 B per chain -
 the front per region (the path's only collective).  `--scaling weak` runs the round-1 variant instead (every rank a
 full 75 000-chain shard of a 300 N-region sweep).
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the K passes and
+prints the headline (value, ms_per_step, ...); `--full` adds what takes work of its own: per-kernel stage times from K further
+staged passes, the roofline, the box's copy bandwidth and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+pass computed (a fixed sample of it) to DIR/*.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -72,15 +75,25 @@ def parse():
     ap.add_argument("--placement-tries", type=int, default=5,
                     help="one-time set-up before the first pass (EkfRunner.tune_placement): time a staged pass on this many "
                          "allocations of the outputs + workspace and keep the fastest (where the allocator puts the ~14 concurrently "
-                         "streamed arrays changes a pass by up to 15 %, DESIGN.md 5); 1 = take what the allocator gives")
+                         "streamed arrays changes a pass by up to 15 %%, DESIGN.md 5); 1 = take what the allocator gives")
     ap.add_argument("--spinup-ms", type=float, default=200.0,
                     help="set-up, before the W warm-up passes: keep running passes until this much wall time has gone by, so that the "
                          "device is at its steady clocks when the timed region starts -- after an idle second the first ~50-150 ms of "
                          "work run 3-15 %% slower (profiles/r05/clock_ramp.txt), which a 2.5 ms pass would carry into ten timed passes "
                          "and a 15.6 ms pass would not; 0 = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample-chains", type=int, default=0, help="0 = sized for ~15 s")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel stage times from K further passes "
+                         "enqueued stage by stage, the roofline, this box's copy bandwidth, the placement mode and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--cpu-sample-chains", type=int, default=0, help="with --full: CPU baseline sample size, 0 = sized for ~15 s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one computed to DIR/<name>.npy (float64, or float32 for "
+                         "--storage f32 outputs): every output for a fixed seeded sample of chains, [T, rows, chains], and the "
+                         "per-chain scores and per-region front, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_workload(args, rank):
@@ -115,7 +128,7 @@ def placement_report(placement, args, ms, wname):
            "chosen": None if placement is None else placement["chosen"]}
     headline = args.workload in ("cfg4", "cfg4-live") and (args.regions, args.eps, args.t_hist, args.horizon) == (300, 250, 400, 120) \
         and args.outputs == "all" and args.storage == "f64" and args.gpus == 1
-    if headline:
+    if headline and ms is not None:       # the stage times: --full
         slow = [k for k, lim in PLACEMENT_SLOW_MS.items() if ms[k] > lim]
         rep["mode"] = "slow: " + ", ".join(slow) + " above the fast mode's stage times" if slow else "fast"
         rep["fast_mode_limits_ms"] = PLACEMENT_SLOW_MS
@@ -210,6 +223,96 @@ def cpu_baseline(w, args):
             "sample": f"{ws.B} of {w.B} chains (every {max(1, w.B // n)}th) x {ws.T} days, all 11 outputs, "
                       f"OpenMP over chains, {dt:.1f} s; C restatement of Tools/*.m (MATLAB unavailable)",
             "single_thread": {"value": w1.B * w1.T / dt1, "cores": 1, "sample": f"{w1.B} chains x {w1.T} days, {dt1:.1f} s"}}
+
+
+def full_report(args, w, m, dev, ms, steps_per_pass, elapsed, world):
+    """--full: the fields of the result line beyond the headline -- per-kernel figures from the staged passes' stage times
+    `ms`, the roofline, this box's copy bandwidth, the box-normalised pass time and the CPU baseline."""
+    res = {}
+    all_out = args.outputs == "all"
+    # algorithmic bytes per region-day step, split by kernel (DESIGN.md): eks_pinv produces no reference
+    # output of its own -- its algorithmic bytes are the P_MINUS it must read (m*m doubles)
+    alg = {"ekf_fwd": BYTES_FWD[m] if all_out else 112, "eks_pinv": 8 * m * m,
+           "eks_bwd": BYTES_BWD[m] if all_out else 8 * (m + 12)}
+    if args.storage == "f32":       # outputs are 4-byte elements; the inputs x, u, R stay fp64 (112 B)
+        alg["ekf_fwd"] = 112 + (alg["ekf_fwd"] - 112) // 2
+        alg["eks_bwd"] //= 2
+    if w.model.startswith("NewCase"):     # no u_opt_smooth output, no separate pinv stage (mrdivide inline)
+        alg["eks_bwd"] = 8 * (m + m * m) if all_out else 8 * m
+        alg["eks_pinv"] = 0
+    dom = max(ms, key=ms.get)
+    dom_bytes = alg[dom] * steps_per_pass
+    achieved = dom_bytes / (ms[dom] * 1e-3) / 1e9
+    step_bytes = (alg["ekf_fwd"] + alg["eks_bwd"]) * steps_per_pass
+    step_gbs = step_bytes / (sum(ms.values()) * 1e-3) / 1e9
+    traffic = pmc_traffic(dom, args)
+    copy_bw = measured_copy_bandwidth(dev)
+    res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom,
+                       # what the kernel actually moves (PMC bytes of the committed profile / this run's duration):
+                       # the smoother reads S+, P+, X back (round 6: no longer S-, P-), ~1.9x the algorithmic figure
+                       "traffic_GBs": None if traffic is None else traffic / (ms[dom] * 1e-3) / 1e9,
+                       "traffic_frac_of_peak": None if traffic is None else traffic / (ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                       "measured_copy": copy_bw,     # this box, this process: bytes read + written per second
+                       "kernel_ms": ms[dom], "algorithmic_bytes_per_launch": dom_bytes,
+                       "limiter": {"ekf_fwd": "HBM writes: 32.4 GB at the box's fill rate; a lone wave per SIMD issues 73 % of the time (profiles/r06/valu_summary.json)",
+                                   "eks_pinv": "fp64 VALU issue (SIMD VALU busy 82 % of the kernel's duration, three waves per SIMD) on top of 13.5 GB of traffic; profiles/r06/valu_summary.json",
+                                   "eks_bwd": "instruction issue of a lone wave per SIMD in two rounds (a wave issues 70 % of its cycles, waits for memory 9 %) and HBM (32.6 GB at 4.9-5.1 TB/s, the first round at the box's copy rate); profiles/r06/valu_summary.json, traffic_summary.json"}[dom]}
+    res["kernels"] = {**{k + "_ms": v for k, v in ms.items()},
+                      **{k + "_GBs": alg[k] * steps_per_pass / (ms[k] * 1e-3) / 1e9 for k in ms},
+                      "whole_step_algorithmic_bytes": step_bytes, "whole_step_GBs": step_gbs,
+                      "whole_step_frac_of_hbm_peak": step_gbs / HBM_PEAK_GBS}
+    # a figure that can be compared across boxes of different HBM speed: the pass time in units of what this box needs
+    # to move the pass's MEASURED traffic at its own copy bandwidth (1.0 = the pass runs at the copy rate on the bytes
+    # its kernels really move; profiles/r*/traffic_summary*.json, same kernel sources)
+    summ = pmc_summary(args) if world == 1 else None
+    if summ is not None:
+        tot = float(sum(v["hbm_bytes"] for v in summ["kernels"].values()))
+        res["box_normalised"] = {"traffic_bytes_per_pass": tot, "copy_GBs": copy_bw["copy_8B_per_lane_GBs"],
+                                 "pass_ms_at_copy_rate": tot / (copy_bw["copy_8B_per_lane_GBs"] * 1e9) * 1e3,
+                                 "pass_over_copy_floor": (elapsed / args.steps) / (tot / (copy_bw["copy_8B_per_lane_GBs"] * 1e9))}
+    if world == 1 and not args.no_cpu_baseline:
+        res["cpu_baseline"] = cpu_baseline(w, args)
+    return res
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+DUMP_SEED = 20240917             # --dump-outputs: the chain sample (the same for every run of the same arguments)
+
+
+def sampled_chains(runner, name, idx):
+    """[T, rows, n] ([T, n]) device tensor of output `name` at chain indices `idx` (int64 on the device), whatever the
+    layout run() wrote it in; no copy of the whole array."""
+    t = runner.out[name]
+    if runner.blk == runner.dw.B or t.dim() == 2:
+        return t[..., idx]               # [T, (rows,) B] and blocked one-row [T, nblk * blk]: chain c is column c
+    return t[:, idx // runner.blk, :, idx % runner.blk].permute(1, 2, 0)     # [T, nblk, rows, blk] -> [n, T, rows] -> [T, rows, n]
+
+
+def dump_outputs(d, runner, sweep, rank):
+    """--dump-outputs: what the last timed pass handed its caller, as .npy files under `d` (rank r > 0 of N > 1: <name>.rank<r>.npy).
+    The filter outputs of a fixed seeded sample of chains (all chains when they fit) and `sweep`, the scoring tail's results
+    (per-chain J0, J1 and the per-region Pareto front and optimum), whole; integer and boolean arrays as float64."""
+    import torch
+    from epidemicmodeling_amd import layout as L_
+    os.makedirs(d, exist_ok=True)
+    dev = runner.dw.device
+    B = runner.dw.B
+    sfx = f".rank{rank}" if rank else ""
+    extra = {k: (v if v.is_floating_point() else v.to(torch.float64)) for k, v in sweep.items()}
+    extra_bytes = sum(v.numel() * v.element_size() for v in extra.values())
+    per_chain = sum(max(1, L_.out_rows(n, runner.dw.m, runner.dw.n_npi)) * runner.dw.T * runner.out[n].element_size()
+                    for n in runner.names)
+    n = int(min(B, max(1, (DUMP_BYTES - extra_bytes) // max(1, per_chain))))
+    if n < B:
+        idx = np.sort(np.random.Generator(np.random.Philox(DUMP_SEED)).choice(B, size=n, replace=False))
+    else:
+        idx = np.arange(B)
+    idx_t = torch.as_tensor(idx, dtype=torch.int64, device=dev)
+    for name in runner.names:
+        np.save(os.path.join(d, name + sfx + ".npy"), sampled_chains(runner, name, idx_t).cpu().numpy())
+    for name, v in extra.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), v.cpu().numpy())
 
 
 def self_launch(n):
@@ -329,6 +432,8 @@ def main():
                                        score_state["J1p"], B=w.B)
                 if whole:
                     score_state["front"] = batch.pareto_front(sc["J0"], sc["J1"], w.Sx)
+        if sc is not None:
+            last["sc"] = sc               # what --dump-outputs writes of the last pass
         if world > 1:
             # the path's only collective, bracketed so that a scaling curve can be decomposed: HIP events on the launch
             # stream (over RCCL the collective is ordered against it) and the host's own clock (gloo rehearsal: the gather
@@ -357,6 +462,7 @@ def main():
             gather_log["host_s"] += time.perf_counter() - tg
 
     gather_log = {"on": False, "events": [], "host_s": 0.0}
+    last = {}
     # EPI_BENCH_STAGED=1: every pass -- the very first and the warm-up included -- is enqueued stage by stage, so that a
     # `rocprofv3 --stats` of the run sees ONE kind of launch per kernel and its averages are the per-kernel durations `roofline`
     # quotes (round 5's CSV held one overlapped call: its monitor launch, beside the pinv grid and the smoother on the helper
@@ -392,9 +498,9 @@ def main():
     torch.cuda.synchronize(dev)
     # The timed passes are the call a user makes (one epi_sweep_run_device per pass): inside it the library overlaps what is
     # off the critical path (monitor, scoring tail, Pareto filter; for a batch that leaves SIMDs idle also the pinv grids of
-    # the forward pass's time segments).  The per-kernel durations come from K further passes enqueued stage by stage, each
-    # bracketed by HIP events on the launch stream.  EPI_BENCH_STAGED=1: time the staged passes instead (round-1 behaviour).
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)]
+    # the forward pass's time segments).  --full: the per-kernel durations come from K further passes enqueued stage by stage,
+    # each bracketed by HIP events on the launch stream.  EPI_BENCH_STAGED=1: time the staged passes instead (round-1 behaviour).
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)] if (staged or args.full) else None
     gather_log["on"] = True
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -424,35 +530,25 @@ def main():
                     "backend": backend, "rccl_ranks": int(dist.get_world_size()),
                     "note": "ms_per_step_by_rank = each rank's own K passes (kernels + its part of the gather) before the closing "
                             "barrier; gather_ms = the end-of-sweep gather of (J0, J1) alone, per pass"}
-    if not staged:
-        for k in range(args.steps):
-            one_step(evs[k])
-        torch.cuda.synchronize(dev)
-    ms_fwd = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
-    ms_pinv = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
-    ms_bwd = float(np.mean([e[2].elapsed_time(e[3]) for e in evs]))
+    if args.dump_outputs:
+        sweep = {}
+        if "sc" in last:
+            sweep["J0"], sweep["J1"] = last["sc"]["J0"], last["sc"]["J1"]
+        if "front" in score_state:
+            sweep["on_front"], sweep["i_opt"] = score_state["front"]
+        dump_outputs(args.dump_outputs, runner, sweep, rank)
+    ms = None
+    if args.full:
+        if not staged:
+            for k in range(args.steps):
+                one_step(evs[k])
+            torch.cuda.synchronize(dev)
+        ms = {"ekf_fwd": float(np.mean([e[0].elapsed_time(e[1]) for e in evs])),
+              "eks_pinv": float(np.mean([e[1].elapsed_time(e[2]) for e in evs])),
+              "eks_bwd": float(np.mean([e[2].elapsed_time(e[3]) for e in evs]))}
     if rank == 0:
         total_steps = (B_total * w.T if strong else steps_per_pass * world) * args.steps
         value = total_steps / elapsed
-        full = args.outputs == "all"
-        # algorithmic bytes per region-day step, split by kernel: eks_pinv produces no reference
-        # output of its own -- its algorithmic bytes are the P_MINUS it must read (m*m doubles)
-        alg = {"ekf_fwd": BYTES_FWD[m] if full else 112, "eks_pinv": 8 * m * m,
-               "eks_bwd": BYTES_BWD[m] if full else 8 * (m + 12)}
-        if args.storage == "f32":       # outputs are 4-byte elements; the inputs x, u, R stay fp64 (112 B)
-            alg["ekf_fwd"] = 112 + (alg["ekf_fwd"] - 112) // 2
-            alg["eks_bwd"] //= 2
-        if w.model.startswith("NewCase"):     # no u_opt_smooth output, no separate pinv stage (mrdivide inline)
-            alg["eks_bwd"] = 8 * (m + m * m) if full else 8 * m
-            alg["eks_pinv"] = 0
-        ms = {"ekf_fwd": ms_fwd, "eks_pinv": ms_pinv, "eks_bwd": ms_bwd}
-        dom = max(ms, key=ms.get)
-        dom_bytes = alg[dom] * steps_per_pass
-        achieved = dom_bytes / (ms[dom] * 1e-3) / 1e9
-        step_bytes = (alg["ekf_fwd"] + alg["eks_bwd"]) * steps_per_pass
-        step_gbs = step_bytes / (sum(ms.values()) * 1e-3) / 1e9
-        traffic = pmc_traffic(dom, args)
-        copy_bw = measured_copy_bandwidth(dev)
         res = {
             "metric": "region-day EKF steps/sec (300 regions x 400 days x 250 costs)",
             "value": value, "unit": "region-day EKF steps/s", "n_gpus": world, "steps": args.steps,
@@ -469,35 +565,11 @@ def main():
                        "parallelism": (f"the fixed sweep's {B_total} chains sharded over {world} GPU(s) by contiguous blocks; "
                                        "end-of-sweep gather of (J0, J1) to rank 0, Pareto filter there") if strong or world == 1 else
                                       f"every rank its own full sweep ({world} x {w.B} chains); end-of-sweep gather of (J0, J1) to rank 0"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom,
-                         # what the kernel actually moves (PMC bytes of the committed profile / this run's duration):
-                         # the smoother reads S+, P+, X back (round 6: no longer S-, P-), ~1.9x the algorithmic figure
-                         "traffic_GBs": None if traffic is None else traffic / (ms[dom] * 1e-3) / 1e9,
-                         "traffic_frac_of_peak": None if traffic is None else traffic / (ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "measured_copy": copy_bw,     # this box, this process: bytes read + written per second
-                         "kernel_ms": ms[dom], "algorithmic_bytes_per_launch": dom_bytes,
-                         "limiter": {"ekf_fwd": "HBM writes: 32.4 GB at the box's fill rate; a lone wave per SIMD issues 73 % of the time (profiles/r06/valu_summary.json)",
-                                     "eks_pinv": "fp64 VALU issue (SIMD VALU busy 82 % of the kernel's duration, three waves per SIMD) on top of 13.5 GB of traffic; profiles/r06/valu_summary.json",
-                                     "eks_bwd": "instruction issue of a lone wave per SIMD in two rounds (a wave issues 70 % of its cycles, waits for memory 9 %) and HBM (32.6 GB at 4.9-5.1 TB/s, the first round at the box's copy rate); profiles/r06/valu_summary.json, traffic_summary.json"}[dom]},
-            "kernels": {**{k + "_ms": v for k, v in ms.items()},
-                        **{k + "_GBs": alg[k] * steps_per_pass / (ms[k] * 1e-3) / 1e9 for k in ms},
-                        "whole_step_algorithmic_bytes": step_bytes, "whole_step_GBs": step_gbs,
-                        "whole_step_frac_of_hbm_peak": step_gbs / HBM_PEAK_GBS},
         }
         if per_rank is not None:
             res["ranks"] = per_rank
-        # a figure that can be compared across boxes of different HBM speed: the pass time in units of what this box needs
-        # to move the pass's MEASURED traffic at its own copy bandwidth (1.0 = the pass runs at the copy rate on the bytes
-        # its kernels really move; profiles/r*/traffic_summary*.json, same kernel sources)
-        summ = pmc_summary(args) if world == 1 else None
-        if summ is not None:
-            tot = float(sum(v["hbm_bytes"] for v in summ["kernels"].values()))
-            res["box_normalised"] = {"traffic_bytes_per_pass": tot, "copy_GBs": copy_bw["copy_8B_per_lane_GBs"],
-                                     "pass_ms_at_copy_rate": tot / (copy_bw["copy_8B_per_lane_GBs"] * 1e9) * 1e3,
-                                     "pass_over_copy_floor": (elapsed / args.steps) / (tot / (copy_bw["copy_8B_per_lane_GBs"] * 1e9))}
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(w, args)
+        if args.full:
+            res.update(full_report(args, w, m, dev, ms, steps_per_pass, elapsed, world))
         print(json.dumps(res))
     if world > 1:
         dist.barrier()

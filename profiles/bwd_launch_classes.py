@@ -1,4 +1,4 @@
-"""Splits the eks_bwd launches of a rocprofv3 kernel trace of bench.py into the three kinds the run contains:
+"""Splits the eks_bwd launches of a rocprofv3 kernel trace of `bench.py --full` into the three kinds the run contains:
   full     -- the whole recursion in one launch (the staged passes the per-kernel HIP events and `roofline` are measured on)
   horizon  -- the first of the two launches of a timed pass (smoother steps T-2 .. t_hist: the horizon days)
   observed -- the second one (steps t_hist-1 .. 0), beside which the scoring tail and the Pareto filter run

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04/bimodal; mkdir -p $O
 for i in 1 2 3 4 5 6; do
-  EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/run$i -o b -- python3 $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/bench$i.json 2>/dev/null
+  EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/run$i -o b -- python3 $R/bench.py --steps 8 --warmup 2 --full --no-cpu-baseline > $O/bench$i.json 2>/dev/null
   python3 - $O/run$i $O/bench$i.json <<'P'
 import csv,glob,json,sys
 f=glob.glob(sys.argv[1]+'/**/b_kernel_stats.csv',recursive=True)[0]

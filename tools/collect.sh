@@ -24,17 +24,17 @@ case $STAGE in
     EPI_FUZZ_EXAMPLES=${1:-3000} timeout -k 10 1150 python -m pytest tests/test_gpu_fuzz.py -m gpu -x -q > $O/fuzz_hunt_${2:-a}.txt 2>&1; rc=$?
     tail -4 $O/fuzz_hunt_${2:-a}.txt; exit $rc ;;
   bench)
-    python3 bench.py > $O/bench_cfg4.json 2>/dev/null && echo cfg4 ok
-    python3 bench.py --workload cfg4-live > $O/bench_cfg4_live.json 2>/dev/null && echo live ok
-    python3 bench.py --no-cpu-baseline --outputs reduced > $O/bench_cfg4_reduced.json 2>/dev/null && echo reduced ok
-    python3 bench.py --no-cpu-baseline --workload cfg3 --steps 20 > $O/bench_cfg3.json 2>/dev/null && echo cfg3 ok
-    python3 bench.py --no-cpu-baseline --workload cfg5 --eps 1024 --storage f32 > $O/bench_cfg5_f32.json 2>/dev/null && echo cfg5 ok
-    python3 bench.py --no-cpu-baseline --workload newcase > $O/bench_newcase.json 2>/dev/null && echo newcase ok
-    python3 bench.py --no-cpu-baseline --regions 75 --eps 125 > $O/bench_shard9375.json 2>/dev/null && echo shard ok ;;
+    python3 bench.py --full > $O/bench_cfg4.json 2>/dev/null && echo cfg4 ok
+    python3 bench.py --full --workload cfg4-live > $O/bench_cfg4_live.json 2>/dev/null && echo live ok
+    python3 bench.py --full --no-cpu-baseline --outputs reduced > $O/bench_cfg4_reduced.json 2>/dev/null && echo reduced ok
+    python3 bench.py --full --no-cpu-baseline --workload cfg3 --steps 20 > $O/bench_cfg3.json 2>/dev/null && echo cfg3 ok
+    python3 bench.py --full --no-cpu-baseline --workload cfg5 --eps 1024 --storage f32 > $O/bench_cfg5_f32.json 2>/dev/null && echo cfg5 ok
+    python3 bench.py --full --no-cpu-baseline --workload newcase > $O/bench_newcase.json 2>/dev/null && echo newcase ok
+    python3 bench.py --full --no-cpu-baseline --regions 75 --eps 125 > $O/bench_shard9375.json 2>/dev/null && echo shard ok ;;
   stats)
     cd /tmp && export TMPDIR=/tmp
-    EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats75k -o bench -- python3 $R/bench.py --no-cpu-baseline --placement-tries 1 > $O/bench_cfg4_staged_under_rocprof.json 2>/dev/null && echo stats75k
-    EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats9375 -o bench -- python3 $R/bench.py --no-cpu-baseline --placement-tries 1 --regions 75 --eps 125 > $O/bench_shard9375_staged_under_rocprof.json 2>/dev/null && echo stats9375
+    EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats75k -o bench -- python3 $R/bench.py --full --no-cpu-baseline --placement-tries 1 > $O/bench_cfg4_staged_under_rocprof.json 2>/dev/null && echo stats75k
+    EPI_BENCH_STAGED=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats9375 -o bench -- python3 $R/bench.py --full --no-cpu-baseline --placement-tries 1 --regions 75 --eps 125 > $O/bench_shard9375_staged_under_rocprof.json 2>/dev/null && echo stats9375
     cd $R
     cp $(find $O/stats75k -name "*kernel_stats.csv" | head -1) $O/bench_cfg4_staged_kernel_stats.csv
     cp $(find $O/stats9375 -name "*kernel_stats.csv" | head -1) $O/bench_shard9375_staged_kernel_stats.csv

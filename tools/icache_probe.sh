@@ -3,7 +3,7 @@
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05/ic_$TAG; mkdir -p $O
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d $O -o p -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $O.log 2>&1
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d $O -o p -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > $O.log 2>&1
 cd $R
 python3 - "$O" > $R/gpurun_out/r05/ic_$TAG.txt <<'PY'
 import csv, glob, collections, sys
