@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "epi_preprocess_workspace_bytes", "epi_preprocess_device", "epi_nnls_affine_fit_device",
     "epi_sweep_run_device", "epi_sweep_prescribe_host", "epi_preprocess_host", "epi_nnls_affine_fit_host", "epi_random_npi_mc_host",
     "epi_sir_sim_device", "epi_sir_sim_host",
+    "epi_lookahead_validate", "epi_lookahead_workspace_bytes", "epi_lookahead_run_device", "epi_lookahead_run_host",
 ]
 
 
@@ -106,6 +107,24 @@ PRE_OUT_NAMES = ("new_refined", "new_smoothed", "zero_lag", "x_new", "x_total", 
 
 class PreOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PRE_OUT_NAMES]
+
+
+class LookaheadDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "model", "R", "LL", "F", "M", "n_npi", "L", "order", "obs_type", "r_mode",
+                                          "shape", "placement_tries")]
+
+
+LA_IN_NAMES = ("x", "u", "R_series", "R_scalar", "prm", "s_init", "Ps_init", "s_final", "Ps_final", "Q", "truth", "population")
+LA_OUT_NAMES = ("est_plus", "est_smooth", "mean_plus", "median_plus", "std_plus", "mean_smooth", "median_smooth", "std_smooth",
+                "S_PLUS", "S_SMOOTH", "status")
+
+
+class LookaheadInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LA_IN_NAMES]
+
+
+class LookaheadOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LA_OUT_NAMES]
 
 
 class NnlsDesc(C.Structure):
@@ -223,6 +242,16 @@ def lib():
         h.epi_nnls_affine_fit_host.argtypes = [C.POINTER(NnlsDesc)] + [C.c_void_p] * 7 + [C.c_int, C.c_char_p]
         h.epi_random_npi_mc_host.restype = C.c_int
         h.epi_random_npi_mc_host.argtypes = [C.POINTER(McDesc)] + [C.c_void_p] * 8 + [C.c_int, C.c_char_p]
+        h.epi_lookahead_validate.restype = C.c_int
+        h.epi_lookahead_validate.argtypes = [C.POINTER(LookaheadDesc), C.c_char_p]
+        h.epi_lookahead_workspace_bytes.restype = C.c_size_t
+        h.epi_lookahead_workspace_bytes.argtypes = [C.POINTER(LookaheadDesc)]
+        h.epi_lookahead_run_device.restype = C.c_int
+        h.epi_lookahead_run_device.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_lookahead_run_host.restype = C.c_int
+        h.epi_lookahead_run_host.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
+                                             C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h
@@ -234,6 +263,17 @@ def check(rc: int, err_buf) -> None:
         msg = err_buf.value.decode(errors="replace") if err_buf is not None and err_buf.value else \
             lib().epi_status_string(rc).decode()
         raise EpiError(rc, msg)
+
+
+def make_lookahead_desc(R, LL, F, M, n_npi, L_, order=1, obs_type="NEWCASES", r_mode=1, shape=0, placement_tries=0,
+                        model="SIAlphaModelEKF") -> LookaheadDesc:
+    d = LookaheadDesc()
+    d.abi_version = ABI_VERSION
+    d.model = L.MODEL_IDS[model] if isinstance(model, str) else int(model)
+    d.R, d.LL, d.F, d.M, d.n_npi, d.L, d.order = int(R), int(LL), int(F), int(M), int(n_npi), int(L_), int(order)
+    d.obs_type = L.OBS_IDS.get(obs_type, 99) if isinstance(obs_type, str) else int(obs_type)
+    d.r_mode, d.shape, d.placement_tries = int(r_mode), int(shape), int(placement_tries)
+    return d
 
 
 def make_desc(model, B, T, Sx, Su, n_npi, L_, order, obs_type, r_mode, out_mask, q_mode=0) -> BatchDesc:

@@ -650,3 +650,91 @@ def score_sweep(u_opt_smooth, t_hist, sp, J0_prefix, J1_prefix, store=False, B=N
                                              _ptr(out["J0"]), _ptr(out["J1"]), C.c_void_p(st.cuda_stream), err)
     _lib.check(rc, err)
     return out
+
+
+LA_TABLES = ("est_plus", "est_smooth")
+LA_STATS = ("mean_plus", "median_plus", "std_plus", "mean_smooth", "median_smooth", "std_smooth")
+
+
+def _lookahead_arrays(w, truth, population):
+    """Per-region arrays of the study in ABI order (a synth.Workload of SIAlphaModelEKF with one chain per region)."""
+    if w.model != "SIAlphaModelEKF":
+        raise _lib.EpiError(-8, "the look-ahead study runs SIAlphaModelEKF (EPI_MODEL_SIA3) only")
+    if w.x_series is not None or w.u_series is not None or w.Sx != w.B or w.Su != w.B:
+        raise ValueError("the look-ahead study takes one column per region (identity series)")
+    return {"x": w.x, "u": w.u, "R_series": w.R_series, "R_scalar": w.R_scalar, "prm": w.prm, "s_init": w.s_init,
+            "Ps_init": w.Ps_init, "s_final": w.s_final, "Ps_final": w.Ps_final, "Q": w.Q, "truth": truth, "population": population}
+
+
+class LookaheadRunner:
+    """The forecast look-ahead error study (Tools/ForecastQualityAssessment.m:359-393, 428-449) as one device call
+    (epi_lookahead_run_device).  `w` holds the per-region inputs of SIAlphaModelEKF (one chain per region, identity series,
+    e.g. pipeline.workload3); truth [LL, R] = NewCasesSmoothed_ENTIRE; population [R].  Inputs stay in HBM, outputs and
+    workspace are pre-allocated; run() only enqueues.  out: est_plus / est_smooth [F, M, R], mean / median / std_{plus,smooth}
+    [M, R] and, with chains=True, S_PLUS / S_SMOOTH [LL, 3, R * F] (chain c = r * F + start - 1) and status [R * F]."""
+
+    def __init__(self, w, truth, population, F, M=60, device="cuda:0", chains=False, shape=0):
+        self.device = dev = torch.device(device)
+        arrs = _lookahead_arrays(w, truth, population)
+        f = lambda a: None if a is None else (a.to(dev, torch.float64).contiguous() if isinstance(a, torch.Tensor) else
+                                              torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev))
+        self.inp = {k: f(v) for k, v in arrs.items()}
+        R, LL = w.B, w.T
+        self.R, self.LL, self.F, self.M = R, LL, int(F), int(M)
+        self.desc = _lib.make_lookahead_desc(R, LL, F, M, w.n_npi, w.L, w.order, w.obs_type,
+                                             1 if w.R_series is not None else 0, shape=shape)
+        self.err = C.create_string_buffer(256)
+        h = _lib.lib()
+        _lib.check(h.epi_lookahead_validate(C.byref(self.desc), self.err), self.err)
+        self.out = {n: torch.empty((self.F, self.M, R), dtype=torch.float64, device=dev) for n in LA_TABLES}
+        self.out.update({n: torch.empty((self.M, R), dtype=torch.float64, device=dev) for n in LA_STATS})
+        if chains:
+            for n in ("S_PLUS", "S_SMOOTH"):
+                self.out[n] = torch.empty((LL, 3, R * self.F), dtype=torch.float64, device=dev)
+            self.out["status"] = torch.zeros((R * self.F,), dtype=torch.int32, device=dev)
+        self.ws_bytes = int(h.epi_lookahead_workspace_bytes(C.byref(self.desc)))
+        self.ws = torch.empty((max(self.ws_bytes, 8) + 7) // 8, dtype=torch.float64, device=dev)
+        self.ins = _lib.LookaheadInputs()
+        for n in _lib.LA_IN_NAMES:
+            setattr(self.ins, n, _ptr(self.inp.get(n)))
+        self.outs = _lib.LookaheadOutputs()
+        for n in _lib.LA_OUT_NAMES:
+            setattr(self.outs, n, _ptr(self.out.get(n)))
+
+    def run(self, stream=None):
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        rc = _lib.lib().epi_lookahead_run_device(C.byref(self.desc), C.byref(self.ins), C.byref(self.outs), _ptr(self.ws),
+                                                 self.ws_bytes, C.c_void_p(st.cuda_stream), self.err)
+        _lib.check(rc, self.err)
+        return self.out
+
+
+def lookahead(w, truth, population, F, M=60, device="cuda:0", chains=False, shape=0):
+    """Convenience: upload, run the study once, return dict name -> numpy array (see LookaheadRunner)."""
+    r = LookaheadRunner(w, truth, population, F, M, device, chains, shape)
+    r.run()
+    torch.cuda.synchronize(r.device)
+    return {n: t.cpu().numpy() for n, t in r.out.items()}
+
+
+def lookahead_host(w, truth, population, F, M=60, device=0, chains=False, shape=0, placement_tries=0):
+    """The same study through the host-pointer entry (epi_lookahead_run_host: NumPy arrays in and out, synchronous; what a
+    MEX gateway would bind).  Returns the dict of lookahead()."""
+    arrs = {k: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+            for k, v in _lookahead_arrays(w, truth, population).items()}
+    R, LL, F, M = w.B, w.T, int(F), int(M)
+    d = _lib.make_lookahead_desc(R, LL, F, M, w.n_npi, w.L, w.order, w.obs_type, 1 if w.R_series is not None else 0,
+                                 shape=shape, placement_tries=placement_tries)
+    out = {n: np.empty((F, M, R)) for n in LA_TABLES}
+    out.update({n: np.empty((M, R)) for n in LA_STATS})
+    if chains:
+        out.update(S_PLUS=np.empty((LL, 3, R * F)), S_SMOOTH=np.empty((LL, 3, R * F)), status=np.zeros(R * F, dtype=np.int32))
+    ins, outs = _lib.LookaheadInputs(), _lib.LookaheadOutputs()
+    for n in _lib.LA_IN_NAMES:
+        setattr(ins, n, None if arrs.get(n) is None else arrs[n].ctypes.data_as(C.c_void_p))
+    for n in _lib.LA_OUT_NAMES:
+        setattr(outs, n, out[n].ctypes.data_as(C.c_void_p) if n in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_lookahead_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out

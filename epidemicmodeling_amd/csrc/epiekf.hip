@@ -830,6 +830,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "rt_expfit.hpp"
 #include "preprocess.hpp"
 #include "nnls.hpp"
+#include "lookahead.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3255,6 +3256,209 @@ int epi_seirp_sim_device(int32_t B, int32_t K, int32_t par_steps, double dt, int
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(err, e, "seirp_sim launch");
     return EPI_OK;
+}
+
+
+// ---- the forecast look-ahead error study (Tools/ForecastQualityAssessment.m:359-393, 428-449; include/epiekf.h) ----
+// Lane mapping of the study's filter when the descriptor leaves it open (shape 0).  At the study's batch sizes one lane per
+// chain wins: 236 regions x 91 starts (21 476 chains) x 366 days 1.36 ms per call against 2.49 with seven chains per
+// wavefront, 300 regions (27 300 chains) 1.53 against 3.41 (profiles/lookahead/bench.json); small studies keep the filter's
+// own small-batch choice.
+static int la_shape(const epi_lookahead_desc *d)
+{
+    if (d->shape != 0) return d->shape;
+    return (int64_t)d->R * d->F <= 2048 ? EPI_SHAPE_WAVE : EPI_SHAPE_LANE;
+}
+
+// the filter call of the study: chain c = r * F + (s - 1), observations materialised per chain, controls shared per region
+static epi_batch_desc la_batch_desc(const epi_lookahead_desc *d, int path_hint)
+{
+    epi_batch_desc b{};
+    b.abi_version = EPIEKF_ABI_VERSION; b.model = EPI_MODEL_SIA3;
+    b.B = d->R * d->F; b.T = d->LL; b.Sx = b.B; b.Su = d->R;
+    b.n_npi = d->n_npi; b.L = d->L; b.order = d->order; b.obs_type = d->obs_type; b.r_mode = d->r_mode; b.q_mode = 0;
+    b.out_mask = EPI_OUT_S_PLUS | EPI_OUT_S_SMOOTH;
+    b.path_hint = path_hint; b.shape = la_shape(d); b.placement_tries = d->placement_tries;
+    return b;
+}
+
+struct LaWs { size_t x, rs, rsc, prm, si, psi, sf, psf, q, us, sp, ss, ekf, ekf_bytes, total; };
+static LaWs la_ws_layout(const epi_lookahead_desc *d)
+{
+    const size_t B = (size_t)d->R * d->F, T = (size_t)d->LL;
+    LaWs w{};
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 255) & ~(size_t)255; return o; };
+    w.x = take(T * B * 8);
+    w.rs = take(d->r_mode == 1 ? T * B * 8 : 0); w.rsc = take(d->r_mode == 0 ? B * 8 : 0);
+    w.prm = take((size_t)EPI_PRM_COUNT * B * 8);
+    w.si = take(3 * B * 8); w.psi = take(9 * B * 8); w.sf = take(3 * B * 8); w.psf = take(9 * B * 8); w.q = take(9 * B * 8);
+    w.us = take(B * 4);
+    w.sp = take(T * 3 * B * 8); w.ss = take(T * 3 * B * 8);      // used when the caller does not take S_PLUS / S_SMOOTH
+    const epi_batch_desc b = la_batch_desc(d, 0);                  // path_hint 0 needs the most workspace
+    w.ekf_bytes = epi_ekf_workspace_bytes(&b);
+    w.ekf = take(w.ekf_bytes);
+    w.total = off;
+    return w;
+}
+
+int epi_lookahead_validate(const epi_lookahead_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->model != EPI_MODEL_SIA3) {
+        set_err(err, "the look-ahead study runs SIAlphaModelEKF (EPI_MODEL_SIA3) only"); return EPI_ERR_UNSUPPORTED;
+    }
+    if (d->R < 1 || d->LL < 1) { set_err(err, "R and LL must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->F < 1) { set_err(err, "F (num_forecast_days) must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->F > d->LL) { set_err(err, "F (num_forecast_days) must not exceed LL: a start masks at most every day"); return EPI_ERR_BAD_ARG; }
+    if (d->F > kLaMaxF) { set_err(err, "F (num_forecast_days) is limited to 1024 (a table column is staged in LDS)"); return EPI_ERR_BAD_ARG; }
+    if (d->M < 1) { set_err(err, "M (MaxLookAheadDays) must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->F > ((int64_t)1 << 23)) { set_err(err, "R * F chains are limited to 2^23"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->M > (int64_t)0x7fffffff) { set_err(err, "M * R table columns exceed the grid"); return EPI_ERR_BAD_ARG; }
+    if (d->shape != 0 && d->shape != EPI_SHAPE_LANE && d->shape != EPI_SHAPE_WAVE) {
+        set_err(err, "shape must be 0 (the study decides), 1 (one lane per chain) or 3 (seven chains per wavefront)"); return EPI_ERR_BAD_ARG;
+    }
+    const epi_batch_desc b = la_batch_desc(d, 0);
+    return epi_ekf_validate(&b, err);
+}
+
+size_t epi_lookahead_workspace_bytes(const epi_lookahead_desc *d)
+{
+    if (epi_lookahead_validate(d, nullptr) != EPI_OK) return 0;
+    return la_ws_layout(d).total;
+}
+
+static int la_args_ok(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out, char *err)
+{
+    int rc = epi_lookahead_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!in || !out) { set_err(err, "NULL inputs/outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->x || !in->u || !in->prm || !in->s_init || !in->Ps_init || !in->s_final || !in->Ps_final || !in->Q) {
+        set_err(err, "NULL input array"); return EPI_ERR_BAD_ARG;
+    }
+    if (!in->truth || !in->population) { set_err(err, "NULL truth / population"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode == 0 && !in->R_scalar) { set_err(err, "r_mode 0 needs R_scalar"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode == 1 && !in->R_series) { set_err(err, "r_mode 1 needs R_series"); return EPI_ERR_BAD_ARG; }
+    if (!out->est_plus || !out->est_smooth || !out->mean_plus || !out->median_plus || !out->std_plus || !out->mean_smooth ||
+        !out->median_smooth || !out->std_smooth) {
+        set_err(err, "NULL output table / statistic"); return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+// expand -> filter + smoother -> error tables -> statistics, all on `st`
+static int la_enqueue(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
+                      void *workspace, size_t workspace_bytes, int path_hint, hipStream_t st, char *err)
+{
+    int rc = la_args_ok(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const LaWs wl = la_ws_layout(d);
+    if (!workspace || workspace_bytes < wl.total) { set_err(err, epi_status_string(EPI_ERR_WORKSPACE)); return EPI_ERR_WORKSPACE; }
+    char *ws = (char *)workspace;
+    const int B = d->R * d->F;
+    LaArgs a{};
+    a.R = d->R; a.LL = d->LL; a.F = d->F; a.M = d->M; a.n_npi = d->n_npi; a.r_mode = d->r_mode;
+    a.x = in->x; a.R_series = in->R_series; a.R_scalar = in->R_scalar; a.prm = in->prm; a.s_init = in->s_init; a.Ps_init = in->Ps_init;
+    a.s_final = in->s_final; a.Ps_final = in->Ps_final; a.Q = in->Q; a.truth = in->truth; a.population = in->population;
+    a.cx = (double *)(ws + wl.x); a.cR_series = d->r_mode == 1 ? (double *)(ws + wl.rs) : nullptr;
+    a.cR_scalar = d->r_mode == 0 ? (double *)(ws + wl.rsc) : nullptr;
+    a.cprm = (double *)(ws + wl.prm); a.cs_init = (double *)(ws + wl.si); a.cPs_init = (double *)(ws + wl.psi);
+    a.cs_final = (double *)(ws + wl.sf); a.cPs_final = (double *)(ws + wl.psf); a.cQ = (double *)(ws + wl.q);
+    a.u_series = (int32_t *)(ws + wl.us);
+    a.S_PLUS = out->S_PLUS ? out->S_PLUS : (double *)(ws + wl.sp);
+    a.S_SMOOTH = out->S_SMOOTH ? out->S_SMOOTH : (double *)(ws + wl.ss);
+    a.est_plus = out->est_plus; a.est_smooth = out->est_smooth;
+    a.mean_plus = out->mean_plus; a.median_plus = out->median_plus; a.std_plus = out->std_plus;
+    a.mean_smooth = out->mean_smooth; a.median_smooth = out->median_smooth; a.std_smooth = out->std_smooth;
+    const int nrows = d->LL * (d->r_mode == 1 ? 2 : 1) + kLaChainRows;
+    hipLaunchKernelGGL(lookahead_expand, dim3((unsigned)((B + 255) / 256), (unsigned)(nrows < 4096 ? nrows : 4096)), dim3(256), 0, st, a, nrows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(err, e, "lookahead_expand launch");
+    const epi_batch_desc b = la_batch_desc(d, path_hint);
+    epi_inputs din{};
+    din.x_series = nullptr; din.u_series = a.u_series;
+    din.x = a.cx; din.u = in->u; din.R_series = a.cR_series; din.R_scalar = a.cR_scalar; din.prm = a.cprm;
+    din.s_init = a.cs_init; din.Ps_init = a.cPs_init; din.s_final = a.cs_final; din.Ps_final = a.cPs_final; din.Q = a.cQ;
+    epi_outputs dout{};
+    dout.S_PLUS = (double *)a.S_PLUS; dout.S_SMOOTH = (double *)a.S_SMOOTH; dout.status = out->status;
+    rc = epi_ekf_run_device(&b, &din, &dout, ws + wl.ekf, wl.ekf_bytes, st, err);
+    if (rc != EPI_OK) return rc;
+    const size_t n_err = (size_t)d->F * d->M * d->R;
+    hipLaunchKernelGGL(lookahead_errors, dim3((unsigned)((n_err + 255) / 256)), dim3(256), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_errors launch");
+    hipLaunchKernelGGL(lookahead_stats, dim3((unsigned)(d->M * d->R), 2), dim3(kWave), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_stats launch");
+    return EPI_OK;
+}
+
+int epi_lookahead_run_device(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
+                             void *workspace, size_t workspace_bytes, void *stream, char *err)
+{
+    return la_enqueue(d, in, out, workspace, workspace_bytes, 0, (hipStream_t)stream, err);
+}
+
+int epi_lookahead_run_host(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
+                           int device, char *err)
+{
+    int rc = la_args_ok(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, T = (size_t)d->LL, F = (size_t)d->F, M = (size_t)d->M, B = R * F, n = (size_t)d->n_npi;
+    HostIO io;
+    const size_t o_x = io.add_in(in->x, T, 8, R, 0, R), o_u = io.add_in(in->u, T * n, 8, R, 0, R);
+    const size_t o_rs = d->r_mode == 1 ? io.add_in(in->R_series, T, 8, R, 0, R) : io.add_in(in->R_scalar, 1, 8, R, 0, R);
+    const size_t o_prm = io.add_in(in->prm, EPI_PRM_COUNT, 8, R, 0, R), o_si = io.add_in(in->s_init, 3, 8, R, 0, R);
+    const size_t o_psi = io.add_in(in->Ps_init, 9, 8, R, 0, R), o_sf = io.add_in(in->s_final, 3, 8, R, 0, R);
+    const size_t o_psf = io.add_in(in->Ps_final, 9, 8, R, 0, R), o_q = io.add_in(in->Q, 9, 8, R, 0, R);
+    const size_t o_tr = io.add_in(in->truth, T, 8, R, 0, R), o_pop = io.add_in(in->population, 1, 8, R, 0, R);
+    double *const *stat_host[6] = {&out->mean_plus, &out->median_plus, &out->std_plus, &out->mean_smooth, &out->median_smooth, &out->std_smooth};
+    const size_t o_ep = io.add_out(out->est_plus, F * M, 8, R, 0, R), o_es = io.add_out(out->est_smooth, F * M, 8, R, 0, R);
+    size_t o_st[6];
+    for (int k = 0; k < 6; k++) o_st[k] = io.add_out(*stat_host[k], M, 8, R, 0, R);
+    const size_t o_sp = out->S_PLUS ? io.add_out(out->S_PLUS, T * 3, 8, B, 0, B) : (size_t)-1;
+    const size_t o_ss = out->S_SMOOTH ? io.add_out(out->S_SMOOTH, T * 3, 8, B, 0, B) : (size_t)-1;
+    const size_t o_status = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : (size_t)-1;
+    const size_t wsb = epi_lookahead_workspace_bytes(d);
+    const size_t o_ws = io.reserve(wsb);
+    // the inputs are per region: the packed kernels' conditions are checked on the host, once per region
+    epi_inputs hin{};
+    hin.s_init = in->s_init; hin.Ps_init = in->Ps_init; hin.s_final = in->s_final; hin.Ps_final = in->Ps_final; hin.Q = in->Q;
+    const int path_hint = host_precheck(3, false, &hin, R, 0, R) ? 1 : 2;
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        auto dp = [&](size_t o) { return (const double *)(base + o); };
+        auto op = [&](size_t o) { return o == (size_t)-1 ? nullptr : (double *)(base + o); };
+        epi_lookahead_inputs din{};
+        din.x = dp(o_x); din.u = dp(o_u);
+        din.R_series = d->r_mode == 1 ? dp(o_rs) : nullptr; din.R_scalar = d->r_mode == 0 ? dp(o_rs) : nullptr;
+        din.prm = dp(o_prm); din.s_init = dp(o_si); din.Ps_init = dp(o_psi); din.s_final = dp(o_sf); din.Ps_final = dp(o_psf);
+        din.Q = dp(o_q); din.truth = dp(o_tr); din.population = dp(o_pop);
+        epi_lookahead_outputs dout{};
+        dout.est_plus = op(o_ep); dout.est_smooth = op(o_es);
+        dout.mean_plus = op(o_st[0]); dout.median_plus = op(o_st[1]); dout.std_plus = op(o_st[2]);
+        dout.mean_smooth = op(o_st[3]); dout.median_smooth = op(o_st[4]); dout.std_smooth = op(o_st[5]);
+        dout.S_PLUS = op(o_sp); dout.S_SMOOTH = op(o_ss);
+        dout.status = o_status == (size_t)-1 ? nullptr : (int32_t *)(base + o_status);
+        const int r = la_enqueue(d, &din, &dout, base + o_ws, wsb, path_hint, cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, d->placement_tries, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
 }
 
 }  // extern "C"

@@ -116,14 +116,11 @@ def _alpha_smooth(w, device):
     return r.out["S_SMOOTH"].cpu().numpy()                 # [T, 3, S]
 
 
-def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regression_days=60, npi_weights=None,
-              W=7, device="cuda:0"):
-    """Run the chain above.  cases/deaths [T,S] cumulative counts (NaN = missing), population [S], ip [T,n,S] (NaN = N/A).
-    Returns a dict with every intermediate and `prescription` [horizon, n, S]: the smoothed optimal plan of each region's
-    Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps]."""
+def _front_half(cases, deaths, N, ip, num_regression_days, W, device):
+    """Preprocessing, EKF round 1, NNLS, round 2, NNLS (TrainPredictPrescribeNPI.m:142-330, ForecastQualityAssessment.m:
+    160-356) over the days given.  Returns pre, alpha_round1, fit1, alpha_round2, fit2, X_reg."""
     T, S = cases.shape
     n = ip.shape[1]
-    N = np.asarray(population, dtype=np.float64)
     u_max = synth.IP_MAXES[:n]
     out = {}
     pre = {k: v.cpu().numpy() for k, v in batch.preprocess(cases, N, deaths, ip, W=W, min_cases=synth.MIN_CASES,
@@ -138,7 +135,22 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
     # round 2: real inputs -> refined alpha -> second regression
     S2 = _alpha_smooth(workload3(x, R, u, N, I0, fit1["a"], fit1["b"]), device)
     fit2 = {k: v.cpu().numpy() for k, v in batch.nnls_affine_fit(X, np.ascontiguousarray(S2[T - D:, 2]), device=device).items()}
-    out.update(alpha_round1=S1[:, 2], fit1=fit1, alpha_round2=S2[:, 2], fit2=fit2)
+    out.update(alpha_round1=S1[:, 2], fit1=fit1, alpha_round2=S2[:, 2], fit2=fit2, X_reg=X)
+    return out
+
+
+def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regression_days=60, npi_weights=None,
+              W=7, device="cuda:0"):
+    """Run the chain above.  cases/deaths [T,S] cumulative counts (NaN = missing), population [S], ip [T,n,S] (NaN = N/A).
+    Returns a dict with every intermediate and `prescription` [horizon, n, S]: the smoothed optimal plan of each region's
+    Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps]."""
+    T, S = cases.shape
+    n = ip.shape[1]
+    N = np.asarray(population, dtype=np.float64)
+    u_max = synth.IP_MAXES[:n]
+    out = _front_half(cases, deaths, N, ip, num_regression_days, W, device)
+    pre, fit2, X = out["pre"], out["fit2"], out["X_reg"]
+    x, R, u, I0 = pre["x_new"], pre["R_v"], pre["ip_filled"], pre["I0"]
     # forecast set-up (:333-341): R_v padded with its mean, observations and (for the sweep) controls NaN over the horizon
     R_mean = R.sum(axis=0) / T
     xh = np.concatenate([x, np.full((horizon, S), np.nan)]); Rh = np.concatenate([R, np.repeat(R_mean[None], horizon, 0)])
@@ -178,4 +190,37 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
                J0=sc["J0"].cpu().numpy().reshape(S, n_eps), J1=sc["J1"].cpu().numpy().reshape(S, n_eps),
                front=front.cpu().numpy(), i_opt=i_opt_h, sweep=w6,
                prescription=best.cpu().numpy())
+    return out
+
+
+def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_lookahead=60, num_regression_days=60, W=7,
+                     device="cuda:0", chains=False, shape=0):
+    """The forecast look-ahead error study of Tools/ForecastQualityAssessment.m for ALL regions in one device call.
+
+    cases / deaths [LL, S] cumulative counts (NaN = missing), population [S], ip [LL, n, S] (NaN = N/A) over the WHOLE window;
+    the first LL - num_forecast_days days are the training window.  The front half (preprocessing, EKF round 1, NNLS, round 2,
+    NNLS: :160-356) runs on the training window exactly as in prescribe(); the whole window is preprocessed too, giving the
+    `_ENTIRE` quantities (:102-132): new_smoothed = NewCasesSmoothed_ENTIRE (the truth), x_new the observations, ip_filled the
+    controls.  R_v of the training window is padded with its mean (:362).  Then every region is filtered once per start
+    s = 1 .. num_forecast_days with its last s observations hidden (:380-393) and the error tables and their statistics over
+    the starts max_lookahead .. num_forecast_days (:428-449) are computed (batch.lookahead).
+    Returns a dict: the front half's intermediates (pre, alpha_round1, fit1, alpha_round2, fit2, X_reg), pre_entire, R_full,
+    workload (the per-region synth.Workload of the study), truth, and est_plus / est_smooth [F, M, S],
+    mean / median / std_{plus,smooth} [M, S] (+ S_PLUS / S_SMOOTH / status of every chain with chains=True)."""
+    LL, S = cases.shape
+    F = int(num_forecast_days)
+    T = LL - F
+    if F < 1 or T < 2:
+        raise ValueError("num_forecast_days must be >= 1 and leave a training window of at least 2 days")
+    N = np.asarray(population, dtype=np.float64)
+    out = _front_half(cases[:T], None if deaths is None else deaths[:T], N, ip[:T], num_regression_days, W, device)
+    fit2, I0, R = out["fit2"], out["pre"]["I0"], out["pre"]["R_v"]
+    ent = {k: v.cpu().numpy() for k, v in batch.preprocess(cases, N, deaths, ip, W=W, min_cases=synth.MIN_CASES,
+                                                            first_num_days=7, device=device).items()}
+    R_mean = R.sum(axis=0) / T
+    R_full = np.concatenate([R, np.repeat(R_mean[None], F, 0)])
+    w = workload3(ent["x_new"], R_full, ent["ip_filled"], N, I0, fit2["a"], fit2["b"])
+    truth = ent["new_smoothed"]
+    res = batch.lookahead(w, truth, N, F, max_lookahead, device=device, chains=chains, shape=shape)
+    out.update(pre_entire=ent, R_mean=R_mean, R_full=R_full, workload=w, truth=truth, **res)
     return out

@@ -426,6 +426,56 @@ typedef struct epi_prescribe_outputs {
 int epi_sweep_prescribe_host(const epi_prescribe_desc *d, const epi_prescribe_inputs *in, const epi_prescribe_outputs *out,
                              int n_devices, const int *device_ids, char *err);
 
+/* ---- the forecast look-ahead error study (Tools/ForecastQualityAssessment.m:359-393, 428-449) as ONE call ----
+ * For every region r and every start s = 1 .. F (F = num_forecast_days) the reference masks the last s observations with
+ * NaN, runs SIAlphaModelEKF (the 3-state model, EPI_MODEL_SIA3) and compares N * s * i * alpha of S_PLUS and of S_SMOOTH with
+ * the smoothed new cases over the hidden tail.  Here all R * F chains run as one batch: chain c = r * F + (s - 1) (the chain
+ * order of synth.make_mask_ensemble); the device expands the per-region inputs, runs the filter and smoother, and reduces.
+ * Inputs (region-minor, the layouts of epi_inputs with B = R):  x [LL][R] observations (NaN = missing), u [LL][n_npi][R]
+ *   controls, R_series [LL][R] (r_mode 1) or R_scalar [R] (r_mode 0), prm [EPI_PRM_COUNT][R], s_init [3][R], Ps_init [9][R],
+ *   s_final [3][R], Ps_final [9][R], Q [9][R];  truth [LL][R] = NewCasesSmoothed_ENTIRE (not normalised);  population [R].
+ * Outputs:  est_plus / est_smooth [F][M][R] = EstError_PLUS / EstError_SMOOTH (M = MaxLookAheadDays): row s, column
+ *   j = 1 .. min(s, M) is, at day t = LL - s + j - 1 (0-based), est = ((N * S(t,1)) * S(t,2)) * S(t,3) and
+ *   (100 * |truth - est|) / truth (IEEE Inf / NaN where truth is 0 are kept); columns j > min(s, M) are 0 (`zeros`);
+ *   mean_* / median_* / std_* [M][R]: statistics of each column over the rows s = M .. F (n = F - M + 1): mean = sum in
+ *   increasing s / n, std = sqrt(sum((x - mean)^2) / (n - 1)) (0 for n = 1), median = NaN if any value is NaN, else the
+ *   middle order statistic (odd n) or a + (b - a) / 2 of the two middle ones, (a + b) / 2 when they differ in sign or one is
+ *   infinite (even n); n <= 0 (F < M) gives NaN in all three.
+ *   Optional (NULL = not returned): S_PLUS / S_SMOOTH [LL][3][R * F] of every chain, status [R * F] (epi_outputs.status).
+ * epi_lookahead_run_device takes DEVICE pointers and enqueues on `stream` (no host synchronisation); the workspace holds the
+ * masked per-chain inputs (x, R_v and the per-chain columns of prm / s_init / ... / Q) and the filter's own workspace.
+ * epi_lookahead_run_host takes HOST pointers and runs on a pooled context of `device` (as epi_ekf_run_host). */
+typedef struct epi_lookahead_desc {
+    int32_t abi_version;
+    int32_t model;           /* EPI_MODEL_SIA3 (the reference's study runs SIAlphaModelEKF); anything else: EPI_ERR_UNSUPPORTED */
+    int32_t R;               /* regions */
+    int32_t LL;              /* days of the whole window */
+    int32_t F;               /* num_forecast_days: starts 1 .. F, 1 <= F <= min(LL, 1024) */
+    int32_t M;               /* MaxLookAheadDays, >= 1 */
+    int32_t n_npi, L, order, obs_type, r_mode;   /* as in epi_batch_desc */
+    int32_t shape;           /* lane mapping of the filter: 0 = the study decides, 1 = one lane per chain, 3 = seven chains per
+                                wavefront (epi_batch_desc.shape; results are bit-identical) */
+    int32_t placement_tries; /* as in epi_batch_desc (epi_lookahead_run_host only) */
+} epi_lookahead_desc;
+typedef struct epi_lookahead_inputs {
+    const double *x, *u, *R_series, *R_scalar, *prm;
+    const double *s_init, *Ps_init, *s_final, *Ps_final, *Q;
+    const double *truth, *population;
+} epi_lookahead_inputs;
+typedef struct epi_lookahead_outputs {
+    double *est_plus, *est_smooth;                              /* [F][M][R] */
+    double *mean_plus, *median_plus, *std_plus;                 /* [M][R] */
+    double *mean_smooth, *median_smooth, *std_smooth;           /* [M][R] */
+    double *S_PLUS, *S_SMOOTH;                                  /* [LL][3][R * F] or NULL */
+    int32_t *status;                                            /* [R * F] or NULL */
+} epi_lookahead_outputs;
+int epi_lookahead_validate(const epi_lookahead_desc *d, char *err);
+size_t epi_lookahead_workspace_bytes(const epi_lookahead_desc *d);
+int epi_lookahead_run_device(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
+                             void *workspace, size_t workspace_bytes, void *stream, char *err);
+int epi_lookahead_run_host(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
+                           int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)
