@@ -7,6 +7,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import layout as L
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +25,7 @@ ABI_SYMBOLS = [
     "epi_sweep_run_device", "epi_sweep_prescribe_host", "epi_preprocess_host", "epi_nnls_affine_fit_host", "epi_random_npi_mc_host",
     "epi_sir_sim_device", "epi_sir_sim_host",
     "epi_lookahead_validate", "epi_lookahead_workspace_bytes", "epi_lookahead_run_device", "epi_lookahead_run_host",
+    "epi_rtwin_validate", "epi_rtwin_run_device", "epi_rtwin_run_host",
 ]
 
 
@@ -125,6 +128,23 @@ class LookaheadInputs(C.Structure):
 
 class LookaheadOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LA_OUT_NAMES]
+
+
+class RtwinDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "L", "wlen", "causal", "generation_period", "methods")] + \
+        [("time_unit", C.c_double)]
+
+
+RTWIN_METHODS = {"LogLinReg": 1, "GenRatios": 2, "NonlinLS": 4}
+RTWIN_OUT_F64 = ("llr_Rt", "llr_A", "llr_Lambda", "llr_ExpFit", "gr_Rt", "gr_Lambda", "gr_RtSmoothed", "gr_LambdaSmoothed",
+                 "nls_Rt", "nls_A", "nls_Lambda", "nls_ExpFit")
+RTWIN_OUT_I32 = ("nls_status", "nls_iters")
+RTWIN_OUT_NAMES = RTWIN_OUT_F64 + RTWIN_OUT_I32
+RTWIN_STATUS = {"outside": 0, "tolx": 1, "tolfun": 2, "maxiter": 3, "stall": 4, "skipped": 5, "model_error": 6}
+
+
+class RtwinOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RTWIN_OUT_NAMES]
 
 
 class NnlsDesc(C.Structure):
@@ -252,6 +272,12 @@ def lib():
         h.epi_lookahead_run_host.restype = C.c_int
         h.epi_lookahead_run_host.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
                                              C.c_int, C.c_char_p]
+        h.epi_rtwin_validate.restype = C.c_int
+        h.epi_rtwin_validate.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_char_p]
+        h.epi_rtwin_run_device.restype = C.c_int
+        h.epi_rtwin_run_device.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_void_p, C.c_char_p]
+        h.epi_rtwin_run_host.restype = C.c_int
+        h.epi_rtwin_run_host.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h
@@ -273,6 +299,25 @@ def make_lookahead_desc(R, LL, F, M, n_npi, L_, order=1, obs_type="NEWCASES", r_
     d.R, d.LL, d.F, d.M, d.n_npi, d.L, d.order = int(R), int(LL), int(F), int(M), int(n_npi), int(L_), int(order)
     d.obs_type = L.OBS_IDS.get(obs_type, 99) if isinstance(obs_type, str) else int(obs_type)
     d.r_mode, d.shape, d.placement_tries = int(r_mode), int(shape), int(placement_tries)
+    return d
+
+
+def rtwin_methods(methods) -> int:
+    """("LogLinReg", "GenRatios", "NonlinLS") names (any subset) or an int of EPI_RTWIN_* bits -> the bits"""
+    if isinstance(methods, (int, np.integer)):
+        return int(methods)
+    if isinstance(methods, str):
+        methods = (methods,)
+    return sum(RTWIN_METHODS[m] for m in set(methods))
+
+
+def make_rtwin_desc(R, L_, wlen, time_unit=1.0, causal=1, generation_period=None, methods=7) -> RtwinDesc:
+    d = RtwinDesc()
+    d.abi_version = ABI_VERSION
+    d.R, d.L, d.wlen, d.causal = int(R), int(L_), int(wlen), int(causal)
+    d.generation_period = 0 if generation_period is None else int(generation_period)
+    d.methods = rtwin_methods(methods)
+    d.time_unit = float(time_unit)
     return d
 
 

@@ -738,3 +738,42 @@ def lookahead_host(w, truth, population, F, M=60, device=0, chains=False, shape=
     rc = _lib.lib().epi_lookahead_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
     _lib.check(rc, err)
     return out
+
+
+def _rtwin_names(methods, status=True):
+    bits = _lib.rtwin_methods(methods)
+    names = []
+    if bits & 1:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("llr_")]
+    if bits & 2:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("gr_")]
+    if bits & 4:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("nls_")] + (list(_lib.RTWIN_OUT_I32) if status else [])
+    return bits, names
+
+
+def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, methods=("LogLinReg", "GenRatios", "NonlinLS"),
+              device="cuda:0"):
+    """Tools/Rt_ExpFitLogLinReg.m, Rt_ExpFitGenRatios.m and Rt_ExpFitNonlinLS.m over every column of new_cases [L, R] (days x
+    regions: the new_smoothed layout of preprocess) in one device call (epi_rtwin_run_device).  `methods` is any subset of the
+    three names (or the EPI_RTWIN_* bits); GenRatios needs generation_period.  Returns a dict of torch tensors [L, R]:
+    llr_{Rt, A, Lambda, ExpFit}, gr_{Rt, Lambda, RtSmoothed, LambdaSmoothed}, nls_{Rt, A, Lambda, ExpFit} and the int32
+    nls_status / nls_iters (status codes in _lib.RTWIN_STATUS), for the methods asked.  Enqueued on the current stream (where
+    the input copy and the outputs are allocated) without a host synchronisation."""
+    dev = torch.device(device)
+    x = new_cases if isinstance(new_cases, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(new_cases), dtype=torch.float64)
+    x = x.to(dev, torch.float64).contiguous()
+    if x.dim() != 2:
+        raise ValueError("new_cases must be [L, R]")
+    L_, R = x.shape
+    bits, names = _rtwin_names(methods)
+    d = _lib.make_rtwin_desc(R, L_, wlen, time_unit, causal, generation_period, bits)
+    out = {n: torch.empty((L_, R), dtype=torch.int32 if n in _lib.RTWIN_OUT_I32 else torch.float64, device=dev) for n in names}
+    outs = _lib.RtwinOutputs()
+    for n in _lib.RTWIN_OUT_NAMES:
+        setattr(outs, n, _ptr(out.get(n)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_rtwin_run_device(C.byref(d), _ptr(x), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out

@@ -831,6 +831,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "preprocess.hpp"
 #include "nnls.hpp"
 #include "lookahead.hpp"
+#include "rt_window.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3455,6 +3456,122 @@ int epi_lookahead_run_host(const epi_lookahead_desc *d, const epi_lookahead_inpu
         return EPI_OK;
     };
     rc = place_and_run(cx, io.off + 256, d->placement_tries, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
+// ---- the sliding-window growth-rate estimators (Tools/Rt_ExpFitLogLinReg.m, Rt_ExpFitGenRatios.m, Rt_ExpFitNonlinLS.m) ----
+int epi_rtwin_validate(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1 || d->L < 1) { set_err(err, "R and L must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->L > (int64_t)0x7fffffff) { set_err(err, "R * L is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->methods == 0) { set_err(err, "methods is empty: ask for LogLinReg (1), GenRatios (2) and / or NonlinLS (4)"); return EPI_ERR_BAD_ARG; }
+    if (d->methods & ~(EPI_RTWIN_LOGLINREG | EPI_RTWIN_GENRATIOS | EPI_RTWIN_NONLINLS)) { set_err(err, "unknown method bit"); return EPI_ERR_BAD_ARG; }
+    if (d->causal != 0 && d->causal != 1) { set_err(err, "causal must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if ((d->methods & EPI_RTWIN_GENRATIOS) && (d->generation_period < 1 || d->generation_period > d->L)) {
+        set_err(err, "generation_period must lie in 1 .. L"); return EPI_ERR_BAD_ARG;
+    }
+    if (!new_cases || !out) { set_err(err, "NULL new_cases / outputs"); return EPI_ERR_BAD_ARG; }
+    if (d->wlen < 2 || d->wlen > kRtwMaxSamples) {
+        set_err(err, "wlen is limited to 2 .. 31 (a window is held in registers)"); return EPI_ERR_UNSUPPORTED;
+    }
+    return EPI_OK;
+}
+
+static RtwArgs rtw_args(const epi_rtwin_desc *d, const double *x, const epi_rtwin_outputs *o)
+{
+    RtwArgs a{};
+    a.R = d->R; a.L = d->L; a.wlen = d->wlen; a.causal = d->causal; a.gp = d->generation_period;
+    const int h = d->wlen / 2;
+    a.nw = d->causal ? d->wlen : 2 * h + 1;
+    a.off = d->causal ? -(d->wlen - 1) : -h;
+    a.lo = -a.off;
+    a.hi = d->L - (a.nw - 1 + a.off);
+    a.time_unit = d->time_unit;
+    double sn = 0.0, sn2 = 0.0;
+    for (int i = 0; i < a.nw; i++) {
+        a.n[i] = (double)(i + a.off);
+        a.t[i] = a.n[i] / d->time_unit;
+        sn = sn + a.n[i];
+        sn2 = sn2 + a.n[i] * a.n[i];
+    }
+    a.En = sn / (double)a.nw; a.En2 = sn2 / (double)a.nw;
+    a.Det = a.En2 - a.En * a.En;
+    a.c_ma = 1.0 / (double)d->wlen;
+    a.x = x;
+    a.llr_Rt = o->llr_Rt; a.llr_A = o->llr_A; a.llr_Lambda = o->llr_Lambda; a.llr_ExpFit = o->llr_ExpFit;
+    a.gr_Rt = o->gr_Rt; a.gr_Lambda = o->gr_Lambda; a.gr_RtSmoothed = o->gr_RtSmoothed; a.gr_LambdaSmoothed = o->gr_LambdaSmoothed;
+    a.nls_Rt = o->nls_Rt; a.nls_A = o->nls_A; a.nls_Lambda = o->nls_Lambda; a.nls_ExpFit = o->nls_ExpFit;
+    a.nls_status = o->nls_status; a.nls_iters = o->nls_iters;
+    return a;
+}
+
+int epi_rtwin_run_device(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, void *stream, char *err)
+{
+    int rc = epi_rtwin_validate(d, new_cases, out, err);
+    if (rc != EPI_OK) return rc;
+    const RtwArgs a = rtw_args(d, new_cases, out);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)d->L * d->R;
+    hipError_t e;
+    if ((d->methods & EPI_RTWIN_LOGLINREG) && (a.llr_Rt || a.llr_A || a.llr_Lambda || a.llr_ExpFit)) {
+        hipLaunchKernelGGL(rtw_loglin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "rtw_loglin launch");
+    }
+    if ((d->methods & EPI_RTWIN_GENRATIOS) && (a.gr_Rt || a.gr_Lambda || a.gr_RtSmoothed || a.gr_LambdaSmoothed)) {
+        hipLaunchKernelGGL(rtw_genratios, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "rtw_genratios launch");
+    }
+    if ((d->methods & EPI_RTWIN_NONLINLS) &&
+        (a.nls_Rt || a.nls_A || a.nls_Lambda || a.nls_ExpFit || a.nls_status || a.nls_iters)) {
+        const size_t lds = (size_t)4 * a.nw * 64 * sizeof(double);
+        hipLaunchKernelGGL(rtw_nonlin, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "rtw_nonlin launch");
+    }
+    return EPI_OK;
+}
+
+int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, int device, char *err)
+{
+    int rc = epi_rtwin_validate(d, new_cases, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, T = (size_t)d->L;
+    HostIO io;
+    const size_t o_x = io.add_in(new_cases, T, 8, R, 0, R);
+    double *const *f64[12] = {&out->llr_Rt, &out->llr_A, &out->llr_Lambda, &out->llr_ExpFit, &out->gr_Rt, &out->gr_Lambda,
+                              &out->gr_RtSmoothed, &out->gr_LambdaSmoothed, &out->nls_Rt, &out->nls_A, &out->nls_Lambda, &out->nls_ExpFit};
+    int32_t *const *i32[2] = {&out->nls_status, &out->nls_iters};
+    size_t o_f[12], o_i[2];
+    for (int k = 0; k < 12; k++) o_f[k] = *f64[k] ? io.add_out(*f64[k], T, 8, R, 0, R) : (size_t)-1;
+    for (int k = 0; k < 2; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], T, 4, R, 0, R) : (size_t)-1;
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        epi_rtwin_outputs dout{};
+        double **df[12] = {&dout.llr_Rt, &dout.llr_A, &dout.llr_Lambda, &dout.llr_ExpFit, &dout.gr_Rt, &dout.gr_Lambda,
+                           &dout.gr_RtSmoothed, &dout.gr_LambdaSmoothed, &dout.nls_Rt, &dout.nls_A, &dout.nls_Lambda, &dout.nls_ExpFit};
+        int32_t **di[2] = {&dout.nls_status, &dout.nls_iters};
+        for (int k = 0; k < 12; k++) *df[k] = o_f[k] == (size_t)-1 ? nullptr : (double *)(base + o_f[k]);
+        for (int k = 0; k < 2; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
+        const int r = epi_rtwin_run_device(d, (const double *)(base + o_x), &dout, cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
     if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
     ctx_release(cx);
     if (have_prev) (void)hipSetDevice(prev);

@@ -133,3 +133,25 @@ def sir(alpha, beta, gamma, s0, i0, r0, K, dt, device=0):
     rc = _lib.lib().epi_sir_sim_host(B, int(K), float(dt), prm.ctypes.data, out.ctypes.data, int(device), err)
     _lib.check(rc, err)
     return out[:, 0], out[:, 1], out[:, 2]
+
+
+def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, methods=("LogLinReg", "GenRatios", "NonlinLS"),
+              device=0):
+    """epi_rtwin_run_host: the three sliding-window growth-rate estimators over new_cases [L, R] (NumPy in and out,
+    synchronous).  Returns the dict of batch.rt_window as NumPy arrays."""
+    keep = []
+    x = np.asarray(new_cases, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("new_cases must be [L, R]")
+    L_, R = x.shape
+    bits = _lib.rtwin_methods(methods)
+    names = [n for n, b in zip(_lib.RTWIN_OUT_NAMES, [1] * 4 + [2] * 4 + [4] * 6) if bits & b]
+    d = _lib.make_rtwin_desc(R, L_, wlen, time_unit, causal, generation_period, bits)
+    out = {n: np.empty((L_, R), dtype=np.int32 if n in _lib.RTWIN_OUT_I32 else np.float64) for n in names}
+    outs = _lib.RtwinOutputs()
+    for n in _lib.RTWIN_OUT_NAMES:
+        setattr(outs, n, out[n].ctypes.data if n in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_rtwin_run_host(C.byref(d), _f(x, keep), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out

@@ -224,3 +224,54 @@ def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_looka
     res = batch.lookahead(w, truth, N, F, max_lookahead, device=device, chains=chains, shape=shape)
     out.update(pre_entire=ent, R_mean=R_mean, R_full=R_full, workload=w, truth=truth, **res)
     return out
+
+
+# testScripts/test04FullFeatureExtMLpipeline.m:203-219: the exponential-fit EKF's settings in the feature-extraction pipeline
+GROWTH_EKF = dict(w_bar=[0.0, 0.0], v_bar=0.0, Q_w=np.diag([250.0 ** 2, 3.0e-3 ** 2]), R_v=10.0 ** 2, beta=0.9, gamma=0.995,
+                  inv_monitor_len=21, params=[1.0, 0.9, 0.1])
+
+
+def growth_rate_ekf_workload(new_smoothed, order, forecast_days=0, s_init_lambda=None):
+    """Rt_ExpFitEKF for every column of new_smoothed [T, S] with test04's settings (:197-219) as one synth.RtWorkload: the
+    last `forecast_days` days hidden (NaN), s_init = [first sample; Lambda_GeoGenRatios(1)] per column (s_init_lambda [S],
+    default 0: GenRatios' first value is always 0), Ps_init = 100 Q_w."""
+    x = np.array(new_smoothed, dtype=np.float64, ndmin=2)
+    T, S = x.shape
+    if forecast_days > 0:
+        x[T - int(forecast_days):] = np.nan
+    e = GROWTH_EKF
+    Q_w = e["Q_w"]
+    rp = np.zeros((synth.RT_PRM_COUNT, S))                  # EPI_RT_* rows of include/epiekf.h
+    rp[0:3] = np.asarray(e["params"])[:, None]
+    rp[3:5] = np.asarray(e["w_bar"])[:, None]
+    rp[5], rp[6], rp[7], rp[8] = e["v_bar"], e["R_v"], e["beta"], e["gamma"]
+    rp[9] = x[0]
+    rp[10] = 0.0 if s_init_lambda is None else np.asarray(s_init_lambda, dtype=np.float64)
+    rp[11:15] = (100.0 * Q_w).reshape(-1, order="F")[:, None]
+    rp[15:19] = Q_w.reshape(-1, order="F")[:, None]
+    return synth.RtWorkload(x=np.ascontiguousarray(x), rp=rp, x_series=None, L=e["inv_monitor_len"], order=int(order))
+
+
+def growth_rates(cases, population, wlen=7, generation_period=3, causal=1, forecast_days=0, time_unit=1.0, device="cuda:0"):
+    """The growth-rate features of testScripts/test04FullFeatureExtMLpipeline.m (:160-219) for ALL regions:
+
+      cumulative cases --batch.preprocess (W = wlen)--> new_smoothed   (test04's MOVINGAVERAGE-CAUSAL branch, :175)
+      --batch.rt_window--> LogLinReg, GenRatios, NonlinLS in one call  (:185-195)
+      --batch.RtRunner, orders 1 and 2--> Rt_ExpFitEKF of every region, one call per order   (:197-219)
+
+    The daily counts come from this project's cleaning (preprocess: diff, negatives clamped to 0, a missing last day filled
+    with the last valid one, other gaps 0); test04's own cleaning differs only in how several missing trailing days are
+    filled.  cases [T, S] cumulative counts (NaN = missing), population [S].  Returns a dict: new_smoothed [T, S], the
+    rt_window outputs [T, S] (llr_*, gr_*, nls_*), and per EKF order k ekf{k}_S_PLUS / ekf{k}_S_SMOOTH [T, 2, S]."""
+    N = np.asarray(population, dtype=np.float64)
+    pre = batch.preprocess(cases, N, W=wlen, min_cases=synth.MIN_CASES, first_num_days=7, outputs=("new_smoothed",),
+                           device=device)
+    ns = pre["new_smoothed"]
+    rw = batch.rt_window(ns, wlen, time_unit, causal, generation_period, ("LogLinReg", "GenRatios", "NonlinLS"), device=device)
+    out = {"new_smoothed": ns.cpu().numpy()}
+    out.update({k: v.cpu().numpy() for k, v in rw.items()})
+    for order in (1, 2):
+        w = growth_rate_ekf_workload(out["new_smoothed"], order, forecast_days, out["gr_Lambda"][0])
+        r = batch.rt_expfit(w, device=device, outputs=("S_PLUS", "S_SMOOTH"))
+        out[f"ekf{order}_S_PLUS"], out[f"ekf{order}_S_SMOOTH"] = r["S_PLUS"], r["S_SMOOTH"]
+    return out

@@ -440,3 +440,42 @@ def NPICost(newcases, inputs, weights, device=0):
     J0, _ = _npi_cost_host(nc, np.zeros((nc.shape[0], 1)), np.zeros(1), device)
     _, J1 = _npi_cost_host(np.zeros(T), u_tn, wd, device)
     return J0, J1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the sliding-window growth-rate estimators: one series per call through epi_rtwin_run_host (the batch is
+# batch.rt_window / hostapi.rt_window); outputs are 1 x L rows like the reference's
+# ---------------------------------------------------------------------------------------------------------------------
+def _rtwin_one(NewCases, wlen, time_unit, causal, gp, method, device):
+    from . import hostapi
+    x = np.asarray(NewCases, dtype=np.float64).reshape(-1, 1)         # NewCases(:)'
+    return hostapi.rt_window(x, wlen, time_unit, causal, gp, (method,), _dev_index(device))
+
+
+def _row(a):
+    return np.asarray(a).reshape(1, -1).copy()
+
+
+def Rt_ExpFitLogLinReg(NewCases, wlen, time_unit, causal=1, device=0):
+    """[Rt, A, Lambda, ExpFit] = Rt_ExpFitLogLinReg(NewCases, wlen, time_unit, causal) -- Tools/Rt_ExpFitLogLinReg.m"""
+    o = _rtwin_one(NewCases, wlen, time_unit, causal, None, "LogLinReg", device)
+    return _row(o["llr_Rt"]), _row(o["llr_A"]), _row(o["llr_Lambda"]), _row(o["llr_ExpFit"])
+
+
+def Rt_ExpFitGenRatios(NewCases, wlen, generation_period, time_unit, device=0):
+    """[Rt, Lambda, RtSmoothed, LambdaSmoothed] = Rt_ExpFitGenRatios(NewCases, wlen, generation_period, time_unit)
+    -- Tools/Rt_ExpFitGenRatios.m"""
+    o = _rtwin_one(NewCases, wlen, time_unit, 1, generation_period, "GenRatios", device)
+    return _row(o["gr_Rt"]), _row(o["gr_Lambda"]), _row(o["gr_RtSmoothed"]), _row(o["gr_LambdaSmoothed"])
+
+
+def Rt_ExpFitNonlinLS(NewCases, wlen, time_unit, causal=1, device=0):
+    """[Rt, A, Lambda, ExpFit] = Rt_ExpFitNonlinLS(NewCases, wlen, time_unit, causal) -- Tools/Rt_ExpFitNonlinLS.m.
+    Raises where MATLAB's nlinfit would (a window with the model-error status: the model returned Inf / NaN, or fewer than 2
+    samples remain)."""
+    o = _rtwin_one(NewCases, wlen, time_unit, causal, None, "NonlinLS", device)
+    bad = np.flatnonzero(o["nls_status"].ravel() == _lib.RTWIN_STATUS["model_error"])
+    if bad.size:
+        raise RuntimeError(f"Rt_ExpFitNonlinLS: nlinfit fails in the window ending / centred at day {bad[0] + 1} "
+                           "(the model returned Inf or NaN, or fewer than 2 samples remain)")
+    return _row(o["nls_Rt"]), _row(o["nls_A"]), _row(o["nls_Lambda"]), _row(o["nls_ExpFit"])

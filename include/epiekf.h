@@ -476,6 +476,58 @@ int epi_lookahead_run_device(const epi_lookahead_desc *d, const epi_lookahead_in
 int epi_lookahead_run_host(const epi_lookahead_desc *d, const epi_lookahead_inputs *in, const epi_lookahead_outputs *out,
                            int device, char *err);
 
+/* ---- the sliding-window growth-rate estimators Tools/Rt_ExpFitLogLinReg.m, Rt_ExpFitGenRatios.m, Rt_ExpFitNonlinLS.m ----
+ * Any subset of the three over R series of L days in ONE call.  Input new_cases [L][R] (day-major, region-minor: the
+ * new_smoothed layout of epi_preprocess_device).  Every output is [L][R]; NULL = not wanted.  Days mm are 1-based below.
+ * Windows: causal n = -wlen+1 .. 0, mm = wlen .. L;  centred h = floor(wlen/2), n = -h .. h (2h + 1 samples, wlen + 1 for an
+ * even wlen), mm = h+1 .. L-h.
+ *   LogLinReg (bit 0): seg = log(window); En = mean(n), En2 = mean(n.^2), Det = En2 - En^2 (means: sequential sum / count);
+ *     ALog = (mean(seg) En2 - mean(n.*seg) En) / Det, r = (mean(n.*seg) - mean(seg) En) / Det, 0 outside the windows;
+ *     Rt = exp(r), A = exp(ALog), Lambda = r / time_unit, ExpFit = A .* Rt.  log(0) = -Inf and NaN propagate.
+ *   GenRatios (bit 1): Lambda = [zeros(1,gp), log(x(1+gp:L) ./ x(1:L-gp))] / gp; LambdaSmoothed = filter(ones(1,wlen), wlen,
+ *     Lambda) in the operation order of preprocessing's moving average; Rt = exp(Lambda time_unit), RtSmoothed = exp(
+ *     LambdaSmoothed time_unit).  `causal` does not apply.
+ *   NonlinLS (bit 2): A starts as filter([zeros(1,wlen-1),1], 1, x) (causal: 0 before day wlen) or x (centred), r as 0.  A
+ *     window with fewer than wlen samples ~= 0 (NaN counts as non-zero) keeps A(mm) = x(mm), r(mm) = 0 (status SKIPPED);
+ *     every other window is fitted with nlinfit's Levenberg-Marquardt (y = A exp(lambda t), t = n / time_unit, start
+ *     [x(mm), 0], TolX = TolFun = 1e-6, MaxIter 250; NaN samples dropped; our reading in DESIGN.md §4.4).  Where MATLAB
+ *     raises an error (the model is Inf / NaN, fewer than 2 samples left) the window's status is MODEL_ERROR and A = r = NaN.
+ *     Rt = exp(r), Lambda = r / time_unit, ExpFit = A .* Rt; status / iters [L][R] int32 (iters = LM iterations run).
+ * log and exp are evaluated in a fixed operation order (epi_log / epi_exp) that tests/rt_window_ref.c shares: results are
+ * reproducible bit for bit.  epi_rtwin_run_device takes DEVICE pointers and enqueues on `stream` (no host synchronisation);
+ * epi_rtwin_run_host takes HOST pointers and runs on a pooled context of `device`. */
+enum { EPI_RTWIN_LOGLINREG = 1, EPI_RTWIN_GENRATIOS = 2, EPI_RTWIN_NONLINLS = 4 };
+enum {
+    EPI_RTWIN_OUTSIDE = 0,       /* day outside the window range: the initial A and r */
+    EPI_RTWIN_TOLX = 1,          /* converged: norm(step) < TolX (sqrt(eps) + norm(beta)) */
+    EPI_RTWIN_TOLFUN = 2,        /* converged: |sse - sseold| <= TolFun sse */
+    EPI_RTWIN_MAXITER = 3,       /* 250 iterations reached */
+    EPI_RTWIN_STALL = 4,         /* lambda passed 1e16 without an SSE that does not increase */
+    EPI_RTWIN_SKIPPED = 5,       /* fewer than wlen non-zero samples: A = x(mm), r = 0 */
+    EPI_RTWIN_MODEL_ERROR = 6    /* MATLAB's error (model Inf / NaN, too few samples): A = r = NaN */
+};
+typedef struct epi_rtwin_desc {
+    int32_t abi_version;
+    int32_t R;                   /* series (regions), >= 1 */
+    int32_t L;                   /* days, >= 1 */
+    int32_t wlen;                /* window length, 2 .. 31 (else EPI_ERR_UNSUPPORTED) */
+    int32_t causal;              /* 1 causal, 0 centred (LogLinReg, NonlinLS) */
+    int32_t generation_period;   /* GenRatios: 1 .. L */
+    int32_t methods;             /* EPI_RTWIN_* bits, != 0 */
+    double time_unit;
+} epi_rtwin_desc;
+typedef struct epi_rtwin_outputs {
+    double *llr_Rt, *llr_A, *llr_Lambda, *llr_ExpFit;                        /* LogLinReg */
+    double *gr_Rt, *gr_Lambda, *gr_RtSmoothed, *gr_LambdaSmoothed;           /* GenRatios */
+    double *nls_Rt, *nls_A, *nls_Lambda, *nls_ExpFit;                        /* NonlinLS */
+    int32_t *nls_status, *nls_iters;
+} epi_rtwin_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor or a NULL descriptor / new_cases / outputs, EPI_ERR_UNSUPPORTED for wlen
+ * outside 2 .. 31 */
+int epi_rtwin_validate(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, char *err);
+int epi_rtwin_run_device(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, void *stream, char *err);
+int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)
