@@ -445,9 +445,13 @@ __global__ __launch_bounds__(kWave) void eks_bwd_lane6(const KArgs a, const int 
 #pragma unroll
             for (int e = 0; e < NS; e++) X[e] = lw_ld<BLK>(rX, ll.v21, d1.o21, e);
         }
-        if (XD) {              // the image the previous step (or the prologue) requested.  It HAS landed: at least 99 vector-memory operations (this
-            // step's 21 loads of P(k|k), the 78 stores of the previous step's results) were issued behind its DMA, a wave has at most 64 in
-            // flight and they complete in order -- and the step loop ends with a full wait for the small inputs requested before it
+        if (XD) {              // the image the previous step (or the prologue) requested.  64 + n_npi vector-memory operations were issued behind its
+            // DMA (this step's 21 loads of P(k|k), then the previous step's 1 + 6 + 36 + n_npi stores: rank word, S_SMOOTH, P_SMOOTH,
+            // u_opt_smooth -- or the same stores at the end of an addressing window), at least 65 at n_npi = 1, and they complete in order:
+            // vmcnt(63) (0xCF7F: bits 15:14 carry the count's top two bits, expcnt and lgkmcnt untouched) therefore cannot pass before the
+            // DMA has landed.  The wait is explicit because nothing tells the compiler that the DMA (its LDS address is an integer) writes
+            // s_xd, so without it the image's ds_reads could be scheduled ahead of those operations (the prologue waits with vmcnt(0))
+            __builtin_amdgcn_s_waitcnt(0xCF7F);
 #pragma unroll
             for (int e = 0; e < NS; e++) X[e] = s_xd[e * BLK + lane];
         }

@@ -153,6 +153,19 @@ def with_time_varying_q(w, seed=0):
     return w2
 
 
+def with_npis(w, n):
+    """Copy of Workload `w` with its first `n` NPIs only: u [T][n][Su] (contiguous), and the per-NPI parameter rows a, u_min,
+    u_max and w zeroed beyond `n` (the padding the library expects of an n_npi < 12 batch)."""
+    import copy
+    w2 = copy.copy(w)
+    w2.n_npi = int(n)
+    w2.u = np.ascontiguousarray(w.u[:, :n, :])
+    w2.prm = w.prm.copy()
+    for f in (L.PRM_A, L.PRM_U_MIN, L.PRM_U_MAX, L.PRM_W_EFF):
+        w2.prm[f + n:f + 12] = 0.0
+    return w2
+
+
 def make_regression_problem(S=40, D=120, n=12, seed=0):
     """Regression windows like TrainPredictPrescribeNPI.m:251-253: X = NPI_MAXES - InterventionPlans (small integers,
     step-like in time, some NPIs never changed => constant / collinear columns, some always at the maximum => zero

@@ -54,9 +54,7 @@ def build(draw):
     # fewer NPIs
     n = draw(st.sampled_from([12, 12, 7, 1]))
     if n < 12:
-        w.n_npi = n; w.u = np.ascontiguousarray(w.u[:, :n, :])
-        for f in (L_.PRM_A, L_.PRM_U_MIN, L_.PRM_U_MAX, L_.PRM_W_EFF):
-            w.prm[f + n:f + 12] = 0.0
+        w = H.with_npis(w, n)
     # noise handling: adaptive scalar R vs per-day R (generic models only); fading memory
     w.prm = w.prm.copy()
     w.prm[L_.PRM_BETA_EKF] = draw(st.sampled_from([1.0, 0.9, 0.5]))
