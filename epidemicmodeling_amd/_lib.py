@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "epi_sir_sim_device", "epi_sir_sim_host",
     "epi_lookahead_validate", "epi_lookahead_workspace_bytes", "epi_lookahead_run_device", "epi_lookahead_run_host",
     "epi_rtwin_validate", "epi_rtwin_run_device", "epi_rtwin_run_host",
+    "epi_lasso_validate", "epi_lasso_run_device", "epi_lasso_run_host",
 ]
 
 
@@ -145,6 +146,37 @@ RTWIN_STATUS = {"outside": 0, "tolx": 1, "tolfun": 2, "maxiter": 3, "stall": 4, 
 
 class RtwinOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in RTWIN_OUT_NAMES]
+
+
+class LassoDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "D", "n", "K", "num_lambda")] + \
+        [("lambda_ratio", C.c_double), ("rel_tol", C.c_double), ("max_iter", C.c_int32)]
+
+
+LASSO_OUT_NAMES = ("a", "b", "lambda", "B", "intercept", "df", "mse", "se", "iters", "idx_min_mse", "idx_1se", "status")
+LASSO_OUT_I32 = ("df", "iters", "idx_min_mse", "idx_1se", "status")
+LASSO_STATUS = {"ok": 0, "null_model": 1, "maxiter": 2, "nonfinite": 3, "bad_folds": 4}
+
+
+class LassoOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LASSO_OUT_NAMES]
+
+
+def lasso_shapes(R, D, n, K, num_lambda):
+    """shape of every output of epi_lasso_run_* (mse, se, a, b and the indices only with K >= 2)"""
+    NL = int(num_lambda)
+    sh = {"lambda": (NL, R), "B": (NL, n, R), "intercept": (NL, R), "df": (NL, R), "iters": (NL, R), "status": (R,)}
+    if K >= 2:
+        sh.update(a=(n, R), b=(R,), mse=(NL, R), se=(NL, R), idx_min_mse=(R,), idx_1se=(R,))
+    return sh
+
+
+def make_lasso_desc(R, D, n, K, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4, max_iter=100000) -> LassoDesc:
+    d = LassoDesc()
+    d.abi_version = ABI_VERSION
+    d.R, d.D, d.n, d.K, d.num_lambda = int(R), int(D), int(n), int(K), int(num_lambda)
+    d.lambda_ratio, d.rel_tol, d.max_iter = float(lambda_ratio), float(rel_tol), int(max_iter)
+    return d
 
 
 class NnlsDesc(C.Structure):
@@ -278,6 +310,13 @@ def lib():
         h.epi_rtwin_run_device.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_void_p, C.c_char_p]
         h.epi_rtwin_run_host.restype = C.c_int
         h.epi_rtwin_run_host.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_int, C.c_char_p]
+        lasso_args = [C.POINTER(LassoDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LassoOutputs)]
+        h.epi_lasso_validate.restype = C.c_int
+        h.epi_lasso_validate.argtypes = lasso_args + [C.c_char_p]
+        h.epi_lasso_run_device.restype = C.c_int
+        h.epi_lasso_run_device.argtypes = lasso_args + [C.c_void_p, C.c_char_p]
+        h.epi_lasso_run_host.restype = C.c_int
+        h.epi_lasso_run_host.argtypes = lasso_args + [C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h

@@ -777,3 +777,67 @@ def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, 
     rc = _lib.lib().epi_rtwin_run_device(C.byref(d), _ptr(x), C.byref(outs), C.c_void_p(st.cuda_stream), err)
     _lib.check(rc, err)
     return out
+
+
+def lasso_folds(D, K, R, seed=0):
+    """A cross-validation partition for lasso_cv: fold [D, R] int32 in 0 .. K-1.  Every region gets its own random
+    permutation of the D days (np.random.default_rng(seed), regions in order); the fold sizes are those of cvpartition's
+    KFold: the first D mod K folds get ceil(D / K) days, the rest floor(D / K).  Deterministic for a given seed."""
+    D, K, R = int(D), int(K), int(R)
+    if not 2 <= K <= D:
+        raise ValueError("lasso_folds needs 2 <= K <= D")
+    rng = np.random.default_rng(seed)
+    sizes = np.full(K, D // K)
+    sizes[:D % K] += 1
+    label = np.repeat(np.arange(K, dtype=np.int32), sizes)
+    fold = np.empty((D, R), dtype=np.int32)
+    for r in range(R):
+        fold[rng.permutation(D), r] = label
+    return fold
+
+
+def check_lasso_folds(fold, K):
+    """ValueError unless fold [D, R] holds only 0 .. K-1 and leaves no fold empty in any region"""
+    f = np.asarray(fold)
+    if f.ndim != 2 or f.min() < 0 or f.max() >= K:
+        raise ValueError("folds must be [D, R] with values in 0 .. K-1")
+    for r in range(f.shape[1]):
+        if np.bincount(f[:, r], minlength=K).min() == 0:
+            raise ValueError(f"region {r}: a fold is empty")
+
+
+def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4, max_iter=100000,
+             device="cuda:0"):
+    """REGRESSION_TYPE = 'LASSO' for every region in one device call (epi_lasso_run_device): lasso(X, y, 'CV', K) with
+    MATLAB's defaults, our reading in DESIGN.md §4.5.  X [D, n, R] = NPI_MAXES - InterventionPlans over the regression window,
+    y [D, R].  folds [D, R] int32 in 0 .. K-1 (default lasso_folds(D, K, R, seed)); K = 0 runs the path only.
+    Returns a dict of torch tensors: lambda, intercept, df, iters [NL, R] (ascending lambda), B [NL, n, R], status [R] and,
+    with K >= 2, mse, se [NL, R], idx_min_mse, idx_1se [R] (0-based), a [n, R] = B at idx_min_mse, b [R] its intercept.
+    Enqueued on the current stream without a host synchronisation (a folds tensor already on the device is not checked
+    here: a bad partition gives its regions status bad_folds)."""
+    dev = torch.device(device)
+    t = lambda v: v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)
+    X, y = t(X).to(dev, torch.float64).contiguous(), t(y).to(dev, torch.float64).contiguous()
+    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    K = int(K)
+    f = None
+    if K >= 2:
+        if folds is None:
+            folds = lasso_folds(D, K, R, seed)
+        if not isinstance(folds, torch.Tensor):
+            check_lasso_folds(folds, K)
+            folds = torch.as_tensor(np.ascontiguousarray(folds, dtype=np.int32))
+        f = folds.to(dev, torch.int32).contiguous()
+    d = _lib.make_lasso_desc(R, D, n, K, num_lambda, lambda_ratio, rel_tol, max_iter)
+    out = {k: torch.empty(sh, dtype=torch.int32 if k in _lib.LASSO_OUT_I32 else torch.float64, device=dev)
+           for k, sh in _lib.lasso_shapes(R, D, n, K, num_lambda).items()}
+    outs = _lib.LassoOutputs()
+    for k in _lib.LASSO_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_lasso_run_device(C.byref(d), _ptr(X), _ptr(y), _ptr(f), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out

@@ -832,6 +832,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "nnls.hpp"
 #include "lookahead.hpp"
 #include "rt_window.hpp"
+#include "lasso.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3578,4 +3579,110 @@ int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const e
     return rc;
 }
 
+// ---- REGRESSION_TYPE = 'LASSO': lasso(X, y, 'CV', K) per region (TrainPredictPrescribeNPI.m:254-290) ----
+int epi_lasso_validate(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                       const epi_lasso_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 2) { set_err(err, "D must be >= 2"); return EPI_ERR_BAD_ARG; }
+    if (d->n < 1) { set_err(err, "n must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->num_lambda < 1) { set_err(err, "num_lambda must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->K < 0 || d->K == 1) { set_err(err, "K must be 0 (path only) or >= 2"); return EPI_ERR_BAD_ARG; }
+    if (d->K > d->D) { set_err(err, "K must not exceed D (every fold needs a day)"); return EPI_ERR_BAD_ARG; }
+    if (!(d->lambda_ratio > 0.0 && d->lambda_ratio < 1.0)) { set_err(err, "lambda_ratio must lie in (0, 1)"); return EPI_ERR_BAD_ARG; }
+    if (!(d->rel_tol > 0.0 && d->rel_tol <= 1.7976931348623157e308)) { set_err(err, "rel_tol must be > 0 and finite"); return EPI_ERR_BAD_ARG; }
+    if (d->max_iter < 1) { set_err(err, "max_iter must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D * d->n > (int64_t)0x7fffffff) { set_err(err, "R * D * n is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (!X || !y || !out) { set_err(err, "NULL X / y / outputs"); return EPI_ERR_BAD_ARG; }
+    if (d->K >= 2 && !fold) { set_err(err, "NULL fold (K >= 2)"); return EPI_ERR_BAD_ARG; }
+    if (!out->status) { set_err(err, "NULL status output"); return EPI_ERR_BAD_ARG; }
+    if (d->K >= 2 && (!out->a || !out->b)) { set_err(err, "NULL a / b output (K >= 2)"); return EPI_ERR_BAD_ARG; }
+    if (d->n > kLsMaxN) { set_err(err, "n is limited to 12"); return EPI_ERR_UNSUPPORTED; }
+    if (d->D > kLsMaxD) { set_err(err, "D is limited to 256 (a region's window and residuals are held in LDS)"); return EPI_ERR_UNSUPPORTED; }
+    if (d->K > kLsMaxK) { set_err(err, "K is limited to 63 (the folds and the full fit share one wavefront)"); return EPI_ERR_UNSUPPORTED; }
+    if (d->num_lambda > kLsMaxNL) { set_err(err, "num_lambda is limited to 100"); return EPI_ERR_UNSUPPORTED; }
+    return EPI_OK;
+}
+
+int epi_lasso_run_device(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                         const epi_lasso_outputs *out, void *stream, char *err)
+{
+    int rc = epi_lasso_validate(d, X, y, fold, out, err);
+    if (rc != EPI_OK) return rc;
+    LsArgs g{};
+    g.R = d->R; g.D = d->D; g.n = d->n; g.K = d->K; g.NL = d->num_lambda; g.max_iter = d->max_iter;
+    g.ratio = d->lambda_ratio; g.rel_tol = d->rel_tol;
+    g.X = X; g.y = y; g.fold = fold;
+    g.a = out->a; g.b = out->b; g.lambda = out->lambda; g.B = out->B; g.intercept = out->intercept; g.mse = out->mse; g.se = out->se;
+    g.df = out->df; g.iters = out->iters; g.idx_min = out->idx_min_mse; g.idx_1se = out->idx_1se; g.status = out->status;
+    const size_t shmem = lasso_lds_bytes(d->D, d->n, d->num_lambda);
+    hipError_t e = hipFuncSetAttribute((const void *)lasso_cv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return hip_fail(err, e, "hipFuncSetAttribute");
+    hipLaunchKernelGGL(lasso_cv, dim3((unsigned)d->R), dim3(64), shmem, (hipStream_t)stream, g);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lasso_cv launch");
+    return EPI_OK;
+}
+
+int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                       const epi_lasso_outputs *out, int device, char *err)
+{
+    int rc = epi_lasso_validate(d, X, y, fold, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, D = (size_t)d->D, n = (size_t)d->n, NL = (size_t)d->num_lambda;
+    if (d->K >= 2) {                     // the partition is on the host here: an argument error, not a region status
+        std::vector<int> cnt((size_t)d->K);
+        for (size_t r = 0; r < R; r++) {
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (size_t i = 0; i < D; i++) {
+                const int32_t f = fold[i * R + r];
+                if (f < 0 || f >= d->K) { set_err(err, "fold value outside 0 .. K-1"); return EPI_ERR_BAD_ARG; }
+                cnt[(size_t)f]++;
+            }
+            for (int f = 0; f < d->K; f++)
+                if (cnt[(size_t)f] == 0) { set_err(err, "empty fold"); return EPI_ERR_BAD_ARG; }
+        }
+    }
+    HostIO io;
+    const size_t o_X = io.add_in(X, D * n, 8, R, 0, R), o_y = io.add_in(y, D, 8, R, 0, R);
+    const size_t o_f = d->K >= 2 ? io.add_in(fold, D, 4, R, 0, R) : (size_t)-1;
+    double *const *f64[7] = {&out->a, &out->b, &out->lambda, &out->B, &out->intercept, &out->mse, &out->se};
+    const size_t f64_rows[7] = {n, 1, NL, NL * n, NL, NL, NL};
+    int32_t *const *i32[5] = {&out->df, &out->iters, &out->idx_min_mse, &out->idx_1se, &out->status};
+    const size_t i32_rows[5] = {NL, NL, 1, 1, 1};
+    size_t o_d[7], o_i[5];
+    for (int k = 0; k < 7; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], f64_rows[k], 8, R, 0, R) : (size_t)-1;
+    for (int k = 0; k < 5; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], i32_rows[k], 4, R, 0, R) : (size_t)-1;
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        epi_lasso_outputs dout{};
+        double **df[7] = {&dout.a, &dout.b, &dout.lambda, &dout.B, &dout.intercept, &dout.mse, &dout.se};
+        int32_t **di[5] = {&dout.df, &dout.iters, &dout.idx_min_mse, &dout.idx_1se, &dout.status};
+        for (int k = 0; k < 7; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
+        for (int k = 0; k < 5; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
+        const int r = epi_lasso_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y),
+                                           o_f == (size_t)-1 ? nullptr : (const int32_t *)(base + o_f), &dout, cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
 }  // extern "C"
+

@@ -155,3 +155,30 @@ def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, 
     rc = _lib.lib().epi_rtwin_run_host(C.byref(d), _f(x, keep), C.byref(outs), int(device), err)
     _lib.check(rc, err)
     return out
+
+
+def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4, max_iter=100000, device=0):
+    """epi_lasso_run_host: lasso(X, y, 'CV', K) for every region (NumPy in and out, synchronous).  X [D, n, R], y [D, R],
+    folds [D, R] (default batch.lasso_folds(D, K, R, seed)).  Returns the dict of batch.lasso_cv as NumPy arrays."""
+    from .batch import lasso_folds
+    keep = []
+    X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if X.ndim != 3 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    K = int(K)
+    f = None
+    if K >= 2:
+        f = np.ascontiguousarray(lasso_folds(D, K, R, seed) if folds is None else folds, dtype=np.int32)
+        keep.append(f)
+    d = _lib.make_lasso_desc(R, D, n, K, num_lambda, lambda_ratio, rel_tol, max_iter)
+    out = {k: np.empty(sh, dtype=np.int32 if k in _lib.LASSO_OUT_I32 else np.float64)
+           for k, sh in _lib.lasso_shapes(R, D, n, K, num_lambda).items()}
+    outs = _lib.LassoOutputs()
+    for k in _lib.LASSO_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_lasso_run_host(C.byref(d), _f(X, keep), _f(y, keep), None if f is None else f.ctypes.data,
+                                       C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out

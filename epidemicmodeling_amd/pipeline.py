@@ -116,9 +116,27 @@ def _alpha_smooth(w, device):
     return r.out["S_SMOOTH"].cpu().numpy()                 # [T, 3, S]
 
 
-def _front_half(cases, deaths, N, ip, num_regression_days, W, device):
-    """Preprocessing, EKF round 1, NNLS, round 2, NNLS (TrainPredictPrescribeNPI.m:142-330, ForecastQualityAssessment.m:
-    160-356) over the days given.  Returns pre, alpha_round1, fit1, alpha_round2, fit2, X_reg."""
+REGRESSIONS = ("nonnegls", "lasso")
+
+
+def _regress(X, y, regression, cv_folds, cv_seed, device):
+    """One regression between the EKF rounds (TrainPredictPrescribeNPI.m:251-290): 'nonnegls' = lsqnonneg + the intercept
+    loop (batch.nnls_affine_fit), 'lasso' = lasso(X, y, 'CV', cv_folds) with folds from cv_seed (batch.lasso_cv; a, b at
+    IndexMinMSE, and the path's lambda, mse, se, idx_min_mse, idx_1se, status ... alongside)."""
+    if regression == "nonnegls":
+        res = batch.nnls_affine_fit(X, y, device=device)
+    else:
+        res = batch.lasso_cv(X, y, K=cv_folds, seed=cv_seed, device=device)
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression="nonnegls", cv_folds=50, cv_seed=0):
+    """Preprocessing, EKF round 1, regression, round 2, regression (TrainPredictPrescribeNPI.m:142-330,
+    ForecastQualityAssessment.m:160-356) over the days given.  regression selects REGRESSION_TYPE: "nonnegls" (the
+    default) or "lasso"; with "lasso" round 1 draws its folds from cv_seed and round 2 from cv_seed + 1 (the reference
+    draws a fresh partition per lasso call).  Returns pre, alpha_round1, fit1, alpha_round2, fit2, X_reg."""
+    if regression not in REGRESSIONS:
+        raise ValueError(f"regression must be one of {REGRESSIONS}")
     T, S = cases.shape
     n = ip.shape[1]
     u_max = synth.IP_MAXES[:n]
@@ -131,24 +149,26 @@ def _front_half(cases, deaths, N, ip, num_regression_days, W, device):
     S1 = _alpha_smooth(workload3(x, R, np.zeros_like(u), N, I0, np.zeros((n, S)), np.zeros(S)), device)
     D = min(num_regression_days, T)
     X = np.ascontiguousarray(u_max[None, :, None] - u[T - D:])
-    fit1 = {k: v.cpu().numpy() for k, v in batch.nnls_affine_fit(X, np.ascontiguousarray(S1[T - D:, 2]), device=device).items()}
+    fit1 = _regress(X, np.ascontiguousarray(S1[T - D:, 2]), regression, cv_folds, cv_seed, device)
     # round 2: real inputs -> refined alpha -> second regression
     S2 = _alpha_smooth(workload3(x, R, u, N, I0, fit1["a"], fit1["b"]), device)
-    fit2 = {k: v.cpu().numpy() for k, v in batch.nnls_affine_fit(X, np.ascontiguousarray(S2[T - D:, 2]), device=device).items()}
+    fit2 = _regress(X, np.ascontiguousarray(S2[T - D:, 2]), regression, cv_folds, cv_seed + 1, device)
     out.update(alpha_round1=S1[:, 2], fit1=fit1, alpha_round2=S2[:, 2], fit2=fit2, X_reg=X)
     return out
 
 
 def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regression_days=60, npi_weights=None,
-              W=7, device="cuda:0"):
+              W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0):
     """Run the chain above.  cases/deaths [T,S] cumulative counts (NaN = missing), population [S], ip [T,n,S] (NaN = N/A).
+    regression = "nonnegls" (REGRESSION_TYPE 'NONNEGATIVELS', the default) or "lasso" ('LASSO': lasso(X, y, 'CV', cv_folds),
+    folds drawn from cv_seed in round 1 and cv_seed + 1 in round 2; the coefficients may be negative).
     Returns a dict with every intermediate and `prescription` [horizon, n, S]: the smoothed optimal plan of each region's
     Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps]."""
     T, S = cases.shape
     n = ip.shape[1]
     N = np.asarray(population, dtype=np.float64)
     u_max = synth.IP_MAXES[:n]
-    out = _front_half(cases, deaths, N, ip, num_regression_days, W, device)
+    out = _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression, cv_folds, cv_seed)
     pre, fit2, X = out["pre"], out["fit2"], out["X_reg"]
     x, R, u, I0 = pre["x_new"], pre["R_v"], pre["ip_filled"], pre["I0"]
     # forecast set-up (:333-341): R_v padded with its mean, observations and (for the sweep) controls NaN over the horizon
@@ -194,7 +214,7 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
 
 
 def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_lookahead=60, num_regression_days=60, W=7,
-                     device="cuda:0", chains=False, shape=0):
+                     device="cuda:0", chains=False, shape=0, regression="nonnegls", cv_folds=50, cv_seed=0):
     """The forecast look-ahead error study of Tools/ForecastQualityAssessment.m for ALL regions in one device call.
 
     cases / deaths [LL, S] cumulative counts (NaN = missing), population [S], ip [LL, n, S] (NaN = N/A) over the WHOLE window;
@@ -203,7 +223,8 @@ def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_looka
     `_ENTIRE` quantities (:102-132): new_smoothed = NewCasesSmoothed_ENTIRE (the truth), x_new the observations, ip_filled the
     controls.  R_v of the training window is padded with its mean (:362).  Then every region is filtered once per start
     s = 1 .. num_forecast_days with its last s observations hidden (:380-393) and the error tables and their statistics over
-    the starts max_lookahead .. num_forecast_days (:428-449) are computed (batch.lookahead).
+    the starts max_lookahead .. num_forecast_days (:428-449) are computed (batch.lookahead).  regression, cv_folds and
+    cv_seed select REGRESSION_TYPE as in prescribe().
     Returns a dict: the front half's intermediates (pre, alpha_round1, fit1, alpha_round2, fit2, X_reg), pre_entire, R_full,
     workload (the per-region synth.Workload of the study), truth, and est_plus / est_smooth [F, M, S],
     mean / median / std_{plus,smooth} [M, S] (+ S_PLUS / S_SMOOTH / status of every chain with chains=True)."""
@@ -213,7 +234,8 @@ def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_looka
     if F < 1 or T < 2:
         raise ValueError("num_forecast_days must be >= 1 and leave a training window of at least 2 days")
     N = np.asarray(population, dtype=np.float64)
-    out = _front_half(cases[:T], None if deaths is None else deaths[:T], N, ip[:T], num_regression_days, W, device)
+    out = _front_half(cases[:T], None if deaths is None else deaths[:T], N, ip[:T], num_regression_days, W, device,
+                      regression, cv_folds, cv_seed)
     fit2, I0, R = out["fit2"], out["pre"]["I0"], out["pre"]["R_v"]
     ent = {k: v.cpu().numpy() for k, v in batch.preprocess(cases, N, deaths, ip, W=W, min_cases=synth.MIN_CASES,
                                                             first_num_days=7, device=device).items()}

@@ -2,6 +2,7 @@
 of the file at once (epidemicmodeling_amd/pipeline.py).
 
     python examples/prescribe_from_csv.py OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 30 out.csv
+    python examples/prescribe_from_csv.py --regression lasso ...     # REGRESSION_TYPE 'LASSO' (lasso with 50-fold CV)
 
 Without arguments a small synthetic tracker file is generated first (there is no data set in this repository)."""
 import os
@@ -31,8 +32,14 @@ def synthetic_files(tmp, S=8, T=200):
 
 
 def main():
-    if len(sys.argv) >= 7:
-        data, pops, start, end, horizon, dst = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5]), sys.argv[6]
+    argv = list(sys.argv)
+    regression = "nonnegls"
+    if "--regression" in argv:
+        i = argv.index("--regression")
+        regression = argv[i + 1]
+        del argv[i:i + 2]
+    if len(argv) >= 7:
+        data, pops, start, end, horizon, dst = argv[1], argv[2], argv[3], argv[4], int(argv[5]), argv[6]
     else:
         tmp = tempfile.mkdtemp()
         data, pops, start, end = synthetic_files(tmp)
@@ -40,11 +47,12 @@ def main():
     d = dataio.read_oxcgrt(data, start, end)
     N = dataio.read_populations(pops, d["geo_ids"])
     keep = np.flatnonzero(np.isfinite(N) & np.isfinite(d["cases"]).any(axis=0))
-    out = pipeline.prescribe(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon=horizon, n_eps=50)
+    out = pipeline.prescribe(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon=horizon, n_eps=50,
+                             regression=regression)
     last = pd.Timestamp(str(d["dates"][-1]))
     days = [int((last + pd.Timedelta(days=k + 1)).strftime("%Y%m%d")) for k in range(horizon)]
     dataio.write_prescriptions(dst, out["prescription"][None], [d["countries"][k] for k in keep], [d["regions"][k] for k in keep], days)
-    print(f"{len(keep)} regions x {horizon} days -> {dst}")
+    print(f"{len(keep)} regions x {horizon} days -> {dst} (regression: {regression})")
     print("Pareto optimum per region (index into the cost-weight grid):", out["i_opt"].tolist())
 
 

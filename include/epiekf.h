@@ -528,6 +528,57 @@ int epi_rtwin_validate(const epi_rtwin_desc *d, const double *new_cases, const e
 int epi_rtwin_run_device(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, void *stream, char *err);
 int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const epi_rtwin_outputs *out, int device, char *err);
 
+/* ---- REGRESSION_TYPE = 'LASSO' between the EKF rounds: [B, FitInfo] = lasso(X, y, 'CV', K), a = B(:, IndexMinMSE),
+ * b = FitInfo.Intercept(IndexMinMSE) (TrainPredictPrescribeNPI.m:254-290, ForecastQualityAssessment.m:256-292) ----
+ * For each of R regions: X [D][n][R] (= NPI_MAXES - InterventionPlans over the regression window, the layout of
+ * epi_nnls_affine_fit_device), y [D][R], fold [D][R] int32 in 0 .. K-1 (the cross-validation partition, given by the
+ * caller; may be NULL when K = 0).  Alpha = 1, Standardize = true, DFmax = Inf, no weights.  Our reading of lasso, point
+ * by point and in the operation order the kernel and tests/lasso_ref.c share bit for bit, is DESIGN.md §4.5.
+ * Outputs (NULL = not wanted, except status; a and b are required when K >= 2); lambda index k is ASCENDING (MATLAB's
+ * order), indices are 0-based:
+ *   lambda [NL][R], B [NL][n][R] (original scale), intercept [NL][R], df [NL][R] (non-zero B), iters [NL][R] (coordinate
+ *   cycles of the full fit), mse / se [NL][R] (K >= 2), idx_min_mse / idx_1se [R], a [n][R], b [R], status [R].
+ * A region whose X or y holds a non-finite value gets status NONFINITE, NaN outputs, df = iters = 0 and indices -1; so does
+ * a region whose fold holds a value outside 0 .. K-1 or leaves a fold empty (BAD_FOLDS: epi_lasso_run_device cannot read
+ * the partition without a host synchronisation; epi_lasso_run_host checks it first and returns EPI_ERR_BAD_ARG).
+ * epi_lasso_run_device takes DEVICE pointers and enqueues one wavefront per region on `stream` (no host synchronisation);
+ * epi_lasso_run_host takes HOST pointers and runs on a pooled context of `device`. */
+enum {
+    EPI_LASSO_OK = 0,
+    EPI_LASSO_NULL_MODEL = 1,    /* lambdaMax = 0 (every column constant, or y constant): Lambda = 0, B = 0, Intercept = mean(y) */
+    EPI_LASSO_MAXITER = 2,       /* some fit reached max_iter cycles at some lambda: its last iterate is kept */
+    EPI_LASSO_NONFINITE = 3,     /* X or y holds Inf / NaN: NaN outputs */
+    EPI_LASSO_BAD_FOLDS = 4      /* fold value outside 0 .. K-1, or an empty fold: NaN outputs */
+};
+typedef struct epi_lasso_desc {
+    int32_t abi_version;
+    int32_t R;                   /* regions, >= 1 */
+    int32_t D;                   /* days, 2 .. 256 (else EPI_ERR_UNSUPPORTED above 256) */
+    int32_t n;                   /* predictors (NPIs), 1 .. 12 */
+    int32_t K;                   /* folds: 0 = path only, or 2 .. min(D, 63) (EPI_ERR_UNSUPPORTED above 63) */
+    int32_t num_lambda;          /* NumLambda, 1 .. 100 (MATLAB's default 100) */
+    double lambda_ratio;         /* LambdaRatio, in (0, 1) (1e-4) */
+    double rel_tol;              /* RelTol, > 0 (1e-4) */
+    int32_t max_iter;            /* MaxIter per lambda, >= 1 (1e5) */
+} epi_lasso_desc;
+typedef struct epi_lasso_outputs {
+    double *a, *b;                          /* [n][R], [R]: the fit at IndexMinMSE */
+    double *lambda, *B, *intercept;         /* [NL][R], [NL][n][R], [NL][R] */
+    int32_t *df;                            /* [NL][R] */
+    double *mse, *se;                       /* [NL][R] */
+    int32_t *iters;                         /* [NL][R] */
+    int32_t *idx_min_mse, *idx_1se;         /* [R] */
+    int32_t *status;                        /* [R] EPI_LASSO_*, required */
+} epi_lasso_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor or a NULL descriptor / X / y / fold (K >= 2) / outputs / status /
+ * a / b (K >= 2), EPI_ERR_UNSUPPORTED for n > 12, D > 256, K > 63 or num_lambda > 100 */
+int epi_lasso_validate(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                       const epi_lasso_outputs *out, char *err);
+int epi_lasso_run_device(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                         const epi_lasso_outputs *out, void *stream, char *err);
+int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
+                       const epi_lasso_outputs *out, int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

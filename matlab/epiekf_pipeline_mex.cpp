@@ -20,11 +20,19 @@
 //   [a, b, min_err, iters] = epiekf_pipeline_mex('nnls', X, y, max_iters)
 //       :251-276 ('NONNEGATIVELS').  X  S x n x D = NPI_MAXES - InterventionPlans over the window;  y  S x D;  a  S x n;
 //       b, min_err, iters  S x 1.
+//   [a, b, lambda, mse, se, idx, idx1se, B, intercept, df] = epiekf_pipeline_mex('lasso', X, y, K, fold)
+//       :254-290 ('LASSO'): lasso(X, y, 'CV', K) per region with MATLAB's defaults, the partition given.
+//       X  R x n x D (as for 'nnls');  y  R x D;  fold  R x D with values 1 .. K (fold(r, t) = k: day t is in the test set
+//       of fold k; [] when K = 0: the path only).  a  R x n = B(:, IndexMinMSE);  b  R x 1 = Intercept(IndexMinMSE);
+//       lambda, mse, se, intercept, df  R x NumLambda (ascending lambda, MATLAB's order);  idx, idx1se  R x 1
+//       (IndexMinMSE, Index1SE, ONE-based);  B  R x n x NumLambda.  A region whose X / y holds Inf or NaN gets NaN outputs
+//       and idx = idx1se = 0; with K = 0, a, b, mse and se are NaN and idx = idx1se = 0.  (No lasso.m is shipped: it would shadow the Statistics Toolbox function.)
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
 // Build on a MATLAB host:  mex -I../include epiekf_pipeline_mex.cpp -L../epidemicmodeling_amd -lepiekf
 #include <string.h>
+#include <limits>
 #include <vector>
 #include "mex.h"
 #include "epiekf.h"
@@ -144,6 +152,56 @@ static void nnls(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void lasso(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('lasso', X, y, K, fold): 5 inputs expected");
+    if (mxGetNumberOfDimensions(prhs[1]) != 3) mexErrMsgTxt("X must be R x n x D");
+    const mwSize *dx = mxGetDimensions(prhs[1]);
+    const mwSize R = dx[0], n = dx[1], D = dx[2];
+    want(prhs[2], R, D, "y");
+    const int K = (int)mxGetScalar(prhs[3]);
+    std::vector<int32_t> fold;
+    if (K >= 2) {
+        want(prhs[4], R, D, "fold");
+        const double *f = mxGetPr(prhs[4]);
+        fold.resize((size_t)(R * D));
+        for (size_t k = 0; k < fold.size(); k++) fold[k] = (int32_t)f[k] - 1;       // MATLAB's 1 .. K -> 0 .. K-1
+    }
+    epi_lasso_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.R = (int32_t)R; d.D = (int32_t)D; d.n = (int32_t)n; d.K = K;
+    d.num_lambda = 100; d.lambda_ratio = 1e-4; d.rel_tol = 1e-4; d.max_iter = 100000;        // lasso's defaults
+    const mwSize NL = (mwSize)d.num_lambda;
+    const bool cv = K >= 2;
+    mxArray *a = mxCreateDoubleMatrix(R, n, mxREAL), *b = mxCreateDoubleMatrix(R, 1, mxREAL);
+    mxArray *lam = mxCreateDoubleMatrix(R, NL, mxREAL), *mse = mxCreateDoubleMatrix(R, NL, mxREAL), *se = mxCreateDoubleMatrix(R, NL, mxREAL);
+    mxArray *idx = mxCreateDoubleMatrix(R, 1, mxREAL), *idx1 = mxCreateDoubleMatrix(R, 1, mxREAL);
+    mxArray *B = dbl3(R, n, NL), *icpt = mxCreateDoubleMatrix(R, NL, mxREAL), *df = mxCreateDoubleMatrix(R, NL, mxREAL);
+    mxArray *o[10] = {a, b, lam, mse, se, idx, idx1, B, icpt, df};
+    std::vector<int32_t> dfv((size_t)(NL * R)), im((size_t)R), i1((size_t)R), st((size_t)R);
+    epi_lasso_outputs out;
+    memset(&out, 0, sizeof out);
+    out.lambda = mxGetPr(lam); out.B = mxGetPr(B); out.intercept = mxGetPr(icpt); out.df = dfv.data(); out.status = st.data();
+    if (cv) {
+        out.a = mxGetPr(a); out.b = mxGetPr(b); out.mse = mxGetPr(mse); out.se = mxGetPr(se);
+        out.idx_min_mse = im.data(); out.idx_1se = i1.data();
+    }
+    // the ABI's [NL][R] and [NL][n][R] are MATLAB's R x NL and R x n x NL: no transposition
+    char err[256] = {0};
+    const int rc = epi_lasso_run_host(&d, mxGetPr(prhs[1]), mxGetPr(prhs[2]), cv ? fold.data() : NULL, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < dfv.size(); k++) mxGetPr(df)[k] = (double)dfv[k];
+    if (!cv)                                                                        // no cross-validation: a, b, mse, se are NaN
+        for (mxArray *m : {a, b, mse, se})
+            for (size_t k = 0; k < mxGetNumberOfElements(m); k++) mxGetPr(m)[k] = std::numeric_limits<double>::quiet_NaN();
+    for (mwSize r = 0; r < R; r++) {
+        mxGetPr(idx)[r] = cv ? (double)(im[r] + 1) : 0.0;
+        mxGetPr(idx1)[r] = cv ? (double)(i1[r] + 1) : 0.0;
+    }
+    for (int k = 0; k < 10; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -179,6 +237,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     if (strcmp(cmd, "prescribe") == 0) prescribe(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "preprocess") == 0) preprocess(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "nnls") == 0) nnls(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
