@@ -363,3 +363,49 @@ def referee_compare(w, got, fx, what):
             fails.append((what, "u_opt_smooth", "more flips vs the exact plan than either frozen fp64 reading", sum(flips),
                           max(int(fx["flips_lap"].sum()), int(fx["flips_C"].sum()))))
     return fails, rep
+
+
+# ---------------------------------------------------------------- poisoned output arenas for optional-output tests
+class GuardArena:
+    """Every output of a call in ONE byte arena, each segment with `guard` bytes before and after it, all of it filled with
+    the byte POISON.  The caller passes ptr(name) for the outputs it requests and NULL for the rest; afterwards untouched(
+    requested) says whether every byte outside the requested segments (guards and unrequested neighbours) is still POISON.
+    specs: [(name, shape, numpy dtype)].  device: a torch device string for device memory, None for host memory."""
+    POISON = 0xA7
+
+    def __init__(self, specs, device=None, guard=256):
+        self.specs, self.device, self.seg = specs, device, {}
+        off = guard
+        for name, shape, dt in specs:
+            nb = int(np.prod(shape)) * np.dtype(dt).itemsize
+            self.seg[name] = (off, nb, tuple(shape), np.dtype(dt))
+            off += (nb + 255) // 256 * 256 + guard
+        if device is None:
+            self.buf = np.full(off, self.POISON, dtype=np.uint8)
+            self.base = self.buf.ctypes.data
+        else:
+            import torch
+            self.buf = torch.full((off,), self.POISON, dtype=torch.uint8, device=device)
+            self.base = self.buf.data_ptr()
+
+    def ptr(self, name):
+        return self.base + self.seg[name][0]
+
+    def _bytes(self):
+        if self.device is None:
+            return self.buf.copy()
+        import torch
+        torch.cuda.synchronize(self.device)
+        return self.buf.cpu().numpy()
+
+    def get(self, name):
+        off, nb, shape, dt = self.seg[name]
+        return self._bytes()[off:off + nb].view(dt).reshape(shape)
+
+    def untouched(self, requested):
+        b = self._bytes()
+        keep = np.ones(b.size, dtype=bool)
+        for name in requested:
+            off, nb, _, _ = self.seg[name]
+            keep[off:off + nb] = False
+        return bool((b[keep] == self.POISON).all())

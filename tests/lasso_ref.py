@@ -264,3 +264,80 @@ def np_lasso(X, y, fold, K, num_lambda, lambda_ratio, rel_tol, max_iter, exp, lo
         o["idx_1se"] = max(k for k in range(NL) if o["mse"][k] <= thr)
     o["status"] = ST_NULL_MODEL if null else ST_MAXITER if hit_any else ST_OK
     return o
+
+
+# ---- the CV half against scikit-learn (one region) -------------------------------------------------------------------
+def sklearn_cv(X, y, fold, K, lam, rel_tol, mu_floor=1e-3):
+    """Refit every fold of one region (X [D, n], y [D], fold [D]) at the lambdas `lam` with sklearn.linear_model.Lasso on
+    that fold's own standardization (training-set mean, population std, constant columns left out; alpha = lambda, no
+    intercept, tol 1e-13), and recompute the held-out MSE = sum of the folds' SSEs / D and SE = std(SSE_f / |f|, ddof=1) /
+    sqrt(K).  Returns mse, se and their gates (NaN where no gate can be derived) as arrays over `lam`.
+
+    Gate.  A fold fit that stopped by the RelTol rule has a KKT residual e with |e_j| <= RelTol sum_k |G_jk| (1 + |b_k|)
+    (1 + RelTol) (G = Xs' Xs / N on the training set; test_lasso_host.py::test_path_meets_the_kkt_conditions), so by strong
+    convexity it lies within ||e|| / mu_min of the optimum, mu_min the smallest eigenvalue of G over the non-constant columns
+    (required > mu_floor; b is taken at sklearn's point, which is the optimum to 1e-13).  A held-out prediction is
+    mean(y_train) + Xs_i b, so it moves by at most d_i = ||Xs_i|| ||e|| / mu_min, the fold's SSE by sum 2 |r_i| d_i + d_i^2
+    (r_i sklearn's residual), the MSE by the sum of those over D.  SE is sqrt(K - 1)^-1 sqrt(K)^-1 times a centred 2-norm,
+    which is 1-Lipschitz: it moves by at most ||(dSSE_f / |f|)_f|| / sqrt((K - 1) K).  Both gates get 1e-12 of their value
+    for rounding."""
+    from sklearn.linear_model import Lasso
+    X, y, fold = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64), np.asarray(fold)
+    D = len(y)
+    NL = len(lam)
+    sse, dsse, cnt = np.zeros((NL, K)), np.zeros((NL, K)), np.zeros(K)
+    for f in range(K):
+        tr, ho = fold != f, fold == f
+        cnt[f] = ho.sum()
+        Xt, yt = X[tr], y[tr]
+        N = tr.sum()
+        mu = Xt.sum(0) / N
+        cst = Xt.max(0) == Xt.min(0)
+        sig = np.sqrt(((Xt - mu) ** 2).sum(0) / N)
+        sig[cst] = 1.0
+        Xs = (Xt - mu) / sig
+        Xs[:, cst] = 0.0
+        Xh = (X[ho] - mu) / sig
+        Xh[:, cst] = 0.0
+        muY = yt.sum() / N
+        G = Xs.T @ Xs / N
+        nc = ~cst
+        mu_min = np.linalg.eigvalsh(G[np.ix_(nc, nc)]).min() if nc.any() else np.inf
+        for k in range(NL):
+            b = Lasso(alpha=lam[k], fit_intercept=False, tol=1e-13, max_iter=1_000_000).fit(Xs, yt - muY).coef_
+            r = y[ho] - (muY + Xh @ b)
+            sse[k, f] = (r ** 2).sum()
+            if mu_min > mu_floor:
+                e = rel_tol * np.abs(G) @ ((1 + np.abs(b)) * (1 + rel_tol))
+                d = np.linalg.norm(Xh, axis=1) * np.linalg.norm(e) / mu_min
+                dsse[k, f] = (2 * np.abs(r) * d + d * d).sum()
+            else:
+                dsse[k, f] = np.nan
+    mse = sse.sum(1) / D
+    msef = sse / cnt
+    se = msef.std(axis=1, ddof=1) / np.sqrt(K)
+    g_mse = dsse.sum(1) / D + 1e-12 * mse
+    g_se = np.linalg.norm(dsse / cnt, axis=1) / np.sqrt((K - 1) * K) + 1e-12 * se
+    return mse, se, g_mse, g_se
+
+
+def cv_indices_agree(mse, se, g_mse, g_se, idx_min, idx_1se, mse_sk, se_sk):
+    """idx_min_mse / idx_1se of a fit whose mse / se lie within the gates of sklearn_cv's: wherever sklearn's MSE margin
+    exceeds the gates the indices must be the ones sklearn's values give (ties to the smaller index, as lasso does).
+    Returns the number of indices that were decidable (and checked)."""
+    checked = 0
+    s_min = int(np.flatnonzero(mse_sk == mse_sk.min())[0])
+    if idx_min != s_min:           # only where the two minima are within the gates of each other
+        assert mse_sk[idx_min] - mse_sk[s_min] <= g_mse[idx_min] + g_mse[s_min], (idx_min, s_min)
+        return checked
+    others = np.arange(len(mse_sk)) != s_min
+    if (mse_sk[others] - mse_sk[s_min] > g_mse[others] + g_mse[s_min]).all():
+        checked += 1
+    thr, g_thr = mse_sk[s_min] + se_sk[s_min], g_mse[s_min] + g_se[s_min]
+    s_1se = int(np.flatnonzero(mse_sk <= thr).max())
+    if idx_1se != s_1se:
+        lo, hi = sorted((idx_1se, s_1se))
+        assert (np.abs(mse_sk[lo:hi + 1] - thr) <= g_mse[lo:hi + 1] + g_thr).any(), (idx_1se, s_1se)
+    elif (np.abs(mse_sk - thr) > g_mse + g_thr).all():
+        checked += 1
+    return checked

@@ -142,3 +142,14 @@ def matlab_loop(S_PLUS, S_SMOOTH, truth, population, F, M):
                 st["std_" + name] = (part.std(axis=0, ddof=1) if part.shape[0] > 1 else
                                      (np.zeros((M, R)) if part.shape[0] == 1 else np.full((M, R), np.nan)))
     return EP, ES, st
+
+
+def golden_workload(g):
+    """The per-region SIAlphaModelEKF Workload stored in tests/golden/aux_lookahead.npz (in_* arrays)."""
+    x = np.ascontiguousarray(g["in_x"])
+    return synth.Workload(model="SIAlphaModelEKF", T=x.shape[0], n_npi=g["in_u"].shape[1], x=x,
+                          u=np.ascontiguousarray(g["in_u"]), R_series=np.ascontiguousarray(g["in_R_series"]), R_scalar=None,
+                          x_series=None, u_series=None, prm=np.ascontiguousarray(g["in_prm"]),
+                          s_init=np.ascontiguousarray(g["in_s_init"]), Ps_init=np.ascontiguousarray(g["in_Ps_init"]),
+                          s_final=np.ascontiguousarray(g["in_s_final"]), Ps_final=np.ascontiguousarray(g["in_Ps_final"]),
+                          Q=np.ascontiguousarray(g["in_Q"]), L=int(g["in_L"]), order=int(g["in_order"]), obs_type="NEWCASES")

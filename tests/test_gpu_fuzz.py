@@ -1,6 +1,7 @@
 """Property-based parity: for randomly drawn problems -- model variant, sizes, missing observations, free controls,
 monitor length, adaptive or per-day R, end-point constraints, noise settings, output layout, chunking -- every output of
 the HIP path equals the CPU oracle bit for bit (NaN patterns included) and the pinv truncation ranks are identical."""
+import itertools
 import os
 
 import numpy as np
@@ -405,3 +406,131 @@ def test_random_tools_calls_match_the_oracle(gpu_device, data):
     assert len(got) == len(names)
     for k, g in zip(names, got):
         assert np.array_equal(np.asarray(g).reshape(-1), np.asarray(ref[k]).reshape(-1), equal_nan=True), (name, T, n, qform, rform, wform, k)
+
+
+# ---------------------------------------------------------------- the look-ahead study, rt_window and LASSO calls
+@pytest.fixture(scope="session")
+def rtw_ref(tmp_path_factory):
+    from tests.rt_window_ref import RtWindowRef
+    return RtWindowRef(tmp_path_factory.mktemp("rtwin_ref_fuzz"))
+
+
+@pytest.fixture(scope="session")
+def lasso_ref(tmp_path_factory):
+    from tests.lasso_ref import LassoRef
+    return LassoRef(tmp_path_factory.mktemp("lasso_ref_fuzz"))
+
+
+@settings(max_examples=_N or 30, deadline=None, suppress_health_check=list(HealthCheck), derandomize=not _N)
+@given(st.data())
+def test_random_lookahead_matches_the_restatement(gpu_device, data):
+    """Random look-ahead studies over the validated descriptor space (R 1..6, LL 2..260, F 1..LL, M 1..F+3: F < M gives the
+    all-NaN statistics), both R modes and observation types, every lane mapping, missing observations, zero truth days
+    (Inf and 0/0 entries) and a population-0 region whose entries are all +-100 (ties).  About one example in four has
+    n = F - M + 1 > 64 rows per column (a second pass of every lane in lookahead_stats).  Bit for bit against
+    tests/lookahead_ref.py: tables, statistics and chains."""
+    from epidemicmodeling_amd import batch
+    from tests import lookahead_ref as LR
+    draw = data.draw
+    # the sizes come from a drawn seed: hypothesis alone keeps them near their minima, and the rows > 64 need large ones
+    rng = np.random.default_rng(draw(st.integers(0, 2 ** 63 - 1)))
+    R = int(rng.integers(1, 7))
+    if rng.random() < 0.25:
+        LL = int(rng.integers(70, 261)); M = int(rng.integers(1, LL - 64)); F = int(rng.integers(M + 64, LL + 1))
+    else:                                                 # at most 64 rows, or none (F < M: all-NaN statistics), F up to LL
+        LL = int(rng.integers(2, 261)); F = int(rng.integers(1, LL + 1)); M = int(rng.integers(max(1, F - 63), F + 4))
+    w = synth.make_cfg3(R, LL)
+    N = synth.make_regions(R)["N"].astype(np.float64)
+    if draw(st.booleans()):
+        w.obs_type = "TOTALCASES"
+        w.x = np.ascontiguousarray(np.nancumsum(w.x, axis=0))
+    if draw(st.booleans()):
+        w.R_scalar = np.ascontiguousarray(np.nanmean(w.R_series, axis=0)); w.R_series = None
+    if draw(st.booleans()):
+        w.x = w.x.copy(); w.x[rng.random(w.x.shape) < draw(st.sampled_from([0.05, 0.3]))] = np.nan
+    truth = w.x * N[None, :] + 50.0
+    truth[~np.isfinite(truth)] = 50.0
+    if draw(st.booleans()):
+        truth[rng.random(truth.shape) < 0.05] = 0.0
+    if draw(st.booleans()):
+        r0 = int(rng.integers(R)); N[r0] = 0.0
+        truth[:, r0] *= np.where(rng.random(LL) < 0.5, -1.0, 1.0)
+    truth = np.ascontiguousarray(truth)
+    shape = draw(st.sampled_from([0, 1, 3]))
+    got = batch.lookahead(w, truth, N, F, M, device=gpu_device, chains=True, shape=shape)
+    exp = LR.expected(w, truth, N, F, M, n_threads=16)
+    for k in ("est_plus", "est_smooth", "mean_plus", "median_plus", "std_plus", "mean_smooth", "median_smooth", "std_smooth",
+              "S_PLUS", "S_SMOOTH"):
+        g, e = got[k], exp[k]
+        nan = np.isnan(e)
+        assert g.shape == e.shape and np.array_equal(np.isnan(g), nan), (R, LL, F, M, k)
+        assert np.array_equal(g[~nan].view(np.int64), e[~nan].view(np.int64)), (R, LL, F, M, k)
+
+
+@settings(max_examples=_N or 40, deadline=None, suppress_health_check=list(HealthCheck), derandomize=not _N)
+@given(st.data())
+def test_random_rt_window_matches_the_restatement(gpu_device, rtw_ref, data):
+    """Random sliding-window problems over the validated descriptor space: R 1..130, L 1..120, wlen 2..31 with both
+    causalities, time_unit in {1, 1.5, 7, 0.25}, generation_period 1..L and any non-empty method subset, on inputs with
+    zeros, NaN, +-Inf, negative values, constant runs and hard_series() pieces.  Every output bit for bit against
+    tests/rt_window_ref.c."""
+    from epidemicmodeling_amd import batch
+    from tests.test_gpu_rt_window import _same, _want
+    from tests.test_rt_window_host import hard_series
+    draw = data.draw
+    rng = np.random.default_rng(draw(st.integers(0, 2 ** 63 - 1)))      # sizes from a drawn seed (see the look-ahead hunt)
+    R = int(rng.integers(1, 131)); L = int(rng.integers(1, 121))
+    wlen = int(rng.integers(2, 32)); causal = draw(st.integers(0, 1))
+    tu = draw(st.sampled_from([1.0, 1.5, 7.0, 0.25])); gp = int(rng.integers(1, L + 1))
+    methods = draw(st.sampled_from([m for k in (1, 2, 3)
+                                    for m in itertools.combinations(("LogLinReg", "GenRatios", "NonlinLS"), k)]))
+    t = np.arange(L)[:, None]
+    x = rng.uniform(1, 1000, R) * np.exp(rng.uniform(-0.1, 0.1, R) * t) * (1.0 + 0.1 * rng.standard_normal((L, R)))
+    m = rng.random((L, R))
+    p = draw(st.sampled_from([0.0, 0.02, 0.1]))
+    x[m < p] = 0.0
+    x[(m >= p) & (m < 1.5 * p)] = np.nan
+    x[(m >= 1.5 * p) & (m < 1.6 * p)] = np.inf
+    x[(m >= 1.6 * p) & (m < 1.7 * p)] = -np.inf
+    if draw(st.booleans()):
+        x[:, ::4] = -np.abs(x[:, ::4])
+    if draw(st.booleans()) and L > 3:
+        a = int(rng.integers(0, L - 2)); x[a:a + int(rng.integers(2, L - a + 1)), ::3] = 17.0
+    if draw(st.booleans()):
+        h = hard_series()
+        for r in range(0, R, 5):
+            n = min(L, len(h)); x[:n, r] = np.roll(h, 11 * r)[:n]
+    x = np.ascontiguousarray(x)
+    got = batch.rt_window(x, wlen, tu, causal, gp, methods, device=gpu_device)
+    _same(got, _want(rtw_ref, x, wlen, tu, causal, gp, methods))
+
+
+LASSO_FUZZ_CAP = 300_000      # R * D * n * (K + 1): keeps one example of the C restatement under about a second
+
+
+@settings(max_examples=_N or 25, deadline=None, suppress_health_check=list(HealthCheck), derandomize=not _N)
+@given(st.data())
+def test_random_lasso_matches_the_restatement(gpu_device, lasso_ref, data):
+    """Random cross-validated LASSO problems over the validated descriptor space: D 2..256, n 1..12, K in {0} and
+    2..min(D, 63), NL 1..100, LambdaRatio, RelTol in {1e-4, 1e-8, 1e-2}, MaxIter in {1e5, 1, 3}, R 1..70 (cut down so that
+    R * D * n * (K + 1) <= LASSO_FUZZ_CAP), make_problem's regions with and without the specials, folds from lasso_folds or
+    an arbitrary valid assignment with uneven sizes.  Every output bit for bit against tests/lasso_ref.c."""
+    from tests.test_gpu_lasso import _run_device, _same
+    from tests.test_lasso_host import make_problem
+    draw = data.draw
+    seed = draw(st.integers(0, 2 ** 63 - 1))                             # sizes from a drawn seed (see the look-ahead hunt)
+    rng = np.random.default_rng(seed)
+    D = int(rng.integers(2, 257)); n = int(rng.integers(1, 13))
+    K = 0 if rng.random() < 0.25 else int(rng.integers(2, min(D, 63) + 1))
+    R = max(1, min(int(rng.integers(1, 71)), LASSO_FUZZ_CAP // (D * n * (K + 1))))
+    NL = int(rng.integers(1, 101)); ratio = draw(st.sampled_from([1e-4, 1e-2, 0.5, 1e-6]))
+    rel_tol = draw(st.sampled_from([1e-4, 1e-8, 1e-2])); max_iter = draw(st.sampled_from([100000, 100000, 1, 3]))
+    seed = seed % 10 ** 9
+    X, y, fold = make_problem(R, D, n, K, seed, specials=draw(st.booleans()))
+    if K >= 2 and draw(st.booleans()):
+        rng = np.random.default_rng(seed + 1)
+        fold = rng.integers(0, K, size=(D, R)).astype(np.int32)
+        for r in range(R):
+            fold[rng.permutation(D)[:K], r] = np.arange(K, dtype=np.int32)
+    got = _run_device(X, y, fold, K, NL, ratio, rel_tol, max_iter, device=gpu_device)
+    _same(got, lasso_ref.run(X, y, fold, K, NL, ratio, rel_tol, max_iter))

@@ -188,3 +188,156 @@ def test_forecast_quality_with_lasso_stage_by_stage(gpu_device, ref):
     from tests import lookahead_ref as LR
     from tests.test_gpu_lookahead import ARRAYS, _same as same_tables
     same_tables(out, LR.expected(w, out["truth"], np.asarray(N, dtype=np.float64), F, M), ARRAYS)
+
+
+# ---------------------------------------------------------------- every limit at once
+LIMIT_CASES = [  # R, n, D, K, NL, max_iter
+    (3, 12, 256, 63, 100, 100000),          # 63 fold lanes x 12 columns x 100 lambdas over 256 days: the LDS maximum
+    (65, 12, 63, 63, 100, 100000),          # K = D: single-day folds, each fold lane trains on D - 1 days
+    (3, 12, 256, 63, 100, 1),               # max_iter = 1 at the maximum shape
+]
+
+
+@pytest.mark.parametrize("R, n, D, K, NL, max_iter", LIMIT_CASES)
+def test_bit_identical_at_the_limits(gpu_device, ref, R, n, D, K, NL, max_iter):
+    if D == 256 and n == 12 and NL == 100:
+        # lasso_lds_bytes (csrc/lasso.hpp): (D n + D + 64 D + 128 + 3 NL + 8) doubles + D ints, inside the 160 KiB of a CU
+        assert (D * n + D + D * 64 + 128 + 3 * NL + 8) * 8 + D * 4 == 162208 <= 160 * 1024
+    X, y, fold = make_problem(R, D, n, K, seed=R * 7 + n + D + K + max_iter)
+    got = _run_device(X, y, fold, K, NL, max_iter=max_iter, device=gpu_device)
+    _same(got, ref.run(X, y, fold, K, NL, max_iter=max_iter))
+    if max_iter == 1:
+        assert ST_MAXITER in set(got["status"].tolist())
+    else:
+        assert ST_OK in set(got["status"].tolist())
+
+
+def _constant_on_one_training_set(R, D, K, f_const, seed):
+    """make_problem without specials, then in every region: column 0 constant on the training set of fold f_const (it
+    varies only on that fold's days), and day 0 moved into fold f_const (so that the column's first day is held out)."""
+    from epidemicmodeling_amd import batch
+    X, y, _ = make_problem(R, D, 6, 0, seed, specials=False)
+    fold = batch.lasso_folds(D, K, R, seed)
+    rng = np.random.default_rng(seed)
+    for r in range(R):
+        f0 = fold[0, r]
+        if f0 != f_const:                     # swap day 0 with a day of fold f_const: fold sizes stay as they were
+            i = np.flatnonzero(fold[:, r] == f_const)[0]
+            fold[i, r], fold[0, r] = f0, f_const
+        hold = fold[:, r] == f_const
+        X[:, 0, r] = 3.0
+        X[hold, 0, r] = 3.0 + rng.uniform(0.5, 2.0, hold.sum())
+        y[:, r] += 0.05 * X[:, 0, r]
+    return X, y, fold
+
+
+@pytest.mark.parametrize("D, K", [(40, 5), (63, 63), (256, 63)])
+def test_constant_column_on_the_last_folds_training_set(gpu_device, ref, D, K):
+    """A column that is constant on the training set of fold K - 1 only (make_problem's special builds it for fold 0):
+    that lane must drop the column, the other lanes and the full fit keep it."""
+    X, y, fold = _constant_on_one_training_set(4, D, K, K - 1, seed=D + K)
+    for r in range(4):
+        train = fold[:, r] != K - 1
+        assert X[train, 0, r].max() == X[train, 0, r].min() and X[:, 0, r].max() != X[:, 0, r].min()
+    got = _run_device(X, y, fold, K, 100, device=gpu_device)
+    _same(got, ref.run(X, y, fold, K, 100))
+    assert np.isfinite(got["mse"]).all() and (got["status"] == ST_OK).all()
+
+
+# ---------------------------------------------------------------- optional outputs: each alone, in a poisoned arena
+LASSO_OPTIONAL = ("lambda", "B", "intercept", "df", "mse", "se", "iters", "idx_min_mse", "idx_1se")
+
+
+@pytest.mark.parametrize("K", [0, 7])
+@pytest.mark.parametrize("entry", ["device", "host"])
+def test_each_output_alone(gpu_device, ref, K, entry):
+    """epi_lasso_outputs may hold NULL for every output but status (and a, b when K >= 2).  Each optional output alone, and
+    mse + se without B, comes back equal to the all-outputs run bit for bit; every byte outside the requested outputs keeps
+    its poison (guards and never-requested neighbours)."""
+    import torch
+    from epidemicmodeling_amd import _lib
+    from tests import helpers as H
+    R, D, n, NL = 9, 50, 6, 20
+    X, y, fold = make_problem(R, D, n, K, seed=31 + K)
+    full = ref.run(X, y, fold, K, NL)
+    shapes = _lib.lasso_shapes(R, D, n, K, NL)
+    specs = [(k, shapes[k], np.int32 if k in _lib.LASSO_OUT_I32 else np.float64) for k in _lib.LASSO_OUT_NAMES if k in shapes]
+    required = ("status", "a", "b") if K >= 2 else ("status",)
+    subsets = [(k,) for k in LASSO_OPTIONAL if k in shapes] + ([("mse", "se", "lambda"), ("a", "b")] if K >= 2 else [("B", "df")])
+    Xc, yc = np.ascontiguousarray(X), np.ascontiguousarray(y)
+    fc = None if K < 2 else np.ascontiguousarray(fold, dtype=np.int32)
+    if entry == "device":
+        Xd, yd = torch.as_tensor(Xc, device=gpu_device), torch.as_tensor(yc, device=gpu_device)
+        fd = None if fc is None else torch.as_tensor(fc, device=gpu_device)
+    d = _lib.make_lasso_desc(R, D, n, K, NL)
+    for sub in subsets:
+        req = tuple(dict.fromkeys(required + sub))
+        ar = H.GuardArena(specs, device=gpu_device if entry == "device" else None)
+        outs = _lib.LassoOutputs()
+        for k in _lib.LASSO_OUT_NAMES:
+            setattr(outs, k, C.c_void_p(ar.ptr(k)) if k in req else None)
+        err = C.create_string_buffer(256)
+        if entry == "device":
+            st = torch.cuda.current_stream(torch.device(gpu_device))
+            rc = _lib.lib().epi_lasso_run_device(C.byref(d), C.c_void_p(Xd.data_ptr()), C.c_void_p(yd.data_ptr()),
+                                                 None if fd is None else C.c_void_p(fd.data_ptr()), C.byref(outs),
+                                                 C.c_void_p(st.cuda_stream), err)
+        else:
+            rc = _lib.lib().epi_lasso_run_host(C.byref(d), C.c_void_p(Xc.ctypes.data), C.c_void_p(yc.ctypes.data),
+                                               None if fc is None else C.c_void_p(fc.ctypes.data), C.byref(outs), 0, err)
+        _lib.check(rc, err)
+        _same({k: ar.get(k) for k in req}, {k: full[k] for k in req})
+        assert ar.untouched(req), sub
+
+
+# ---------------------------------------------------------------- the device path against the optimality conditions
+def test_device_path_meets_the_kkt_conditions_at_the_maximum_shape(gpu_device, ref):
+    """test_lasso_host.py::test_path_meets_the_kkt_conditions on the GPU's B path at D = 256, n = 12, NL = 100 (with 63 fold
+    lanes beside the full fit), with the same bound: at every lambda g = Xs' (Y0 - Xs b) / N equals lambda sign(b_j) where
+    b_j != 0 and lies in [-lambda, lambda] where b_j = 0, up to RelTol sum_k |G_jk| (1 + |b_k|) (1 + RelTol) plus 1e-12 of the
+    scale of g."""
+    from tests.test_lasso_host import _standardized
+    R, D, n, K = 4, 256, 12, 63
+    X, y, fold = make_problem(R, D, n, K, seed=77, specials=False)
+    got = _run_device(X, y, fold, K, 100, device=gpu_device)
+    rel_tol = 1e-4
+    for r in range(R):
+        assert got["status"][r] == ST_OK
+        Xs, Y0, sig, cst = _standardized(X[:, :, r], y[:, r])
+        G = Xs.T @ Xs / D
+        for k in range(100):
+            lam = got["lambda"][k, r]
+            b = got["B"][k, :, r] * sig
+            g = Xs.T @ (Y0 - Xs @ b) / D
+            bound = rel_tol * np.abs(G) @ ((1 + np.abs(b)) * (1 + rel_tol)) + 1e-12 * (np.abs(Xs).T @ np.abs(Y0) / D + lam)
+            act = (b != 0) & ~cst
+            assert np.all(np.abs(g[act] - lam * np.sign(b[act])) <= bound[act]), (r, k)
+            zero = (b == 0) & ~cst
+            assert np.all(np.abs(g[zero]) <= lam + bound[zero]), (r, k)
+
+
+def test_device_cv_half_agrees_with_sklearn(gpu_device, ref):
+    """The CV half against code this project did not write: every fold of every region refitted at every lambda with
+    sklearn.linear_model.Lasso on the fold's own standardization, the held-out MSE and SE recomputed
+    (tests/lasso_ref.py::sklearn_cv, whose docstring derives the gates from the KKT bound of the RelTol stopping rule and
+    the strong convexity of each fold's objective).  The GPU's mse / se must lie within those gates, and idx_min_mse /
+    idx_1se must be sklearn's wherever the MSE margin exceeds them.  RelTol 1e-8 makes the gates tight enough to decide
+    indices."""
+    pytest.importorskip("sklearn")
+    from tests.lasso_ref import cv_indices_agree, sklearn_cv
+    R, D, n, K, rel_tol = 6, 40, 6, 5, 1e-8
+    X, y, fold = make_problem(R, D, n, K, seed=12, specials=False)
+    got = _run_device(X, y, fold, K, 100, rel_tol=rel_tol, device=gpu_device)
+    _same(got, ref.run(X, y, fold, K, 100, rel_tol=rel_tol))
+    decided = gated = 0
+    for r in range(R):
+        assert got["status"][r] == ST_OK
+        mse, se, g_mse, g_se = sklearn_cv(X[:, :, r], y[:, r], fold[:, r], K, got["lambda"][:, r], rel_tol)
+        ok = ~np.isnan(g_mse)
+        gated += ok.sum()
+        assert np.all(np.abs(got["mse"][ok, r] - mse[ok]) <= g_mse[ok]), r
+        assert np.all(np.abs(got["se"][ok, r] - se[ok]) <= g_se[ok]), r
+        if ok.all():
+            decided += cv_indices_agree(got["mse"][:, r], got["se"][:, r], g_mse, g_se, int(got["idx_min_mse"][r]),
+                                        int(got["idx_1se"][r]), mse, se)
+    assert gated >= 300 and decided > 0

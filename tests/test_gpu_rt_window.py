@@ -175,3 +175,148 @@ def test_example_script_runs(hip_lib, gpu_device, tmp_path):
     assert r.returncode == 0, r.stderr
     text = out.read_text().splitlines()
     assert text[0].startswith("region,day,new_smoothed,llr_Lambda") and len(text) > 10
+
+
+# ---------------------------------------------------------------- window shapes at the limits
+def _nw(wlen, causal):
+    return wlen if causal else 2 * (wlen // 2) + 1
+
+
+@pytest.mark.parametrize("wlen, causal", [(31, 1), (30, 0), (30, 1), (3, 0)])
+@pytest.mark.parametrize("dL", [None, -1, 0, 1])
+def test_window_lengths_around_the_series_length(hip_lib, gpu_device, ref, wlen, causal, dL):
+    """L in {1, nw - 1, nw, nw + 1} for the longest causal window (31 samples), both parities of a 30-day window and the
+    shortest centred one; generation_period 1 and L, time units 7 and 0.25, R = 1 and R = 65 (a second wavefront)."""
+    from epidemicmodeling_amd import batch
+    import torch
+    L = 1 if dL is None else _nw(wlen, causal) + dL
+    for R in (1, 65):
+        x = _cases(R, L, 1000 * wlen + 10 * L + causal)
+        for gp, tu in ((1, 7.0), (L, 0.25)):
+            got = batch.rt_window(x, wlen, tu, causal, gp, ALL, device=gpu_device)
+            torch.cuda.synchronize()
+            _same(got, _want(ref, x, wlen, tu, causal, gp, ALL))
+            if L >= _nw(wlen, causal):
+                assert (got["nls_status"].cpu().numpy() != 0).any()
+
+
+# ---------------------------------------------------------------- optional outputs: each alone, in a poisoned arena
+SUBSETS = [(n,) for n in ("llr_Rt", "llr_A", "llr_Lambda", "llr_ExpFit", "gr_Rt", "gr_Lambda", "gr_RtSmoothed",
+                          "gr_LambdaSmoothed", "nls_Rt", "nls_A", "nls_Lambda", "nls_ExpFit", "nls_status", "nls_iters")]
+SUBSETS += [("llr_ExpFit", "nls_iters"), ("gr_Lambda", "nls_status"), ("llr_A", "gr_RtSmoothed", "nls_ExpFit")]
+
+
+@pytest.mark.parametrize("entry", ["device", "host"])
+def test_each_output_alone(hip_lib, gpu_device, entry):
+    """epi_rtwin_outputs may hold NULL for any output.  With all three methods on, each output alone (and a few mixed subsets)
+    comes back equal to the all-outputs run bit for bit; every byte of the arena outside the requested outputs (guards and
+    the never-requested neighbours) keeps its poison.  The dispatcher decides per method from an OR of the pointers."""
+    import ctypes as C
+    from epidemicmodeling_amd import _lib, batch
+    import torch
+    from tests import helpers as H
+    R, L, wlen = 67, 40, 7
+    x = np.ascontiguousarray(_cases(R, L, 21))
+    full = {k: v.cpu().numpy() for k, v in batch.rt_window(x, wlen, 1.5, 1, 3, ALL, device=gpu_device).items()}
+    specs = [(n, (L, R), np.int32 if n in _lib.RTWIN_OUT_I32 else np.float64) for n in _lib.RTWIN_OUT_NAMES]
+    d = _lib.make_rtwin_desc(R, L, wlen, 1.5, 1, 3, 7)
+    xd = torch.as_tensor(x, device=gpu_device)
+    for req in SUBSETS:
+        ar = H.GuardArena(specs, device=gpu_device if entry == "device" else None)
+        outs = _lib.RtwinOutputs()
+        for n in _lib.RTWIN_OUT_NAMES:
+            setattr(outs, n, C.c_void_p(ar.ptr(n)) if n in req else None)
+        err = C.create_string_buffer(256)
+        if entry == "device":
+            st = torch.cuda.current_stream(torch.device(gpu_device))
+            rc = _lib.lib().epi_rtwin_run_device(C.byref(d), C.c_void_p(xd.data_ptr()), C.byref(outs), C.c_void_p(st.cuda_stream),
+                                                 err)
+        else:
+            rc = _lib.lib().epi_rtwin_run_host(C.byref(d), C.c_void_p(x.ctypes.data), C.byref(outs), 0, err)
+        _lib.check(rc, err)
+        _same({n: ar.get(n) for n in req}, {n: full[n] for n in req})
+        assert ar.untouched(req), req
+
+
+# ---------------------------------------------------------------- LogLinReg and GenRatios against 50-digit arithmetic
+def _gamma(k):
+    u = 2.0 ** -53
+    return k * u / (1 - k * u)
+
+
+@pytest.mark.parametrize("wlen, causal", [(2, 1), (2, 0), (31, 1), (31, 0)])
+def test_loglinreg_and_genratios_against_high_precision(hip_lib, gpu_device, wlen, causal):
+    """The window regression and the generation ratios evaluated in 50-digit arithmetic (mpmath) from the fp64 inputs.
+    Bound (u = 2^-53, gamma_k = k u / (1 - k u)): epi_log is within 1 ulp <= 2 u |seg_i| of log x_i.  r = sum c_i seg_i with
+    c_i = (n_i - En) / (nw Det) moves by at most sum |c_i| 2 u |seg_i| through the logs; the kernel's sums s and ns carry
+    gamma_nw sum |seg_i| and gamma_nw sum |n_i seg_i| (n_i are exact integers), the means one rounding each, the products and
+    the difference in the numerator one each, En / En2 / Det (exact sums of integers, a division each and a difference) a
+    relative gamma_3 (En2 + En^2) / Det, and the last division one: the error of r is bounded by
+      (E_log + gamma_nw+2 (sum |n_i seg_i| + |En| sum |seg_i|) / nw) / Det + (gamma_3 (En2 + En^2) / Det + 2 u) |r|
+    and ALog likewise with (En2, En) in place of (1, En) on (ms, mns).  Lambda = r / time_unit adds one rounding.  A = exp(ALog)
+    (epi_exp within 1 ulp): relative error |dALog| + 2 u.  GenRatios: lambda = log(x_t / x_t-gp) / gp: the quotient's rounding
+    moves the log by u, the log adds 1 ulp and the division one rounding: |d lambda| <= u / gp + 3 u |lambda|; the moving
+    average of wlen terms c lambda (c = 1 / wlen rounded) adds gamma_wlen+2 sum |lambda| / wlen on top of the propagated errors
+    of its terms."""
+    pytest.importorskip("mpmath")
+    from epidemicmodeling_amd import batch
+    x = _smooth_cases(wlen, causal)
+    got = {k: v.cpu().numpy() for k, v in batch.rt_window(x, wlen, 0.25, causal, 4, ("LogLinReg", "GenRatios"),
+                                                           device=gpu_device).items()}
+    _check_against_high_precision(got, x, wlen, causal, 4, 0.25)
+
+
+def _smooth_cases(wlen, causal):
+    rng = np.random.default_rng(wlen * 3 + causal)
+    R, L = 5, 70
+    t = np.arange(L)[:, None]
+    x = rng.uniform(5, 5e4, R) * np.exp(rng.uniform(-0.1, 0.1, R) * t) * (1 + 0.3 * rng.random((L, R)))
+    return np.ascontiguousarray(x)
+
+
+def _check_against_high_precision(got, x, wlen, causal, gp, tu):
+    import mpmath as mp
+    mp.mp.dps = 50
+    u = 2.0 ** -53
+    L, R = x.shape
+    nw = _nw(wlen, causal)
+    off = -(wlen - 1) if causal else -(wlen // 2)
+    n = np.arange(nw) + off
+    En, En2 = mp.mpf(int(n.sum())) / nw, mp.mpf(int((n * n).sum())) / nw
+    Det = En2 - En ** 2
+    fDet = float(Det)
+    checked = 0
+    for r_ in range(R):
+        lg = [mp.log(mp.mpf(float(v))) for v in x[:, r_]]
+        for mm in range(-off, L - (nw - 1 + off)):
+            seg = [lg[mm + off + i] for i in range(nw)]
+            ms = mp.fsum(seg) / nw
+            mns = mp.fsum(mp.mpf(int(n[i])) * seg[i] for i in range(nw)) / nw
+            r = (mns - ms * En) / Det
+            ALog = (ms * En2 - mns * En) / Det
+            sabs = float(mp.fsum(abs(s) for s in seg))
+            nsabs = float(mp.fsum(abs(int(n[i]) * seg[i]) for i in range(nw)))
+            cdet = _gamma(3) * float(En2 + En ** 2) / fDet
+            e_log_r = sum(abs(float(n[i] - En)) / (nw * fDet) * 2 * u * abs(float(seg[i])) for i in range(nw))
+            e_r = (e_log_r + _gamma(nw + 2) * (nsabs + abs(float(En)) * sabs) / nw / fDet) + (cdet + 2 * u) * abs(float(r))
+            e_log_a = sum(abs(float(En2 - n[i] * En)) / (nw * fDet) * 2 * u * abs(float(seg[i])) for i in range(nw))
+            e_a = (e_log_a + _gamma(nw + 2) * (float(En2) * sabs + abs(float(En)) * nsabs) / nw / fDet) + (cdet + 2 * u) * abs(float(ALog))
+            lam = got["llr_Lambda"][mm, r_]
+            assert abs(lam - float(r / tu)) <= (e_r / tu) * (1 + 1e-6) + u * abs(lam), (r_, mm)
+            A = got["llr_A"][mm, r_]
+            exA = mp.exp(ALog)
+            assert abs(mp.mpf(float(A)) - exA) <= exA * (e_a * (1 + 1e-6) + 2 * u) * (1 + 1e-6), (r_, mm)
+            checked += 1
+        # GenRatios
+        lam_ex = [mp.mpf(0)] * gp + [mp.log(mp.mpf(float(x[t_, r_])) / mp.mpf(float(x[t_ - gp, r_]))) / gp for t_ in range(gp, L)]
+        e_lam = [0.0] * gp + [u / gp + 3 * u * abs(float(v)) for v in lam_ex[gp:]]
+        for t_ in range(L):
+            g = got["gr_Lambda"][t_, r_]
+            assert abs(g - float(lam_ex[t_])) <= e_lam[t_] * (1 + 1e-6) + 1e-300, (r_, t_)
+            terms = [lam_ex[t_ - k] for k in range(wlen) if t_ - k >= 0]
+            sm = mp.fsum(terms) / wlen
+            e_sm = (sum(e_lam[t_ - k] for k in range(wlen) if t_ - k >= 0) / wlen
+                    + _gamma(wlen + 2) * float(mp.fsum(abs(v) for v in terms)) / wlen)
+            gs = got["gr_LambdaSmoothed"][t_, r_]
+            assert abs(gs - float(sm)) <= e_sm * (1 + 1e-6) + 1e-300, (r_, t_)
+    assert checked > 0

@@ -645,6 +645,41 @@ def test_oracle_reproduces_aux_golden_vectors():
         assert np.array_equal(on, g["out_on_front"][r]) and io == g["out_i_opt"][r]
 
 
+def test_restatements_reproduce_the_newer_aux_golden_vectors(tmp_path):
+    """Committed fixtures of the look-ahead study, the sliding-window estimators and the LASSO (tests/golden/
+    make_golden_aux.py, generated only where the loop transcription, NumPy / SciPy and KKT / scikit-learn agree): the
+    restatements the GPU suite compares against reproduce them bit for bit (NaN payloads free)."""
+    from tests import lookahead_ref as LR
+    from tests.lasso_ref import LassoRef
+    from tests.rt_window_ref import RtWindowRef
+
+    def same(a, b, what):
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.shape == b.shape, what
+        if b.dtype == np.float64:
+            nan = np.isnan(b)
+            assert np.array_equal(np.isnan(a), nan) and np.array_equal(a[~nan].view(np.int64), b[~nan].view(np.int64)), what
+        else:
+            assert np.array_equal(a, b), what
+    g = _aux("aux_lookahead")
+    exp = LR.expected(LR.golden_workload(g), g["in_truth"], g["in_population"], int(g["in_F"]), int(g["in_M"]))
+    for k in g.files:
+        if k.startswith("out_"):
+            same(exp[k[4:]], g[k], k)
+    g = _aux("aux_rt_window")
+    rw = RtWindowRef(tmp_path)
+    for c in range(2):
+        out = rw.all(g["in_x"], int(g[f"in_c{c}_wlen"]), float(g[f"in_c{c}_time_unit"]), int(g[f"in_c{c}_causal"]),
+                     int(g[f"in_c{c}_gp"]))
+        for k, v in out.items():
+            same(v, g[f"out_c{c}_{k}"], (c, k))
+    g = _aux("aux_lasso")
+    o = LassoRef(tmp_path).run(g["in_X"], g["in_y"], g["in_fold"], int(g["in_K"]), int(g["in_NL"]))
+    assert {"out_" + k for k in o} == {k for k in g.files if k.startswith("out_")}
+    for k, v in o.items():
+        same(v, g["out_" + k], k)
+
+
 # ---------------------------------------------------------------- property-based: two readings of the .m files
 def test_random_problems_c_oracle_vs_numpy_restatement():
     """hypothesis: random model variants / sizes / gaps / free controls / monitor lengths / noise settings -- the C oracle
