@@ -2874,9 +2874,16 @@ int epi_pareto_front_device(int32_t R, int32_t P, const double *J0, const double
         hipError_t e = hipFuncSetAttribute((const void *)pareto_front, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         if (e != hipSuccess) return hip_fail(err, e, "hipFuncSetAttribute");
     }
-    hipLaunchKernelGGL(pareto_front, dim3(R), dim3(256), shmem, (hipStream_t)stream, P, J0, J1, on_front, i_opt, (const int32_t *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(err, e, "pareto_front launch");
+    // one 256-lane workgroup per region, in slices: a launch's thread count is a 32-bit number in the HIP runtime and wraps
+    // silently beyond it (2^24 regions and more in one launch)
+    constexpr int64_t kSlice = (int64_t)1 << 22;
+    for (int64_t r0 = 0; r0 < R; r0 += kSlice) {
+        const int64_t nr = R - r0 < kSlice ? R - r0 : kSlice;
+        hipLaunchKernelGGL(pareto_front, dim3((unsigned)nr), dim3(256), shmem, (hipStream_t)stream, P, J0 + r0 * P, J1 + r0 * P,
+                           on_front ? on_front + r0 * P : nullptr, i_opt ? i_opt + r0 : nullptr, (const int32_t *)nullptr);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(err, e, "pareto_front launch");
+    }
     return EPI_OK;
 }
 
@@ -3387,10 +3394,19 @@ static int la_enqueue(const epi_lookahead_desc *d, const epi_lookahead_inputs *i
     rc = epi_ekf_run_device(&b, &din, &dout, ws + wl.ekf, wl.ekf_bytes, st, err);
     if (rc != EPI_OK) return rc;
     const size_t n_err = (size_t)d->F * d->M * d->R;
-    hipLaunchKernelGGL(lookahead_errors, dim3((unsigned)((n_err + 255) / 256)), dim3(256), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_errors launch");
-    hipLaunchKernelGGL(lookahead_stats, dim3((unsigned)(d->M * d->R), 2), dim3(kWave), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_stats launch");
+    for (size_t e0 = 0; e0 < n_err; e0 += kLaLaunchElements) {   // in slices: see LaArgs
+        a.e0 = e0;
+        const size_t ne = n_err - e0 < kLaLaunchElements ? n_err - e0 : kLaLaunchElements;
+        hipLaunchKernelGGL(lookahead_errors, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_errors launch");
+    }
+    const int64_t n_col = (int64_t)d->M * d->R;                  // <= 2^31 - 1 (epi_lookahead_validate)
+    for (int64_t col0 = 0; col0 < n_col; col0 += kLaLaunchColumns) {
+        a.col0 = (int)col0;
+        const int64_t nc = n_col - col0 < kLaLaunchColumns ? n_col - col0 : kLaLaunchColumns;
+        hipLaunchKernelGGL(lookahead_stats, dim3((unsigned)nc, 2), dim3(kWave), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lookahead_stats launch");
+    }
     return EPI_OK;
 }
 
@@ -3620,8 +3636,12 @@ int epi_lasso_run_device(const epi_lasso_desc *d, const double *X, const double 
     const size_t shmem = lasso_lds_bytes(d->D, d->n, d->num_lambda);
     hipError_t e = hipFuncSetAttribute((const void *)lasso_cv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return hip_fail(err, e, "hipFuncSetAttribute");
-    hipLaunchKernelGGL(lasso_cv, dim3((unsigned)d->R), dim3(64), shmem, (hipStream_t)stream, g);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lasso_cv launch");
+    for (int64_t r0 = 0; r0 < d->R; r0 += kLsLaunchRegions) {    // one 64-lane workgroup per region, in slices (lasso.hpp)
+        g.r0 = (int)r0;
+        const int64_t nr = d->R - r0 < kLsLaunchRegions ? d->R - r0 : kLsLaunchRegions;
+        hipLaunchKernelGGL(lasso_cv, dim3((unsigned)nr), dim3(64), shmem, (hipStream_t)stream, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "lasso_cv launch");
+    }
     return EPI_OK;
 }
 

@@ -22,12 +22,17 @@ constexpr int kLsMaxN = 12, kLsMaxD = 256, kLsMaxK = 63, kLsMaxNL = 100;
 
 struct LsArgs {
     int R, D, n, K, NL, max_iter;
+    int r0;                        // first region of this launch (the regions are launched in slices, see kLsLaunchRegions)
     double ratio, rel_tol;
     const double *X, *y;           // [D][n][R], [D][R]
     const int32_t *fold;           // [D][R] (K >= 2)
     double *a, *b, *lambda, *B, *intercept, *mse, *se;
     int32_t *df, *iters, *idx_min, *idx_1se, *status;
 };
+
+// regions per launch: a launch's thread count (workgroups x 64 lanes) is a 32-bit number in the HIP runtime, beyond it the count
+// wraps silently (2^26 + 1000 regions in one launch ran 1 000 of them and returned hipSuccess)
+constexpr int kLsLaunchRegions = 1 << 25;
 
 inline size_t lasso_lds_bytes(int D, int n, int NL)
 {
@@ -123,7 +128,7 @@ __global__ __launch_bounds__(64) void lasso_cv(const LsArgs a)
 {
     extern __shared__ double ls_lds[];
     const int D = a.D, n = a.n, K = a.K, NL = a.NL, R = a.R;
-    const int reg = blockIdx.x, lane = threadIdx.x;
+    const int reg = a.r0 + (int)blockIdx.x, lane = threadIdx.x;
     const bool cv = K >= 2;
     double *sX = ls_lds, *sy = sX + (size_t)D * n, *sr = sy + D, *ssse = sr + (size_t)D * 64, *smf = ssse + 64;
     double *slam = smf + 64, *smse = slam + NL, *sse = smse + NL, *smisc = sse + NL;

@@ -7,8 +7,14 @@
 // reduces each table column.  Operation order is MATLAB's, one IEEE rounding per written operation (-ffp-contract=off).
 #pragma once
 
+constexpr int kLaLaunchColumns = 1 << 25;             // lookahead_stats: columns (64-lane workgroups) per launch
+constexpr size_t kLaLaunchElements = (size_t)1 << 31; // lookahead_errors: table elements (lanes) per launch
 struct LaArgs {
     int R, LL, F, M, n_npi, r_mode;
+    // first table column of a lookahead_stats launch and first table element of a lookahead_errors launch: both grids are
+    // launched in slices, a launch's thread count being a 32-bit number in the HIP runtime (beyond it the count wraps silently)
+    int col0;
+    size_t e0;
     // per-region inputs
     const double *x, *R_series, *R_scalar, *prm, *s_init, *Ps_init, *s_final, *Ps_final, *Q, *truth, *population;
     // per-chain copies (workspace)
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(256) void lookahead_expand(const LaArgs a, int nrow
 __global__ __launch_bounds__(256) void lookahead_errors(const LaArgs a)
 {
     const size_t n = (size_t)a.F * a.M * a.R;
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t e = a.e0 + (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
     const int r = (int)(e % a.R);
     const int j = (int)((e / a.R) % a.M) + 1;
@@ -92,7 +98,7 @@ __global__ __launch_bounds__(kWave) void lookahead_stats(const LaArgs a)
     __shared__ double v[kLaMaxF];
     __shared__ double mid[2];
     __shared__ int has_nan;
-    const int col = blockIdx.x;                                   // col = j0 * R + r
+    const int col = a.col0 + (int)blockIdx.x;                     // col = j0 * R + r
     const int lane = threadIdx.x;
     const bool smooth = blockIdx.y == 1;
     const double *tbl = smooth ? a.est_smooth : a.est_plus;

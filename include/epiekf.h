@@ -256,7 +256,12 @@ int epi_ekf_preferred_lane_block(const epi_batch_desc *d);
 
 /* All pointers in `in`/`out`/`workspace` are DEVICE pointers on the current HIP
  * device; `stream` is a hipStream_t (NULL = default stream).  Asynchronous:
- * returns after enqueueing.  Outputs not selected in out_mask may be NULL. */
+ * returns after enqueueing.  Outputs not selected in out_mask may be NULL.
+ * Alignment: every array needs the alignment of its element only (8 bytes for the fp64 arrays, 4 for int32 and fp32
+ * storage), a slice of a larger allocation included.  The smoothers that fetch P_PLUS and X with 16-byte-per-lane LDS-DMA
+ * (eks_bwd_lane6, eks_bwd_hex) give the same bits on arrays 8 bytes off a 16-byte boundary
+ * (tests/test_gpu_addressing_limits.py).
+ * Limits (epi_ekf_validate): B, Sx, Su and B rounded up to lane_block <= 2^23; each is run at its value there. */
 int epi_ekf_run_device(const epi_batch_desc *d, const epi_inputs *in, const epi_outputs *out,
                        void *workspace, size_t workspace_bytes, void *stream, char *err);
 
@@ -357,7 +362,8 @@ int epi_random_npi_mc_device(const epi_mc_desc *d, const double *sp, const doubl
 /* Pareto-front filter and optimum of the sweep (Tools/TrainPredictPrescribeNPI.m:624-633), per region:
  * on_front(ii) = (sum(J0 < J0(ii) & J1 < J1(ii)) == 0);  [~, I_opt] = min((J0/max(J0)).^2 + (J1/max(J1)).^2).
  * J0, J1 [R][P] (region-major -- the chain order of the sweep); on_front [R][P] (0/1) or NULL; i_opt [R] 0-based or
- * NULL.  P <= 8192 (the points of a region are staged in LDS). */
+ * NULL.  P <= 8192 (the points of a region are staged in LDS); any R (one workgroup per region, launched in slices of 2^22
+ * regions: the thread count of one launch is a 32-bit number). */
 int epi_pareto_front_device(int32_t R, int32_t P, const double *J0, const double *J1, int32_t *on_front,
                             int32_t *i_opt, void *stream, char *err);
 

@@ -409,3 +409,288 @@ class GuardArena:
             off, nb, _, _ = self.seg[name]
             keep[off:off + nb] = False
         return bool((b[keep] == self.POISON).all())
+
+
+# ---------------------------------------------------------------- batches at the edges of the kernels' 32-bit addressing
+# (tests/test_gpu_addressing_limits.py).  Chains are independent, so a sampled chain of a batch far too large for the oracle
+# must equal, bit for bit, the oracle's run of that chain alone -- provided the chains differ, so that an offset that wraps or
+# lands in a neighbouring block cannot read a twin.  Every per-chain input is therefore a closed form of the chain index that
+# torch evaluates on the device for the whole batch and NumPy re-evaluates for the sample: integer hashing, gathers, and
+# integer x power-of-two products (exact in fp64), nothing whose device and host bits could differ.
+POISON64 = 0x7FF80000DEADBEEF       # a quiet NaN with a payload no arithmetic produces: "this word was never stored"
+POISON32 = 0x7FC0BEEF
+POISON_RANK, POISON_STATUS = -7, -1
+
+
+def chain_hash(c, k):
+    """32-bit hash of chain index c (int64 array, NumPy or torch: the same integer operations on both) in stream k.  Every
+    intermediate stays below 2^63."""
+    h = (c * 2654435761 + (k * 40503 + 12345)) & 0xFFFFFFFF
+    h = h ^ (h >> 15)
+    h = (h * 73244475) & 0xFFFFFFFF
+    h = h ^ (h >> 13)
+    h = (h * 73244475) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+class FormulaBatch:
+    """B chains of a generic model derived from a small `base` Workload with one chain per region (S regions, identity series):
+    chain c takes region r(c) = chain_hash(c, 1) mod S -- its parameters, covariances and end-point -- and, of its own,
+        epsilon(c) = (1 + (chain_hash(c, 2) >> 9)) 2^-24       in (0, 1/2]
+        i0(c)      = 2^-20 + (c + 1) 2^-43,   s0(c) = 1 - i0(c)   (injective in c: no two chains share their inputs)
+    x_mode / u_mode: "regions" = the S series of the base, chain c reads series r(c) (Sx = S); "one" = a single shared series
+    (Sx = 1, region 0's); "own" = one series per chain (Sx = B, identity: column c is a copy of region r(c)'s).
+    u_mode = "table" (with Su): a table of Su control series by formula -- integer NPI levels table_level(day, k, s) on the
+    days region 0 has controls, free (NaN) where it has none -- of which chain c reads series table_series(c): 0, Su - 1 and
+    the middle ones for c mod 8 < 4, a hashed one otherwise.
+    A base with a scalar R_v (the NewCase models) passes R_scalar of region r(c).
+    plant(chain, row, value) overrides one entry of Ps_init (a covariance that overflows in mid-run)."""
+
+    def __init__(self, base, B, x_mode="regions", u_mode="regions", Su=None):
+        assert base.x_series is None and base.u_series is None and base.Sx == base.B and base.Su == base.B
+        assert np.ndim(base.Q) == 2
+        self.base, self.B, self.S, self.x_mode, self.u_mode = base, int(B), base.B, x_mode, u_mode
+        self.m = base.m
+        self.Su_table = None if Su is None else int(Su)
+        self.planted = []
+
+    def table_series(self, c):
+        Su = self.Su_table
+        fixed = (c % 8 == 0) * 0 + (c % 8 == 1) * (Su - 1) + (c % 8 == 2) * (Su // 2) + (c % 8 == 3) * (Su // 2 - 1)
+        return fixed * (c % 8 < 4) + (chain_hash(c, 6) % Su) * (c % 8 >= 4)
+
+    def table_level(self, t, k, s, umax):
+        """Integer NPI level of day t, NPI k, series s (int64 arrays that broadcast; umax the integer maxima, same shape as k)."""
+        n = self.base.n_npi
+        return chain_hash((t * n + k) * self.Su_table + s, 5) % (umax + 1)
+
+    def plant(self, chain, row, value):
+        self.planted.append((int(chain), int(row), float(value)))
+
+    # -- the closed forms: c is an int64 array of chain indices, NumPy or torch
+    def region(self, c):
+        return chain_hash(c, 1) % self.S
+
+    @staticmethod
+    def epsilon_bits(c):
+        return (chain_hash(c, 2) >> 9) + 1            # x 2^-24
+
+    @staticmethod
+    def i0_bits(c):
+        return c + 1 + (1 << 23)                      # x 2^-43
+
+    def _series_index(self, mode, r):
+        return {"regions": r, "one": r * 0, "own": None}[mode]
+
+    def host_workload(self, idx):
+        """synth.Workload of the chains `idx`, by NumPy."""
+        from epidemicmodeling_amd import synth
+        b = self.base
+        c = np.asarray(idx, dtype=np.int64)
+        r = self.region(c)
+        prm = np.ascontiguousarray(b.prm[:, r])
+        prm[L.PRM_EPSILON] = self.epsilon_bits(c).astype(np.float64) * 2.0 ** -24
+        s_init = np.ascontiguousarray(b.s_init[:, r])
+        s_init[1] = self.i0_bits(c).astype(np.float64) * 2.0 ** -43
+        s_init[0] = 1.0 - s_init[1]
+        Ps_init = np.ascontiguousarray(b.Ps_init[:, r])
+        for ch, row, v in self.planted:
+            Ps_init[row, c == ch] = v
+
+        def series(mode, a):
+            if mode == "own":
+                return np.ascontiguousarray(a[..., r]), None
+            if mode == "one":
+                return np.ascontiguousarray(a[..., :1]), np.zeros(c.size, dtype=np.int32)
+            return a, r.astype(np.int32)
+        x, xs = series(self.x_mode, b.x)
+        Rs = None if b.R_series is None else series(self.x_mode, b.R_series)[0]
+        Rsc = None if b.R_scalar is None else np.ascontiguousarray(b.R_scalar[r])
+        if self.u_mode == "table":
+            used, us = np.unique(self.table_series(c), return_inverse=True)
+            umax = b.prm[L.PRM_U_MAX:L.PRM_U_MAX + b.n_npi, 0].astype(np.int64)
+            tt, kk = np.arange(b.T, dtype=np.int64)[:, None, None], np.arange(b.n_npi, dtype=np.int64)[None, :, None]
+            u = self.table_level(tt, kk, used[None, None, :], umax[None, :, None]).astype(np.float64)
+            u[np.isnan(b.u[:, 0, 0])] = np.nan
+            us = us.astype(np.int32)
+        else:
+            u, us = series(self.u_mode, b.u)
+        return synth.Workload(model=b.model, T=b.T, n_npi=b.n_npi, x=x, u=u, R_series=Rs, R_scalar=Rsc, x_series=xs, u_series=us,
+                              prm=prm, s_init=s_init, Ps_init=Ps_init, s_final=np.ascontiguousarray(b.s_final[:, r]),
+                              Ps_final=np.ascontiguousarray(b.Ps_final[:, r]), Q=np.ascontiguousarray(b.Q[:, r]), L=b.L,
+                              order=b.order, obs_type=b.obs_type)
+
+    def device_workload(self, device):
+        """batch.DeviceWorkload of all B chains, evaluated by torch on the device (nothing of size B exists on the host)."""
+        import torch
+        from epidemicmodeling_amd import batch
+        b = self.base
+        dev = torch.device(device)
+        f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev)
+        c = torch.arange(self.B, dtype=torch.int64, device=dev)
+        r = self.region(c)
+        dw = batch.DeviceWorkload.__new__(batch.DeviceWorkload)
+        dw.device = dev
+        dw.model, dw.T, dw.n_npi, dw.L, dw.order, dw.obs_type = b.model, b.T, b.n_npi, b.L, b.order, b.obs_type
+        dw.m, dw.B = b.m, self.B
+        dw.prm = f(b.prm).index_select(1, r)
+        dw.prm[L.PRM_EPSILON] = self.epsilon_bits(c).to(torch.float64) * 2.0 ** -24
+        dw.s_init = f(b.s_init).index_select(1, r)
+        dw.s_init[1] = self.i0_bits(c).to(torch.float64) * 2.0 ** -43
+        dw.s_init[0] = 1.0 - dw.s_init[1]
+        dw.Ps_init = f(b.Ps_init).index_select(1, r)
+        for ch, row, v in self.planted:
+            dw.Ps_init[row, ch] = v
+        dw.s_final, dw.Ps_final, dw.Q = (f(a).index_select(1, r) for a in (b.s_final, b.Ps_final, b.Q))
+
+        def series(mode, a):
+            t = f(a)
+            if mode == "own":
+                return t.index_select(t.dim() - 1, r), None
+            if mode == "one":
+                return t[..., :1].contiguous(), torch.zeros(self.B, dtype=torch.int32, device=dev)
+            return t, r.to(torch.int32)
+        dw.x, dw.x_series = series(self.x_mode, b.x)
+        dw.R_series = None if b.R_series is None else series(self.x_mode, b.R_series)[0]
+        dw.R_scalar = None if b.R_scalar is None else f(b.R_scalar).index_select(0, r)
+        if self.u_mode == "table":
+            Su = self.Su_table
+            umax = torch.as_tensor(b.prm[L.PRM_U_MAX:L.PRM_U_MAX + b.n_npi, 0].astype(np.int64), device=dev)
+            kk, ss = torch.arange(b.n_npi, dtype=torch.int64, device=dev)[:, None], torch.arange(Su, dtype=torch.int64, device=dev)[None, :]
+            dw.u = torch.empty((b.T, b.n_npi, Su), dtype=torch.float64, device=dev)
+            for t in range(b.T):                                 # a day at a time: the hash's temporaries stay small
+                if np.isnan(b.u[t, 0, 0]):
+                    dw.u[t] = float("nan")
+                else:
+                    dw.u[t] = self.table_level(t, kk, ss, umax[:, None]).to(torch.float64)
+            dw.u_series = self.table_series(c).to(torch.int32)
+        else:
+            dw.u, dw.u_series = series(self.u_mode, b.u)
+        dw.Sx, dw.Su = dw.x.shape[1], dw.u.shape[2]
+        dw.r_mode, dw.q_mode = (1 if b.R_series is not None else 0), 0
+        return dw
+
+    def inputs_of(self, dw, idx):
+        """The per-chain inputs of chains `idx` as the device holds them, in host_workload's form (for the bit-for-bit check of
+        the two evaluations before a run)."""
+        import torch
+        sel = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dw.device)
+        g = lambda t: t.index_select(t.dim() - 1, sel).cpu().numpy()
+        d = {k: g(getattr(dw, k)) for k in ("prm", "s_init", "Ps_init", "s_final", "Ps_final", "Q")}
+        if dw.R_scalar is not None:
+            d["R_scalar"] = g(dw.R_scalar)
+        if self.x_mode != "own":
+            d["x_series"] = g(dw.x_series)
+        if self.u_mode not in ("own", "table"):
+            d["u_series"] = g(dw.u_series)
+        if self.x_mode == "own":
+            d["x"] = g(dw.x)
+            if dw.R_series is not None:
+                d["R_series"] = g(dw.R_series)
+        if self.u_mode == "own":
+            d["u"] = g(dw.u)
+        if self.u_mode == "table":               # the series each sampled chain reads, whole
+            us = g(dw.u_series).astype(np.int64)
+            d["u_of_chain"] = dw.u.index_select(2, torch.as_tensor(us, device=dw.device)).cpu().numpy()
+        return d
+
+
+def chain_offsets(c, rows, B, blk):
+    """Byte offsets [rows, n] of chains c within ONE day of a `rows`-row fp64 array: blocked layout [nblk][rows][blk] when
+    blk < B, else classic [rows][B]."""
+    c = np.asarray(c, dtype=np.int64)
+    row = np.arange(rows, dtype=np.int64)[:, None]
+    if blk >= B:
+        return (row * B + c[None]) * 8
+    return ((c // blk)[None] * rows * blk + row * blk + (c % blk)[None]) * 8
+
+
+def extreme_sample(B, blk, units=(), n_spread=200, rows=(36, 21), itemsize=8):
+    """The chains a test at an addressing limit compares against the oracle: 0, 1, B-2, B-1; both sides of the boundary
+    nearest to B/2 and to B of every unit in `units` (layout block, wavefront, workgroup, chain range); for each row count in
+    `rows`, both sides of the chain where the byte offset within a day slice first reaches 2^31 and 2^32 (any row), when the
+    slice is that large; n_spread more by linspace.  Returns (idx, classes): classes maps a name to the chains of that class."""
+    cls = {"ends": [0, 1, B - 2, B - 1]}
+    for u in sorted(set(int(v) for v in units if 1 < v < B)):
+        near = []
+        for target in (B // 2, B):
+            k = max(1, min((B - 1) // u, int(round(target / u))))
+            near += [k * u - 1, k * u, k * u + 1]
+        cls["unit%d" % u] = near
+    for r in rows:
+        for bit in (31, 32):
+            lim = (1 << bit) // (itemsize)             # element index within the day slice
+            if blk >= B:                                # classic: element = row * B + c; the first row that reaches it
+                hits = [lim - row * B for row in range(r) if 0 <= lim - row * B < B]
+            else:                                       # blocked: element = cb * r * blk + row * blk + cr
+                cb = lim // (r * blk)
+                hits = [cb * blk + d for d in (0, blk - 1)] + [(cb + 1) * blk]
+                hits = [h for h in hits if h < B]
+                if lim >= ((B + blk - 1) // blk) * r * blk:
+                    hits = []
+            if hits:
+                cls["rows%d_bit%d" % (r, bit)] = sorted({h + d for h in hits for d in (-1, 0, 1)})
+    cls["spread"] = np.linspace(0, B - 1, n_spread).astype(np.int64).tolist()
+    idx = np.unique(np.concatenate([np.asarray(v, dtype=np.int64) for v in cls.values()]))
+    idx = idx[(idx >= 0) & (idx < B)]
+    return idx, {k: [int(x) for x in v if 0 <= x < B] for k, v in cls.items()}
+
+
+def poison_runner(r):
+    """Every output, the workspace and the extras of an EkfRunner filled with the poison patterns."""
+    import torch
+    for t in list(r.out.values()) + [r.ws]:
+        if t.dtype == torch.float32:
+            t.view(torch.int32).fill_(POISON32)
+        else:
+            t.view(torch.int64).fill_(POISON64)
+    if r.pinv_rank is not None:
+        r.pinv_rank.fill_(POISON_RANK)
+        r.status.fill_(POISON_STATUS)
+
+
+def surviving_poison(r):
+    """{name: count} of the words of every selected output (pinv_rank and status included) that still hold the poison pattern
+    after a run, over the WHOLE batch -- the lanes a blocked layout pads the last block with are not outputs and not counted."""
+    import torch
+    B, blk, nblk = r.dw.B, r.blk, r.nblk
+    left = {}
+    tensors = dict(r.out)
+    if r.pinv_rank is not None:
+        tensors["pinv_rank"], tensors["status"] = r.pinv_rank, r.status
+    for name, t in tensors.items():
+        n = 0
+        if name == "status":
+            n = int((t == POISON_STATUS).sum())
+        else:
+            for day in range(t.shape[0]):
+                s = t[day]
+                if s.dtype == torch.int32:
+                    hit = s == POISON_RANK
+                elif s.dtype == torch.float32:
+                    hit = s.view(torch.int32) == POISON32
+                else:
+                    hit = s.view(torch.int64) == POISON64
+                if blk < B and s.dim() == 3:                    # [nblk, rows, blk]
+                    n += int(hit[:nblk - 1].sum()) + int(hit[nblk - 1, :, :B - (nblk - 1) * blk].sum())
+                else:                                           # [rows, B] or [B (padded)]
+                    n += int(hit[..., :B].sum())
+        if n:
+            left[name] = n
+    return left
+
+
+def sampled_output(r, name, idx):
+    """[T, rows, n] ([T, n]) NumPy array of chains idx of output `name` (or "pinv_rank"), gathered on the device from the
+    layout run() wrote -- the offsets restated here (chain_offsets), without a copy of the whole array."""
+    import torch
+    t = r.pinv_rank if name == "pinv_rank" else r.out[name]
+    dev = t.device
+    B, blk = r.dw.B, r.blk
+    T = t.shape[0]
+    if t.dim() == 2:
+        return t.index_select(1, torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dev)).cpu().numpy()
+    rows = t.shape[-2]
+    pos = chain_offsets(idx, rows, B, blk) // 8
+    got = t.reshape(T, -1).index_select(1, torch.as_tensor(pos.reshape(-1), device=dev))
+    return got.reshape(T, rows, len(idx)).cpu().numpy()
