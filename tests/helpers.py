@@ -694,3 +694,180 @@ def sampled_output(r, name, idx):
     pos = chain_offsets(idx, rows, B, blk) // 8
     got = t.reshape(T, -1).index_select(1, torch.as_tensor(pos.reshape(-1), device=dev))
     return got.reshape(T, rows, len(idx)).cpu().numpy()
+
+
+# ---------------------------------------------------------------- whole-batch comparisons of the full-size runs
+# ("Every chain of the full-size runs").  The equality is the suite's np.array_equal(..., equal_nan=True): NaN equals
+# NaN whatever its payload, +0 equals -0, nothing else is equal that is not the same number.  words_equal() is that rule element
+# by element on torch tensors, so that it can be evaluated where the data lies (tests/test_whole_batch_helpers.py holds it
+# against NumPy's).
+def words_equal(a, b):
+    """bool tensor: a[i] and b[i] are the same number, or both NaN (integers: the same value)."""
+    import torch
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    eq = a == b
+    if a.dtype.is_floating_point:
+        eq |= torch.isnan(a) & torch.isnan(b)
+    return eq
+
+
+def _runner_tensors(r, names=None, status=False):
+    """{name: tensor}: names=None -- every output the runner holds (in OUT_NAMES order) and pinv_rank; else exactly `names`.
+    status=True adds the per-chain status words."""
+    if names is None:
+        d = {n: r.out[n] for n in OUT_NAMES if n in r.out}
+        if r.pinv_rank is not None:
+            d["pinv_rank"] = r.pinv_rank
+    else:
+        d = {n: (r.pinv_rank if n == "pinv_rank" else r.out[n]) for n in names}
+    assert d and all(t is not None for t in d.values()), (names, list(r.out))
+    if status and r.status is not None:
+        d["status"] = r.status
+    return d
+
+
+def chain_slice(t, lo, hi, B, blk):
+    """[T', rows, hi - lo] ([T', hi - lo]) of chains [lo, hi) of an output in the runner's layout -- classic [T', rows, B] /
+    [T', B (padded)] or blocked [T', nblk, rows, blk]; lo a multiple of blk when blocked.  Only the blocks that hold the range
+    are unblocked (a copy of that slice, never of the array)."""
+    if t.dim() == 2 or blk >= B:
+        return t[..., lo:hi]
+    assert lo % blk == 0, (lo, blk)
+    s = t[:, lo // blk:(hi + blk - 1) // blk]
+    T, nb, rows, _ = s.shape
+    return s.permute(0, 2, 1, 3).reshape(T, rows, nb * blk)[:, :, :hi - lo]
+
+
+def chain_ranges(B, blk, chunk):
+    """[(lo, hi)] that cover chains 0 .. B-1 exactly once, at most `chunk` chains each (one layout block where a block is larger),
+    every lo a multiple of the layout block `blk` (blk >= B: classic layout, any start)."""
+    step = int(chunk) if blk >= B else max(blk, int(chunk) // blk * blk)
+    assert step >= 1
+    return [(lo, min(B, lo + step)) for lo in range(0, B, step)]
+
+
+def describe_mismatch(name, got, ref, lo, day0, blk, B, what, first=6):
+    """The failure message of a whole-batch comparison.  got / ref: NumPy arrays [T', rows, n] ([T', n]) of chains lo .. lo+n-1
+    and days day0 .. day0+T'-1 that differ somewhere."""
+    g3, r3 = (a[:, None, :] if a.ndim == 2 else a for a in (got, ref))
+    with np.errstate(invalid="ignore"):
+        bad = ~((g3 == r3) | ((g3 != g3) & (r3 != r3)))
+    chains = np.flatnonzero(bad.any(axis=(0, 1)))
+    cells = np.argwhere(bad.transpose(2, 0, 1))              # (chain, day, row), chain-major
+    lines = []
+    for c, d, row in cells[:first]:
+        lines.append("(chain %d, day %d, row %d): got %r, expected %r" % (lo + c, day0 + d, row, g3[d, row, c].item(), r3[d, row, c].item()))
+    msg = "%s: %s differs in %d chain(s) of [%d, %d), %d word(s)" % (what, name, chains.size, lo, lo + g3.shape[2], int(bad.sum()))
+    if blk < B:
+        badc, n = bad.any(axis=(0, 1)), g3.shape[2]
+        blocks = np.unique((lo + chains) // blk)
+        whole = [int(b) for b in blocks if b * blk >= lo and min(B, (b + 1) * blk) <= lo + n
+                 and badc[b * blk - lo:min(B, (b + 1) * blk) - lo].all()]
+        msg += "; layout blocks (chain // %d): %s%s" % (blk, blocks[:12].tolist(), " ..." if blocks.size > 12 else "")
+        msg += ("; EVERY chain of block(s) %s" % whole[:12]) if whole else "; no block differs in all its chains"
+    days = day0 + np.flatnonzero(bad.any(axis=(1, 2)))
+    msg += "; days %d .. %d (%d of them)" % (days.min(), days.max(), days.size)
+    return msg + "\n  " + "\n  ".join(lines)
+
+
+def all_chains_equal_oracle(r, w, names=None, chunk=2400, what=""):
+    """EVERY chain of runner `r`'s outputs (and pinv_rank) against the C oracle's run of Workload `w`, bit for bit: the batch is
+    walked in chain ranges that start on layout blocks and cover 0 .. B-1 exactly once; per range the oracle runs those chains
+    alone, its arrays go to where the outputs lie and are compared there with words_equal (fp32 storage: against the oracle's
+    result rounded once).  Host memory is bounded by the range (2 400 six-state chains x 520 days x all outputs: 1.6 GB).  The
+    first range that differs fails the call -- no further range is run -- with the output, the number of differing chains, the
+    first (chain, day, row) with both values and the layout blocks they fall in.  The number of chains compared is asserted to be
+    w.B: no chain may be left out.  Returns {"chains", "ranges", "oracle_s", "transfer_s", "compare_s"} (and prints it)."""
+    import time
+    import torch
+    B, blk = r.dw.B, r.blk
+    assert B == w.B, (B, w.B)
+    tensors = _runner_tensors(r, names)
+    stat = {"chains": 0, "ranges": 0, "oracle_s": 0.0, "transfer_s": 0.0, "compare_s": 0.0}
+    dev = next(iter(tensors.values())).device
+    sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
+    seen_to = 0
+    for lo, hi in chain_ranges(B, blk, chunk):
+        assert lo == seen_to and hi > lo and (blk >= B or lo % blk == 0), (lo, hi, seen_to, blk)
+        t0 = time.perf_counter()
+        ref = oracle_batch(w.select(np.arange(lo, hi)))
+        stat["oracle_s"] += time.perf_counter() - t0
+        for name, t in tensors.items():
+            assert name in ref, name
+            e = ref[name].astype(np.float32) if t.dtype == torch.float32 else ref[name]
+            t0 = time.perf_counter()
+            exp = torch.from_numpy(np.ascontiguousarray(e)).to(dev)
+            sync()
+            t1 = time.perf_counter()
+            got = chain_slice(t, lo, hi, B, blk)
+            assert got.shape == exp.shape and got.shape[-1] == hi - lo, (name, got.shape, exp.shape)
+            same = bool(words_equal(got, exp).all())
+            t2 = time.perf_counter()
+            stat["transfer_s"] += t1 - t0
+            stat["compare_s"] += t2 - t1
+            if not same:
+                raise AssertionError(describe_mismatch(name, got.cpu().numpy(), e, lo, 0, blk, B, what or "against the oracle"))
+            del exp, got
+        stat["chains"] += hi - lo
+        stat["ranges"] += 1
+        seen_to = hi
+    assert stat["chains"] == w.B and seen_to == w.B, (stat["chains"], w.B)
+    print("all_chains_equal_oracle%s: %d of %d chains in %d ranges equal the oracle in %s; oracle %.1f s, transfers %.1f s, compare %.1f s"
+          % (" [" + what + "]" if what else "", stat["chains"], w.B, stat["ranges"], ", ".join(tensors), stat["oracle_s"],
+             stat["transfer_s"], stat["compare_s"]))
+    return stat
+
+
+def snapshot_outputs(r):
+    """Clones of every output of a runner, pinv_rank and status, where they lie (what device_outputs_equal compares against)."""
+    return {n: t.clone() for n, t in _runner_tensors(r, status=True).items()}
+
+
+def snapshot_views(r):
+    """The same dict of the runner's own tensors, not clones (to hold ANOTHER runner against, e.g. fp32 storage against fp64)."""
+    return dict(_runner_tensors(r, status=True))
+
+
+def device_outputs_equal(r, saved, days=8, rounded=False, what=""):
+    """Every word of every output of runner `r` (pinv_rank and status too) against `saved` -- clones taken earlier
+    (snapshot_outputs), or another runner's tensors of the same layout -- with words_equal, evaluated where the tensors lie, `days`
+    days at a time (the temporaries stay small).  The lanes a blocked layout pads its last block with are not outputs and not
+    compared.  rounded=True: `saved` holds fp64 results and `r` fp32 storage; each saved word is rounded once first.  The first
+    output that differs fails the call, in all_chains_equal_oracle's terms.  Returns {"chains", "words", "compare_s"}."""
+    import time
+    import torch
+    B, blk = r.dw.B, r.blk
+    tensors = _runner_tensors(r, status=True)
+    assert set(tensors) == set(saved), (sorted(tensors), sorted(saved))
+    dev = next(iter(tensors.values())).device
+    t0 = time.perf_counter()
+    words = 0
+    for name, t in tensors.items():
+        s = saved[name]
+        assert s.shape == t.shape and s.device == t.device and s.data_ptr() != t.data_ptr(), name
+        assert s.dtype == t.dtype or (rounded and t.dtype == torch.float32 and s.dtype == torch.float64), (name, s.dtype, t.dtype)
+        if name == "status":
+            a, b = t[None, :B], s[None, :B]               # one "day"
+        else:
+            a, b = t, s
+        for d0 in range(0, a.shape[0], days):
+            ga, gb = (chain_slice(x[d0:d0 + days], 0, B, B, blk) for x in (a, b))
+            if gb.dtype != ga.dtype:
+                gb = gb.to(ga.dtype)
+            assert ga.shape[-1] == B
+            words += ga.numel()
+            if not bool(words_equal(ga, gb).all()):
+                bad = (~words_equal(ga, gb)).reshape(ga.shape[0], -1, B).any(dim=1).any(dim=0)
+                c0 = int(torch.nonzero(bad)[0])
+                lo = c0 if blk >= B else c0 // blk * blk
+                hi = min(B, lo + max(blk if blk < B else 0, 2400))
+                raise AssertionError(describe_mismatch(name, ga[..., lo:hi].cpu().numpy(), gb[..., lo:hi].cpu().numpy(), lo, d0, blk, B,
+                                                       (what or "against the saved outputs") + " (%d chain(s) of the batch differ in these days)"
+                                                       % int(bad.sum())))
+            del ga, gb
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    stat = {"chains": B, "words": words, "compare_s": time.perf_counter() - t0}
+    print("device_outputs_equal%s: %d chains, %d words in %s equal; %.1f s"
+          % (" [" + what + "]" if what else "", B, words, ", ".join(tensors), stat["compare_s"]))
+    return stat

@@ -36,6 +36,47 @@ def _run(w, device, **kw):
     return batch.run_workload(w, device=device, **kw)
 
 
+def _room_for_clones(r, device):
+    """Before a second copy of a runner's outputs is taken on the device: assert that it fits (a failure, not a skip)."""
+    import torch
+    torch.cuda.empty_cache()
+    need = r.output_bytes() + (r.pinv_rank.numel() + r.status.numel()) * 4
+    free, total = torch.cuda.mem_get_info(device)
+    assert free >= need + (2 << 30), ("clones of the outputs (%.1f GB) do not fit beside them: %.1f GB of %.1f GB free"
+                                      % (need / 1e9, free / 1e9, total / 1e9))
+
+
+def _peak_memory(tag):
+    import torch
+    print("peak device memory [%s]: %.1f GB" % (tag, torch.cuda.max_memory_allocated() / 1e9))
+
+
+def _back_to_back_and_graph_replay(r, saved, enqueue, what):
+    """The conditions bench.py times under, which one cold pass behind a synchronise does not meet ("Every chain of the
+    full-size runs"): every output and the workspace poisoned by stream-ordered fills, then FIVE passes (bench.py's documented
+    --steps 5; a fixed count, not a loop until something differs) enqueued back to back without a synchronisation between them,
+    one synchronise, and the whole batch against `saved` (clones of outputs that equalled the oracle chain by chain).  Then the
+    same call captured into a HIP graph behind a warm-up pass, the outputs poisoned again, ONE replay, and the whole batch again.
+    enqueue(): one pass on the current stream."""
+    import torch
+    H.poison_runner(r)
+    for _ in range(5):
+        enqueue()
+    torch.cuda.synchronize()
+    H.device_outputs_equal(r, saved, what=what + ", last of 5 passes back to back")
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        r.run()                                         # warm-up outside the capture (helper streams get created)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        r.run(stream=s)
+    H.poison_runner(r)
+    g.replay(); torch.cuda.synchronize()
+    H.device_outputs_equal(r, saved, what=what + ", graph replay")
+    del g
+
+
 SHAPES = ["lane", "quad", "wave", "hex"]     # epi_batch_desc.shape: one lane / four lanes / one wavefront / six lanes per chain (6-state generic models)
 
 
@@ -1109,8 +1150,13 @@ def test_time_pipelined_launch_with_blocked_layout(gpu_device, blk):
 def test_headline_sweep_at_full_size_sampled_chains(gpu_device, lane_block, live):
     """BASELINE's headline configuration at full size -- 300 regions x 250 cost weights x (400 + 120) days = 75 000 chains,
     all 11 outputs (49 GB) -- checked through a size-independent property: chains are independent, so every chain of the
-    big batch must equal, bit for bit, the oracle's run of that chain alone.  257 chains spread over the batch (first,
-    last, wave and block boundaries included).  live: the same sweep on the living multi-wave epidemic
+    big batch must equal, bit for bit, the oracle's run of that chain alone.  First 257 chains spread over the batch (first,
+    last, wave and block boundaries included: where an error that depends on a chain's PLACE would sit), then ALL 75 000, in chain
+    ranges (H.all_chains_equal_oracle: an error that depends on WHEN something happens -- a stale LDS-DMA image, a missing event
+    edge between the chain ranges' launches -- hits a few waves somewhere, and the sample would see one bad wave of 1 875 with
+    13 %).  The second pass, through the one-call sweep entry into poisoned outputs, is compared over the whole batch with device
+    clones of the first; on the library's own layout and the dead workload also the last of five sweep passes enqueued back to
+    back and the replay of a captured graph (_back_to_back_and_graph_replay).  live: the same sweep on the living multi-wave epidemic
     (synth.make_cfg4(live=True), `bench.py --workload cfg4-live`), whose covariances keep full rank for ~150 days and then
     drop to rank 1 -- another mix of the pinv routes than the survey's series."""
     _headline_sweep_sampled(gpu_device, lane_block, live)
@@ -1119,13 +1165,15 @@ def test_headline_sweep_at_full_size_sampled_chains(gpu_device, lane_block, live
 def test_headline_sweep_at_full_size_one_npi(gpu_device):
     """The headline sweep at full size with n_npi = 1, on the library's own 40-chain layout: the one-lane smoother that takes X
     by LDS-DMA (eks_bwd_lane6 with XD = 1) then issues the fewest vector-memory operations between that DMA and the image's
-    reads (64 + n_npi), and this is the one test that runs it under the memory pressure of 75 000 chains."""
+    reads (64 + n_npi), and this is the one test that runs it under the memory pressure of 75 000 chains -- all of which are
+    compared with the oracle, not a sample of them (a stale image would be whole 40-chain blocks from one day down)."""
     _headline_sweep_sampled(gpu_device, "auto", False, n=1)
 
 
 def _headline_sweep_sampled(gpu_device, lane_block, live, n=12):
     import torch
     from epidemicmodeling_amd import batch, synth
+    torch.cuda.reset_peak_memory_stats()
     w = synth.make_cfg4(live=live)
     assert (w.B, w.T) == (75000, 520)
     if n < 12:
@@ -1157,9 +1205,15 @@ def _headline_sweep_sampled(gpu_device, lane_block, live, n=12):
         mid = np.sqrt(ti[30:].min(axis=0) * ti[30:].max(axis=0))
         waves = ((ti[31:] > mid) & (ti[30:-1] <= mid)).sum(axis=0)
         assert waves.min() >= 2, waves.min()
+    # every chain, not the sample: 75 000 of 75 000 (the count is asserted inside)
+    tag = "headline lane_block=%s live=%s n_npi=%d" % (lane_block, live, n)
+    assert H.all_chains_equal_oracle(r, w, what=tag)["chains"] == 75000
     # the same batch through the one-call sweep entry (what bench.py times): the smoother cut in two, scoring and Pareto
-    # filter beside its second launch.  Outputs poisoned first; the sampled chains again, and (J0, J1), front, I_opt against
-    # the separate scoring / filter calls on the first run's u_opt_smooth
+    # filter beside its second launch.  Outputs poisoned first; the sampled chains again, the WHOLE batch against device clones
+    # of the outputs verified above, and (J0, J1), front, I_opt against the separate scoring / filter calls on the first run's
+    # u_opt_smooth
+    _room_for_clones(r, gpu_device)
+    saved = H.snapshot_outputs(r)
     rng = np.random.default_rng(4)
     sp, j0p, j1p = _sweep_scoring_inputs(w, rng)
     to = lambda a: torch.as_tensor(a, dtype=torch.float64).to(gpu_device)
@@ -1177,15 +1231,24 @@ def _headline_sweep_sampled(gpu_device, lane_block, live, n=12):
     assert torch.equal(sc1["J0"], J0_0) and torch.equal(sc1["J1"], J1_0)
     assert torch.equal(sc1["on_front"].bool(), on0) and torch.equal(sc1["i_opt"], io0)
     assert np.array_equal(r.status.cpu().numpy(), st)
-    del r, dw
+    assert H.device_outputs_equal(r, saved, what=tag + ", sweep entry")["chains"] == 75000
+    if lane_block == "auto" and not live and n == 12:
+        for k, v in (("J0", float("nan")), ("J1", float("nan")), ("on_front", -1), ("i_opt", -1)):
+            sc1[k].fill_(v)
+        _back_to_back_and_graph_replay(r, saved, lambda: r.run_sweep(400, sp_d, j0_d, j1_d, n_regions=w.Sx), tag)
+        assert torch.equal(sc1["J0"], J0_0) and torch.equal(sc1["J1"], J1_0)        # sc1 holds the views the sweep passes wrote
+        assert torch.equal(sc1["on_front"].bool(), on0) and torch.equal(sc1["i_opt"], io0)
+    _peak_memory(tag)
+    del r, dw, saved
     torch.cuda.empty_cache()
 
 
 def test_monte_carlo_eks_at_full_size_sampled_chains(gpu_device):
     """BASELINE config 5 at full size (300 regions x 1024 draws x 400 days = 307 200 three-state chains, fp64): sampled
-    chains equal the oracle's run of the same chains alone, bit for bit."""
+    chains, and then all 307 200 in chain ranges, equal the oracle's run of the same chains alone, bit for bit."""
     import torch
     from epidemicmodeling_amd import batch, synth
+    torch.cuda.reset_peak_memory_stats()
     w = synth.make_cfg5(300, 1024, 400)
     assert w.B == 307200
     idx = np.unique(np.concatenate([np.linspace(0, w.B - 1, 200).astype(np.int64), [55, 56, 57, 63, 64, 1023, 1024, 307199]]))
@@ -1197,6 +1260,8 @@ def test_monte_carlo_eks_at_full_size_sampled_chains(gpu_device):
     sel = torch.as_tensor(idx, device=gpu_device)
     for n in H.OUT_NAMES:
         assert np.array_equal(r.unblocked(n).index_select(-1, sel).cpu().numpy(), ref[n], equal_nan=True), n
+    assert H.all_chains_equal_oracle(r, w, what="Monte-Carlo EKS fp64")["chains"] == 307200
+    _peak_memory("Monte-Carlo EKS fp64")
     del r, dw
     torch.cuda.empty_cache()
 
@@ -1491,9 +1556,11 @@ def test_bench_contract_single_and_two_ranks(gpu_device, tmp_path):
 def test_newcase_sweep_at_full_size_sampled_chains(gpu_device):
     """BASELINE's "NewCaseEKFEstimatorWithOptimalNPI: 300 regions x 250 NPI-cost weights x 120-day horizon" at full size
     (75 000 dense-kernel chains x 520 days, mrdivide smoother): every sampled chain of the big batch equals the oracle's run
-    of that chain alone, bit for bit (first, last, wave and layout-block boundaries included)."""
+    of that chain alone, bit for bit (first, last, wave and layout-block boundaries included), and then every chain of all 75 000
+    does (the outputs the reference has; its mrdivide smoother has no pinv ranks)."""
     import torch
     from epidemicmodeling_amd import batch, synth
+    torch.cuda.reset_peak_memory_stats()
     w = synth.make_newcase_sweep()
     assert (w.B, w.T) == (75000, 520)
     idx = np.unique(np.concatenate([np.linspace(0, w.B - 1, 121).astype(np.int64),
@@ -1509,6 +1576,8 @@ def test_newcase_sweep_at_full_size_sampled_chains(gpu_device):
     for n in names:
         got = r.unblocked(n).index_select(-1, sel).cpu().numpy()
         assert np.array_equal(got, ref[n], equal_nan=True), n
+    assert H.all_chains_equal_oracle(r, w, names=names, what="NewCase sweep")["chains"] == 75000
+    _peak_memory("NewCase sweep")
     del r, dw
     torch.cuda.empty_cache()
 
@@ -1823,12 +1892,16 @@ def test_strong_scaling_shard_at_full_size(gpu_device, rank, shape):
     """What one of 8 GPUs runs when the FIXED headline sweep (75 000 chains x 520 days) is sharded by chain blocks
     (bench.py --gpus 8): 9 375 chains, which the library maps six lanes per chain, ten chains per wavefront (shape auto,
     round 5; four lanes per chain until round 4 -- still run here when asked for).  Sampled chains of the shard -- lane-group,
-    wavefront and layout-block boundaries of both shapes included -- equal the oracle's run of those chains alone."""
+    wavefront and layout-block boundaries of both shapes included -- equal the oracle's run of those chains alone, and then all
+    9 375 do (938 hex wavefronts: the stale image of DESIGN.md 4.1 sat in about 3 of them, which the sample saw with 35 %).  Rank
+    0 on the library's own shape also runs five passes back to back and one replay of a captured graph -- the fork/join of the
+    reverse-time pipeline inside it -- into poisoned outputs, each compared over the whole shard (_back_to_back_and_graph_replay)."""
     import torch
     from epidemicmodeling_amd import batch, synth
     w = synth.make_cfg4()
     lo, hi = batch.shard_chains(w.B, rank, 8)
     assert hi - lo == 9375
+    torch.cuda.reset_peak_memory_stats()
     ws = w.select(np.arange(lo, hi))
     idx = np.unique(np.concatenate([np.linspace(0, ws.B - 1, 120).astype(np.int64),
                                     [9, 10, 11, 15, 16, 17, 59, 60, 63, 64, 9359, 9360, 9369, 9370, 9374]]))
@@ -1842,6 +1915,13 @@ def test_strong_scaling_shard_at_full_size(gpu_device, rank, shape):
     for n in H.OUT_NAMES:
         assert np.array_equal(r.unblocked(n).index_select(-1, sel).cpu().numpy(), ref[n], equal_nan=True), n
     assert np.array_equal(r.unblocked("pinv_rank").index_select(-1, sel).cpu().numpy(), ref["pinv_rank"])
+    tag = "shard rank %d shape %s" % (rank, shape)
+    assert H.all_chains_equal_oracle(r, ws, what=tag)["chains"] == 9375
+    if rank == 0 and shape == "auto":
+        _room_for_clones(r, gpu_device)
+        saved = H.snapshot_outputs(r)
+        _back_to_back_and_graph_replay(r, saved, r.run, tag)
+    _peak_memory(tag)
 
 
 def _sweep_params(w, device, seed=5):
@@ -1862,10 +1942,20 @@ def _sweep_params(w, device, seed=5):
 
 
 def _check_sweep_entry(r, w, t_hist, n_regions, ref, device, sel=None):
-    """run_sweep against the oracle (filter outputs) and against the separate scoring / Pareto calls on the u_opt_smooth it wrote"""
+    """run_sweep against the oracle (filter outputs) and against the separate scoring / Pareto calls on the u_opt_smooth it wrote.
+    sel given (a batch too large to bring down whole; `ref` holds chains sel only): a plain run() first, EVERY chain of it against
+    the oracle in chain ranges, device clones of that; then run_sweep into poisoned outputs, its sampled chains against `ref` and
+    its whole batch against the clones."""
     import torch
     from epidemicmodeling_amd import batch
     sp, j0, j1 = _sweep_params(w, device)
+    saved = None
+    if sel is not None:
+        r.run()
+        torch.cuda.synchronize()
+        assert H.all_chains_equal_oracle(r, w, what="reverse-time pipeline, %d chains x %d days" % (w.B, w.T))["chains"] == w.B
+        _room_for_clones(r, device)
+        saved = H.snapshot_outputs(r)
     for t in list(r.out.values()) + [r.ws]:
         t.fill_(float("nan"))
     sc = r.run_sweep(t_hist, sp, j0, j1, n_regions=n_regions)
@@ -1874,6 +1964,8 @@ def _check_sweep_entry(r, w, t_hist, n_regions, ref, device, sel=None):
     for n in r.out:
         assert np.array_equal(pick(r.unblocked(n)).cpu().numpy(), ref[n], equal_nan=True), n
     assert np.array_equal(pick(r.unblocked("pinv_rank")).cpu().numpy(), ref["pinv_rank"])
+    if saved is not None:
+        assert H.device_outputs_equal(r, saved, what="sweep entry, %d chains x %d days" % (w.B, w.T))["chains"] == w.B
     sc2 = batch.score_sweep(r.out["u_opt_smooth"], t_hist, sp, j0, j1, B=w.B)
     assert torch.equal(sc["J0"], sc2["J0"]) and torch.equal(sc["J1"], sc2["J1"])
     if n_regions:
@@ -1935,8 +2027,8 @@ def test_hex_reverse_time_pipeline_forced_at_small_batches(gpu_device, window):
 def test_sweep_entry_through_the_reverse_time_pipeline_at_size(gpu_device, regions, eps, T_hist, hor):
     """The call bench.py times for the 8-GPU shard -- epi_sweep_run_device on 9 375 chains x 520 days -- and a batch beyond one hex
     wavefront per SIMD with T >= 128 (10 375 chains x 132 days: the smoother's no-prefetch variant resuming from hand-over rows)
-    both take the reverse-time pipeline by themselves: sampled chains against the oracle, (J0, J1) / front / I_opt against the
-    separate calls."""
+    both take the reverse-time pipeline by themselves: sampled chains and then all 9 375 / 10 375 against the oracle (a plain call),
+    the sweep entry's whole batch against device clones of that, (J0, J1) / front / I_opt against the separate calls."""
     import torch
     from epidemicmodeling_amd import batch, synth
     w = synth.make_cfg4(n_regions=regions, n_eps=eps, T_hist=T_hist, horizon=hor)
@@ -2021,8 +2113,8 @@ def test_one_lane_batch_cut_into_two_chain_ranges(gpu_device):
 def test_hex_two_waves_per_simd_kernels(gpu_device, window):
     """Beyond one hex wavefront per SIMD (10 240 chains on MI355X) the library launches the hex kernels' other variants -- no
     prefetch set in the smoother, no register clobber in the forward kernel, two waves per SIMD -- which no smaller test reaches:
-    10 375 chains x 26 days, sampled chains against the oracle's run of those chains alone; once more with short addressing
-    windows (see test_hex_addressing_windows)."""
+    10 375 chains x 26 days, sampled chains and then all 10 375 against the oracle's run of those chains alone; once more with
+    short addressing windows (see test_hex_addressing_windows)."""
     import torch
     from epidemicmodeling_amd import batch, synth
     w = synth.make_cfg4(n_regions=83, n_eps=125, T_hist=20, horizon=6)
@@ -2038,6 +2130,40 @@ def test_hex_two_waves_per_simd_kernels(gpu_device, window):
     for n in H.OUT_NAMES:
         assert np.array_equal(r.unblocked(n).index_select(-1, sel).cpu().numpy(), ref[n], equal_nan=True), n
     assert np.array_equal(r.unblocked("pinv_rank").index_select(-1, sel).cpu().numpy(), ref["pinv_rank"])
+    assert H.all_chains_equal_oracle(r, w, what="hex, two waves per SIMD, window %d" % window)["chains"] == 10375
+
+
+def test_whole_batch_comparisons_see_one_word_on_the_device(gpu_device):
+    """The whole-batch helpers (tests/test_whole_batch_helpers.py tests them on CPU tensors) where the full-size tests use them: on
+    device tensors the library wrote, hex shape on its 10-chain layout with a padded last block.  One word of the device's output
+    moved by 1 ulp, in a chain the full-size tests' kind of sample does not hold, fails both comparisons with its (chain, day, row)
+    and block; put back, both pass again."""
+    import torch
+    from epidemicmodeling_amd import batch, synth
+    w = synth.make_cfg4(n_regions=9, n_eps=37, T_hist=20, horizon=6)            # 333 chains: 34 blocks of 10, the last one of 3
+    r = batch.EkfRunner(batch.DeviceWorkload(w, gpu_device), extras=True, lane_block=10, shape="hex")
+    r.run()
+    torch.cuda.synchronize()
+    assert H.all_chains_equal_oracle(r, w, chunk=100)["chains"] == 333
+    saved = H.snapshot_outputs(r)
+    idx = np.unique(np.concatenate([np.linspace(0, w.B - 1, 3).astype(np.int64), [9, 10, 11, 59, 60, 63, 64, w.B - 1]]))
+    chain, day, row = 217, 13, 7
+    assert chain not in idx
+    word = r.out["P_SMOOTH"][day, chain // 10, row]
+    old = float(word[chain % 10])
+    assert np.isfinite(old) and old != 0.0
+    word[chain % 10] = float(np.nextafter(old, np.inf))
+    where = "(chain %d, day %d, row %d)" % (chain, day, row)
+    for check in (lambda: H.all_chains_equal_oracle(r, w, chunk=100), lambda: H.device_outputs_equal(r, saved)):
+        with pytest.raises(AssertionError) as e:
+            check()
+        assert "P_SMOOTH differs in 1 chain(s)" in str(e.value) and where in str(e.value) and "(chain // 10): [21]" in str(e.value), str(e.value)
+    word[chain % 10] = old
+    H.all_chains_equal_oracle(r, w, chunk=100)
+    H.device_outputs_equal(r, saved)
+    H.poison_runner(r)
+    with pytest.raises(AssertionError):
+        H.device_outputs_equal(r, saved)
 
 
 def test_host_entry_keeps_the_fastest_of_several_arenas(gpu_device):
@@ -2204,9 +2330,13 @@ def test_fp32_storage_outputs_are_the_fp64_results_rounded_once(gpu_device):
 
 def test_monte_carlo_eks_fp32_storage_at_full_size_sampled_chains(gpu_device):
     """BASELINE config 5 as written -- 300 regions x 1024 draws x 400 days, fp32 storage -- at full size (307 200 chains):
-    sampled chains of the big batch equal float32(the oracle's fp64 run of those chains alone), bit for bit."""
+    sampled chains of the big batch equal float32(the oracle's fp64 run of those chains alone), bit for bit.  The rule "fp32
+    storage is the fp64 result rounded once" is then checked on the device over ALL 307 200 chains against an fp64 run of the same
+    batch -- the run that test_monte_carlo_eks_at_full_size_sampled_chains holds against the oracle chain by chain (the oracle is
+    not run a second time over 123 M chain-days; here the fp64 run's sampled chains are held against it)."""
     import torch
     from epidemicmodeling_amd import batch, synth
+    torch.cuda.reset_peak_memory_stats()
     w = synth.make_cfg5(300, 1024, 400)
     idx = np.unique(np.concatenate([np.linspace(0, w.B - 1, 200).astype(np.int64), [55, 56, 57, 63, 64, 1023, 1024, 307199]]))
     ref = H.oracle_batch(w.select(idx))
@@ -2218,13 +2348,25 @@ def test_monte_carlo_eks_fp32_storage_at_full_size_sampled_chains(gpu_device):
     for n in H.OUT_NAMES:
         got = r.unblocked(n).index_select(-1, sel).cpu().numpy()
         assert got.dtype == np.float32 and np.array_equal(got, ref[n].astype(np.float32), equal_nan=True), n
+    torch.cuda.empty_cache()
+    r64 = batch.EkfRunner(dw, extras=True, lane_block="auto")
+    assert r64.blk == r.blk
+    r64.run()
+    torch.cuda.synchronize()
+    for n in H.OUT_NAMES:
+        assert np.array_equal(r64.unblocked(n).index_select(-1, sel).cpu().numpy(), ref[n], equal_nan=True), n
+    st = H.device_outputs_equal(r, H.snapshot_views(r64), rounded=True, what="fp32 storage against the fp64 run rounded once")
+    assert st["chains"] == 307200
+    _peak_memory("Monte-Carlo EKS fp32 storage + fp64 run")
+    del r64
     del r, dw
     torch.cuda.empty_cache()
 
 
 def test_seirp_ensemble_at_full_size_sampled_members(gpu_device):
     """BASELINE config 2 at full size: a 10 000-member parameter ensemble x 365 days at dt = 0.1 (K = 3 650 Euler steps,
-    SEIRP.m:26-32; the reference has no RK4 -- SURVEY.md 0).  Sampled members equal the oracle bit for bit; the mass
+    SEIRP.m:26-32; the reference has no RK4 -- SURVEY.md 0).  Sampled members, and then all 10 000 (the oracle's simulator takes a
+    member in well under a millisecond), equal the oracle bit for bit; the mass
     s + e + i + r + p stays 1 for EVERY member and step (a size-independent property: the right-hand sides sum to zero)."""
     import ctypes as C
     import torch
@@ -2249,6 +2391,22 @@ def test_seirp_ensemble_at_full_size_sampled_members(gpu_device):
         got = out[:, :, c].cpu().numpy()
         for q in range(5):
             assert np.array_equal(got[:, q], res[q]), (c, q)
+    compared, step = 0, 500
+    cols = [np.empty(K) for _ in range(7)]
+    for lo in range(0, B, step):
+        hi = min(B, lo + step)
+        exp = np.zeros((hi - lo, 5, K))
+        for c in range(lo, hi):
+            for j in range(7):
+                cols[j].fill(par[0, j, c])
+            lib.orc_seirp(*[dp(v) for v in cols], *[C.c_double(init[q, c]) for q in range(5)], C.c_int(K), C.c_double(dt),
+                          *[dp(exp[c - lo, q]) for q in range(5)])
+        got = out[:, :, lo:hi].permute(2, 1, 0).contiguous().cpu().numpy()
+        if not np.array_equal(got, exp, equal_nan=True):
+            bad = np.argwhere(got != exp)
+            raise AssertionError("members [%d, %d): %d words differ, first (member, state, step) %s" % (lo, hi, len(bad), (bad[0] + [lo, 0, 0]).tolist()))
+        compared += hi - lo
+    assert compared == B == 10000
     del out
     torch.cuda.empty_cache()
 
