@@ -64,31 +64,15 @@ EPI_DEV HexLane hx_lane(const KArgs &a)
     const int c = a.c0 + (int)blockIdx.x * kHG + h.g;
     h.live = h.g < kHG && c < a.c0 + a.cn;
     h.c = h.live ? c : a.c0 + a.cn - 1;           // idle groups mirror the last chain: what they compute is dropped
-#ifdef EPI_HEX_NOSTORE           // timing probe: no lane stores anything (results are wrong)
-    h.dead = kHexDead;
-#else
     h.dead = h.live ? 0u : kHexDead;
-#endif
     return h;
 }
 // Ordering of the LDS exchanges.  The hardware executes a wave's LDS operations in issue order, so all that is needed is that
 // the compiler keeps a read behind the write it depends on -- and it must, without being told: every exchange has an LDS array of
 // its own, and in each a lane's write (slot j, or element j of a row) and its reads (element j of every slot, or the whole row)
 // overlap for some j, so they may alias and stay in program order; accesses to DIFFERENT exchanges' arrays are free to move,
-// which is what lets a lone wave fill one exchange's latency with the next one's arithmetic.  EPI_HEX_FENCE=1 puts a
-// wavefront-scope fence around every exchange instead (measured slower).
-#ifndef EPI_HEX_FENCE
-#define EPI_HEX_FENCE 0
-#endif
-#ifndef EPI_HEX_BRANCHLESS
-#define EPI_HEX_BRANCHLESS 0
-#endif
-EPI_DEV void hx_fence()
-{
-#if EPI_HEX_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#endif
-}
+// which is what lets a lone wave fill one exchange's latency with the next one's arithmetic.  (A wavefront-scope fence
+// around every exchange instead measured slower.)
 
 // The stores of this shape are non-temporal but NOT written through (`sc1`, what the other shapes' stores add): a layout row of
 // ten chains is 80 bytes, so a store instruction's 480 contiguous bytes begin and end inside cache lines that the neighbouring
@@ -113,9 +97,7 @@ EPI_DEV void hx_get_tr(const double *t, double (&v)[6])
 // transpose: lane j gives v (column j, or row j) and receives element j of the six lanes' vectors
 EPI_DEV void hx_transpose(double *tile_g, int j, const double (&v)[6], double (&o)[6])
 {
-    hx_fence();
     hx_put6(tile_g + 6 * j, v);
-    hx_fence();
     hx_get_tr(tile_g + j, o);
 }
 // all 36 values of my chain's tile, slot-major: m[6 s + e] = element e of slot s
@@ -286,10 +268,8 @@ EPI_DEV void hx_resolve(const QPrm &p, const HexNpi &n, const ModelFlags &mf, do
 // my two values of a 12-vector to the chain's NPI row, then all twelve in NPI order
 EPI_DEV void hx_gather12(double *row_g, int j, const double (&v2)[2], double (&v)[kNpi])
 {
-    hx_fence();
     row_g[j] = v2[0];
     row_g[j + 6] = v2[1];
-    hx_fence();
     const hx_d2 *q = (const hx_d2 *)row_g;
 #pragma unroll
     for (int e = 0; e < 6; e++) {
@@ -301,9 +281,7 @@ EPI_DEV void hx_gather12(double *row_g, int j, const double (&v2)[2], double (&v
 // my value of a 6-vector to the chain's vector row, then all six
 EPI_DEV void hx_gather6(double *row_g, int j, double mine, double (&v)[6])
 {
-    hx_fence();
     row_g[j] = mine;
-    hx_fence();
     const hx_d2 *q = (const hx_d2 *)row_g;
 #pragma unroll
     for (int e = 0; e < 3; e++) {
@@ -489,12 +467,8 @@ __global__ __launch_bounds__(kWave, SOLO ? 1 : 2) void ekf_fwd_hex(const KArgs a
 
         double innov, Kj, sk_plus[M], Ppc[M];
         const bool valid = !is_nan(xk);                                     // :122 (per chain)
-        // EPI_HEX_BRANCHLESS: every chain goes through the update and one without an observation keeps its values by select
-        // (:130-135) -- the day is then ONE basic block, and the scheduler can fill the update's LDS round trips with the
-        // arithmetic of the state map and the Jacobian, which only need the gain
-        const bool upd = EPI_HEX_BRANCHLESS ? true : valid;
-        if (upd) {
-            innov = valid ? xk - xk_minus : 0.0;
+        if (valid) {
+            innov = xk - xk_minus;
             // (P C')(j) = P(j, 0:2) C(0:2)' -- P(j, k) == P(k, j): my column.  (C P)(k) holds the same bits.
             double PCj = Pc[0] * C[0];
             PCj = fma(Pc[1], C[1], PCj);
@@ -506,13 +480,13 @@ __global__ __launch_bounds__(kWave, SOLO ? 1 : 2) void ekf_fwd_hex(const KArgs a
             CPCt = fma(PC[2], C[2], CPCt);
             const double den = CPCt + gamma * Rk;                           // :124 (D = 1, Hessian terms 0)
             const double Kraw = PCj / den;
-            Kj = valid ? Kraw : 0.0;
+            Kj = Kraw;
             double Kg[M], K[M];
             hx_gather6(vKg, j, Kraw, Kg);
 #pragma unroll
             for (int i = 0; i < M; i++) K[i] = Kg[i];
 #pragma unroll
-            for (int i = 0; i < M; i++) sk_plus[i] = valid ? sk_minus[i] + K[i] * innov : sk_minus[i];   // :129
+            for (int i = 0; i < M; i++) sk_plus[i] = sk_minus[i] + K[i] * innov;   // :129
             // I - K C: its first three columns (C(4:6) = 0: the others are those of the identity)
             double IK[M][3];
 #pragma unroll
@@ -541,7 +515,7 @@ __global__ __launch_bounds__(kWave, SOLO ? 1 : 2) void ekf_fwd_hex(const KArgs a
             }
             hx_transpose(tBg, j, Fr, Fc);
 #pragma unroll
-            for (int i = 0; i < M; i++) Ppc[i] = valid ? (Fc[i] + Fr[i]) / 2.0 : Pc[i];     // :138
+            for (int i = 0; i < M; i++) Ppc[i] = (Fc[i] + Fr[i]) / 2.0;     // :138
         } else {                                                            // :130-135
             innov = 0.0;
             Kj = 0.0;
@@ -628,31 +602,20 @@ __global__ __launch_bounds__(kWave, SOLO ? 1 : 2) void ekf_fwd_hex(const KArgs a
 // ---------------------------------------------------------------------------
 // backward recursion: GenericExtendedKalmanFilter.m:189-230 (X = pinv(P_MINUS) comes from eks_pinv, packed)
 // ---------------------------------------------------------------------------
-// EPI_HEX_SHARE_LOADS: what all six lanes of a chain need of the stored forward quantities (S+, S-, the 21 packed entries of X)
+// What all six lanes of a chain need of the stored forward quantities (S+, S-, the 21 packed entries of X)
 // is loaded ONCE -- lane j its element of the vectors and the packed entries j, j + 6, j + 12, j + 18 of X -- and handed round
 // through LDS at the start of the step: 21 instead of 48 vector-memory instructions per step and lane (the six lanes'
 // replicated loads hit the same cache lines, but every one of them passes through the CU's one address unit, which four such
 // waves keep busy 57 % of the time)
-#ifndef EPI_HEX_SHARE_LOADS
-#define EPI_HEX_SHARE_LOADS 1
-#endif
-// EPI_HEX_BWD_RECOMPUTE: P(k+1|k) is NOT read back: it is formed again from the P(k|k), S+(k), u(k) the step loads anyway, by
+// P(k+1|k) is NOT read back: it is formed again from the P(k|k), S+(k), u(k) the step loads anyway, by
 // the forward kernel's own instruction sequence (hx_mul_A, the two transposes, + Q, the symmetrisation) -- the same bits -- and
 // its first product A P(k|k) is the (P+ A') row the gain needs in any case.  The smoother of this shape moves 6.2 GB in 1.30 ms
 // at the 9 375-chain shard, the box's copy rate, with its vector unit busy 29 % of the time: 288 of its 1 272 bytes per step
 // for 27 fma and two LDS transposes.  (The one-lane kernels lost with this in rounds 1-2: they pay every instruction.)
-#ifndef EPI_HEX_BWD_RECOMPUTE
-#define EPI_HEX_BWD_RECOMPUTE 1
-#endif
-
-#if EPI_HEX_SHARE_LOADS
-struct HexBwdIn { double Spj, Sm1j, u[2], Ppc[6], Pm1c[6], Xp[4]; int rk; };
-#else
-struct HexBwdIn { double Sp[6], Sm1[6], u[2], Ppc[6], Pm1c[6], X[21]; int rk; };
-#endif
+struct HexBwdIn { double Spj, Sm1j, u[2], Ppc[6], Xp[4]; int rk; };
 
 // PF = 1: a step's inputs are requested one step ahead into one of two register sets (256 + 22 registers: one wave per SIMD) --
-// for launches of at most one wave per SIMD; PF = 0: requested at the start of the step (242 registers, no accumulation
+// for launches of at most one wave per SIMD in the classic layout (BLK = 0; ten-chain blocks take PF = 2); PF = 0: requested at the start of the step (242 registers, no accumulation
 // registers: TWO waves per SIMD, which hide each other's memory latency) -- for larger launches.
 // PF = 2 (round 6, BLK = 10 only): one step ahead as with PF = 1, but by LDS-DMA (`buffer_load_dwordx4 ... lds`).  With ten chains
 // per layout block a day of a wave's S_PLUS / S_MINUS / P_PLUS / X is ONE contiguous run of 480 / 480 / 2 880 / 1 680 bytes, which
@@ -663,7 +626,7 @@ constexpr int kHxImgSp = 0, kHxImgSm = 60, kHxImgP = 120, kHxImgX = 480, kHxImg 
 typedef __attribute__((address_space(3))) void *hx_lds_ptr_t;
 EPI_DEV void hx_dma16(rsrc_t r, unsigned lds_addr, unsigned voff, unsigned soff)
 {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (hx_lds_ptr_t)(uintptr_t)lds_addr, 16, voff, soff, 0, EPI_LD_STREAM_AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (hx_lds_ptr_t)(uintptr_t)lds_addr, 16, voff, soff, 0, kLdStreamAux);
 }
 template <int FLIP, int BLK, int PF = 1>
 __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, const int *__restrict__ dense_flag)
@@ -673,13 +636,7 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
     __shared__ __attribute__((aligned(16))) double imgA[PF == 2 ? kHxImg : 2], imgB[PF == 2 ? kHxImg : 2];
     __shared__ __attribute__((aligned(16))) double tJ[kHGp * kHT], tB[kHGp * kHT], tC[kHGp * kHT];
     __shared__ __attribute__((aligned(16))) double vS[kHGp * kHV], vTm[kHGp * kHN];
-
-#if EPI_HEX_SHARE_LOADS
     __shared__ __attribute__((aligned(16))) double vSp[kHGp * kHV], vSm[kHGp * kHV], tXs[kHGp * 24];
-#endif
-#ifdef EPI_HEX_BWD_PRIO
-    __builtin_amdgcn_s_setprio(3);             // probe: the smoother's waves ahead of the pinv waves beside them
-#endif
     if (*dense_flag) return;
     const HexLane h = hx_lane(a);
     const int B = a.B, T = a.T, c = h.c, j = h.j;
@@ -687,15 +644,11 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
     const Lay lay = make_lay(a, c);
     double *tJg = tJ + kHT * h.g, *tBg = tB + kHT * h.g, *tCg = tC + kHT * h.g;
     double *vSg = vS + kHV * h.g, *vTmg = vTm + kHN * h.g;
-#if EPI_HEX_BWD_RECOMPUTE
     double *tDg = tBg, *tEg = tCg;               // the recomputation's two transposes come before the recursion's: same tiles
     double Qv[M];
 #pragma unroll
     for (int i = 0; i < M; i++) Qv[i] = (i == j) ? a.Q[(size_t)IXM(j, j) * B + c] : 0.0;   // Q_w diagonal (ekf_precheck): row j of it
-#endif
-#if EPI_HEX_SHARE_LOADS
     double *vSpg = vSp + kHV * h.g, *vSmg = vSm + kHV * h.g, *tXg = tXs + 24 * h.g;
-#endif
     QPrm p;
     HexNpi np;
     hx_load_prm(p, np, a, B, h);
@@ -711,7 +664,7 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
     double Ss[M], Psc[M];
     // the arrays of the current addressing window (see kHexDead): bases at its first day `tw`, days counted from there
     struct {
-        const double *S_PLUS, *P_PLUS, *X, *S_MINUS, *P_MINUS, *u;
+        const double *S_PLUS, *P_PLUS, *X, *S_MINUS, *u;
         const int32_t *rankbuf;
         double *S_SMOOTH, *P_SMOOTH, *u_opt_smooth;
         int32_t *pinv_rank;
@@ -721,7 +674,7 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
         tw = t0;
         const size_t bp = lay.bp;
         w.S_PLUS = hx_rebase(a.S_PLUS, t0, 6 * bp); w.S_MINUS = hx_rebase(a.S_MINUS, t0, 6 * bp); w.S_SMOOTH = hx_rebase(a.S_SMOOTH, t0, 6 * bp);
-        w.P_PLUS = hx_rebase(a.P_PLUS, t0, 36 * bp); w.P_MINUS = hx_rebase(a.P_MINUS, t0, 36 * bp); w.P_SMOOTH = hx_rebase(a.P_SMOOTH, t0, 36 * bp);
+        w.P_PLUS = hx_rebase(a.P_PLUS, t0, 36 * bp); w.P_SMOOTH = hx_rebase(a.P_SMOOTH, t0, 36 * bp);
         w.X = hx_rebase(a.X, t0, 21 * bp);
         w.rankbuf = hx_rebase(a.rankbuf, t0, bp); w.pinv_rank = hx_rebase(a.pinv_rank, t0, bp);
         w.u_opt_smooth = hx_rebase(a.u_opt_smooth, t0, (size_t)a.n_npi * bp);
@@ -765,7 +718,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
     // everything step k reads is requested one iteration ahead: the stored forward quantities come from HBM
     // (dt: the day of step k, tpos(k); dt1: the day after it in filter order, tpos(k + 1) -- see HexDay)
     auto fetch = [&](const HexDay &dt, const HexDay &dt1, HexBwdIn &d) __attribute__((always_inline)) {
-#if EPI_HEX_SHARE_LOADS
         d.Spj = hx_load_elem<BLK>(w.S_PLUS, HexAt{dt.o6}, lay, j);
         hx_load_u_at(w.u, a, dt.ou, su, j, d.u);
         d.rk = hx_load_word(w.rankbuf, HexAt{dt1.o1 >> 1}, lay);
@@ -779,25 +731,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
             d.Xp[3] = hx_ld<BLK>(r, voff + (unsigned)(j < 3 ? j : 2) * rowb, 18u, rowb, dt1.o21);     // packed entries 18..20 exist for j < 3
         }
         d.Sm1j = hx_load_elem<BLK>(w.S_MINUS, HexAt{dt1.o6}, lay, j);
-#if !EPI_HEX_BWD_RECOMPUTE
-        hx_load_col<BLK>(w.P_MINUS, HexAt{dt1.o36}, lay, j, d.Pm1c);
-#endif
-#else
-        hx_load_vec<BLK>(w.S_PLUS, HexAt{dt.o6}, lay, d.Sp);
-        hx_load_u_at(w.u, a, dt.ou, su, j, d.u);
-        d.rk = hx_load_word(w.rankbuf, HexAt{dt1.o1 >> 1}, lay);
-        hx_load_col<BLK>(w.P_PLUS, HexAt{dt.o36}, lay, j, d.Ppc);
-        {
-            unsigned voff, rowb;
-            const rsrc_t r = hx_slice<BLK>(w.X, HexAt{dt1.o21}, 21, lay, voff, rowb);  // (garbage where the :211 guard fired, rk < 0: unused)
-#pragma unroll
-            for (int e = 0; e < 21; e++) d.X[e] = hx_ld<BLK>(r, voff, (unsigned)e, rowb, dt1.o21);
-        }
-        hx_load_vec<BLK>(w.S_MINUS, HexAt{dt1.o6}, lay, d.Sm1);
-#if !EPI_HEX_BWD_RECOMPUTE
-        hx_load_col<BLK>(w.P_MINUS, HexAt{dt1.o36}, lay, j, d.Pm1c);
-#endif
-#endif
     };
     // PF = 2: the same inputs by DMA into an image, the two small ones (controls, rank word) into registers
     struct HexSmall { double u[2]; int rk; };
@@ -820,7 +753,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
     };
     // my entries out of an image: element (row r, chain g) of a run lies at r * 10 + g
     auto unpack = [&](const double *img, const HexSmall &sm, HexBwdIn &d) __attribute__((always_inline)) {
-#if EPI_HEX_SHARE_LOADS
         const int g = h.g;
         d.Spj = img[kHxImgSp + j * 10 + g];
         d.Sm1j = img[kHxImgSm + j * 10 + g];
@@ -830,10 +762,8 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
         for (int m = 0; m < 3; m++) d.Xp[m] = img[kHxImgX + (j + 6 * m) * 10 + g];
         d.Xp[3] = img[kHxImgX + (18 + (j < 3 ? j : 2)) * 10 + g];
         d.u[0] = sm.u[0]; d.u[1] = sm.u[1]; d.rk = sm.rk;
-#endif
     };
     auto step = [&](const HexDay &dt, const HexBwdIn &cur) __attribute__((always_inline)) {
-#if EPI_HEX_SHARE_LOADS
         double Sp[M], Sm1[M], X[24];
         hx_gather6(vSpg, j, cur.Spj, Sp);
         hx_gather6(vSmg, j, cur.Sm1j, Sm1);
@@ -848,11 +778,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
                 X[2 * e + 1] = x.y;
             }
         }
-#else
-        const double (&Sp)[M] = cur.Sp;
-        const double (&Sm1)[M] = cur.Sm1;
-        const double (&X)[21] = cur.X;
-#endif
 
         double A[M * M];
         {
@@ -875,7 +800,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
                 for (int q = 1; q < M; q++) acc = fma(PAr[q], X[sidx(q, i)], acc);
                 Jr[i] = guard ? 0.0 : acc;
             }
-#if EPI_HEX_BWD_RECOMPUTE
             // P(k+1|k) = sym(A P+ A' + Q) exactly as ekf_fwd_hex formed it: (A P+)(:, j) is PAr
             double Tr[M], Gr[M], Gc[M];
             hx_transpose(tDg, j, PAr, Tr);
@@ -885,10 +809,6 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
             hx_transpose(tEg, j, Gr, Gc);
 #pragma unroll
             for (int i = 0; i < M; i++) Pm1c[i] = (Gc[i] + Gr[i]) / 2.0;
-#else
-#pragma unroll
-            for (int i = 0; i < M; i++) Pm1c[i] = cur.Pm1c[i];
-#endif
         }
         if (guard) st_guard = 1;
         else {
@@ -902,20 +822,14 @@ __global__ __launch_bounds__(kWave, PF ? 1 : 2) void eks_bwd_hex(const KArgs a, 
             double acc = Jr[0] * (Ss[0] - Sm1[0]);
 #pragma unroll
             for (int q = 1; q < M; q++) acc = fma(Jr[q], Ss[q] - Sm1[q], acc);
-#if EPI_HEX_SHARE_LOADS
             const double mine = cur.Spj + acc;
-#else
-            const double mine = hx_pick(Sp, j) + acc;
-#endif
             const double clamped = fmin(my_hi, fmax(my_lo, mine));
             hx_gather6(vSg, j, (j < 3) ? clamped : mine, Sn);
         }
         // P_SMOOTH(k) = sym(P+ - (J D) J'),  D = P_MINUS(k+1) - P_SMOOTH(k+1)   :223-226
         {
             double Jall[36], Dc[M], JDc[M], JDr[M], Fr[M], Fc[M];
-            hx_fence();
             hx_put6(tJg + 6 * j, Jr);                                       // slot j = row j of J
-            hx_fence();
             hx_get_all(tJg, Jall);                                          // Jall[6 i + q] = J(i, q)
 #pragma unroll
             for (int i = 0; i < M; i++) Dc[i] = Pm1c[i] - Psc[i];           // D(:, j)

@@ -23,13 +23,6 @@ constexpr int kQC = kWave / 4;   // chains per wavefront
 // One wavefront per workgroup.  (Workgroups of four wavefronts -- one per SIMD of a CU -- were measured: every wave ran
 // 30-45 % slower, 1.65 instead of 1.13 ms for the forward kernel at 300 chains; waves that share a CU get in each other's
 // way, so the fewer per CU the better, and single-wave workgroups spread over all CUs first.)
-#ifndef EPI_QUAD_BWD_PF
-#define EPI_QUAD_BWD_PF 0         // smoother: 1 = request a step's inputs one iteration ahead (two register sets); measured
-                                  // level with 0 (1.49 vs 1.46 ms, 9 375 chains): the quad kernels are issue-bound, not latency-bound
-#endif
-#ifndef EPI_QUAD_WAVES
-#define EPI_QUAD_WAVES 1          // minimum waves per SIMD the quad kernels are compiled for (register cap 512 / n)
-#endif
 
 #define EPI_QP(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 constexpr int QP_ROW_L = EPI_QP(0, 0, 2, 2);   // block (bi, 0) of my block row
@@ -785,9 +778,8 @@ __global__ __launch_bounds__(kWave) void eks_bwd_quad(const KArgs a, const int *
         qstore_scalar(a.pinv_rank, tT, lay, (int32_t)-1);
     }
 
-    // Everything step k reads is requested one iteration ahead (EPI_QUAD_BWD_PF): a lone wave then never sits through a
-    // memory round trip at the top of a step.  Two register sets used alternately (the loop body exists twice), so the
-    // prefetched values are consumed where they landed -- copying them costs more than the latency (measured).
+    // Everything step k reads is requested at the top of the step.  (Requesting it one iteration ahead into a second register
+    // set measured level, 1.49 vs 1.46 ms at 9 375 chains: the quad kernels are issue-bound, not latency-bound.)
     struct In { double Sp[M], Sm1[M], u[3]; blk3 Pp, X, Pm1; int rk; };
     auto fetch = [&](int k, In &d) {
         const int t = tpos<FLIP>(k, T), t1 = tpos<FLIP>(k + 1, T);
@@ -905,27 +897,11 @@ __global__ __launch_bounds__(kWave) void eks_bwd_quad(const KArgs a, const int *
             qstore_u<BLK>(a.u_opt_smooth, a, t, lay, Q, ur);
         }
     };
-#if EPI_QUAD_BWD_PF
-    {
-        In bufA, bufB;
-        int k = k_from;
-        if (k >= k_to) fetch(k, bufA);
-        while (k >= k_to) {
-            if (k > k_to) fetch(k - 1, bufB);
-            step(k, bufA);
-            if (--k < k_to) break;
-            if (k > k_to) fetch(k - 1, bufA);
-            step(k, bufB);
-            --k;
-        }
-    }
-#else
     for (int k = k_from; k >= k_to; k--) {
         In cur;
         fetch(k, cur);
         step(k, cur);
     }
-#endif
     if (k_to > 0) {        // hand-over to the launch that continues with step k_to - 1
         if (Q.q == 0) {
 #pragma unroll

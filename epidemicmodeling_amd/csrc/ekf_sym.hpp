@@ -113,35 +113,21 @@ __global__ __launch_bounds__(256) void ekf_precheck(const KArgs a, int *__restri
 // ---------------------------------------------------------------------------
 // Launch bounds.  Capping at two waves per SIMD (kWave, 2 => 256 VGPRs) makes hipcc 7.2 spill ~430-680 B
 // per lane to scratch, which measured slower (15.3 / 26.0 ms) than one spill-free wave per SIMD
-// (11.8 / 14.1 ms) on the headline sweep; see DESIGN.md "Occupancy and the wave-count quantum".
-#ifndef EPI_FWD_LB
-#define EPI_FWD_LB kWave
-#endif
-#ifndef EPI_BWD_LB
-#define EPI_BWD_LB kWave
-#endif
-#ifndef EPI_FWD3_WAVES
-#define EPI_FWD3_WAVES 3          // waves per SIMD the 3-state forward variant with LDS-resident a / u_max is compiled for
-#endif
-// Two knobs of the packed smoother, settled by A/B runs on the headline sweep (profiles/ab_phase.py 4, medians):
-//   EPI_BWD_PREFETCH  what is requested one step ahead (bit 0: state, controls, rank word; bit 1: P_PLUS; bit 2: X)
-//   EPI_BWD_RECOMPUTE 1: s(k+1|k), P(k+1|k) are recomputed from the stored s(k|k), P(k|k), u with the forward kernel's
-//                     own functions (bit-identical, 27 fewer loads per step, 10 GB less traffic per pass) -- but the
-//                     kernel then needs all 512 registers, and with the prefetch and the blocked-layout addressing on
-//                     top it spills (56 B of scratch per lane: 12.5 ms);  0: they are read back at their point of use.
+// (11.8 / 14.1 ms) on the headline sweep; see DESIGN.md "Occupancy and the wave-count quantum".  Both packed kernels
+// therefore ask for kWave lanes and set no minimum of waves per SIMD.
+//
+// The packed smoother's two choices, settled by A/B runs on the headline sweep (profiles/ab_phase.py 4, medians).  Prefetch:
+// what is requested one step ahead (1: state, controls, rank word; 2: P_PLUS; 4: X).  Recompute 1: s(k+1|k), P(k+1|k) are
+// recomputed from the stored s(k|k), P(k|k), u with the forward kernel's own functions (bit-identical, 27 fewer loads per
+// step, 10 GB less traffic per pass) -- but the six-state kernel then needs all 512 registers, and with the prefetch and the
+// blocked-layout addressing on top it spills (56 B of scratch per lane: 12.5 ms);  0: they are read back at their point of use.
 //   chain-blocked outputs, blk = 8:  recompute 0 / prefetch 1: 8.0 ms (372 VGPRs)   0 / 5: 8.1   0 / 0: 8.4   1 / 0: 9.5
 //   classic [T][rows][B]:            0 / 1: 8.6   0 / 0: 9.1   1 / 0: 9.6
-#ifndef EPI_BWD_PREFETCH
-#define EPI_BWD_PREFETCH 1
-#endif
-#ifndef EPI_BWD_RECOMPUTE
-#define EPI_BWD_RECOMPUTE 0
-#endif
+// eks_bwd_sym<6> therefore prefetches the small group and reads back; eks_bwd_sym<3> does neither (see there).
 constexpr int kPipeLanes = 40;   // lanes per workgroup of the LP = 1 forward variant
 // where the forward kernel keeps the model constants (see ekf_fwd_sym)
 template <int LP> struct PrmSelect { typedef ChainPrm type; };
 template <> struct PrmSelect<1> { typedef LitePrm<VecLdsS> type; };
-template <> struct PrmSelect<2> { typedef LitePrm<VecLds2> type; };     // 3-state: a, u_max in LDS (64-lane stride), see ekf_fwd_sym
 template <int M>
 EPI_DEV void init_prm(ChainPrm &p, const KArgs &a, int B, int c, double *, int) { load_prm<M>(p, a.prm, B, c, a.mf.lo_is_zero); }
 template <int M>
@@ -155,18 +141,6 @@ EPI_DEV void init_prm(LitePrm<VecLdsS> &p, const KArgs &a, int B, int c, double 
         col[(1 * kNpi + k) * stride] = a.prm[(size_t)(EPI_PRM_U_MIN + k) * B + c];
         col[(2 * kNpi + k) * stride] = a.prm[(size_t)(EPI_PRM_U_MAX + k) * B + c];
         col[(3 * kNpi + k) * stride] = a.prm[(size_t)(EPI_PRM_W_EFF + k) * B + c];
-    }
-}
-
-template <int M>
-EPI_DEV void init_prm(LitePrm<VecLds2> &p, const KArgs &a, int B, int c, double *col, int)
-{
-    load_lite(p, a.prm, B, c, a.mf.lo_is_zero);
-    p.v.base = col;
-#pragma unroll
-    for (int k = 0; k < kNpi; k++) {
-        col[(0 * kNpi + k) * kWave] = a.prm[(size_t)(EPI_PRM_A + k) * B + c];
-        col[(1 * kNpi + k) * kWave] = a.prm[(size_t)(EPI_PRM_U_MAX + k) * B + c];
     }
 }
 
@@ -229,7 +203,7 @@ EPI_DEV void predict_cov_sym(const double (&A)[M * M], const double (&Pp)[M * (M
 //         4.23 -> 3.86 ms; with all outputs, where it is bound by its 104 store rows per day, two resident waves per SIMD write
 //         WORSE (5.7 -> 6.0 ms), and the 3-state kernels use the controls too early in the day (config 5: 8.7 -> 9.4 ms).
 template <int M, int FLIP, int LP, int STOR = 0, int MON = 1, int USD = 0>
-__global__ __launch_bounds__(EPI_FWD_LB, (M == 3 && LP == 2) ? EPI_FWD3_WAVES : 1) void ekf_fwd_sym(const KArgs a, const int *__restrict__ dense_flag)
+__global__ __launch_bounds__(kWave) void ekf_fwd_sym(const KArgs a, const int *__restrict__ dense_flag)
 {
     extern __shared__ double lds[];   // three sliding windows [3][L][stride], one column per lane (+ [48][stride], LP)
     if (*dense_flag) return;          // ekf_fwd (dense) runs instead
@@ -284,36 +258,13 @@ __global__ __launch_bounds__(EPI_FWD_LB, (M == 3 && LP == 2) ? EPI_FWD3_WAVES : 
     double r_nxt = fixed_R ? 0.0 : ldg(a.R_series + (size_t)k_begin * a.Sx, voff_x);
     double u_nxt[kNpi];
     if (!USD) load_u(a, tpos<FLIP>(k_begin, T), su, u_nxt);
-    // LP = 2 (3-state): NlinStateUpdate returns u as it came (SIAlphaModelEKF.m:39) and its fma chain (gamma a')(u_max - u)
-    // does not depend on the state, so a day's controls are consumed when they ARRIVE -- at the end of the day before: u_opt
-    // stored, the dot product formed -- and only that scalar crosses into the day (one control vector live instead of two)
-    double dot_cur = 0.0;
-    auto consume_u = [&](int tt, bool store) __attribute__((always_inline)) {
-        if (store) {
-            store_u(a.u_opt, a, tt, lay, u_nxt);
-            if (STOR) store_rows_f32<kNpi>(a.f.u_opt, tt, (unsigned)a.n_npi, lay, u_nxt);
-        }
-        dot_cur = (p.gamma * p.A(0)) * (p.Umax(0) - u_nxt[0]);
-#pragma unroll
-        for (int q = 1; q < kNpi; q++) dot_cur = fma(p.gamma * p.A(q), p.Umax(q) - u_nxt[q], dot_cur);
-    };
-    if (LP == 2 && k_begin < k_end) consume_u(tpos<FLIP>(k_begin, T), true);
-
     for (int k = k_begin; k < k_end; k++) {
         const int t = tpos<FLIP>(k, T);
         const double Rk = fixed_R ? R_next : r_nxt;
         const double xk = x_nxt;
-        if constexpr (LP == 2) {
-            // the LDS column's address is made opaque once a day: hipcc otherwise hoists the 24 reads of a(k), u_max(k) out of
-            // the loop -- back into the 48 registers the LDS copy is there to free
-            const double *q = p.v.base;
-            asm volatile("" : "+v"(q));
-            p.v.base = q;
-        }
         double u_in[kNpi];
-        const double dot_day = dot_cur;
         if (USD) load_u(a, t, su, u_in);
-        else if (LP != 2) {
+        else {
 #pragma unroll
             for (int q = 0; q < kNpi; q++) u_in[q] = u_nxt[q];
         }
@@ -398,13 +349,7 @@ __global__ __launch_bounds__(EPI_FWD_LB, (M == 3 && LP == 2) ? EPI_FWD3_WAVES : 
         }
         state_hard_margins<M>(p, sk_plus);
 
-        if constexpr (LP == 2) {
-            state_map<M, FLIP>(p, dot_day, sk_plus, sk_minus);
-            double A[M * M];
-            jacobian_entries<M, FLIP>(p, sk_plus, 0.0, A);         // no slope term for three states
-            predict_cov_sym<M>(A, Pp, Qd, Pm);
-            if (k + 1 < T) consume_u(tpos<FLIP>(k + 1, T), k + 1 < k_end);   // tomorrow's controls have arrived
-        } else {
+        {
             double u_app[kNpi];
 #pragma unroll
             for (int q = 0; q < kNpi; q++) u_app[q] = u_in[q];
@@ -466,7 +411,7 @@ struct BwdIn {   // everything smoother step k reads: forward quantities of step
     int rk;
 };
 template <int M, int FLIP, int STOR = 0>
-__global__ __launch_bounds__(EPI_BWD_LB) void eks_bwd_sym(const KArgs a, const int *__restrict__ dense_flag)
+__global__ __launch_bounds__(kWave) void eks_bwd_sym(const KArgs a, const int *__restrict__ dense_flag)
 {
     constexpr int NV = (M == 6) ? 4 : 2;        // 6 states: a, u_min, u_max, w; 3 states: a, u_max (VecLds2)
     __shared__ double vlds[NV * kNpi * kWave];  // one column per lane
@@ -550,8 +495,8 @@ __global__ __launch_bounds__(EPI_BWD_LB) void eks_bwd_sym(const KArgs a, const i
     // iteration's loads have been issued.
     BwdIn<M> cur;
     // the inputs of a step in two groups: the small ones that the step needs first (state, controls, rank word) and the
-    // two packed 6 x 6 (P_PLUS, X).  EPI_BWD_PREFETCH selects what is requested one step ahead (bit 0: the small group,
-    // bit 1: P_PLUS, bit 2: X); whatever is not prefetched is loaded at the top of its own step.
+    // two packed 6 x 6 (P_PLUS, X).  The six-state kernel requests the small group one step ahead (PF); whatever is not
+    // prefetched is loaded at the top of its own step.
     auto fetch_small = [&](int k, BwdIn<M> &d) {
         const int t = tpos<FLIP>(k, T), t1 = tpos<FLIP>(k + 1, T);
         load_vec<M>(a.S_PLUS, t, lay, d.Sp);
@@ -585,16 +530,16 @@ __global__ __launch_bounds__(EPI_BWD_LB) void eks_bwd_sym(const KArgs a, const i
     // double buffering: the inputs of step k-1 are requested at the top of step k (ahead of the stores of step k+1's
     // results) and consumed one iteration later, so that a lone wave does not sit through a full memory round trip
     // at the start of every step
-    constexpr int PF = (M == 6) ? EPI_BWD_PREFETCH : 0;   // the 3-state kernel would drop from two waves per SIMD to one
-    constexpr bool RC = (M == 3) || EPI_BWD_RECOMPUTE;    // ... and has the registers to recompute s(k+1|k), P(k+1|k)
+    constexpr bool PF = (M == 6);         // the 3-state kernel would drop from two waves per SIMD to one
+    constexpr bool RC = (M == 3);         // ... and has the registers to recompute s(k+1|k), P(k+1|k)
     BwdIn<M> nxt;
     auto step = [&](int k) {
         const int t = tpos<FLIP>(k, T);
-        if (PF & 1) { if (k > k_to) fetch_small(k - 1, nxt); } else fetch_small(k, cur);
-        if (PF & 2) { if (k > k_to) fetch_pp(k - 1, nxt); } else fetch_pp(k, cur);
-        if (PF & 4) { if (k > k_to) fetch_x(k - 1, nxt); } else fetch_x(k, cur);
+        if (PF) { if (k > k_to) fetch_small(k - 1, nxt); } else fetch_small(k, cur);
+        fetch_pp(k, cur);
+        fetch_x(k, cur);
         flush();
-        // s(k+1|k) and P(k+1|k): read back at their point of use, or (EPI_BWD_RECOMPUTE) recomputed from the stored
+        // s(k+1|k) and P(k+1|k): read back at their point of use, or (RC) recomputed from the stored
         // s(k|k), P(k|k), u(:,k) with the forward kernel's own functions (:155-164) -- bit-identical either way
         double A[M * M], Sm1[M];
         state_jacobians<M, FLIP>(p, cur.u, cur.Sp, A);         // :206 (and :157 of the forward pass)
@@ -700,25 +645,15 @@ __global__ __launch_bounds__(EPI_BWD_LB) void eks_bwd_sym(const KArgs a, const i
         }
         t_pend = t;
         rank_pend = rank;
-        if (PF & 1) {
+        if (PF) {
 #pragma unroll
             for (int i = 0; i < M; i++) cur.Sp[i] = nxt.Sp[i];
 #pragma unroll
             for (int q = 0; q < kNpi; q++) cur.u[q] = nxt.u[q];
             cur.rk = nxt.rk;
         }
-        if (PF & 2) {
-#pragma unroll
-            for (int e = 0; e < NS; e++) cur.Pp[e] = nxt.Pp[e];
-        }
-        if (PF & 4) {
-#pragma unroll
-            for (int e = 0; e < NS; e++) cur.X[e] = nxt.X[e];
-        }
     };
-    if ((PF & 1) && k_from >= k_to) fetch_small(k_from, cur);
-    if ((PF & 2) && k_from >= k_to) fetch_pp(k_from, cur);
-    if ((PF & 4) && k_from >= k_to) fetch_x(k_from, cur);
+    if (PF && k_from >= k_to) fetch_small(k_from, cur);
     for (int k = k_from; k >= k_to; k--) step(k);
     flush();
     if (k_to > 0) {        // hand-over to the launch that continues with step k_to - 1

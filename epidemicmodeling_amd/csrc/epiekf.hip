@@ -126,20 +126,14 @@ EPI_DEV double bld(rsrc_t r, unsigned voff, unsigned soff)
 // where the L2's tag pipeline stalls on the concurrently streamed arrays ("where the arrays lie"): forward kernel
 // 7.05 -> 6.67 ms on one box, smoother 7.8 -> 7.0 ms on another, three boxes 16.1-16.9 -> 15.6-15.9 ms per pass.  `sc1` on the
 // stream LOADS as well (aux 18) brings the slow mode back; `sc0 | sc1 | nt` (19) on them is level with `nt` alone.
-#ifndef EPI_ST_AUX
-#define EPI_ST_AUX 18
-#endif
-#ifndef EPI_ST32_AUX
-#define EPI_ST32_AUX 18           // the fp32-storage twins of the stores (BASELINE config 5)
-#endif
+constexpr int kStAux = 18;
+constexpr int kSt32Aux = 18;      // the fp32-storage twins of the stores (BASELINE config 5)
 // (`sc0 | sc1 | nt` = 19 on the stream loads: -0.24 +- 0.10 ms per headline pass against `nt` alone over 20 paired runs on four
 // boxes, smoother -0.13, slow outliers 16.6-17.2 -> at most 16.8 ms; `sc1 | nt` = 18 brings the smoother's slow mode back)
-#ifndef EPI_LD_STREAM_AUX
-#define EPI_LD_STREAM_AUX 19
-#endif
+constexpr int kLdStreamAux = 19;
 EPI_DEV void bst(rsrc_t r, unsigned voff, unsigned soff, double v)
 {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, EPI_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, kStAux);
 }
 // non-temporal only: for layouts whose rows are not whole cache lines (the hex shape's ten-chain blocks, ekf_hex.hpp), where
 // writing through (`sc1`) turns every partial line into a memory transaction of its own
@@ -150,7 +144,7 @@ EPI_DEV void bst_nt(rsrc_t r, unsigned voff, unsigned soff, double v)
 // a load of data that this launch reads exactly once (stored forward quantities, X)
 EPI_DEV double bld_s(rsrc_t r, unsigned voff, unsigned soff)
 {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, EPI_LD_STREAM_AUX));
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, kLdStreamAux));
 }
 EPI_DEV double ldg(const double *__restrict__ row, unsigned voff)
 {
@@ -278,7 +272,7 @@ EPI_DEV rsrc_t lay_slice_f32(const float *p, int t, unsigned rows, const Lay &l,
 }
 EPI_DEV void bst32(rsrc_t r, unsigned voff, unsigned soff, double v)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v), r, voff, soff, EPI_ST32_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v), r, voff, soff, kSt32Aux);
 }
 template <int N>
 EPI_DEV void store_rows_f32(float *__restrict__ dst, int t, unsigned rows, const Lay &l, const double (&v)[N])
@@ -1166,17 +1160,13 @@ template <int FLIP>
 static hipError_t launch_monitor(const KArgs &ka, int dev, hipStream_t st)
 {
     if (!ka.mon_hoist || !(ka.rho || ka.f.rho)) return hipSuccess;
-#ifdef EPI_PROBE_NO_MONITOR        // timing probe: rho is not computed
-    return hipSuccess;
-#endif
     const size_t shm = (size_t)4 * ka.L * kWave * sizeof(double);
     const int mb = (ka.B + kWave - 1) / kWave;
-#ifndef EPI_MONITOR_PAR_MAX_WAVES
-#define EPI_MONITOR_PAR_MAX_WAVES 2       // use the scan-free grid (ekf_monitor_par) while the batch has at most TWO 64-chain waves per SIMD (131 072 chains;
-                                          // round 6: the headline's 75 000 chains included -- forward stage + monitor 5.45-5.6 against 5.8-6.3 ms, the pass
-                                          // 0.3-0.5 ms shorter in each of four alternating runs, profiles/r06/ab_monitor_par.txt; round 5 had it at one)
-#endif
-    if (ka.L == 21 && !ka.mon_scan && (long)mb <= (long)EPI_MONITOR_PAR_MAX_WAVES * simd_count(dev)) {
+    // use the scan-free grid (ekf_monitor_par) while the batch has at most TWO 64-chain waves per SIMD (131 072 chains; round 6: the
+    // headline's 75 000 chains included -- forward stage + monitor 5.45-5.6 against 5.8-6.3 ms, the pass 0.3-0.5 ms shorter in each of
+    // four alternating runs, profiles/r06/ab_monitor_par.txt; round 5 had it at one)
+    constexpr int kMonitorParMaxWaves = 2;
+    if (ka.L == 21 && !ka.mon_scan && (long)mb <= (long)kMonitorParMaxWaves * simd_count(dev)) {
         constexpr int D = 8;
         hipLaunchKernelGGL((ekf_monitor_par<FLIP, 21, D>), dim3(mb, (ka.T + D - 1) / D), dim3(kWave), 0, st, ka, ka.dense_flag);
         return hipGetLastError();
@@ -1192,12 +1182,6 @@ static hipError_t launch_monitor(const KArgs &ka, int dev, hipStream_t st)
     return hipGetLastError();
 }
 
-#ifndef EPI_FWD3_LEAN
-#define EPI_FWD3_LEAN 0
-#endif
-#ifndef EPI_FWD3_LDS_PAD
-#define EPI_FWD3_LDS_PAD 0          // probe: extra dynamic LDS per workgroup of the 3-state LP = 2 forward variant (caps its waves per SIMD)
-#endif
 // forward kernel(s) over filter steps [ka.k_begin, ka.k_end) of all chains
 template <int M, int FLIP, int GENERIC>
 static hipError_t enqueue_fwd(KArgs ka, const Launch &L, hipStream_t st, int c0 = 0, int cn = -1)
@@ -1284,16 +1268,10 @@ static hipError_t enqueue_fwd(KArgs ka, const Launch &L, hipStream_t st, int c0 
             const bool lp = M == 6 && ka.lw <= kPipeLanes && per_lane * kPipeLanes * 4 <= 160u * 1024u;
             if (ka.mon_hoist) {         // no windows in LDS: only the LP variant's model vectors
                 const size_t lp_shm = (size_t)4 * kNpi * kPipeLanes * sizeof(double);
-#if EPI_FWD3_LEAN
-                // Measured and NOT adopted (round 5, verdict r04 item 3): the 3-state forward kernel with a, u_max in LDS and a day's
-                // controls consumed on arrival (LP = 2) needs 166 registers, no scratch -- THREE clean waves per SIMD -- and takes
-                // 11.4-11.8 ms on BASELINE config 5 against 8.8-9.5 for the 224-register kernel at two (capped at two waves by an LDS
-                // pad: 12.3): the 24 LDS reads a day on the alpha map's dependent chain cost more than the third wave returns
-                // (profiles/r05/ab_cfg5_three_waves.txt).  -DEPI_FWD3_LEAN=1 builds it.
-                if (ka.stor && M == 3 && ka.lw == kWave)
-                    hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, (M == 3 ? 2 : 0), 1, 0>), dim3(blocks), dim3(kWave), (size_t)2 * kNpi * kWave * sizeof(double) + EPI_FWD3_LDS_PAD, st, ka, ka.dense_flag);
-                else
-#endif
+                // (Measured and not adopted, round 5: a 3-state forward kernel with a, u_max in LDS and a day's controls consumed on
+                // arrival -- 166 registers, THREE clean waves per SIMD -- took 11.4-11.8 ms on BASELINE config 5 against 8.8-9.5 for the
+                // 224-register kernel at two: the 24 LDS reads a day on the alpha map's dependent chain cost more than the third wave
+                // returns, profiles/r05/ab_cfg5_three_waves.txt.)
                 if (ka.stor) hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 0, 1, 0>), dim3(blocks), dim3(kWave), 0, st, ka, ka.dense_flag);
                 else if (lp && M == 6 && ka.ws_upper == 3)     // reduced outputs: the variant that fits two waves per SIMD (USD)
                     hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 1, 0, 0, 1>), dim3(blocks), dim3(kWave), lp_shm, st, ka, ka.dense_flag);
@@ -1369,11 +1347,7 @@ static hipError_t enqueue_bwd(KArgs ka, const Launch &L, hipStream_t st, int c0 
                 const unsigned hblocks = (unsigned)((ka.cn + kHG - 1) / kHG);
                 const bool pf = (long)hblocks <= (long)simd_count(L.dev);      // one wave per SIMD: prefetch; beyond: two waves per SIMD
                 if (ka.blk == kHG) {
-#ifndef EPI_HEX_BWD_DMA
-#define EPI_HEX_BWD_DMA 1
-#endif
-                    if (pf && EPI_HEX_BWD_DMA) hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 2>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                    else if (pf) hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 1>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
+                    if (pf) hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 2>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
                     else hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 0>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
                 } else {
                     if (pf) hipLaunchKernelGGL((eks_bwd_hex<FLIP, 0, 1>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
@@ -1397,16 +1371,13 @@ static hipError_t enqueue_bwd(KArgs ka, const Launch &L, hipStream_t st, int c0 
             // waves, the N = 2 shard of the headline sweep: 37 500 chains -- the kernel measured 3.84 against eks_bwd_sym's 3.5 ms:
             // such a batch is not issue-bound, profiles/r06/ab_n2_shard.txt)
             const bool l6_ok = lane6_block(ka.blk);
-            if (!done && EPI_LANE6_BWD && !ka.stor && l6_ok && (long)ka.blk * ka.nblk <= (1L << 20)) {
+            if (!done && !ka.stor && l6_ok && (long)ka.blk * ka.nblk <= (1L << 20)) {
                 const int lblocks = (ka.cn + ka.blk - 1) / ka.blk;
-#if EPI_LANE6_BWD == 3
-                if (ka.blk == 40) hipLaunchKernelGGL((eks_bwd_lane6d<FLIP, 40>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-#else
-                if (ka.blk == 40 && EPI_LANE6_XD && ka.cn % 40 == 0) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, (EPI_LANE6_BWD > 1), EPI_LANE6_LATE_PF, 1>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else if (ka.blk == 40) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, (EPI_LANE6_BWD > 1)>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-#endif
-                else if (ka.blk == 48) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 48, (EPI_LANE6_BWD > 1)>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 56, (EPI_LANE6_BWD > 1)>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
+                // (X by LDS-DMA where every lane of the launch is alive, see eks_bwd_lane6)
+                if (ka.blk == 40 && ka.cn % 40 == 0) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, 1>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
+                else if (ka.blk == 40) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
+                else if (ka.blk == 48) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 48, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
+                else hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 56, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
                 done = true;
             }
         }
@@ -1446,10 +1417,7 @@ static hipError_t enqueue_tail(const KArgs &ka, const Tail &t, hipStream_t st, c
 // between the end of the forward pass and the start of the smoother: the last segments are short.
 // (re-measured in round 3 with the cheaper pinv: four segments ending at 50 / 85 / 97 / 100 % give 3.06-3.11 ms against
 // 3.12-3.16 for five ending at 40 / 70 / 90 / 98 / 100 % at 9 375 chains, level at 18 750: profiles/r03/time_cuts.txt)
-#ifndef EPI_TIME_CUTS
-#define EPI_TIME_CUTS 0, 50, 85, 97, 100
-#endif
-constexpr int kTimeCuts[] = {EPI_TIME_CUTS};
+constexpr int kTimeCuts[] = {0, 50, 85, 97, 100};
 constexpr int kTimeSeg = (int)(sizeof(kTimeCuts) / sizeof(kTimeCuts[0])) - 1;
 
 // epi_batch_desc.exact_nonfinite.  The packed / quad kernels skip products with structural zeros, which is exact for finite
@@ -1568,10 +1536,7 @@ static hipError_t launch_chain(const KArgs &ka, const Launch &L, hipStream_t st)
     // run on the helper stream beside the smoother's first launches, and the smoother is cut where they end (the hand-over rows of
     // the horizon / observed-days split).  Beside the FORWARD kernel a pinv grid takes exactly what it saves (both want the vector
     // unit: forward segments 1.07 -> 1.50 ms); the smoother of this shape waits on memory most of the time.
-#ifndef EPI_REVERSE_PIPE
-#define EPI_REVERSE_PIPE 1
-#endif
-    const bool rp = force_rp || (EPI_REVERSE_PIPE && !tp && ka.hex && ka.mon_hoist && T >= 128 && L.time_pipe >= 0);
+    const bool rp = force_rp || (!tp && ka.hex && ka.mon_hoist && T >= 128 && L.time_pipe >= 0);
     // (Round 6, measured and not adopted: the hex shape beyond one wavefront per SIMD -- 10 241 .. 20 480 chains, the shard of the headline
     // sweep on one of 4 GPUs -- as TWO chain ranges through the one-wave-per-SIMD kernels, pipelined across the ranges (the pinv grid of
     // the first beside the forward kernel of the second, the grid of the second beside the smoother of the first) instead of the
@@ -1585,21 +1550,12 @@ static hipError_t launch_chain(const KArgs &ka, const Launch &L, hipStream_t st)
         // three parts; segment s needs X of filter steps lo+1 ... hi+1
         int seg_hi[8], seg_lo[8], ns = 0, tail_seg = -1;
         int top = T - 2;
-#ifndef EPI_RP_PARTS
-#define EPI_RP_PARTS 3
-#endif
-#ifndef EPI_RP_FIRST
-#define EPI_RP_FIRST 0            // > 0: a first segment of that many days ahead of everything (probe)
-#endif
-        if (EPI_RP_FIRST > 0 && L.tail && L.tail->t_hist >= 1 && T - 2 - EPI_RP_FIRST > L.tail->t_hist) {
-            seg_hi[ns] = top; seg_lo[ns] = top - EPI_RP_FIRST + 1; ns++;
-            top -= EPI_RP_FIRST;
-        }
+        constexpr int kRpParts = 3;
         if (L.tail && L.tail->t_hist >= 1 && L.tail->t_hist <= T - 2) {
             seg_hi[ns] = top; seg_lo[ns] = L.tail->t_hist; tail_seg = ns; ns++;
             top = L.tail->t_hist - 1;
         }
-        const int parts = (top + 1 >= 96 || (force_rp && top + 1 >= 6)) ? EPI_RP_PARTS : 1;
+        const int parts = (top + 1 >= 96 || (force_rp && top + 1 >= 6)) ? kRpParts : 1;
         for (int q = 0; q < parts; q++) {
             const int lo = (int)((long)(top + 1) * (parts - 1 - q) / parts);
             seg_hi[ns] = top; seg_lo[ns] = lo; ns++;
@@ -1651,15 +1607,12 @@ static hipError_t launch_chain(const KArgs &ka, const Launch &L, hipStream_t st)
         // the forward kernel of the second (whose 851 waves leave SIMDs and registers free at 75 000 chains; the forward kernel is
         // bound by its stores, the grid by the vector unit): 0.15 ms of the grid's 3.0 hidden (profiles/r06/ab_pinv_beside_fwd.txt).
         // epi_batch_desc.test_flags bit 2 cuts ANY one-lane batch of two waves or more in the middle the same way (test hook).
-#ifndef EPI_PINV_BESIDE_FWD
-#define EPI_PINV_BESIDE_FWD 1
-#endif
         const int lwf = balanced_lanes(ka.B, M == 6 ? 1 : 2, L.dev);
         const long wavesf = ((long)ka.B + lwf - 1) / lwf;
         const int cA = force_split ? (int)(wavesf / 2) * lwf : simd_count(L.dev) * lwf;
         // (not when neither P(k|k-1) nor P(k|k) is an output: that forward kernel fits TWO waves per SIMD and the headline's 1 875 are
         // resident at once -- cut in two launches it took 1.1 ms longer, bench_cfg4_reduced 13.6 -> 14.7 ms)
-        if (EPI_PINV_BESIDE_FWD && M == 6 && GENERIC && !ka.hex && !ka.quad && !ka.wave && !ka.only && L.hint != 2 && cA > 0 && cA < ka.B &&
+        if (M == 6 && GENERIC && !ka.hex && !ka.quad && !ka.wave && !ka.only && L.hint != 2 && cA > 0 && cA < ka.B &&
             (force_split || (lwf < kWave && ka.ws_upper != 3))) {
             if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st, 0, cA)) != hipSuccess) return e;
             if ((e = fork(st, h->stream)) != hipSuccess) return e;
@@ -1682,14 +1635,11 @@ static hipError_t launch_chain(const KArgs &ka, const Launch &L, hipStream_t st)
     bool mon_late = false;
     int first_round = 0;
     if constexpr (M == 6 && GENERIC) {
-#ifndef EPI_MONITOR_LATE
-#define EPI_MONITOR_LATE 1
-#endif
         const bool cut = force_split && !ka.hex && !ka.quad && !ka.wave && ka.nblk >= 2;        // test hook: the two launches at any size
         // (a first launch of 1 004 / 984 / 964 / 944 waves instead of the 1 024 that are resident at once: level, 14.41-14.88 ms per pass
         // whatever the cut; the monitor ahead of the first launch instead of between the two: +0.15 ms -- profiles/r06/ab_bwd_balance*.txt)
         first_round = cut ? (ka.nblk / 2) * ka.blk : simd_count(L.dev) * ka.blk;
-        mon_late = EPI_MONITOR_LATE && !tp && (in_rounds || cut) && EPI_LANE6_BWD && !ka.stor && lane6_block(ka.blk) && (long)ka.blk * ka.nblk <= (1L << 20) &&
+        mon_late = !tp && (in_rounds || cut) && !ka.stor && lane6_block(ka.blk) && (long)ka.blk * ka.nblk <= (1L << 20) &&
                    ka.mon_hoist && (ka.rho || ka.f.rho) && first_round < ka.B;
     }
     if (!mon_late && ka.mon_hoist && (ka.rho || ka.f.rho)) {

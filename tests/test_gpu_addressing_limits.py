@@ -148,7 +148,7 @@ def run_case(device, fb, idx, classes, outputs=None, oracle_threads=16, dense=Fa
 # eks_bwd_lane6 runs while blk * nblk <= 2^20 (enqueue_bwd); one block more and eks_bwd_sym<6> takes the batch.  The library
 # reports no kernel names, so which smoother ran is asserted through the guard's own operands (blk * nblk of the runner).
 A1 = [  # id, lane_block, B, outputs
-    # 26 214 blocks of 40, every lane alive: eks_bwd_lane6<FLIP, 40, ..., XD = 1> (X by LDS-DMA); all 11 outputs, ~19 GB
+    # 26 214 blocks of 40, every lane alive: eks_bwd_lane6<FLIP, 40, 1> (XD = 1: X by LDS-DMA); all 11 outputs, ~19 GB
     ("blk40-at-guard-xd-all", 40, 1048560, None),
     # the same padded batch, the last block ragged: XD = 0
     ("blk40-at-guard-ragged-all", 40, 1048560 - 13, None),

@@ -72,13 +72,13 @@ SIA6_LAUNCHES = [
     ("lane-classic", "b80", dict(shape="lane")),
     # the same kernels on 8-chain blocks (blk is not a lane6 block)
     ("lane-blk8", "b80", dict(shape="lane", lane_block=8)),
-    # eks_bwd_lane6<FLIP, 48, 1>: st_u's per-row branch, one 48-chain block and a ragged one
+    # eks_bwd_lane6<FLIP, 48, 0>: st_u's per-row branch, one 48-chain block and a ragged one
     ("lane-blk48", "b80", dict(shape="lane", lane_block=48)),
-    # eks_bwd_lane6<FLIP, 56, 1>
+    # eks_bwd_lane6<FLIP, 56, 0>
     ("lane-blk56", "b80", dict(shape="lane", lane_block=56)),
-    # eks_bwd_lane6<FLIP, 40, 1, LATE_PF, 1> (XD = 1, X of the next step by LDS-DMA): 80 chains = two workgroups, every lane alive
+    # eks_bwd_lane6<FLIP, 40, 1> (XD = 1, X of the next step by LDS-DMA): 80 chains = two workgroups, every lane alive
     ("lane-blk40-xd", "b80", dict(shape="lane", lane_block=40)),
-    # eks_bwd_lane6<FLIP, 40, 1> (XD = 0): 70 chains are not a multiple of 40
+    # eks_bwd_lane6<FLIP, 40, 0> (XD = 0): 70 chains are not a multiple of 40
     ("lane-blk40-ragged", "b70", dict(shape="lane", lane_block=40)),
     # test_flags bit 2: forward kernel and pinv grid in two chain ranges, the XD smoother in two launches with the monitor between
     ("lane-blk40-split", "b80", dict(shape="lane", lane_block=40, time_pipe=-1, test_flags=4)),
