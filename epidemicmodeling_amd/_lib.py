@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "epi_lookahead_validate", "epi_lookahead_workspace_bytes", "epi_lookahead_run_device", "epi_lookahead_run_host",
     "epi_rtwin_validate", "epi_rtwin_run_device", "epi_rtwin_run_host",
     "epi_lasso_validate", "epi_lasso_run_device", "epi_lasso_run_host",
+    "epi_ens_validate", "epi_ens_run_device", "epi_ens_run_host",
 ]
 
 
@@ -179,6 +180,42 @@ def make_lasso_desc(R, D, n, K, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4,
     return d
 
 
+class EnsDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "n_q", "storage", "derive_newcases")] + \
+        [("q", C.c_double * 16)]
+
+
+ENS_OUT_NAMES = ("mean", "std", "min", "max", "quantiles", "count")
+ENS_DEFAULT_Q = (0.025, 0.25, 0.5, 0.75, 0.975)
+
+
+class EnsOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ENS_OUT_NAMES]
+
+
+def ens_shapes(T, rows, R, n_q, derive_newcases=0):
+    """shape of every output of epi_ens_run_* (rows' = rows + derive_newcases)"""
+    ro = int(rows) + int(derive_newcases)
+    sh = {k: (T, ro, R) for k in ("mean", "std", "min", "max", "count")}
+    sh["quantiles"] = (T, int(n_q), ro, R)
+    return sh
+
+
+def make_ens_desc(T, rows, R, D, q=ENS_DEFAULT_Q, storage=0, derive_newcases=0) -> EnsDesc:
+    """storage: 0 / "f64" = double source, 1 / "f32" = float source.  More than 16 probabilities reach the library's own
+    check as n_q = len(q) (only the first 16 fit the descriptor)."""
+    d = EnsDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.rows, d.R, d.D = int(T), int(rows), int(R), int(D)
+    q = [float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))]
+    d.n_q = len(q)
+    for k, v in enumerate(q[:16]):
+        d.q[k] = v
+    d.storage = {"f64": 0, "f32": 1}.get(storage, storage)
+    d.derive_newcases = int(derive_newcases)
+    return d
+
+
 class NnlsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "S", "D", "n", "max_iters")]
 
@@ -317,6 +354,13 @@ def lib():
         h.epi_lasso_run_device.argtypes = lasso_args + [C.c_void_p, C.c_char_p]
         h.epi_lasso_run_host.restype = C.c_int
         h.epi_lasso_run_host.argtypes = lasso_args + [C.c_int, C.c_char_p]
+        ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
+        h.epi_ens_validate.restype = C.c_int
+        h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]
+        h.epi_ens_run_device.restype = C.c_int
+        h.epi_ens_run_device.argtypes = ens_args + [C.c_void_p, C.c_char_p]
+        h.epi_ens_run_host.restype = C.c_int
+        h.epi_ens_run_host.argtypes = ens_args + [C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h

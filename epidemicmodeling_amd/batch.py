@@ -841,3 +841,53 @@ def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, 
     rc = _lib.lib().epi_lasso_run_device(C.byref(d), _ptr(X), _ptr(y), _ptr(f), C.byref(outs), C.c_void_p(st.cuda_stream), err)
     _lib.check(rc, err)
     return out
+
+
+def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
+    """Monte-Carlo ensemble statistics in one device call (epi_ens_run_device): src [T, rows, B] or [T, B]
+    (float32 or float64, on the device) is an output array of B = R * D chains in the classic layout, region-major (chain =
+    r * D + d: synth.make_cfg5); every (day, row, region) is summarised over its D draws.  NaN members are excluded.
+    population [R] appends the derived row ((N * row0) * row1) * row2 (the day's new cases of the 3-state model).
+    outputs: names out of mean, std, min, max, quantiles (default: all); count is always returned.
+    Returns a dict of device tensors: mean, std, min, max [T, rows', R] float64, quantiles [T, n_q, rows', R] (MATLAB's
+    quantile rule = NumPy's method="hazen"), count [T, rows', R] int32.  Enqueued on `stream` (default: the current stream)
+    without a host synchronisation.  A chain-blocked output (EkfRunner(lane_block=...)) is not accepted."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a torch tensor (NumPy arrays: hostapi.ensemble_summary)")
+    if src.dim() == 4:
+        raise ValueError("src is a chain-blocked tensor [T, nblk, rows, blk]; ensemble_summary takes the classic layout "
+                         "[T, rows, B]: pass EkfRunner.unblocked(name).contiguous(), or run with lane_block=0")
+    if src.dim() not in (2, 3):
+        raise ValueError("src must be [T, rows, B] or [T, B]")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError("src must be float32 or float64")
+    R, D = int(R), int(D)
+    if src.shape[-1] != R * D:
+        raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
+    dev = src.device
+    src = src.contiguous()
+    T, rows = src.shape[0], (1 if src.dim() == 2 else src.shape[1])
+    pop = None
+    if population is not None:
+        pop = (population if isinstance(population, torch.Tensor) else
+               torch.as_tensor(np.ascontiguousarray(population, dtype=np.float64))).to(dev, torch.float64).contiguous()
+        if tuple(pop.shape) != (R,):
+            raise ValueError("population must be [R]")
+    d = _lib.make_ens_desc(T, rows, R, D, q, storage=1 if src.dtype == torch.float32 else 0, derive_newcases=int(pop is not None))
+    names = [k for k in _lib.ENS_OUT_NAMES if k != "count"] if outputs is None else list(outputs)
+    bad = [k for k in names if k not in _lib.ENS_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    err = C.create_string_buffer(256)
+    shapes = _lib.ens_shapes(T, rows, R, d.n_q, d.derive_newcases)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "count" else torch.float64, device=dev)
+           for k in _lib.ENS_OUT_NAMES if k == "count" or k in names}
+    if src.dim() == 2:
+        out = {k: v.squeeze(-2) for k, v in out.items()}
+    outs = _lib.EnsOutputs()
+    for k in _lib.ENS_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    rc = _lib.lib().epi_ens_run_device(C.byref(d), _ptr(src), _ptr(pop), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out

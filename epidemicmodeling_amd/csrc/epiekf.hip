@@ -827,6 +827,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "lookahead.hpp"
 #include "rt_window.hpp"
 #include "lasso.hpp"
+#include "ens_summary.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3654,5 +3655,97 @@ int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y
     return rc;
 }
 
-}  // extern "C"
+// ---- Monte-Carlo ensemble statistics over the draws of every region (BASELINE config 5) ----
+int epi_ens_validate(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->rows < 1) { set_err(err, "rows must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1 || d->D > kEnsMaxD) { set_err(err, "D must lie in 1 .. 4096 (a wavefront holds the draws of an item in registers)"); return EPI_ERR_BAD_ARG; }
+    if (d->n_q < 1 || d->n_q > kEnsMaxQ) { set_err(err, "n_q must lie in 1 .. 16"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->n_q; k++)
+        if (!(d->q[k] >= 0.0 && d->q[k] <= 1.0)) { set_err(err, "every q must be finite and lie in [0, 1]"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases != 0 && d->derive_newcases != 1) { set_err(err, "derive_newcases must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && d->rows < 3) { set_err(err, "derive_newcases needs at least 3 rows"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && !population) { set_err(err, "NULL population (derive_newcases)"); return EPI_ERR_BAD_ARG; }
+    if (!src || !out) { set_err(err, "NULL src / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!out->count) { set_err(err, "NULL count output"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
 
+int epi_ens_run_device(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out,
+                       void *stream, char *err)
+{
+    int rc = epi_ens_validate(d, src, population, out, err);
+    if (rc != EPI_OK) return rc;
+    EnsArgs g{};
+    g.T = d->T; g.rows = d->rows; g.rows_out = d->rows + d->derive_newcases; g.R = d->R; g.D = d->D; g.n_q = d->n_q;
+    g.f32 = d->storage; g.derive = d->derive_newcases;
+    g.src = src; g.population = population;
+    for (int k = 0; k < d->n_q; k++) g.q[k] = d->q[k];
+    g.mean = out->mean; g.std = out->std; g.mn = out->min; g.mx = out->max; g.quant = out->quantiles; g.count = out->count;
+    const int64_t items = (int64_t)d->T * g.rows_out * d->R;
+    for (int64_t i0 = 0; i0 < items; i0 += kEnsLaunchItems) {      // one 64-lane workgroup per item, in slices (ens_summary.hpp)
+        g.item0 = (long long)i0;
+        const unsigned ni = (unsigned)(items - i0 < kEnsLaunchItems ? items - i0 : kEnsLaunchItems);
+        const hipStream_t st = (hipStream_t)stream;
+        hipError_t e;
+        if (d->D <= 64) e = ens_launch<1>(g, ni, st);              // registers per lane: P / 64, P the power of two >= D
+        else if (d->D <= 128) e = ens_launch<2>(g, ni, st);
+        else if (d->D <= 256) e = ens_launch<4>(g, ni, st);
+        else if (d->D <= 512) e = ens_launch<8>(g, ni, st);
+        else if (d->D <= 1024) e = ens_launch<16>(g, ni, st);
+        else if (d->D <= 2048) e = ens_launch<32>(g, ni, st);
+        else e = ens_launch<64>(g, ni, st);
+        if (e != hipSuccess) return hip_fail(err, e, "ens_summary launch");
+    }
+    return EPI_OK;
+}
+
+int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out,
+                     int device, char *err)
+{
+    int rc = epi_ens_validate(d, src, population, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, B = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases);
+    HostIO io;
+    const size_t o_src = io.add_in(src, T * (size_t)d->rows, d->storage ? 4 : 8, B, 0, B);
+    const size_t o_pop = d->derive_newcases ? io.add_in(population, 1, 8, R, 0, R) : (size_t)-1;
+    double *const *f64[5] = {&out->mean, &out->std, &out->min, &out->max, &out->quantiles};
+    size_t o_d[5];
+    for (int k = 0; k < 5; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], T * ro * (k == 4 ? (size_t)d->n_q : 1), 8, R, 0, R) : (size_t)-1;
+    const size_t o_cnt = io.add_out(out->count, T * ro, 4, R, 0, R);
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        epi_ens_outputs dout{};
+        double **df[5] = {&dout.mean, &dout.std, &dout.min, &dout.max, &dout.quantiles};
+        for (int k = 0; k < 5; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
+        dout.count = (int32_t *)(base + o_cnt);
+        const int r = epi_ens_run_device(d, base + o_src, o_pop == (size_t)-1 ? nullptr : (const double *)(base + o_pop), &dout,
+                                         cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
+}  // extern "C"

@@ -182,3 +182,40 @@ def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, 
                                        C.byref(outs), int(device), err)
     _lib.check(rc, err)
     return out
+
+
+def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
+    """epi_ens_run_host: the Monte-Carlo ensemble statistics of batch.ensemble_summary on NumPy arrays (synchronous).
+    src [T, rows, B] or [T, B], float32 or float64 (anything else is converted to float64), B = R * D region-major.
+    Returns the dict of batch.ensemble_summary as NumPy arrays."""
+    src = np.asarray(src)
+    if src.dtype not in (np.float32, np.float64):
+        src = src.astype(np.float64)
+    src = np.ascontiguousarray(src)
+    if src.ndim not in (2, 3):
+        raise ValueError("src must be [T, rows, B] or [T, B]")
+    R, D = int(R), int(D)
+    if src.shape[-1] != R * D:
+        raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
+    T, rows = src.shape[0], (1 if src.ndim == 2 else src.shape[1])
+    keep = []
+    pop = _f(population, keep)
+    if population is not None and keep[0].shape != (R,):
+        raise ValueError("population must be [R]")
+    d = _lib.make_ens_desc(T, rows, R, D, q, storage=1 if src.dtype == np.float32 else 0, derive_newcases=int(population is not None))
+    names = [k for k in _lib.ENS_OUT_NAMES if k != "count"] if outputs is None else list(outputs)
+    bad = [k for k in names if k not in _lib.ENS_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    shapes = _lib.ens_shapes(T, rows, R, d.n_q, d.derive_newcases)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k == "count" else np.float64)
+           for k in _lib.ENS_OUT_NAMES if k == "count" or k in names}
+    outs = _lib.EnsOutputs()
+    for k in _lib.ENS_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_ens_run_host(C.byref(d), src.ctypes.data, pop, C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    if src.ndim == 2:
+        out = {k: v.reshape(v.shape[:-2] + v.shape[-1:]) for k, v in out.items()}
+    return out

@@ -297,3 +297,25 @@ def growth_rates(cases, population, wlen=7, generation_period=3, causal=1, forec
         r = batch.rt_expfit(w, device=device, outputs=("S_PLUS", "S_SMOOTH"))
         out[f"ekf{order}_S_PLUS"], out[f"ekf{order}_S_SMOOTH"] = r["S_PLUS"], r["S_SMOOTH"]
     return out
+
+
+def monte_carlo_eks(w, n_regions, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, storage="f32", outputs=("S_SMOOTH",),
+                    device="cuda:0"):
+    """BASELINE config 5 end to end: the Monte-Carlo smoother on a region-major workload (chain = region * n_draws + draw,
+    synth.make_cfg5) and, for every output array named in `outputs`, its distribution over the draws of each region
+    (batch.ensemble_summary: mean, std, min, max, quantiles at `q`, count per day, row and region).  The chains stay in
+    HBM (`storage`: "f32" as config 5 stores them, or "f64"); only the summaries are returned, as device tensors.
+    population [n_regions] appends the new-case row ((N * s) * i) * alpha to the summary of a 3-row output.
+    Returns {output name: dict of batch.ensemble_summary} and "runner", the EkfRunner that holds the chains."""
+    n_regions = int(n_regions)
+    if w.B % n_regions:
+        raise ValueError("the workload does not hold the same number of draws for every region")
+    D = w.B // n_regions
+    dw = batch.DeviceWorkload(w, device)
+    r = batch.EkfRunner(dw, outputs=list(outputs), storage=storage)
+    r.run()
+    res = {name: batch.ensemble_summary(r.out[name], n_regions, D, q=q,
+                                        population=population if r.out[name].dim() == 3 and r.out[name].shape[1] >= 3 else None)
+           for name in outputs}
+    res["runner"] = r
+    return res

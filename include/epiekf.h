@@ -585,6 +585,47 @@ int epi_lasso_run_device(const epi_lasso_desc *d, const double *X, const double 
 int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y, const int32_t *fold,
                        const epi_lasso_outputs *out, int device, char *err);
 
+/* ---- Monte-Carlo ensemble statistics: the distribution over the D draws of every region (BASELINE config 5) ----
+ * src [T][rows][B] is an output array of the filter in the classic layout (S_SMOOTH, S_PLUS, ...: double, or float when the
+ * filter ran with storage = 1), B = R * D chains, region-major: chain = r * D + d (synth.make_cfg5).  An item is one (day t,
+ * row, region r) with the D members v[d] = src[t][row][r * D + d], widened to double.  With derive_newcases = 1 (rows >= 3,
+ * population [R] given) one row is appended after the source's: ((N_r * v0) * v1) * v2 of rows 0, 1, 2 of the same chain and
+ * day.  NaN members are excluded, n = the others (+-Inf take part); x(1 .. n) = the members ascending.  Per item:
+ *   count = n;  min = x(1), max = x(n);
+ *   quantile at p (MATLAB's quantile / prctile, NumPy's method="hazen"): h = n * p + 0.5, k = floor(h), g = h - k;
+ *     x(1) if k < 1, x(n) if k >= n, else x(k) + g * (x(k+1) - x(k));
+ *   mean = tree(v) / n, std = sqrt(tree(dev .* dev) / (n - 1)) with dev = v - mean (0 when n = 1), where tree() is the
+ *     pairwise sum in draw order: excluded members and the padding to P (the power of two >= D) are +0.0, then
+ *     a[i] = a[i] + a[i + h] for i < h, h = P/2, P/4, .., 1, and the sum is a[0];
+ *   n = 0: every statistic is NaN.
+ * One IEEE rounding per written operation: results are reproducible bit for bit, up to the sign of a zero.
+ * Outputs (NULL = not wanted, except count): mean, std, min, max, count [T][rows'][R], quantiles [T][n_q][rows'][R],
+ * rows' = rows + derive_newcases.  epi_ens_run_device takes DEVICE pointers and enqueues one wavefront per item on `stream`
+ * (no host synchronisation); epi_ens_run_host takes HOST pointers and runs on a pooled context of `device`. */
+typedef struct epi_ens_desc {
+    int32_t abi_version;
+    int32_t T;                   /* days, >= 1 */
+    int32_t rows;                /* rows of src, >= 1 */
+    int32_t R;                   /* regions, >= 1 */
+    int32_t D;                   /* draws per region, 1 .. 4096; R * D <= INT32_MAX */
+    int32_t n_q;                 /* quantiles, 1 .. 16 */
+    int32_t storage;             /* element type of src: 0 = double, 1 = float (epi_batch_desc.storage) */
+    int32_t derive_newcases;     /* 0, or 1: append the row ((N * row0) * row1) * row2 */
+    double q[16];                /* probabilities, each finite and in [0, 1]; the first n_q are read */
+} epi_ens_desc;
+typedef struct epi_ens_outputs {
+    double *mean, *std, *min, *max;         /* [T][rows'][R] */
+    double *quantiles;                      /* [T][n_q][rows'][R] */
+    int32_t *count;                         /* [T][rows'][R], required */
+} epi_ens_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for anything outside the limits above or a NULL descriptor / src / population
+ * (derive_newcases) / outputs / count */
+int epi_ens_validate(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out, char *err);
+int epi_ens_run_device(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out,
+                       void *stream, char *err);
+int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out,
+                     int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

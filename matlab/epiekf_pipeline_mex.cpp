@@ -27,6 +27,12 @@
 //       lambda, mse, se, intercept, df  R x NumLambda (ascending lambda, MATLAB's order);  idx, idx1se  R x 1
 //       (IndexMinMSE, Index1SE, ONE-based);  B  R x n x NumLambda.  A region whose X / y holds Inf or NaN gets NaN outputs
 //       and idx = idx1se = 0; with K = 0, a, b, mse and se are NaN and idx = idx1se = 0.  (No lasso.m is shipped: it would shadow the Statistics Toolbox function.)
+//   [mean, std, min, max, quantiles, count] = epiekf_pipeline_mex('ens_summary', src, D, q, population)
+//       Monte-Carlo ensemble statistics (BASELINE config 5).  src  B x rows x T (or B x T), B = R * D chains,
+//       region-major (chain = (r-1) * D + d): a filter output such as S_SMOOTH;  D  draws per region;  q  1 .. 16
+//       probabilities in [0, 1] (quantile(x, q)'s rule);  population ([] = none)  R x 1: appends the row
+//       ((N * row1) * row2) * row3.  NaN members are excluded.  mean, std, min, max, count  R x rows' x T;  quantiles
+//       R x rows' x n_q x T.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -202,6 +208,42 @@ static void lasso(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('ens_summary', src, D, q, population): 5 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1])) mexErrMsgTxt("src must be a double array B x rows x T (or B x T)");
+    const mwSize *ds = mxGetDimensions(prhs[1]);
+    const mwSize B = ds[0], rows = nd == 3 ? ds[1] : 1, T = nd == 3 ? ds[2] : ds[1];
+    const double Dd = mxGetScalar(prhs[2]);
+    if (!(Dd >= 1.0 && Dd <= 4096.0) || (double)(mwSize)Dd != Dd || B % (mwSize)Dd != 0) mexErrMsgTxt("D must be an integer in 1 .. 4096 that divides the number of chains");
+    const mwSize D = (mwSize)Dd, R = B / D, nq = mxGetNumberOfElements(prhs[3]);
+    if (nq < 1 || nq > 16) mexErrMsgTxt("q must hold 1 .. 16 probabilities");
+    const bool derive = !mxIsEmpty(prhs[4]);
+    if (derive && mxGetNumberOfElements(prhs[4]) != R) mexErrMsgTxt("population must have one entry per region");
+    epi_ens_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.rows = (int32_t)rows; d.R = (int32_t)R; d.D = (int32_t)D;
+    d.n_q = (int32_t)nq; d.storage = 0; d.derive_newcases = derive ? 1 : 0;
+    for (mwSize k = 0; k < nq; k++) d.q[k] = mxGetPr(prhs[3])[k];
+    const mwSize ro = rows + (derive ? 1 : 0);
+    const mwSize d4[4] = {R, ro, nq, T};
+    mxArray *o[6] = {dbl3(R, ro, T), dbl3(R, ro, T), dbl3(R, ro, T), dbl3(R, ro, T), mxCreateNumericArray(4, d4, mxDOUBLE_CLASS, mxREAL),
+                     dbl3(R, ro, T)};
+    std::vector<int32_t> cnt((size_t)(R * ro * T));
+    epi_ens_outputs out;
+    memset(&out, 0, sizeof out);
+    out.mean = mxGetPr(o[0]); out.std = mxGetPr(o[1]); out.min = mxGetPr(o[2]); out.max = mxGetPr(o[3]); out.quantiles = mxGetPr(o[4]);
+    out.count = cnt.data();
+    // the ABI's [T][rows'][R] and [T][n_q][rows'][R] are MATLAB's R x rows' x T and R x rows' x n_q x T: no transposition
+    char err[256] = {0};
+    const int rc = epi_ens_run_host(&d, mxGetPr(prhs[1]), derive ? mxGetPr(prhs[4]) : NULL, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < cnt.size(); k++) mxGetPr(o[5])[k] = (double)cnt[k];
+    for (int k = 0; k < 6; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -238,6 +280,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "preprocess") == 0) preprocess(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "nnls") == 0) nnls(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }

@@ -1,0 +1,108 @@
+"""epi_ens_validate and the argument checks of epi_ens_run_host, through the C ABI (no GPU needed: every case is rejected
+before a device is touched), and the argument checks of the Python entry points."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+T_, ROWS_, R_, D_ = 2, 3, 4, 5
+
+
+def _call(fn="validate", **kw):
+    from epidemicmodeling_amd import _lib
+    args = dict(T=T_, rows=ROWS_, R=R_, D=D_, q=(0.025, 0.5, 0.975), storage=0, derive_newcases=0)
+    args.update({k: v for k, v in kw.items() if k in args})
+    d = _lib.make_ens_desc(**args)
+    for k in ("abi_version", "n_q"):
+        if k in kw:
+            setattr(d, k, kw[k])
+    src = np.ones((T_, ROWS_, R_ * D_), dtype=np.float32 if args["storage"] == 1 else np.float64)
+    pop = np.ones(R_)
+    outs = _lib.EnsOutputs()
+    bufs = {k: np.empty(sh, dtype=np.int32 if k == "count" else np.float64)
+            for k, sh in _lib.ens_shapes(T_, ROWS_, R_, 16, 1).items()}
+    for k, v in bufs.items():
+        setattr(outs, k, v.ctypes.data)
+    for k in kw.get("null_outs", ()):
+        setattr(outs, k, None)
+    err = C.create_string_buffer(256)
+    sp = None if kw.get("null_src") else src.ctypes.data
+    pp = pop.ctypes.data if kw.get("with_pop") else None
+    op = None if kw.get("null_out") else C.byref(outs)
+    dp = None if kw.get("null_desc") else C.byref(d)
+    lib = _lib.lib()
+    if fn == "validate":
+        rc = lib.epi_ens_validate(dp, sp, pp, op, err)
+    else:
+        rc = lib.epi_ens_run_host(dp, sp, pp, op, 0, err)
+    return rc, err.value.decode()
+
+
+BAD = [
+    (dict(null_desc=True), "NULL descriptor"),
+    (dict(abi_version=5), "ABI"),
+    (dict(T=0), "T must be"),
+    (dict(rows=0), "rows must be"),
+    (dict(R=0), "R must be"),
+    (dict(D=0), "D must lie in 1 .. 4096"),
+    (dict(D=4097), "D must lie in 1 .. 4096"),
+    (dict(n_q=0), "n_q must lie in 1 .. 16"),
+    (dict(n_q=17), "n_q must lie in 1 .. 16"),
+    (dict(q=(0.5, -0.1)), "every q must be finite"),
+    (dict(q=(1.1,)), "every q must be finite"),
+    (dict(q=(0.5, float("nan"))), "every q must be finite"),
+    (dict(q=(float("inf"),)), "every q must be finite"),
+    (dict(R=(2 ** 31 - 1) // 4096 + 1, D=4096), "R * D is limited"),
+    (dict(storage=2), "storage must be"),
+    (dict(derive_newcases=2, with_pop=True), "derive_newcases must be 0 or 1"),
+    (dict(derive_newcases=1, rows=2, with_pop=True), "at least 3 rows"),
+    (dict(derive_newcases=1), "NULL population"),
+    (dict(null_src=True), "NULL src"),
+    (dict(null_out=True), "NULL src"),
+    (dict(null_outs=("count",)), "NULL count"),
+]
+
+
+@pytest.mark.parametrize("kw, msg", BAD)
+def test_validate_rejects(hip_lib, kw, msg):
+    got, text = _call("validate", **kw)
+    assert got == -5 and msg in text, (got, text)
+    got, text = _call("run_host", **kw)                     # the host entry validates first, before any device work
+    assert got == -5 and msg in text, (got, text)
+
+
+def test_validate_accepts(hip_lib):
+    assert _call("validate") == (0, "")
+    assert _call("validate", D=1, q=(0.0,))[0] == 0
+    assert _call("validate", D=4096, q=tuple(np.linspace(0.0, 1.0, 16)), storage=1)[0] == 0
+    assert _call("validate", derive_newcases=1, with_pop=True, null_outs=("mean", "std", "min", "max", "quantiles"))[0] == 0
+    assert _call("validate", R=(2 ** 31 - 1) // 4096, D=4096)[0] == 0
+
+
+def test_descriptor_matches_the_header(hip_lib):
+    """8 int32 and 16 doubles, no padding: what include/epiekf.h declares"""
+    from epidemicmodeling_amd import _lib
+    assert C.sizeof(_lib.EnsDesc) == 8 * 4 + 16 * 8 and _lib.EnsDesc.q.offset == 32
+    assert C.sizeof(_lib.EnsOutputs) == 6 * C.sizeof(C.c_void_p)
+    d = _lib.make_ens_desc(2, 3, 4, 5, q=(0.1, 0.9), storage="f32", derive_newcases=1)
+    assert (d.n_q, d.storage, d.derive_newcases, d.q[0], d.q[1]) == (2, 1, 1, 0.1, 0.9)
+
+
+def test_python_entry_points_check_their_arguments(hip_lib):
+    import torch
+    from epidemicmodeling_amd import batch, hostapi
+    from epidemicmodeling_amd._lib import EpiError
+    with pytest.raises(ValueError, match="EkfRunner.unblocked"):
+        batch.ensemble_summary(torch.zeros((2, 3, 3, 8)), 4, 5)                 # chain-blocked [T, nblk, rows, blk]
+    with pytest.raises(ValueError, match="R \\* D"):
+        batch.ensemble_summary(torch.zeros((2, 3, 21)), 4, 5)
+    with pytest.raises(TypeError, match="float32 or float64"):
+        batch.ensemble_summary(torch.zeros((2, 3, 20), dtype=torch.int32), 4, 5)
+    with pytest.raises(ValueError, match="R \\* D"):
+        hostapi.ensemble_summary(np.zeros((2, 3, 21)), 4, 5)
+    with pytest.raises(EpiError, match="every q must be finite"):
+        hostapi.ensemble_summary(np.zeros((2, 3, 20)), 4, 5, q=(1.5,))
+    with pytest.raises(EpiError, match="n_q must lie"):
+        hostapi.ensemble_summary(np.zeros((2, 3, 20)), 4, 5, q=tuple(np.linspace(0, 1, 17)))
+    with pytest.raises(EpiError, match="at least 3 rows"):
+        hostapi.ensemble_summary(np.zeros((2, 20)), 4, 5, population=np.ones(4))
