@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "epi_rtwin_validate", "epi_rtwin_run_device", "epi_rtwin_run_host",
     "epi_lasso_validate", "epi_lasso_run_device", "epi_lasso_run_host",
     "epi_ens_validate", "epi_ens_run_device", "epi_ens_run_host",
+    "epi_arfc_validate", "epi_arfc_run_device", "epi_arfc_run_host",
 ]
 
 
@@ -216,6 +217,37 @@ def make_ens_desc(T, rows, R, D, q=ENS_DEFAULT_Q, storage=0, derive_newcases=0) 
     return d
 
 
+class ArfcDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "D", "L", "p", "H", "fit", "nv_mode", "Sd", "reserved")] + \
+        [("dt", C.c_double)]
+
+
+ARFC_IN_NAMES = ("seg", "beta", "s0", "i0", "z", "drive", "drive_series", "A", "noise_var")
+ARFC_OUT_NAMES = ("S", "A_out", "noise_var_out", "status")
+ARFC_OK, ARFC_RANK_DEFICIENT, ARFC_BAD_INPUT = 0, 1, 2
+
+
+class ArfcInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ARFC_IN_NAMES]
+
+
+class ArfcOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ARFC_OUT_NAMES]
+
+
+def arfc_shapes(R, D, L, p, H):
+    """shape of every output of epi_arfc_run_*"""
+    return {"S": (int(L) + int(H), 3, int(R) * int(D)), "A_out": (int(p), int(R)), "noise_var_out": (int(R),), "status": (int(R),)}
+
+
+def make_arfc_desc(R, D, L, p, H, dt, fit=1, nv_mode=0, Sd=0) -> ArfcDesc:
+    d = ArfcDesc()
+    d.abi_version = ABI_VERSION
+    d.R, d.D, d.L, d.p, d.H = int(R), int(D), int(L), int(p), int(H)
+    d.fit, d.nv_mode, d.Sd, d.reserved, d.dt = int(fit), int(nv_mode), int(Sd), 0, float(dt)
+    return d
+
+
 class NnlsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "S", "D", "n", "max_iters")]
 
@@ -361,6 +393,13 @@ def lib():
         h.epi_ens_run_device.argtypes = ens_args + [C.c_void_p, C.c_char_p]
         h.epi_ens_run_host.restype = C.c_int
         h.epi_ens_run_host.argtypes = ens_args + [C.c_int, C.c_char_p]
+        arfc_args = [C.POINTER(ArfcDesc), C.POINTER(ArfcInputs), C.POINTER(ArfcOutputs)]
+        h.epi_arfc_validate.restype = C.c_int
+        h.epi_arfc_validate.argtypes = arfc_args + [C.c_char_p]
+        h.epi_arfc_run_device.restype = C.c_int
+        h.epi_arfc_run_device.argtypes = arfc_args + [C.c_void_p, C.c_char_p]
+        h.epi_arfc_run_host.restype = C.c_int
+        h.epi_arfc_run_host.argtypes = arfc_args + [C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h

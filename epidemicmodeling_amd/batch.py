@@ -891,3 +891,75 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
     rc = _lib.lib().epi_ens_run_device(C.byref(d), _ptr(src), _ptr(pop), C.byref(outs), C.c_void_p(st.cuda_stream), err)
     _lib.check(rc, err)
     return out
+
+
+def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series=None, A=None, noise_var=None, nv_mode=0,
+                stream=None, device="cuda:0"):
+    """The autoregressive alpha forecaster of Tools/PrescribeNPI.m:204-215 for R regions x D draws in one device call
+    (epi_arfc_run_device): ar(seg, p) -> filtic -> filter(sqrt(nv), A, z, zi) (+ drive) -> negatives to 0 ->
+    SI_Controlled over [segment, forecast].  seg [L, R] (the last L days of each region's alpha), beta / s0 / i0 [R], dt a
+    number; chain = region * D + draw, B = R * D.  z [H, B] standard-normal draws (None = zeros: the deterministic
+    continuation); drive [H, Sd] with drive_series [B] (None: Sd == B), added before the clamp: gamma * (u' * a + b).  A
+    NumPy drive_series is range-checked on the host; one that is already a device tensor is NOT read back and must hold
+    entries in 0 .. Sd-1 (the library trusts it, as it trusts alpha_series).
+    A [p, R] (a_1 .. a_p) and noise_var [R] together select the given-model mode (MATLAB's get(ar_sys, 'A')(2:end) and
+    'NoiseVariance'); otherwise the model is fitted, with nv_mode 0 = (forward RSS + backward RSS) / (2 (L - p)) or
+    1 = forward RSS / (L - p) as its noise variance.  Inputs are torch tensors (taken where they are) or NumPy arrays (copied
+    to `device`).  Returns a dict of device tensors: S [L + H, 3, B] with rows (s, i, alpha_hat) -- what
+    ensemble_summary(S, R, D, population=N) takes -- A [p, R], noise_var [R], status [R] int32 (_lib.ARFC_OK,
+    ARFC_RANK_DEFICIENT: NaN from day L on, ARFC_BAD_INPUT: NaN everywhere).  Enqueued on `stream` (default: the current
+    stream) without a host synchronisation."""
+    if (A is None) != (noise_var is None):
+        raise ValueError("A and noise_var are given together (the given-model mode) or not at all")
+    tensors = [v for v in (seg, beta, s0, i0, z, drive, drive_series, A, noise_var) if isinstance(v, torch.Tensor)]
+    dev = tensors[0].device if tensors else torch.device(device)
+
+    def put(v, dtype=torch.float64):
+        if v is None:
+            return None
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32 if dtype == torch.int32 else np.float64))
+        return v.to(dev, dtype).contiguous()
+
+    seg = put(seg)
+    if seg.dim() != 2:
+        raise ValueError("seg must be [L, R]")
+    L, R = seg.shape
+    p, H, D = int(p), int(H), int(D)
+    B = R * D
+    beta, s0, i0, z, drive, A, noise_var = (put(v) for v in (beta, s0, i0, z, drive, A, noise_var))
+    if drive_series is not None and not isinstance(drive_series, torch.Tensor) and drive is not None:
+        hs = np.asarray(drive_series)                   # checked on the host, before the upload: no read-back
+        if hs.size and (hs.min() < 0 or hs.max() >= np.shape(drive)[-1]):
+            raise ValueError("drive_series must hold entries in 0 .. Sd-1")
+    ser = put(drive_series, torch.int32)
+    for name, v in (("beta", beta), ("s0", s0), ("i0", i0), ("noise_var", noise_var)):
+        if v is not None and tuple(v.shape) != (R,):
+            raise ValueError(f"{name} must be [R]")
+    if z is not None and tuple(z.shape) != (H, B):
+        raise ValueError("z must be [H, R * D]")
+    if A is not None and tuple(A.shape) != (p, R):
+        raise ValueError("A must be [p, R]")
+    Sd = 0
+    if drive is not None:
+        if drive.dim() != 2 or drive.shape[0] != H:
+            raise ValueError("drive must be [H, Sd]")
+        Sd = drive.shape[1]
+        if ser is not None and tuple(ser.shape) != (B,):
+            raise ValueError("drive_series must be [R * D]")
+    elif ser is not None:
+        raise ValueError("drive_series without drive")
+    d = _lib.make_arfc_desc(R, D, L, p, H, dt, fit=int(A is None), nv_mode=nv_mode, Sd=Sd)
+    ins = _lib.ArfcInputs()
+    for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, ser, A, noise_var)):
+        setattr(ins, k, _ptr(v))
+    err = C.create_string_buffer(256)
+    shapes = _lib.arfc_shapes(R, D, L, p, H)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float64, device=dev) for k in _lib.ARFC_OUT_NAMES}
+    outs = _lib.ArfcOutputs()
+    for k in _lib.ARFC_OUT_NAMES:
+        setattr(outs, k, _ptr(out[k]))
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    rc = _lib.lib().epi_arfc_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}

@@ -828,6 +828,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "rt_window.hpp"
 #include "lasso.hpp"
 #include "ens_summary.hpp"
+#include "ar_forecast.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3737,6 +3738,131 @@ int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *popul
         dout.count = (int32_t *)(base + o_cnt);
         const int r = epi_ens_run_device(d, base + o_src, o_pop == (size_t)-1 ? nullptr : (const double *)(base + o_pop), &dout,
                                          cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
+// ---- the autoregressive alpha forecaster, R regions x D draws (Tools/PrescribeNPI.m:204-215) ----
+int epi_arfc_validate(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1) { set_err(err, "D must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->p < 1 || d->p > kArMaxP) { set_err(err, "p must lie in 1 .. 32"); return EPI_ERR_BAD_ARG; }
+    if (d->L < d->p + 1) { set_err(err, "L must be at least p + 1"); return EPI_ERR_BAD_ARG; }
+    if (d->L - d->p > kArMaxRows) { set_err(err, "L - p is limited to 256 (the stacked matrix of a region lives in LDS)"); return EPI_ERR_BAD_ARG; }
+    if (2 * (d->L - d->p) < d->p + 1) { set_err(err, "2 (L - p) must be at least p + 1 (more equations than unknowns)"); return EPI_ERR_BAD_ARG; }
+    if (d->H < 1) { set_err(err, "H must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->fit != 0 && d->fit != 1) { set_err(err, "fit must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->nv_mode != 0 && d->nv_mode != 1) { set_err(err, "nv_mode must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (!(fabs(d->dt) < (double)INFINITY)) { set_err(err, "dt must be finite"); return EPI_ERR_BAD_ARG; }
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->seg || !in->beta || !in->s0 || !in->i0) { set_err(err, "NULL seg / beta / s0 / i0"); return EPI_ERR_BAD_ARG; }
+    if (d->fit == 0 && (!in->A || !in->noise_var)) { set_err(err, "fit = 0 needs A and noise_var"); return EPI_ERR_BAD_ARG; }
+    if (d->fit == 1 && (!out->A_out || !out->noise_var_out)) { set_err(err, "fit = 1 needs A_out and noise_var_out (the fit hands its model to the simulation through them)"); return EPI_ERR_BAD_ARG; }
+    if (in->drive && d->Sd < 1) { set_err(err, "Sd must be >= 1 with a drive"); return EPI_ERR_BAD_ARG; }
+    if (in->drive && !in->drive_series && (int64_t)d->Sd != (int64_t)d->R * d->D) { set_err(err, "drive without drive_series needs Sd == R * D"); return EPI_ERR_BAD_ARG; }
+    if (!out->S) { set_err(err, "NULL S output"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, void *stream, char *err)
+{
+    int rc = epi_arfc_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    const double *A = in->A, *nv = in->noise_var;
+    if (d->fit) {
+        ArFitArgs f{};
+        f.L = d->L; f.p = d->p; f.R = d->R; f.nv_mode = d->nv_mode;
+        f.seg = in->seg; f.A = out->A_out; f.nv = out->noise_var_out; f.status = out->status;
+        const size_t shm = ar_fit_lds_bytes(d->L, d->p);
+        // always the worst case (p = 32, L = 288), never this call's size: concurrent callers with different (L, p) then set the
+        // same value, so the attribute cannot change between another thread's set and its launch
+        if ((e = hipFuncSetAttribute((const void *)ar_fit, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)ar_fit_lds_bytes(kArMaxP + kArMaxRows, kArMaxP))) != hipSuccess)
+            return hip_fail(err, e, "hipFuncSetAttribute");
+        for (int64_t r0 = 0; r0 < d->R; r0 += kArLaunchBlocks) {           // one 64-lane workgroup per region, in slices
+            f.r0 = (long long)r0;
+            const unsigned nb = (unsigned)(d->R - r0 < kArLaunchBlocks ? d->R - r0 : kArLaunchBlocks);
+            hipLaunchKernelGGL(ar_fit, dim3(nb), dim3(64), shm, st, f);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ar_fit launch");
+        }
+        A = out->A_out; nv = out->noise_var_out;
+    } else {
+        const size_t R = (size_t)d->R;
+        if (out->A_out && (e = hipMemcpyAsync(out->A_out, in->A, (size_t)d->p * R * sizeof(double), hipMemcpyDeviceToDevice, st)) != hipSuccess)
+            return hip_fail(err, e, "copy of A");
+        if (out->noise_var_out && (e = hipMemcpyAsync(out->noise_var_out, in->noise_var, R * sizeof(double), hipMemcpyDeviceToDevice, st)) != hipSuccess)
+            return hip_fail(err, e, "copy of noise_var");
+        if (out->status) {
+            hipLaunchKernelGGL(ar_given_status, dim3((unsigned)((d->R + 63) / 64)), dim3(64), 0, st, d->L, d->R, in->seg, out->status);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ar_given_status launch");
+        }
+    }
+    ArSimArgs g{};
+    g.L = d->L; g.p = d->p; g.H = d->H; g.R = d->R; g.D = d->D; g.Sd = d->Sd; g.bpr = (d->D + 63) / 64; g.dt = d->dt;
+    g.seg = in->seg; g.beta = in->beta; g.s0 = in->s0; g.i0 = in->i0; g.A = A; g.nv = nv; g.z = in->z; g.drive = in->drive;
+    g.drive_series = in->drive_series; g.S = out->S;
+    const size_t shm = ar_sim_lds_bytes(d->L, d->p);
+    const int64_t blocks = (int64_t)d->R * g.bpr;
+    for (int64_t b0 = 0; b0 < blocks; b0 += kArLaunchBlocks) {
+        g.blk0 = (long long)b0;
+        const unsigned nb = (unsigned)(blocks - b0 < kArLaunchBlocks ? blocks - b0 : kArLaunchBlocks);
+        hipLaunchKernelGGL(ar_simulate, dim3(nb), dim3(64), shm, st, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ar_simulate launch");
+    }
+    return EPI_OK;
+}
+
+int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err)
+{
+    int rc = epi_arfc_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, B = R * (size_t)d->D, K = (size_t)d->L + (size_t)d->H, none = (size_t)-1;
+    HostIO io;
+    const size_t o_seg = io.add_in(in->seg, (size_t)d->L, 8, R, 0, R);
+    const size_t o_beta = io.add_in(in->beta, 1, 8, R, 0, R), o_s0 = io.add_in(in->s0, 1, 8, R, 0, R), o_i0 = io.add_in(in->i0, 1, 8, R, 0, R);
+    const size_t o_z = in->z ? io.add_in(in->z, (size_t)d->H, 8, B, 0, B) : none;
+    const size_t o_drv = in->drive ? io.add_in(in->drive, (size_t)d->H, 8, (size_t)d->Sd, 0, (size_t)d->Sd) : none;
+    const size_t o_ser = in->drive && in->drive_series ? io.add_in(in->drive_series, 1, 4, B, 0, B) : none;
+    const size_t o_A = d->fit ? none : io.add_in(in->A, (size_t)d->p, 8, R, 0, R);
+    const size_t o_nv = d->fit ? none : io.add_in(in->noise_var, 1, 8, R, 0, R);
+    const size_t o_S = io.add_out(out->S, K * 3, 8, B, 0, B);
+    const size_t o_Ao = io.add_out(out->A_out, (size_t)d->p, 8, R, 0, R);          // device copies exist even when not wanted
+    const size_t o_nvo = io.add_out(out->noise_var_out, 1, 8, R, 0, R);
+    const size_t o_st = io.add_out(out->status, 1, 4, R, 0, R);
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        auto dp = [&](size_t o) { return o == none ? nullptr : (const double *)(base + o); };
+        epi_arfc_inputs din{};
+        din.seg = dp(o_seg); din.beta = dp(o_beta); din.s0 = dp(o_s0); din.i0 = dp(o_i0); din.z = dp(o_z); din.drive = dp(o_drv);
+        din.drive_series = o_ser == none ? nullptr : (const int32_t *)(base + o_ser);
+        din.A = dp(o_A); din.noise_var = dp(o_nv);
+        epi_arfc_outputs dout{};
+        dout.S = (double *)(base + o_S); dout.A_out = (double *)(base + o_Ao); dout.noise_var_out = (double *)(base + o_nvo);
+        dout.status = (int32_t *)(base + o_st);
+        const int r = epi_arfc_run_device(d, &din, &dout, cx->stream, err);
         if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
         if (ev1) (void)hipEventRecord(ev1, cx->stream);
         return EPI_OK;

@@ -219,3 +219,50 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
     if src.ndim == 2:
         out = {k: v.reshape(v.shape[:-2] + v.shape[-1:]) for k, v in out.items()}
     return out
+
+
+def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series=None, A=None, noise_var=None, nv_mode=0,
+                device=0):
+    """epi_arfc_run_host: the autoregressive alpha forecaster of batch.ar_forecast on NumPy arrays (synchronous).
+    seg [L, R], beta / s0 / i0 [R], z [H, R * D] or None, drive [H, Sd] or None with drive_series [R * D] or None, A [p, R]
+    and noise_var [R] (both or neither).  Returns the dict of batch.ar_forecast as NumPy arrays."""
+    if (A is None) != (noise_var is None):
+        raise ValueError("A and noise_var are given together (the given-model mode) or not at all")
+    keep = []
+    seg = np.ascontiguousarray(seg, dtype=np.float64)
+    if seg.ndim != 2:
+        raise ValueError("seg must be [L, R]")
+    Ls, R = seg.shape
+    p, H, D = int(p), int(H), int(D)
+    B = R * D
+    for name, v, shape in (("beta", beta, (R,)), ("s0", s0, (R,)), ("i0", i0, (R,)), ("z", z, (H, B)), ("A", A, (p, R)),
+                           ("noise_var", noise_var, (R,)), ("drive_series", drive_series, (B,))):
+        if v is not None and np.shape(v) != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+    Sd = 0
+    if drive is not None:
+        drive = np.ascontiguousarray(drive, dtype=np.float64)
+        if drive.ndim != 2 or drive.shape[0] != H:
+            raise ValueError("drive must be [H, Sd]")
+        Sd = drive.shape[1]
+    elif drive_series is not None:
+        raise ValueError("drive_series without drive")
+    ser = None
+    if drive_series is not None:
+        ser = np.ascontiguousarray(drive_series, dtype=np.int32)
+        if ser.min() < 0 or ser.max() >= Sd:
+            raise ValueError("drive_series must hold entries in 0 .. Sd-1")
+    d = _lib.make_arfc_desc(R, D, Ls, p, H, dt, fit=int(A is None), nv_mode=nv_mode, Sd=Sd)
+    ins = _lib.ArfcInputs()
+    for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, None, A, noise_var)):
+        setattr(ins, k, _f(v, keep))
+    ins.drive_series = None if ser is None else ser.ctypes.data
+    err = C.create_string_buffer(256)
+    shapes = _lib.arfc_shapes(R, D, Ls, p, H)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k == "status" else np.float64) for k in _lib.ARFC_OUT_NAMES}
+    outs = _lib.ArfcOutputs()
+    for k in _lib.ARFC_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data)
+    rc = _lib.lib().epi_arfc_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}

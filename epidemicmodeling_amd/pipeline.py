@@ -319,3 +319,45 @@ def monte_carlo_eks(w, n_regions, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=
            for name in outputs}
     res["runner"] = r
     return res
+
+
+def ar_forecast(cases, deaths, population, ip, horizon=90, ar_order=24, history=120, n_draws=256, plan=None,
+                q=(0.025, 0.25, 0.5, 0.75, 0.975), seed=0, regression="nonnegls", nv_mode=0, num_regression_days=60, W=7,
+                cv_folds=50, cv_seed=0, device="cuda:0"):
+    """The autoregressive alpha forecast of Tools/PrescribeNPI.m:204-241 as a Monte-Carlo fan chart for ALL regions: the front
+    half (preprocessing, EKF round 1, regression, round 2, regression), then ar(alpha(end-history+1:end), ar_order) ->
+    filtic -> filter over n_draws noise realisations per region -> negatives to 0 -> SI_Controlled from ((N - I0) / N, I0 / N)
+    over [segment, forecast] (batch.ar_forecast, one device call), then the distribution over the draws of s, i, alpha_hat and
+    the new cases ((N s) i) alpha per day and region (batch.ensemble_summary, one more; nothing is copied back in between).
+    The noise is torch.randn on the device from `seed`.  plan [horizon, n, S] (None = no exogenous term) adds
+    gamma * ((u_max - u)' a + b) of the second regression to the continuation before the clamp: the regressor is the one the
+    regression was trained on (X = u_max - u), where PrescribeNPI.m:237 multiplies the raw plan.
+    Returns the front half's intermediates, seg [history, S], `forecast` (the dict of batch.ar_forecast: S [history + horizon,
+    3, S * n_draws], A, noise_var, status), `summary` (the dict of batch.ensemble_summary, rows s, i, alpha_hat, new cases),
+    z and drive."""
+    T, S = cases.shape
+    n = ip.shape[1]
+    history, horizon, n_draws = int(history), int(horizon), int(n_draws)
+    if history > T:
+        raise ValueError("history exceeds the number of days given")
+    N = np.asarray(population, dtype=np.float64)
+    out = _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression, cv_folds, cv_seed)
+    I0, fit2 = out["pre"]["I0"], out["fit2"]
+    seg = np.ascontiguousarray(out["alpha_round2"][T - history:])
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    z = torch.randn((horizon, S * n_draws), dtype=torch.float64, device=dev, generator=gen)
+    drive = ser = None
+    if plan is not None:
+        plan = np.asarray(plan, dtype=np.float64)
+        if plan.shape != (horizon, n, S):
+            raise ValueError("plan must be [horizon, n, S]")
+        x = synth.IP_MAXES[:n][None, :, None] - plan
+        drive = synth.MODEL_GAMMA * ((x * fit2["a"][None]).sum(axis=1) + fit2["b"][None])          # [horizon, S]
+        ser = np.repeat(np.arange(S, dtype=np.int32), n_draws)
+    fc = batch.ar_forecast(seg, np.full(S, synth.MODEL_BETA), (N - I0) / N, I0 / N, 1.0, ar_order, horizon, n_draws, z=z,
+                           drive=drive, drive_series=ser, nv_mode=nv_mode, device=device)
+    summary = batch.ensemble_summary(fc["S"], S, n_draws, q=q, population=N)
+    out.update(seg=seg, forecast=fc, summary=summary, z=z, drive=drive)
+    return out

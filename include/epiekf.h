@@ -626,6 +626,68 @@ int epi_ens_run_device(const epi_ens_desc *d, const void *src, const double *pop
 int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *population, const epi_ens_outputs *out,
                      int device, char *err);
 
+/* ---- The autoregressive alpha forecaster as a Monte-Carlo batch: Tools/PrescribeNPI.m:204-215 ----
+ *   ar_sys = ar(seg, p);  zi = filtic(sqrt(nv), A, seg(end:-1:1));  y = filter(sqrt(nv), A, randn(1, H), zi)';
+ *   AlphaHat = [seg ; y + drive]';  AlphaHat(AlphaHat < 0) = 0;  [s, i] = SI_Controlled(AlphaHat, beta, s0, i0, L + H, dt)
+ * for R regions x D draws, chain c = r * D + d (region-major: what epi_ens_run_* consumes), B = R * D, K = L + H.
+ * Fit (fit = 1): ar's default, the forward-backward approach without windowing or mean removal.  A = [1, a_1 .. a_p]
+ *   minimises sum_{t = p+1 .. L} (y(t) + sum_k a_k y(t-k))^2 + (y(t-p) + sum_k a_k y(t-p+k))^2, solved as ONE stacked
+ *   least-squares problem of M = 2 (L - p) rows (forward rows first, t ascending, then the backward rows) by Householder QR,
+ *   never by the normal equations.  A region with some |r_jj| <= max(M, p) * eps * (largest 2-norm of an original column)
+ *   gets status EPI_ARFC_RANK_DEFICIENT: its A, noise variance and every row of S from day L on are NaN.  Nothing is thrown.
+ *   Noise variance: nv_mode 0 = (forward RSS + backward RSS) / (2 (L - p)), 1 = forward RSS / (L - p).  WHICH VALUE MATLAB's
+ *   ar RETURNS AS NoiseVariance IS NOT PINNED BY ANYTHING IN THE REFERENCE (its normalisation is undocumented); a caller who
+ *   needs MATLAB's own model passes it in:
+ * Given model (fit = 0): A [p][R] (a_1 .. a_p, without the leading 1) and noise_var [R] are inputs: get(ar_sys, 'A')(2:end),
+ *   get(ar_sys, 'NoiseVariance').  A region whose model holds a non-finite number is NaN from day L on.
+ * Forecast: b0 = sqrt(nv); y(t) = b0 z(t) - sum_{k=1..p} a_k y(t-k), one fma chain with k ascending, the past taken from the
+ *   unclamped segment first: filter() with filtic()'s state to rounding, not bit for bit.  z [H][B] standard-normal draws are
+ *   an INPUT (NULL = zeros: the deterministic continuation).  drive [H][Sd] (NULL = none), picked by drive_series [B] (NULL:
+ *   Sd == B), is added to y before the clamp: the caller's gamma * (u' * a + b).  alpha_hat = [seg ; y + drive] with every
+ *   negative entry set to 0.  Then SI_Controlled.m:19-22 statement for statement, in the same kernel.
+ * A non-finite entry of seg gives status EPI_ARFC_BAD_INPUT and NaN in every row of S of the region on every day; its A_out and
+ * noise_var_out are NaN with fit = 1 and, with fit = 0, the copies of the given model they always are in that mode.
+ * The arithmetic is pinned (restated in tests/ar_forecast_ref.c): results are reproducible bit for bit.
+ * Outputs: S [K][3][B], rows (s, i, alpha_hat), the filter outputs' layout (epi_ens_run_* with derive_newcases appends
+ * ((N s) i) alpha unchanged); A_out [p][R], noise_var_out [R], status [R].  With fit = 1 the fit hands its model to the
+ * simulation THROUGH A_out and noise_var_out (the call allocates nothing), so they are required then; with fit = 0 they are
+ * optional copies of the inputs.  status is always optional.
+ * Limits: 1 <= p <= 32, p + 1 <= L, L - p <= 256, 2 (L - p) >= p + 1, H >= 1, R * D <= INT32_MAX. */
+#define EPI_ARFC_OK 0
+#define EPI_ARFC_RANK_DEFICIENT 1
+#define EPI_ARFC_BAD_INPUT 2
+typedef struct epi_arfc_desc {
+    int32_t abi_version;
+    int32_t R, D;                /* regions, draws per region */
+    int32_t L, p, H;             /* segment length, order, horizon */
+    int32_t fit;                 /* 1 = fit the model on seg, 0 = A and noise_var are given */
+    int32_t nv_mode;             /* fit = 1: 0 = (fRSS + bRSS) / (2 (L - p)), 1 = fRSS / (L - p) */
+    int32_t Sd;                  /* series of drive (read when drive != NULL) */
+    int32_t reserved;            /* 0 */
+    double dt;
+} epi_arfc_desc;
+typedef struct epi_arfc_inputs {
+    const double *seg;           /* [L][R] */
+    const double *beta, *s0, *i0;/* [R] */
+    const double *z;             /* [H][B] or NULL */
+    const double *drive;         /* [H][Sd] or NULL */
+    const int32_t *drive_series; /* [B], each in 0 .. Sd-1, or NULL (Sd == B) */
+    const double *A;             /* [p][R] (fit = 0) */
+    const double *noise_var;     /* [R] (fit = 0) */
+} epi_arfc_inputs;
+typedef struct epi_arfc_outputs {
+    double *S;                   /* [L + H][3][B], required */
+    double *A_out;               /* [p][R] */
+    double *noise_var_out;       /* [R] */
+    int32_t *status;             /* [R] */
+} epi_arfc_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG with a message for anything outside the limits or a missing array; nothing is clipped */
+int epi_arfc_validate(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, char *err);
+/* DEVICE pointers; two kernels (ar_fit with fit = 1, ar_simulate) enqueued on `stream`: no host synchronisation, no allocation */
+int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` */
+int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

@@ -33,6 +33,15 @@
 //       probabilities in [0, 1] (quantile(x, q)'s rule);  population ([] = none)  R x 1: appends the row
 //       ((N * row1) * row2) * row3.  NaN members are excluded.  mean, std, min, max, count  R x rows' x T;  quantiles
 //       R x rows' x n_q x T.
+//   [S, A, noise_var, status] = epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode)
+//       The autoregressive alpha forecaster of Tools/PrescribeNPI.m:204-241 for R regions x D draws:
+//       ar(seg, p) -> filtic -> filter(sqrt(nv), A, z, zi) (+ drive) -> negatives to 0 -> SI_Controlled.  seg  R x L;  prm  R x 3
+//       (beta, s0, i0);  z ([] = zeros)  B x H standard-normal draws, B = R * D, chain = (r-1) * D + d;  drive ([] = none)
+//       Sd x H, added before the clamp;  drive_series ([] : Sd == B)  B x 1, ONE-based;  A, noise_var ([] , [] = fit the
+//       model)  R x p and R x 1: get(ar_sys, 'A')(2:end) and get(ar_sys, 'NoiseVariance') -- which normalisation MATLAB's
+//       NoiseVariance uses is not pinned by the reference, nv_mode (0 or 1) chooses ours when the model is fitted.
+//       S  B x 3 x (L + H), rows (s, i, alpha_hat): what 'ens_summary' takes;  A  R x p (a_1 .. a_p);  noise_var, status
+//       R x 1 (0 ok, 1 rank-deficient: NaN from day L + 1 on, 2 non-finite seg: NaN).
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -244,6 +253,69 @@ static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected");
+    if (mxIsEmpty(prhs[1]) || mxGetNumberOfDimensions(prhs[1]) != 2) mexErrMsgTxt("seg must be R x L");
+    const mwSize R = mxGetM(prhs[1]), L = mxGetN(prhs[1]);
+    want(prhs[2], R, 3, "prm");
+    for (int k = 3; k <= 6; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k]) || mxGetNumberOfElements(prhs[k]) != 1) mexErrMsgTxt("dt, p, H and D must be double scalars");
+    if (mxIsEmpty(prhs[12]) || !mxGetPr(prhs[12]) || mxGetNumberOfElements(prhs[12]) != 1) mexErrMsgTxt("nv_mode must be a double scalar (0 or 1)");
+    const double pd = mxGetScalar(prhs[4]), Hd = mxGetScalar(prhs[5]), Dd = mxGetScalar(prhs[6]), nvd = mxGetScalar(prhs[12]);
+    if (nvd != 0.0 && nvd != 1.0) mexErrMsgTxt("nv_mode must be 0 or 1");
+    if (!(pd >= 0.0 && pd <= 1e6 && Hd >= 0.0 && Hd <= 1e9 && Dd >= 1.0 && Dd <= 2147483647.0) || (double)(mwSize)pd != pd || (double)(mwSize)Hd != Hd || (double)(mwSize)Dd != Dd)
+        mexErrMsgTxt("p, H and D must be integers (D >= 1)");
+    const mwSize p = (mwSize)pd, H = (mwSize)Hd, D = (mwSize)Dd;
+    if ((double)R * (double)D > 2147483647.0) mexErrMsgTxt("R * D is limited to 2^31 - 1");
+    const mwSize B = R * D, K = L + H;
+    if (!mxIsEmpty(prhs[7])) want(prhs[7], B, H, "z");
+    mwSize Sd = 0;
+    if (!mxIsEmpty(prhs[8])) {
+        if (mxGetN(prhs[8]) != H) mexErrMsgTxt("drive must be Sd x H");
+        Sd = mxGetM(prhs[8]);
+    }
+    std::vector<int32_t> ser;
+    if (!mxIsEmpty(prhs[9])) {
+        if (!Sd) mexErrMsgTxt("drive_series without drive");
+        if (mxGetNumberOfElements(prhs[9]) != B) mexErrMsgTxt("drive_series must have one entry per chain");
+        ser.resize((size_t)B);
+        for (mwSize c = 0; c < B; c++) {
+            const double v = mxGetPr(prhs[9])[c];
+            if (!(v >= 1.0 && v <= (double)Sd) || (double)(mwSize)v != v) mexErrMsgTxt("drive_series value outside 1 .. Sd");
+            ser[(size_t)c] = (int32_t)v - 1;
+        }
+    }
+    const bool given = !mxIsEmpty(prhs[10]) || !mxIsEmpty(prhs[11]);
+    if (given) {
+        if (mxIsEmpty(prhs[10]) || mxIsEmpty(prhs[11])) mexErrMsgTxt("A and noise_var are given together or not at all");
+        want(prhs[10], R, p, "A");
+        if (mxGetNumberOfElements(prhs[11]) != R) mexErrMsgTxt("noise_var must have one entry per region");
+    }
+    epi_arfc_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.R = (int32_t)R; d.D = (int32_t)D; d.L = (int32_t)L; d.p = (int32_t)p; d.H = (int32_t)H;
+    d.fit = given ? 0 : 1; d.nv_mode = (int32_t)nvd; d.Sd = (int32_t)Sd; d.dt = mxGetScalar(prhs[3]);
+    epi_arfc_inputs in;
+    memset(&in, 0, sizeof in);
+    const double *prm = mxGetPr(prhs[2]);
+    in.seg = mxGetPr(prhs[1]); in.beta = prm; in.s0 = prm + R; in.i0 = prm + 2 * R;
+    in.z = opt(prhs[7]); in.drive = opt(prhs[8]); in.drive_series = ser.empty() ? NULL : ser.data();
+    in.A = given ? mxGetPr(prhs[10]) : NULL; in.noise_var = given ? mxGetPr(prhs[11]) : NULL;
+    // the ABI's [K][3][B], [p][R] are MATLAB's B x 3 x K, R x p: no transposition
+    mxArray *o[4] = {dbl3(B, 3, K ? K : 1), mxCreateDoubleMatrix(R, p ? p : 1, mxREAL), mxCreateDoubleMatrix(R, 1, mxREAL), mxCreateDoubleMatrix(R, 1, mxREAL)};
+    std::vector<int32_t> st((size_t)R);
+    epi_arfc_outputs out;
+    memset(&out, 0, sizeof out);
+    out.S = mxGetPr(o[0]); out.A_out = mxGetPr(o[1]); out.noise_var_out = mxGetPr(o[2]); out.status = st.data();
+    char err[256] = {0};
+    const int rc = epi_arfc_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < st.size(); k++) mxGetPr(o[3])[k] = (double)st[k];
+    for (int k = 0; k < 4; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -281,6 +353,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "nnls") == 0) nnls(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
