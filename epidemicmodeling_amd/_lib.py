@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "epi_lasso_validate", "epi_lasso_run_device", "epi_lasso_run_host",
     "epi_ens_validate", "epi_ens_run_device", "epi_ens_run_host",
     "epi_arfc_validate", "epi_arfc_run_device", "epi_arfc_run_host",
+    "epi_fuse_validate", "epi_fuse_run_device", "epi_fuse_run_host",
 ]
 
 
@@ -248,6 +249,43 @@ def make_arfc_desc(R, D, L, p, H, dt, fit=1, nv_mode=0, Sd=0) -> ArfcDesc:
     return d
 
 
+class FuseDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "m", "B", "T", "lane_block", "storage", "form", "p_solver", "reserved")]
+
+
+FUSE_IN_NAMES = ("sf", "Pf", "sb", "Pb")
+FUSE_OUT_NAMES = ("s_out", "P_out", "d2", "rank", "status")
+FUSE_NONFINITE, FUSE_SWEEP_CAP = 1, 2          # bits of status
+
+
+class FuseInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FUSE_IN_NAMES]
+
+
+class FuseOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FUSE_OUT_NAMES]
+
+
+def fuse_shapes(m, B, T, lane_block=0):
+    """shape of every array of epi_fuse_run_* (sf / sb as s_out, Pf / Pb as P_out): classic [T, rows, B], or chain-blocked
+    [T, nblk, rows, blk] as EkfRunner allocates its outputs"""
+    m, B, T, blk = int(m), int(B), int(T), int(lane_block)
+    if blk <= 0 or blk >= B:
+        vec, mat = (T, m, B), (T, m * m, B)
+    else:
+        nblk = (B + blk - 1) // blk
+        vec, mat = (T, nblk, m, blk), (T, nblk, m * m, blk)
+    return {"s_out": vec, "P_out": mat, "d2": (T, B), "rank": (T, B), "status": (B,)}
+
+
+def make_fuse_desc(m, B, T, form, p_solver=0, lane_block=0, storage=0) -> FuseDesc:
+    d = FuseDesc()
+    d.abi_version = ABI_VERSION
+    d.m, d.B, d.T, d.lane_block, d.storage = int(m), int(B), int(T), int(lane_block), int(storage)
+    d.form, d.p_solver, d.reserved = int(form), int(p_solver), 0
+    return d
+
+
 class NnlsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "S", "D", "n", "max_iters")]
 
@@ -400,6 +438,13 @@ def lib():
         h.epi_arfc_run_device.argtypes = arfc_args + [C.c_void_p, C.c_char_p]
         h.epi_arfc_run_host.restype = C.c_int
         h.epi_arfc_run_host.argtypes = arfc_args + [C.c_int, C.c_char_p]
+        fuse_args = [C.POINTER(FuseDesc), C.POINTER(FuseInputs), C.POINTER(FuseOutputs)]
+        h.epi_fuse_validate.restype = C.c_int
+        h.epi_fuse_validate.argtypes = fuse_args + [C.c_char_p]
+        h.epi_fuse_run_device.restype = C.c_int
+        h.epi_fuse_run_device.argtypes = fuse_args + [C.c_void_p, C.c_char_p]
+        h.epi_fuse_run_host.restype = C.c_int
+        h.epi_fuse_run_host.argtypes = fuse_args + [C.c_int, C.c_char_p]
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h

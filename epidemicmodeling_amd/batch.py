@@ -963,3 +963,76 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     rc = _lib.lib().epi_arfc_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
     _lib.check(rc, err)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
+
+
+FUSE_OUTPUTS = ("s", "P", "d2", "rank", "status")
+
+
+def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, lane_block=0, outputs=FUSE_OUTPUTS, stream=None, B=None):
+    """The forward-backward filter fusion of Tools/TrainPredictPrescribeNPI.m:464-478 for every (chain, day) in one device
+    call (epi_fuse_run_device).  sf, sb [T, m, B] and Pf, Pb [T, m*m, B] device tensors, m = 3 or 6, all
+    float64 or all float32 -- or, with lane_block = an EkfRunner's `blk`, its chain-blocked outputs [T, nblk, rows, blk] as
+    they lie (runner.out["S_PLUS"], ...: nothing is unblocked or copied) with B = the number of chains (default nblk * blk:
+    the padding lanes of the last block then count as chains).  The call does not care which filter outputs the
+    four are: forward S_PLUS / P_PLUS with backward S_MINUS / P_MINUS counts day t's observation once, PLUS with PLUS is the
+    reference's choice.
+    form = 1 (the default here; the C ABI has none) is the information form of the two-filter smoother,
+        S = Pf + Pb, X = pinv(S):  s = Pb X sf + Pf X sb,  P = Pf X Pb, symmetrised,
+    which is what fusing two independent estimates means.  form = 0 is the reference's two lines as written,
+        s = X (Pb sf + Pf sb),  P = S \\ (Pf Pb)  (p_solver 0, LU) or X (Pf Pb)  (p_solver 1), not symmetrised;
+    they equal form 1 only when Pf, Pb and X commute -- presumably why the reference keeps the block commented out -- and
+    are offered for parity with it, not as an estimator.
+    A non-finite entry of Pf + Pb (upper triangle), sf or sb gives NaN outputs, rank -1 and bit 0 (_lib.FUSE_NONFINITE) of
+    the chain's status; bit 1 (_lib.FUSE_SWEEP_CAP) reports a Jacobi sweep cap.  outputs: any of "s", "P" (same layout and
+    dtype as the inputs), "d2" [T, B] float64 (the squared Mahalanobis distance (sf - sb)' X (sf - sb)), "rank" [T, B] int32
+    (rank kept by pinv), "status" [B] int32; at least one of s / P / d2.  Returns a dict of device tensors.  Enqueued on
+    `stream` (default: the current stream) without a host synchronisation."""
+    for name, v in (("sf", sf), ("Pf", Pf), ("sb", sb), ("Pb", Pb)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+        if not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not (sf.dtype == Pf.dtype == sb.dtype == Pb.dtype) or sf.dtype not in (torch.float64, torch.float32):
+        raise ValueError("sf, Pf, sb, Pb must all be float64 or all float32")
+    if sb.shape != sf.shape or Pb.shape != Pf.shape:
+        raise ValueError("sb / Pb must have the shapes of sf / Pf")
+    blk = int(lane_block)
+    if sf.dim() == 3 and Pf.dim() == 3:
+        T, m, nB = sf.shape
+        if 0 < blk < nB:
+            raise ValueError("lane_block given with classic [T, rows, B] tensors")
+        if B is not None and int(B) != nB:
+            raise ValueError("B does not match the tensors")
+        B, blk = nB, 0
+    elif sf.dim() == 4 and Pf.dim() == 4:
+        T, nblk, m, bl = sf.shape
+        if bl != blk:
+            raise ValueError("chain-blocked tensors [T, nblk, rows, blk] need lane_block = blk")
+        B = nblk * blk if B is None else int(B)
+        if nblk != (B + blk - 1) // blk or blk >= B:
+            raise ValueError("B does not match nblk blocks of lane_block chains")
+    else:
+        raise ValueError("sf / Pf must be [T, m, B] / [T, m*m, B] or [T, nblk, m, blk] / [T, nblk, m*m, blk]")
+    if m not in (3, 6) or tuple(Pf.shape) != tuple(sf.shape[:-2]) + (m * m, sf.shape[-1]):
+        raise ValueError("m must be 3 or 6 and Pf must hold m*m rows")
+    outputs = tuple(outputs)
+    for k in outputs:
+        if k not in FUSE_OUTPUTS:
+            raise ValueError(f"unknown output {k!r}")
+    dev = sf.device
+    d = _lib.make_fuse_desc(m, B, T, form, p_solver=p_solver, lane_block=blk, storage=int(sf.dtype == torch.float32))
+    shapes = _lib.fuse_shapes(m, B, T, blk)
+    abi = {"s": "s_out", "P": "P_out", "d2": "d2", "rank": "rank", "status": "status"}
+    dt = {"s": sf.dtype, "P": sf.dtype, "d2": torch.float64, "rank": torch.int32, "status": torch.int32}
+    out = {k: torch.empty(shapes[abi[k]], dtype=dt[k], device=dev) for k in outputs}
+    ins = _lib.FuseInputs()
+    for k, v in zip(_lib.FUSE_IN_NAMES, (sf, Pf, sb, Pb)):
+        setattr(ins, k, _ptr(v))
+    outs = _lib.FuseOutputs()
+    for k in outputs:
+        setattr(outs, abi[k], _ptr(out[k]))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    rc = _lib.lib().epi_fuse_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out

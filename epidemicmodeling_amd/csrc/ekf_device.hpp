@@ -14,6 +14,12 @@
 // k ascending.  The Jacobi eigen-solver behind pinv uses fma() in its rotations.
 // The CPU oracle uses the same fma() in the same places => bit-identical results.
 // Citations: Tools/*.m of the reference, file:line.
+//
+// Host-compilation contract: tests/two_filter_emu.cpp compiles THIS header with the host compiler, one lane at a time, against
+// a three-line stand-in for <hip/hip_runtime.h> (__device__, __host__, __forceinline__) and macros for the only device
+// builtins the header uses: __builtin_amdgcn_ballot_w64 (the lane's own predicate) and __builtin_amdgcn_readfirstlane (the
+// lane's own value).  Everything else here is standard C++ and <math.h>.  A new device-only builtin in this header needs a
+// one-line stand-in at the top of that file (the non-GPU suite fails at its compile step otherwise, naming the builtin).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -829,6 +829,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "lasso.hpp"
 #include "ens_summary.hpp"
 #include "ar_forecast.hpp"
+#include "two_filter.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3863,6 +3864,108 @@ int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const e
         dout.S = (double *)(base + o_S); dout.A_out = (double *)(base + o_Ao); dout.noise_var_out = (double *)(base + o_nvo);
         dout.status = (int32_t *)(base + o_st);
         const int r = epi_arfc_run_device(d, &din, &dout, cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
+// ---- the forward-backward filter fusion, one item per (chain, day) (Tools/TrainPredictPrescribeNPI.m:464-478) ----
+int epi_fuse_validate(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->m != 3 && d->m != 6) { set_err(err, "m must be 3 or 6"); return EPI_ERR_BAD_ARG; }
+    if (d->B < 1) { set_err(err, "B must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->lane_block < 0 || d->lane_block > d->B) { set_err(err, "lane_block must lie in 0 .. B (0 or B: the classic [T][rows][B])"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->form != 0 && d->form != 1) { set_err(err, "form must be 0 (the reference as written) or 1 (the information form)"); return EPI_ERR_BAD_ARG; }
+    if (d->p_solver != 0 && d->p_solver != 1) { set_err(err, "p_solver must be 0 (S \\ C) or 1 (pinv(S) * C)"); return EPI_ERR_BAD_ARG; }
+    if (d->form == 1 && d->p_solver != 0) { set_err(err, "p_solver must be 0 with form = 1"); return EPI_ERR_BAD_ARG; }
+    if (d->reserved != 0) { set_err(err, "reserved must be 0"); return EPI_ERR_BAD_ARG; }
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->sf || !in->Pf || !in->sb || !in->Pb) { set_err(err, "NULL sf / Pf / sb / Pb"); return EPI_ERR_BAD_ARG; }
+    if (!out->s_out && !out->P_out && !out->d2) { set_err(err, "no output requested: at least one of s_out / P_out / d2"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_fuse_run_device(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, void *stream, char *err)
+{
+    int rc = epi_fuse_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    FuseArgs g{};
+    g.B = d->B; g.T = d->T; g.f32 = d->storage; g.form = d->form; g.p_solver = d->p_solver;
+    g.blk = (d->lane_block <= 0 || d->lane_block >= d->B) ? d->B : d->lane_block;
+    g.nblk = (d->B + g.blk - 1) / g.blk;
+    g.sf = in->sf; g.Pf = in->Pf; g.sb = in->sb; g.Pb = in->Pb;
+    g.s_out = out->s_out; g.P_out = out->P_out; g.d2 = out->d2; g.rank = out->rank; g.status = out->status;
+    if (out->status && (e = hipMemsetAsync(out->status, 0, (size_t)d->B * sizeof(int32_t), st)) != hipSuccess)
+        return hip_fail(err, e, "hipMemsetAsync of status");
+    const int wgs = d->m == 6 ? pinv_wg<6>() : pinv_wg<3>();
+    g.tiles = (unsigned)(((int64_t)d->B + wgs - 1) / wgs);
+    const long long groups = (long long)g.tiles * d->T;
+    for (long long w0 = 0; w0 < groups; w0 += kFuseLaunchGroups) {     // in slices (two_filter.hpp)
+        g.wg0 = w0;
+        const unsigned nb = (unsigned)(groups - w0 < kFuseLaunchGroups ? groups - w0 : kFuseLaunchGroups);
+        if (d->m == 6) hipLaunchKernelGGL(two_filter<6>, dim3(nb), dim3(pinv_wg<6>()), 0, st, g);
+        else hipLaunchKernelGGL(two_filter<3>, dim3(nb), dim3(pinv_wg<3>()), 0, st, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "two_filter launch");
+    }
+    return EPI_OK;
+}
+
+int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, int device, char *err)
+{
+    int rc = epi_fuse_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t B = (size_t)d->B, T = (size_t)d->T, m = (size_t)d->m, none = (size_t)-1;
+    const size_t blk = (d->lane_block <= 0 || d->lane_block >= d->B) ? B : (size_t)d->lane_block;
+    const size_t Bp = (B + blk - 1) / blk * blk, es = d->storage ? 4 : 8;       // a day of a blocked array holds rows * Bp elements
+    HostIO io;
+    const size_t o_sf = io.add_in(in->sf, T * m, es, Bp, 0, Bp), o_Pf = io.add_in(in->Pf, T * m * m, es, Bp, 0, Bp);
+    const size_t o_sb = io.add_in(in->sb, T * m, es, Bp, 0, Bp), o_Pb = io.add_in(in->Pb, T * m * m, es, Bp, 0, Bp);
+    const size_t o_s = out->s_out ? io.add_out(out->s_out, T * m, es, Bp, 0, Bp) : none;
+    const size_t o_P = out->P_out ? io.add_out(out->P_out, T * m * m, es, Bp, 0, Bp) : none;
+    const size_t o_d2 = out->d2 ? io.add_out(out->d2, T, 8, B, 0, B) : none;
+    const size_t o_rk = out->rank ? io.add_out(out->rank, T, 4, B, 0, B) : none;
+    const size_t o_st = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : none;
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        // the padding lanes of a blocked output are never written by the kernel: the host entry returns them as zeros, not as
+        // arena bytes (include/epiekf.h says so)
+        if (Bp != B) {
+            if (o_s != none && (e = hipMemsetAsync(base + o_s, 0, T * m * Bp * es, cx->stream)) != hipSuccess) {
+                (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "hipMemsetAsync of s_out");
+            }
+            if (o_P != none && (e = hipMemsetAsync(base + o_P, 0, T * m * m * Bp * es, cx->stream)) != hipSuccess) {
+                (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "hipMemsetAsync of P_out");
+            }
+        }
+        epi_fuse_inputs din{};
+        din.sf = base + o_sf; din.Pf = base + o_Pf; din.sb = base + o_sb; din.Pb = base + o_Pb;
+        epi_fuse_outputs dout{};
+        dout.s_out = o_s == none ? nullptr : base + o_s; dout.P_out = o_P == none ? nullptr : base + o_P;
+        dout.d2 = o_d2 == none ? nullptr : (double *)(base + o_d2);
+        dout.rank = o_rk == none ? nullptr : (int32_t *)(base + o_rk); dout.status = o_st == none ? nullptr : (int32_t *)(base + o_st);
+        const int r = epi_fuse_run_device(d, &din, &dout, cx->stream, err);
         if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
         if (ev1) (void)hipEventRecord(ev1, cx->stream);
         return EPI_OK;

@@ -266,3 +266,41 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     rc = _lib.lib().epi_arfc_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
     _lib.check(rc, err)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
+
+
+def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, outputs=("s", "P", "d2", "rank", "status"), device=0):
+    """epi_fuse_run_host: the forward-backward filter fusion of batch.two_filter on NumPy arrays (synchronous).  sf, sb
+    [T, m, B], Pf, Pb [T, m*m, B] (m = 3 or 6; all float32 = float storage, anything else is taken as float64); the arrays
+    of a single chain may drop the last axis.  Returns the dict of batch.two_filter as NumPy arrays."""
+    dt = np.float32 if all(np.asarray(v).dtype == np.float32 for v in (sf, Pf, sb, Pb)) else np.float64
+    arrs = [np.ascontiguousarray(v, dtype=dt) for v in (sf, Pf, sb, Pb)]
+    single = arrs[0].ndim == 2
+    if single:
+        arrs = [v[:, :, None] for v in arrs]
+    arrs = [np.ascontiguousarray(v) for v in arrs]
+    sf, Pf, sb, Pb = arrs
+    if sf.ndim != 3 or Pf.ndim != 3:
+        raise ValueError("sf must be [T, m, B] and Pf [T, m*m, B]")
+    T, m, B = sf.shape
+    if m not in (3, 6) or Pf.shape != (T, m * m, B) or sb.shape != sf.shape or Pb.shape != Pf.shape:
+        raise ValueError("m must be 3 or 6, Pf [T, m*m, B], and sb / Pb shaped as sf / Pf")
+    for k in outputs:
+        if k not in ("s", "P", "d2", "rank", "status"):
+            raise ValueError(f"unknown output {k!r}")
+    d = _lib.make_fuse_desc(m, B, T, form, p_solver=p_solver, lane_block=0, storage=int(dt == np.float32))
+    shapes = _lib.fuse_shapes(m, B, T, 0)
+    abi = {"s": "s_out", "P": "P_out", "d2": "d2", "rank": "rank", "status": "status"}
+    odt = {"s": dt, "P": dt, "d2": np.float64, "rank": np.int32, "status": np.int32}
+    out = {k: np.empty(shapes[abi[k]], dtype=odt[k]) for k in outputs}
+    ins = _lib.FuseInputs()
+    for k, v in zip(_lib.FUSE_IN_NAMES, arrs):
+        setattr(ins, k, v.ctypes.data)
+    outs = _lib.FuseOutputs()
+    for k in outputs:
+        setattr(outs, abi[k], out[k].ctypes.data)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_fuse_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    if single:
+        out = {k: (v if k == "status" else v[..., 0]) for k, v in out.items()}
+    return out

@@ -361,3 +361,34 @@ def ar_forecast(cases, deaths, population, ip, horizon=90, ar_order=24, history=
     summary = batch.ensemble_summary(fc["S"], S, n_draws, q=q, population=N)
     out.update(seg=seg, forecast=fc, summary=summary, z=z, drive=drive)
     return out
+
+
+def two_filter_smooth(w, form=1, backward="minus", storage="f64", device="cuda:0", lane_block="auto", p_solver=0):
+    """The "Backward filtering (under test)" step of Tools/TrainPredictPrescribeNPI.m:464-478 on the device: run the forward
+    filter of `w` (a synth.Workload of SIAlphaModelEKF or SIAlphaModelEKFOptControlled), run its reverse-time twin
+    (synth.as_backward: the SIAlphaModelBackwardEKF[OptControlled] model with the same fifteen arguments, as the commented
+    reference call passes them; the library flips the time axis internally and returns its outputs un-flipped), and fuse the
+    two per (chain, day) with batch.two_filter -- from the runners' chain-blocked arrays as they lie, nothing is copied back
+    or unblocked in between.
+    backward = "minus" (default) fuses forward S_PLUS / P_PLUS with backward S_MINUS / P_MINUS, so that day t's observation is
+    counted once; "plus" takes the backward S_PLUS / P_PLUS, the reference's choice.  form = 1 (default) is the information
+    form of the two-filter smoother; form = 0 with backward = "plus" is the reference's formula as written (see
+    batch.two_filter for why that is not the default).  storage "f32": both runs store float32 and the fusion reads and
+    writes float32.
+    Returns {"forward": EkfRunner, "backward": EkfRunner, "fused": dict of batch.two_filter (s, P in the runners' layout,
+    d2, rank, status), "lane_block": blk, "B": chains}.  No host synchronisation."""
+    if backward not in ("minus", "plus"):
+        raise ValueError('backward must be "minus" or "plus"')
+    if w.model not in ("SIAlphaModelEKF", "SIAlphaModelEKFOptControlled"):
+        raise ValueError("w must be a forward workload of the 3- or 6-state SI-alpha model")
+    wb = synth.as_backward(w)
+    names_f = ["S_PLUS", "P_PLUS"]
+    names_b = ["S_MINUS", "P_MINUS"] if backward == "minus" else ["S_PLUS", "P_PLUS"]
+    rf = batch.EkfRunner(batch.DeviceWorkload(w, device), names_f, lane_block=lane_block, storage=storage)
+    # one layout for both runs: the backward runner takes the forward one's block size
+    rb = batch.EkfRunner(batch.DeviceWorkload(wb, device), names_b, lane_block=0 if rf.blk == w.B else rf.blk, storage=storage)
+    rf.run()
+    rb.run()
+    fused = batch.two_filter(rf.out[names_f[0]], rf.out[names_f[1]], rb.out[names_b[0]], rb.out[names_b[1]], form=form,
+                             p_solver=p_solver, lane_block=0 if rf.blk == w.B else rf.blk, B=w.B)
+    return {"forward": rf, "backward": rb, "fused": fused, "lane_block": rf.blk, "B": w.B}

@@ -688,6 +688,71 @@ int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const
 /* HOST pointers, on a pooled context of `device` */
 int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err);
 
+/* ---- The forward-backward filter fusion: Tools/TrainPredictPrescribeNPI.m:464-478 ("Backward filtering (under test)") ----
+ *   P_FRW_BCK(:,:,hh) = (P_PLUS_f + P_PLUS_b) \ (P_PLUS_f * P_PLUS_b);
+ *   S_FRW_BCK(:,hh)   = pinv(P_PLUS_f + P_PLUS_b) * (P_PLUS_b * S_PLUS_f + P_PLUS_f * S_PLUS_b);
+ * for every (chain c, day t) of two filter runs, m = 3 or 6, one independent item each: what the reverse-time models
+ * (EPI_MODEL_*_BWD) exist for.  The call takes four arrays (sf, Pf) and (sb, Pb) and does not care which filter outputs they are:
+ * forward S_PLUS / P_PLUS with backward S_MINUS / P_MINUS counts day t's observation once (the two-filter smoother's choice),
+ * PLUS with PLUS is the reference's.
+ * Off the commuting case the reference's two lines are NOT the two-filter smoother, P = Pf S^-1 Pb, s = Pb S^-1 sf + Pf S^-1 sb
+ * with S = Pf + Pb: they write S^-1 (Pf Pb) and S^-1 (Pb sf + Pf sb), which agree with it only when Pf, Pb and S^-1 commute.
+ * Both are built, and `form` is required (neither is a default of this ABI).
+ * Arithmetic (pinned; restated in tests/two_filter_ref.py).  Double throughout, one rounding per written
+ * operation; every inner product is acc = a_0 b_0, acc = acc + a_k b_k with k ascending (no fma).
+ *   S(i,j) = Pf(i,j) + Pb(i,j) for i <= j, mirrored: only the upper triangles of Pf and Pb enter S.
+ *   Any non-finite entry of S, sf or sb: every output of the item is NaN, rank = -1, bit 0 of status[c] is set and the
+ *   pseudo-inverse is not evaluated.
+ *   X = pinv(S): the smoother's symmetric pseudo-inverse (MATLAB's rule, tol = m eps(max singular value)), the two-sided Jacobi
+ *   route for an S that is not positive semi-definite up to rounding; rank = the rank kept; bit 1 of status[c] is set if a Jacobi
+ *   iteration hit its sweep cap.
+ *   form 0:  w = Pb sf + Pf sb (two matrix-vector products over the matrices as stored, one add per row);  s = X w;
+ *            C = Pf Pb;  P = S \ C evaluated as (C' / S')' by the library's mrdivide (p_solver 0) or P = X C (p_solver 1).
+ *            P is not symmetrised: the reference does not.  PARITY UNPINNED: p_solver 0 is MATLAB's general square path (dgetf2 +
+ *            dgetrs); for an exactly symmetric S with a positive diagonal MATLAB's backslash would try a Cholesky factorisation
+ *            first, and nothing in the reference pins which path ran.
+ *   form 1:  s = Pb (X sf) + Pf (X sb);  Y = X Pb;  P = Pf Y;  P = (P + P') / 2 (GenericExtendedKalmanFilter.m:138).
+ *            p_solver must be 0.
+ *   d2 = e' (X e), e = sf - sb, summed with i ascending: the squared Mahalanobis distance between the two estimates, the
+ *   consistency check the forward-against-backward plots of :592-598 were drawn for.
+ * Layout: sf, sb, s_out have m rows, Pf, Pb, P_out m*m rows (entry (i, j) in row i + m j), each in the filter outputs' layout,
+ *   element (t, row, c) at ((t * nblk + c / blk) * rows + row) * blk + c % blk, blk = lane_block, nblk = ceil(B / blk);
+ *   lane_block 0 or B is the classic [T][rows][B].  The chain-blocked outputs of epi_ekf_run_* are consumed in place.  The
+ *   padding lanes of a last, partial block are never read; epi_fuse_run_device does not write them, epi_fuse_run_host (which
+ *   moves whole arrays) overwrites them with zeros in s_out / P_out.  d2, rank are [T][B], status [B], never blocked.
+ * storage 0 / 1: sf, Pf, sb, Pb, s_out, P_out are double / float arrays; a float is widened on load and a result rounded once on
+ *   store.  d2, rank, status are always double / int32 / int32.  No output may overlap an input.
+ * Every output is optional; at least one of s_out / P_out / d2 is required.  status is zeroed by the call and accumulated with
+ * an atomic OR over the days. */
+typedef struct epi_fuse_desc {
+    int32_t abi_version;
+    int32_t m;                   /* 3 or 6 */
+    int32_t B, T;                /* chains, days */
+    int32_t lane_block;          /* 0 or B: classic; else chains per layout block */
+    int32_t storage;             /* 0 = double, 1 = float */
+    int32_t form;                /* 0 = the reference as written, 1 = the information form; required */
+    int32_t p_solver;            /* form 0: 0 = S \ C (LU), 1 = pinv(S) * C; form 1: 0 */
+    int32_t reserved;            /* 0 */
+} epi_fuse_desc;
+typedef struct epi_fuse_inputs {
+    const void *sf, *Pf;         /* [T][nblk][m][blk], [T][nblk][m*m][blk] */
+    const void *sb, *Pb;
+} epi_fuse_inputs;
+typedef struct epi_fuse_outputs {
+    void *s_out, *P_out;         /* as sf, Pf; each may be NULL */
+    double *d2;                  /* [T][B] or NULL */
+    int32_t *rank;               /* [T][B] or NULL */
+    int32_t *status;             /* [B] or NULL */
+} epi_fuse_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG with a message for anything outside the limits or a missing array */
+int epi_fuse_validate(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, char *err);
+/* DEVICE pointers; one kernel (in slices of 2^23 workgroups: 64 items each for m = 6, 256 for m = 3, i.e. beyond 2^29 /
+ * 2^31 items) and the clearing of status enqueued on `stream`: no host
+ * synchronisation, no allocation */
+int epi_fuse_run_device(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` */
+int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

@@ -42,6 +42,13 @@
 //       NoiseVariance uses is not pinned by the reference, nv_mode (0 or 1) chooses ours when the model is fitted.
 //       S  B x 3 x (L + H), rows (s, i, alpha_hat): what 'ens_summary' takes;  A  R x p (a_1 .. a_p);  noise_var, status
 //       R x 1 (0 ok, 1 rank-deficient: NaN from day L + 1 on, 2 non-finite seg: NaN).
+//   [S_FRW_BCK, P_FRW_BCK, d2, rank] = epiekf_pipeline_mex('fuse', S_f, P_f, S_b, P_b, form, p_solver)
+//       The "Backward filtering (under test)" fusion of :464-478 for one chain.  S_f, S_b  m x T and P_f, P_b
+//       m x m x T (m = 3 or 6): the outputs of a forward filter and of its reverse-time twin as they come back (un-flipped);
+//       forward S_PLUS / P_PLUS with backward S_MINUS / P_MINUS counts day t's observation once, PLUS with PLUS is the
+//       reference's choice.  form  0 = the reference's two lines as written (p_solver 0: S \ C by LU, 1: pinv(S) * C),
+//       1 = the information form Pf X Pb, symmetrised (p_solver 0); both required.  S_FRW_BCK  m x T;  P_FRW_BCK  m x m x T;
+//       d2  1 x T, (S_f - S_b)' pinv(P_f + P_b) (S_f - S_b);  rank  1 x T, the rank pinv kept (-1: a non-finite day, NaN).
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -316,6 +323,46 @@ static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void fuse(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 7) mexErrMsgTxt("epiekf_pipeline_mex('fuse', S_f, P_f, S_b, P_b, form, p_solver): 7 inputs expected");
+    for (int k = 1; k <= 4; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("S_f, P_f, S_b and P_b must be non-empty double arrays");
+    if (mxGetNumberOfDimensions(prhs[1]) != 2) mexErrMsgTxt("S_f must be m x T");
+    const mwSize m = mxGetM(prhs[1]), T = mxGetN(prhs[1]);
+    if (m != 3 && m != 6) mexErrMsgTxt("m must be 3 or 6");
+    want(prhs[3], m, T, "S_b");
+    for (int k = 2; k <= 4; k += 2) {
+        // m x m x T; MATLAB drops a trailing singleton: m x m for T = 1
+        const mwSize nd = mxGetNumberOfDimensions(prhs[k]);
+        const mwSize *dm = mxGetDimensions(prhs[k]);
+        if (nd < 2 || nd > 3 || dm[0] != m || dm[1] != m || (nd == 3 ? dm[2] : 1) != T)
+            mexErrMsgTxt(k == 2 ? "P_f must be m x m x T" : "P_b must be m x m x T");
+    }
+    for (int k = 5; k <= 6; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k]) || mxGetNumberOfElements(prhs[k]) != 1) mexErrMsgTxt("form and p_solver must be double scalars");
+    const double fd = mxGetScalar(prhs[5]), pd = mxGetScalar(prhs[6]);
+    if ((fd != 0.0 && fd != 1.0) || (pd != 0.0 && pd != 1.0)) mexErrMsgTxt("form and p_solver must be 0 or 1");
+    epi_fuse_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.m = (int32_t)m; d.B = 1; d.T = (int32_t)T; d.form = (int32_t)fd; d.p_solver = (int32_t)pd;
+    epi_fuse_inputs in;
+    memset(&in, 0, sizeof in);
+    in.sf = mxGetPr(prhs[1]); in.Pf = mxGetPr(prhs[2]); in.sb = mxGetPr(prhs[3]); in.Pb = mxGetPr(prhs[4]);
+    // the ABI's [T][m][1], [T][m*m][1] (entry (i, j) in row i + m j) are MATLAB's m x T, m x m x T: no transposition
+    mxArray *o[4] = {mxCreateDoubleMatrix(m, T, mxREAL), dbl3(m, m, T), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL)};
+    std::vector<int32_t> rk((size_t)T);
+    epi_fuse_outputs out;
+    memset(&out, 0, sizeof out);
+    out.s_out = mxGetPr(o[0]); out.P_out = mxGetPr(o[1]); out.d2 = mxGetPr(o[2]); out.rank = rk.data();
+    char err[256] = {0};
+    const int rc = epi_fuse_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) mxDestroyArray(a); fail_if(rc, err); }
+    for (size_t k = 0; k < rk.size(); k++) mxGetPr(o[3])[k] = (double)rk[k];
+    for (int k = 0; k < 4; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -354,6 +401,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }

@@ -1,0 +1,80 @@
+"""The kernel's source without a GPU: tests/two_filter_emu.cpp compiles csrc/two_filter.hpp (with the pseudo-inverse and LU
+routines of csrc/ekf_device.hpp) for the host and runs it one lane at a time; s, P, d2, rank and status equal the restatement
+tests/two_filter_ref.py bit for bit on the planted-rank cases of the GPU suite (B = 70, T = 5, both layouts, both storages,
+all three form / p_solver pairs, three workgroups per day past the end of the batch) and on the real filter outputs."""
+import ctypes as C
+import functools
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import helpers as H
+from tests import two_filter_ref as TF
+
+FORMS = [(0, 0), (0, 1), (1, 0)]
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.fail("no C++ compiler for tests/two_filter_emu.cpp")
+    d = tmp_path_factory.mktemp("two_filter_emu")
+    os.makedirs(d / "hip")
+    (d / "hip" / "hip_runtime.h").write_text("#pragma once\n#define __device__\n#define __host__\n"
+                                             "#define __forceinline__ inline __attribute__((always_inline))\n")
+    so = str(d / "emu.so")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-I" + str(d),
+                    "-I" + os.path.join(H.ROOT, "epidemicmodeling_amd", "csrc"), os.path.join(H.ROOT, "tests", "two_filter_emu.cpp"),
+                    "-o", so], check=True)
+    return C.CDLL(so)
+
+
+def _run(lib, arrs, m, B, T, form, ps, storage="f64", blk=0):
+    dt = np.float32 if storage == "f32" else np.float64
+    a = [np.ascontiguousarray(TF.to_blocked(x.astype(dt), blk, np.nan) if blk else x.astype(dt)) for x in arrs]
+    nblk = (B + blk - 1) // blk if blk else 1
+    s, P = np.full(a[0].shape, -7.0, dt), np.full(a[1].shape, -7.0, dt)
+    d2, rk, st = np.full((T, B), -7.0), np.full((T, B), -7, np.int32), np.full(B, -7, np.int32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    lib.emu_fuse(m, B, T, blk or B, nblk, int(storage == "f32"), form, ps, p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(s), p(P), p(d2), p(rk), p(st))
+    if blk:
+        pad = s.transpose(0, 2, 1, 3).reshape(T, m, nblk * blk)[:, :, B:]
+        assert (pad == -7.0).all()                           # padding lanes are not written
+        s, P = TF.from_blocked(s, B), TF.from_blocked(P, B)
+    return dict(s=s, P=P, d2=d2, rank=rk, status=st)
+
+
+@functools.lru_cache(maxsize=None)
+def _planted(m):
+    return TF.planted(m, 5, 70, seed=100 * m + 70)
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32"])
+@pytest.mark.parametrize("form, p_solver", FORMS)
+@pytest.mark.parametrize("m", [3, 6])
+def test_planted_ranks(emu, m, form, p_solver, storage):
+    want = TF.fuse(*_planted(m), form, p_solver, storage=storage)
+    assert len(set(want["rank"].ravel().tolist())) >= 3 and 1 in want["route"] and (want["rank"] == -1).sum() == 1
+    for blk in (0, 40):
+        got = _run(emu, _planted(m), m, 70, 5, form, p_solver, storage, blk)
+        for k, v in got.items():
+            assert TF.same_bits(v, want[k]), (k, blk)
+
+
+@pytest.mark.parametrize("which", [3, 6])
+def test_real_filter_outputs(emu, which):
+    from epidemicmodeling_amd import synth
+    w = synth.make_cfg3(7, 40) if which == 3 else synth.make_cfg4(2, 5, 30, 30)
+    f, b = H.oracle_batch(w), H.oracle_batch(synth.as_backward(w))
+    arrs = (f["S_PLUS"], f["P_PLUS"], b["S_MINUS"], b["P_MINUS"])
+    for form, ps in FORMS:
+        want = TF.fuse(*arrs, form, ps)
+        if which == 6:
+            assert (want["rank"] < 6).mean() >= 0.1
+        got = _run(emu, arrs, which, w.B, w.T, form, ps, "f64", 4)
+        for k, v in got.items():
+            assert TF.same_bits(v, want[k]), (form, ps, k)

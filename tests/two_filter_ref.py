@@ -1,0 +1,192 @@
+"""The forward-backward filter fusion of DESIGN.md §4.9 (include/epiekf.h, epi_fuse_*) restated in plain Python loops: what
+the kernel csrc/two_filter.hpp is held to bit for bit.  Scalar Python floats are IEEE doubles and every written operation
+rounds once, so `acc = acc + a * b` below is the kernel's `acc = acc + a * b`.  The pseudo-inverse and the LU solve are the
+oracle's orc_sym_pinv_ex / orc_mrdivide (oracle/libekf_oracle.so), reached through ctypes.
+
+The restatement cannot see a Jacobi sweep cap (the oracle does not report one), so its status never holds bit 1."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAN = float("nan")
+
+_lib = None
+
+
+def _oracle():
+    global _lib
+    if _lib is None:
+        from oracle import oracle_lib as olib
+        olib.build()
+        _lib = C.CDLL(os.path.join(ROOT, "oracle", "libekf_oracle.so"))
+        _lib.orc_sym_pinv_ex.restype = C.c_int
+        _lib.orc_mrdivide.restype = None
+    return _lib
+
+
+def sym_pinv(m, S):
+    """(X [m][m] as nested lists, rank, route) of orc_sym_pinv_ex for the symmetric S (nested lists)"""
+    A = np.array([[S[i][j] for i in range(m)] for j in range(m)], dtype=np.float64).ravel()   # column-major: e = i + m j
+    X = np.zeros(m * m)
+    route, sweeps = C.c_int(0), C.c_int(0)
+    rank = _oracle().orc_sym_pinv_ex(C.c_int(m), A.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p), C.byref(route),
+                                     C.byref(sweeps))
+    return [[float(X[i + m * j]) for j in range(m)] for i in range(m)], int(rank), int(route.value)
+
+
+def mrdivide(m, Bm, A):
+    """Bm / A of orc_mrdivide (nested lists in, nested lists out)"""
+    b = np.array([[Bm[i][j] for i in range(m)] for j in range(m)], dtype=np.float64).ravel()
+    a = np.array([[A[i][j] for i in range(m)] for j in range(m)], dtype=np.float64).ravel()
+    X = np.zeros(m * m)
+    _oracle().orc_mrdivide(C.c_int(m), b.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p))
+    return [[float(X[i + m * j]) for j in range(m)] for i in range(m)]
+
+
+def _dot(row, col):
+    acc = row[0] * col[0]
+    for k in range(1, len(row)):
+        acc = acc + row[k] * col[k]
+    return acc
+
+
+def _matvec(A, v):
+    return [_dot(A[i], v) for i in range(len(A))]
+
+
+def _matmul(A, Bm):
+    m = len(A)
+    return [[_dot(A[i], [Bm[k][j] for k in range(m)]) for j in range(m)] for i in range(m)]
+
+
+def fuse_item(m, sf, Pf, sb, Pb, form, p_solver=0):
+    """One (chain, day).  sf, sb: m floats; Pf, Pb: m x m nested lists of floats.  Returns dict s (m), P (m x m), d2, rank,
+    bad, route (of the pseudo-inverse, -1 when it was not evaluated)."""
+    S = [[0.0] * m for _ in range(m)]
+    for j in range(m):
+        for i in range(j + 1):
+            S[i][j] = Pf[i][j] + Pb[i][j]
+            S[j][i] = S[i][j]
+    bad = any(not math.isfinite(S[i][j]) for i in range(m) for j in range(m)) or any(not math.isfinite(v) for v in sf) or \
+        any(not math.isfinite(v) for v in sb)
+    if bad:
+        return dict(s=[NAN] * m, P=[[NAN] * m for _ in range(m)], d2=NAN, rank=-1, bad=True, route=-1)
+    X, rank, route = sym_pinv(m, S)
+    e = [sf[i] - sb[i] for i in range(m)]
+    Xe = _matvec(X, e)
+    d2 = e[0] * Xe[0]
+    for i in range(1, m):
+        d2 = d2 + e[i] * Xe[i]
+    if form == 0:
+        a, b = _matvec(Pb, sf), _matvec(Pf, sb)
+        w = [a[i] + b[i] for i in range(m)]
+        s = _matvec(X, w)
+        Cm = _matmul(Pf, Pb)
+        if p_solver == 0:
+            Ct = [[Cm[j][i] for j in range(m)] for i in range(m)]
+            St = [[S[j][i] for j in range(m)] for i in range(m)]
+            R = mrdivide(m, Ct, St)                          # C' / S'
+            P = [[R[j][i] for j in range(m)] for i in range(m)]
+        else:
+            P = _matmul(X, Cm)
+    else:
+        assert p_solver == 0
+        t1, t2 = _matvec(X, sf), _matvec(X, sb)
+        a, b = _matvec(Pb, t1), _matvec(Pf, t2)
+        s = [a[i] + b[i] for i in range(m)]
+        Y = _matmul(X, Pb)
+        P = _matmul(Pf, Y)
+        Q = [[(P[i][j] + P[j][i]) / 2.0 for j in range(m)] for i in range(m)]
+        P = Q
+    return dict(s=s, P=P, d2=d2, rank=rank, bad=False, route=route)
+
+
+def fuse(sf, Pf, sb, Pb, form, p_solver=0, storage="f64"):
+    """The whole call on classic arrays: sf, sb [T, m, B], Pf, Pb [T, m*m, B] (row e = i + m j).  storage "f32": the inputs are
+    rounded to float first (what a float array holds) and s / P are rounded once at the end.  Returns dict s [T, m, B],
+    P [T, m*m, B], d2 [T, B], rank [T, B] int32, status [B] int32, route [T, B] (test-side: the pseudo-inverse route)."""
+    sf, Pf, sb, Pb = (np.asarray(v) for v in (sf, Pf, sb, Pb))
+    if storage == "f32":
+        sf, Pf, sb, Pb = (v.astype(np.float32).astype(np.float64) for v in (sf, Pf, sb, Pb))
+    T, m, B = sf.shape
+    out = dict(s=np.empty((T, m, B)), P=np.empty((T, m * m, B)), d2=np.empty((T, B)), rank=np.empty((T, B), dtype=np.int32),
+               status=np.zeros(B, dtype=np.int32), route=np.empty((T, B), dtype=np.int32))
+    for t in range(T):
+        for c in range(B):
+            mat = lambda A: [[float(A[t, i + m * j, c]) for j in range(m)] for i in range(m)]
+            vec = lambda v: [float(v[t, i, c]) for i in range(m)]
+            r = fuse_item(m, vec(sf), mat(Pf), vec(sb), mat(Pb), form, p_solver)
+            out["s"][t, :, c] = r["s"]
+            for j in range(m):
+                for i in range(m):
+                    out["P"][t, i + m * j, c] = r["P"][i][j]
+            out["d2"][t, c], out["rank"][t, c], out["route"][t, c] = r["d2"], r["rank"], r["route"]
+            if r["bad"]:
+                out["status"][c] |= 1
+    if storage == "f32":
+        with np.errstate(over="ignore"):
+            out["s"], out["P"] = out["s"].astype(np.float32), out["P"].astype(np.float32)
+    return out
+
+
+def to_blocked(a, blk, fill=0.0):
+    """[T, rows, B] -> the chain-blocked [T, nblk, rows, blk] of DESIGN.md §3 (padding lanes = fill)"""
+    T, rows, B = a.shape
+    nblk = (B + blk - 1) // blk
+    o = np.full((T, rows, nblk * blk), fill, dtype=a.dtype)
+    o[:, :, :B] = a
+    return np.ascontiguousarray(o.reshape(T, rows, nblk, blk).transpose(0, 2, 1, 3))
+
+
+def from_blocked(a, B):
+    T, nblk, rows, blk = a.shape
+    return np.ascontiguousarray(a.transpose(0, 2, 1, 3).reshape(T, rows, nblk * blk)[:, :, :B])
+
+
+def same_bits(a, b):
+    """equal bit for bit, any NaN equal to any NaN"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(u)[~na], b.view(u)[~nb]))
+
+
+def planted(m, T, B, seed, indefinite=True, nonfinite=True):
+    """Synthetic inputs with planted ranks of S = Pf + Pb: item (t, c) gets rank (t * B + c) % (m + 1) -- Pf = U diag(df) U',
+    Pb = U diag(db) U' with df, db > 0 on the first r axes of a random orthogonal U and 0 on the others (rank deficient up to
+    rounding, which pinv's tolerance cuts; the rank the restatement reports is what counts, and the tests assert the spread
+    on IT).  One item gets an indefinite S (route 1),
+    one a non-finite entry.  Returns sf, Pf, sb, Pb as [T, m, B] / [T, m*m, B] float64."""
+    rng = np.random.default_rng(seed)
+    sf, sb = rng.standard_normal((T, m, B)), rng.standard_normal((T, m, B))
+    Pf, Pb = np.zeros((T, m * m, B)), np.zeros((T, m * m, B))
+    for t in range(T):
+        for c in range(B):
+            r = (t * B + c) % (m + 1)
+            U, _ = np.linalg.qr(rng.standard_normal((m, m)))
+            df, db = np.zeros(m), np.zeros(m)
+            df[:r], db[:r] = rng.uniform(0.5, 2.0, r), rng.uniform(0.5, 2.0, r)
+            if r == m and (t + c) % 3 == 0:
+                db[-1] = 1e-9                                # full rank, badly scaled: the Jacobi route, not the certified one
+            A = (U * df) @ U.T
+            Bm = (U * db) @ U.T
+            A, Bm = (A + A.T) / 2.0, (Bm + Bm.T) / 2.0
+            Pf[t, :, c], Pb[t, :, c] = A.T.ravel(), Bm.T.ravel()
+    if indefinite and T * B >= 3:
+        t, c = (T - 1, B - 2) if B >= 2 else (T - 1, 0)
+        D = np.diag(np.r_[1.0, -0.5, np.ones(m - 2)])
+        U, _ = np.linalg.qr(rng.standard_normal((m, m)))
+        A = U @ D @ U.T
+        A = (A + A.T) / 2.0
+        Pf[t, :, c], Pb[t, :, c] = A.T.ravel(), 0.25 * A.T.ravel()
+    if nonfinite and T * B >= 2:
+        t, c = (T // 2, min(B - 1, 3))
+        Pf[t, m + 1, c] = np.inf                             # entry (1, 1): on the diagonal, in the upper triangle
+    return sf, Pf, sb, Pb
