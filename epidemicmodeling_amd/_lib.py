@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "epi_ens_validate", "epi_ens_run_device", "epi_ens_run_host",
     "epi_arfc_validate", "epi_arfc_run_device", "epi_arfc_run_host",
     "epi_fuse_validate", "epi_fuse_run_device", "epi_fuse_run_host",
+    "epi_robfit_validate", "epi_robfit_run_device", "epi_robfit_run_host",
 ]
 
 
@@ -180,6 +181,44 @@ def make_lasso_desc(R, D, n, K, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4,
     d.R, d.D, d.n, d.K, d.num_lambda = int(R), int(D), int(n), int(K), int(num_lambda)
     d.lambda_ratio, d.rel_tol, d.max_iter = float(lambda_ratio), float(rel_tol), int(max_iter)
     return d
+
+
+class RobfitDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "D", "n", "robust", "max_iter")] + \
+        [("lower_a", C.c_double), ("upper_a", C.c_double)]
+
+
+ROBFIT_OUT_NAMES = ("a", "b_item", "sigma", "iters", "status", "weights", "b")
+ROBFIT_OUT_I32 = ("iters", "status")
+ROBFIT_STATUS_BITS = {"nonfinite": 1, "const": 2, "slope_lost": 4, "maxiter": 8, "bound": 16}
+
+
+class RobfitOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ROBFIT_OUT_NAMES]
+
+
+def robfit_shapes(R, D, n):
+    """shape of every output of epi_robfit_run_*"""
+    return {"a": (n, R), "b_item": (n, R), "sigma": (n, R), "iters": (n, R), "status": (n, R), "weights": (D, n, R), "b": (R,)}
+
+
+def make_robfit_desc(R, D, n, robust=1, max_iter=50, lower_a=0.0, upper_a=float("inf")) -> RobfitDesc:
+    d = RobfitDesc()
+    d.abi_version = ABI_VERSION
+    d.R, d.D, d.n, d.robust, d.max_iter = int(R), int(D), int(n), int(robust), int(max_iter)
+    d.lower_a, d.upper_a = float(lower_a), float(upper_a)
+    return d
+
+
+def robfit_out_names(outputs):
+    """the validated list of output names (default: all but weights)"""
+    names = [k for k in ROBFIT_OUT_NAMES if k != "weights"] if outputs is None else list(outputs)
+    bad = [k for k in names if k not in ROBFIT_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    if not names:
+        raise ValueError("no output requested")
+    return names
 
 
 class EnsDesc(C.Structure):
@@ -424,6 +463,13 @@ def lib():
         h.epi_lasso_run_device.argtypes = lasso_args + [C.c_void_p, C.c_char_p]
         h.epi_lasso_run_host.restype = C.c_int
         h.epi_lasso_run_host.argtypes = lasso_args + [C.c_int, C.c_char_p]
+        robfit_args = [C.POINTER(RobfitDesc), C.c_void_p, C.c_void_p, C.POINTER(RobfitOutputs)]
+        h.epi_robfit_validate.restype = C.c_int
+        h.epi_robfit_validate.argtypes = robfit_args + [C.c_char_p]
+        h.epi_robfit_run_device.restype = C.c_int
+        h.epi_robfit_run_device.argtypes = robfit_args + [C.c_void_p, C.c_char_p]
+        h.epi_robfit_run_host.restype = C.c_int
+        h.epi_robfit_run_host.argtypes = robfit_args + [C.c_int, C.c_char_p]
         ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
         h.epi_ens_validate.restype = C.c_int
         h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]

@@ -843,6 +843,35 @@ def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, 
     return out
 
 
+def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter=50, outputs=None, device="cuda:0"):
+    """REGRESSION_TYPE = 'NONNEGATIVELS-ELEMENT-WISE' for every region in one device call (epi_robfit_run_device): for every
+    NPI k on its own fit(X(:,k), y, 'a*x+b', 'Robust','on', 'Lower',[lower -inf]) as bisquare iteratively reweighted least
+    squares (our reading: DESIGN.md §4.10), then b = mean(y - X a).  X [D, n, R] = NPI_MAXES - InterventionPlans over the
+    regression window, y [D, R].  robust=False stops after the bounded least-squares start.
+    outputs: names out of a, b_item, sigma, iters, status [n, R], weights [D, n, R], b [R] (default: all but weights).
+    Returns a dict of torch tensors (iters, status int32; status is a set of _lib.ROBFIT_STATUS_BITS).  Enqueued on the
+    current stream without a host synchronisation."""
+    dev = torch.device(device)
+    t = lambda v: v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)
+    X, y = t(X).to(dev, torch.float64).contiguous(), t(y).to(dev, torch.float64).contiguous()
+    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    names = _lib.robfit_out_names(outputs)
+    d = _lib.make_robfit_desc(R, D, n, int(bool(robust)), max_iter, lower, upper)
+    shapes = _lib.robfit_shapes(R, D, n)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.ROBFIT_OUT_I32 else torch.float64, device=dev)
+           for k in _lib.ROBFIT_OUT_NAMES if k in names}
+    outs = _lib.RobfitOutputs()
+    for k in _lib.ROBFIT_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_robfit_run_device(C.byref(d), _ptr(X), _ptr(y), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
     """Monte-Carlo ensemble statistics in one device call (epi_ens_run_device): src [T, rows, B] or [T, B]
     (float32 or float64, on the device) is an output array of B = R * D chains in the classic layout, region-major (chain =

@@ -830,6 +830,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "ens_summary.hpp"
 #include "ar_forecast.hpp"
 #include "two_filter.hpp"
+#include "robust_fit.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3646,6 +3647,108 @@ int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y
         for (int k = 0; k < 5; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
         const int r = epi_lasso_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y),
                                            o_f == (size_t)-1 ? nullptr : (const int32_t *)(base + o_f), &dout, cx->stream, err);
+        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
+        if (ev1) (void)hipEventRecord(ev1, cx->stream);
+        return EPI_OK;
+    };
+    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
+    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
+    ctx_release(cx);
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
+// ---- REGRESSION_TYPE = 'NONNEGATIVELS-ELEMENT-WISE': a robust bounded affine fit per (NPI, region) (TrainPredictPrescribeNPI.m:279-292) ----
+int epi_robfit_validate(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 3) { set_err(err, "D must be >= 3"); return EPI_ERR_BAD_ARG; }
+    if (d->n < 1) { set_err(err, "n must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->robust != 0 && d->robust != 1) { set_err(err, "robust must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->max_iter < 1 || d->max_iter > 100000) { set_err(err, "max_iter must lie in 1 .. 100000"); return EPI_ERR_BAD_ARG; }
+    if (d->lower_a != d->lower_a || d->upper_a != d->upper_a) { set_err(err, "lower_a / upper_a must not be NaN"); return EPI_ERR_BAD_ARG; }
+    if (d->lower_a > d->upper_a) { set_err(err, "lower_a must not exceed upper_a"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D * d->n > (int64_t)0x7fffffff) { set_err(err, "R * D * n is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (!X || !y || !out) { set_err(err, "NULL X / y / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!out->a && !out->b_item && !out->sigma && !out->iters && !out->status && !out->weights && !out->b) { set_err(err, "every output is NULL"); return EPI_ERR_BAD_ARG; }
+    if (d->n > kRfMaxN) { set_err(err, "n is limited to 12"); return EPI_ERR_UNSUPPORTED; }
+    if (d->D > kRfMaxD) { set_err(err, "D is limited to 1024 (a wavefront holds an item's days in registers)"); return EPI_ERR_UNSUPPORTED; }
+    return EPI_OK;
+}
+
+static hipError_t rf_dispatch(const RfArgs &g, unsigned blocks, bool intercept, hipStream_t st)
+{
+    if (g.D <= 64) return rf_launch<1>(g, blocks, intercept, st);   // registers per lane: P / 64, P the power of two >= D
+    if (g.D <= 128) return rf_launch<2>(g, blocks, intercept, st);
+    if (g.D <= 256) return rf_launch<4>(g, blocks, intercept, st);
+    if (g.D <= 512) return rf_launch<8>(g, blocks, intercept, st);
+    return rf_launch<16>(g, blocks, intercept, st);
+}
+
+int epi_robfit_run_device(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out,
+                          void *stream, char *err)
+{
+    int rc = epi_robfit_validate(d, X, y, out, err);
+    if (rc != EPI_OK) return rc;
+    RfArgs g{};
+    g.R = d->R; g.D = d->D; g.n = d->n; g.robust = d->robust; g.max_iter = d->max_iter; g.lower = d->lower_a; g.upper = d->upper_a;
+    g.X = X; g.y = y;
+    g.a = out->a; g.b_item = out->b_item; g.sigma = out->sigma; g.iters = out->iters; g.status = out->status;
+    g.weights = out->weights; g.b = out->b;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (out->a || out->b_item || out->sigma || out->iters || out->status || out->weights) {
+        const int64_t items = (int64_t)d->n * d->R;
+        for (int64_t i0 = 0; i0 < items; i0 += kRfLaunchItems) {   // one 64-lane workgroup per item, in slices (robust_fit.hpp)
+            g.item0 = (long long)i0;
+            const unsigned ni = (unsigned)(items - i0 < kRfLaunchItems ? items - i0 : kRfLaunchItems);
+            if ((e = rf_dispatch(g, ni, false, st)) != hipSuccess) return hip_fail(err, e, "robfit_items launch");
+        }
+    }
+    if (out->b) {
+        for (int64_t r0 = 0; r0 < d->R; r0 += kRfLaunchItems) {    // one 64-lane workgroup per region, behind the items
+            g.item0 = (long long)r0;
+            const unsigned nr = (unsigned)(d->R - r0 < kRfLaunchItems ? d->R - r0 : kRfLaunchItems);
+            if ((e = rf_dispatch(g, nr, true, st)) != hipSuccess) return hip_fail(err, e, "robfit_intercept launch");
+        }
+    }
+    return EPI_OK;
+}
+
+int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out,
+                        int device, char *err)
+{
+    int rc = epi_robfit_validate(d, X, y, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, D = (size_t)d->D, n = (size_t)d->n;
+    HostIO io;
+    const size_t o_X = io.add_in(X, D * n, 8, R, 0, R), o_y = io.add_in(y, D, 8, R, 0, R);
+    double *const *f64[5] = {&out->a, &out->b_item, &out->sigma, &out->weights, &out->b};
+    const size_t f64_rows[5] = {n, n, n, D * n, 1};
+    int32_t *const *i32[2] = {&out->iters, &out->status};
+    size_t o_d[5], o_i[2];
+    for (int k = 0; k < 5; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], f64_rows[k], 8, R, 0, R) : (size_t)-1;
+    for (int k = 0; k < 2; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], n, 4, R, 0, R) : (size_t)-1;
+    hipError_t e = hipSuccess;
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
+    HostCtx *cx = ctx_acquire(device, &e);
+    if (!cx || e != hipSuccess) {
+        if (cx) ctx_release(cx);
+        if (have_prev) (void)hipSetDevice(prev);
+        return hip_fail(err, e, "hipSetDevice / context");
+    }
+    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
+        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+        epi_robfit_outputs dout{};
+        double **df[5] = {&dout.a, &dout.b_item, &dout.sigma, &dout.weights, &dout.b};
+        int32_t **di[2] = {&dout.iters, &dout.status};
+        for (int k = 0; k < 5; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
+        for (int k = 0; k < 2; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
+        const int r = epi_robfit_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), &dout, cx->stream, err);
         if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
         if (ev1) (void)hipEventRecord(ev1, cx->stream);
         return EPI_OK;

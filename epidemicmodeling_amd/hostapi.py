@@ -184,6 +184,28 @@ def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, 
     return out
 
 
+def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter=50, outputs=None, device=0):
+    """epi_robfit_run_host: the element-wise robust regression of batch.robust_affine_fit on NumPy arrays (synchronous).
+    X [D, n, R], y [D, R].  Returns the dict of batch.robust_affine_fit as NumPy arrays."""
+    keep = []
+    X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if X.ndim != 3 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    names = _lib.robfit_out_names(outputs)
+    d = _lib.make_robfit_desc(R, D, n, int(bool(robust)), max_iter, lower, upper)
+    shapes = _lib.robfit_shapes(R, D, n)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.ROBFIT_OUT_I32 else np.float64)
+           for k in _lib.ROBFIT_OUT_NAMES if k in names}
+    outs = _lib.RobfitOutputs()
+    for k in _lib.ROBFIT_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_robfit_run_host(C.byref(d), _f(X, keep), _f(y, keep), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
     """epi_ens_run_host: the Monte-Carlo ensemble statistics of batch.ensemble_summary on NumPy arrays (synchronous).
     src [T, rows, B] or [T, B], float32 or float64 (anything else is converted to float64), B = R * D region-major.

@@ -116,15 +116,19 @@ def _alpha_smooth(w, device):
     return r.out["S_SMOOTH"].cpu().numpy()                 # [T, 3, S]
 
 
-REGRESSIONS = ("nonnegls", "lasso")
+REGRESSIONS = ("nonnegls", "lasso", "elementwise")
 
 
 def _regress(X, y, regression, cv_folds, cv_seed, device):
     """One regression between the EKF rounds (TrainPredictPrescribeNPI.m:251-290): 'nonnegls' = lsqnonneg + the intercept
     loop (batch.nnls_affine_fit), 'lasso' = lasso(X, y, 'CV', cv_folds) with folds from cv_seed (batch.lasso_cv; a, b at
-    IndexMinMSE, and the path's lambda, mse, se, idx_min_mse, idx_1se, status ... alongside)."""
+    IndexMinMSE, and the path's lambda, mse, se, idx_min_mse, idx_1se, status ... alongside), 'elementwise' = the robust
+    bounded fit of every NPI on its own and b = mean(y - X a) (:279-292, batch.robust_affine_fit; b_item, sigma, iters,
+    status alongside)."""
     if regression == "nonnegls":
         res = batch.nnls_affine_fit(X, y, device=device)
+    elif regression == "elementwise":
+        res = batch.robust_affine_fit(X, y, device=device)
     else:
         res = batch.lasso_cv(X, y, K=cv_folds, seed=cv_seed, device=device)
     return {k: v.cpu().numpy() for k, v in res.items()}
@@ -133,7 +137,7 @@ def _regress(X, y, regression, cv_folds, cv_seed, device):
 def _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression="nonnegls", cv_folds=50, cv_seed=0):
     """Preprocessing, EKF round 1, regression, round 2, regression (TrainPredictPrescribeNPI.m:142-330,
     ForecastQualityAssessment.m:160-356) over the days given.  regression selects REGRESSION_TYPE: "nonnegls" (the
-    default) or "lasso"; with "lasso" round 1 draws its folds from cv_seed and round 2 from cv_seed + 1 (the reference
+    default), "lasso" or "elementwise"; with "lasso" round 1 draws its folds from cv_seed and round 2 from cv_seed + 1 (the reference
     draws a fresh partition per lasso call).  Returns pre, alpha_round1, fit1, alpha_round2, fit2, X_reg."""
     if regression not in REGRESSIONS:
         raise ValueError(f"regression must be one of {REGRESSIONS}")
@@ -161,7 +165,9 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
               W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0):
     """Run the chain above.  cases/deaths [T,S] cumulative counts (NaN = missing), population [S], ip [T,n,S] (NaN = N/A).
     regression = "nonnegls" (REGRESSION_TYPE 'NONNEGATIVELS', the default) or "lasso" ('LASSO': lasso(X, y, 'CV', cv_folds),
-    folds drawn from cv_seed in round 1 and cv_seed + 1 in round 2; the coefficients may be negative).
+    folds drawn from cv_seed in round 1 and cv_seed + 1 in round 2; the coefficients may be negative) or "elementwise"
+    (REGRESSION_TYPE 'NONNEGATIVELS-ELEMENT-WISE': a robust fit of alpha against every NPI on its own, slope >= 0,
+    DESIGN.md §4.10; it needs num_regression_days >= 3).
     Returns a dict with every intermediate and `prescription` [horizon, n, S]: the smoothed optimal plan of each region's
     Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps]."""
     T, S = cases.shape
@@ -224,7 +230,7 @@ def forecast_quality(cases, deaths, population, ip, num_forecast_days, max_looka
     controls.  R_v of the training window is padded with its mean (:362).  Then every region is filtered once per start
     s = 1 .. num_forecast_days with its last s observations hidden (:380-393) and the error tables and their statistics over
     the starts max_lookahead .. num_forecast_days (:428-449) are computed (batch.lookahead).  regression, cv_folds and
-    cv_seed select REGRESSION_TYPE as in prescribe().
+    cv_seed select REGRESSION_TYPE as in prescribe() ("elementwise": REGRESSION_TYPE 'NONNEGATIVELS-ELEMENT-WISE').
     Returns a dict: the front half's intermediates (pre, alpha_round1, fit1, alpha_round2, fit2, X_reg), pre_entire, R_full,
     workload (the per-region synth.Workload of the study), truth, and est_plus / est_smooth [F, M, S],
     mean / median / std_{plus,smooth} [M, S] (+ S_PLUS / S_SMOOTH / status of every chain with chains=True)."""

@@ -3,6 +3,7 @@ of the file at once (epidemicmodeling_amd/pipeline.py).
 
     python examples/prescribe_from_csv.py OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 30 out.csv
     python examples/prescribe_from_csv.py --regression lasso ...     # REGRESSION_TYPE 'LASSO' (lasso with 50-fold CV)
+    python examples/prescribe_from_csv.py --regression elementwise ...   # 'NONNEGATIVELS-ELEMENT-WISE' (robust fit per NPI)
 
 Without arguments a small synthetic tracker file is generated first (there is no data set in this repository)."""
 import os

@@ -753,6 +753,49 @@ int epi_fuse_run_device(const epi_fuse_desc *d, const epi_fuse_inputs *in, const
 /* HOST pointers, on a pooled context of `device` */
 int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const epi_fuse_outputs *out, int device, char *err);
 
+/* ---- REGRESSION_TYPE = 'NONNEGATIVELS-ELEMENT-WISE' between the EKF rounds (TrainPredictPrescribeNPI.m:279-292, :340-353;
+ * ForecastQualityAssessment.m:281-294, :342-355): for every NPI k on its own
+ *     ffit = fit(X(:,k), y, fittype('a*x+b'), 'Robust','on', 'Lower',[0 -inf], 'Startpoint',[0 0]);  a(k) = ffit.a
+ * and then b = mean(y - X*a), for every region in ONE call.  X [D][n][R] and y [D][R] as for epi_nnls_* / epi_lasso_*.
+ * One item = (NPI k, region r).  The estimator is the documented one -- bisquare iteratively reweighted least squares,
+ * residuals adjusted by leverage, scale from the median absolute deviation, every weighted sub-problem solved in closed
+ * form with the slope clamped to [lower_a, upper_a] -- in the operation order of DESIGN.md §4.10, which the kernel,
+ * tests/robust_fit_ref.c and tests/robust_fit_ref.py share bit for bit.  robust = 0 stops after the ordinary bounded
+ * least-squares start (iters = 0, sigma = NaN, weights 1).
+ * status [n][R] is a set of bits; an item with a non-finite x or y has NONFINITE alone, NaN a / b_item / sigma / weights,
+ * iters = 0, and its region's b is NaN.
+ * epi_robfit_run_device takes DEVICE pointers and enqueues one wavefront per item and then one per region on `stream` (no
+ * host synchronisation, no allocation); epi_robfit_run_host takes HOST pointers and runs on a pooled context of `device`. */
+enum {
+    EPI_ROBFIT_NONFINITE = 1,    /* x or y holds Inf / NaN: NaN outputs */
+    EPI_ROBFIT_CONST = 2,        /* max(x) == min(x): the slope is fixed at 0, the iteration gives the robust intercept */
+    EPI_ROBFIT_SLOPE_LOST = 4,   /* x is not constant, but the final weights leave the slope unidentified: a = 0 */
+    EPI_ROBFIT_MAXITER = 8,      /* max_iter reweightings without meeting the stop rule: the last iterate is kept */
+    EPI_ROBFIT_BOUND = 16        /* the clamp to [lower_a, upper_a] changed the slope in the last solve */
+};
+typedef struct epi_robfit_desc {
+    int32_t abi_version;
+    int32_t R;                   /* regions, >= 1 */
+    int32_t D;                   /* days, 3 .. 1024 (else EPI_ERR_UNSUPPORTED above 1024) */
+    int32_t n;                   /* NPIs, 1 .. 12 */
+    int32_t robust;              /* 1: 'Robust','on' (bisquare); 0: the least-squares start only */
+    int32_t max_iter;            /* reweightings, 1 .. 100000 (robustfit's 50) */
+    double lower_a, upper_a;     /* bounds of the slope, lower_a <= upper_a, +-Inf allowed (the reference: 0, +Inf) */
+} epi_robfit_desc;
+typedef struct epi_robfit_outputs {     /* each may be NULL, but not all of them */
+    double *a, *b_item, *sigma;         /* [n][R]: ffit.a, the item's own intercept (the reference discards it), the last scale */
+    int32_t *iters, *status;            /* [n][R] */
+    double *weights;                    /* [D][n][R]: the final bisquare weights */
+    double *b;                          /* [R]: mean(y - X a).  Without `a` the region's n fits run once more, one after the other */
+} epi_robfit_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor or a NULL descriptor / X / y / outputs / every output,
+ * EPI_ERR_UNSUPPORTED for n > 12 or D > 1024 */
+int epi_robfit_validate(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out, char *err);
+int epi_robfit_run_device(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out,
+                          void *stream, char *err);
+int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out,
+                        int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

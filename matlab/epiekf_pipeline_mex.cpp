@@ -27,6 +27,12 @@
 //       lambda, mse, se, intercept, df  R x NumLambda (ascending lambda, MATLAB's order);  idx, idx1se  R x 1
 //       (IndexMinMSE, Index1SE, ONE-based);  B  R x n x NumLambda.  A region whose X / y holds Inf or NaN gets NaN outputs
 //       and idx = idx1se = 0; with K = 0, a, b, mse and se are NaN and idx = idx1se = 0.  (No lasso.m is shipped: it would shadow the Statistics Toolbox function.)
+//   [a, b, b_item, sigma, iters, status, weights] = epiekf_pipeline_mex('robustfit', X, y, robust, lower, upper, max_iter)
+//       :279-292 ('NONNEGATIVELS-ELEMENT-WISE'): for every NPI on its own fit(X(:,k), y, 'a*x+b', 'Robust','on',
+//       'Lower',[lower -inf]) as bisquare iteratively reweighted least squares, then b = mean(y - X*a).
+//       X  R x n x D (as for 'nnls');  y  R x D;  robust  0 or 1;  lower, upper  the slope's bounds (the reference: 0, Inf);
+//       max_iter  1 .. 100000 (50).  a, b_item, sigma, iters, status  R x n (status: bits 1 non-finite, 2 constant column,
+//       4 slope lost, 8 iteration cap, 16 bound active);  b  R x 1;  weights  R x n x D (only when requested).
 //   [mean, std, min, max, quantiles, count] = epiekf_pipeline_mex('ens_summary', src, D, q, population)
 //       Monte-Carlo ensemble statistics (BASELINE config 5).  src  B x rows x T (or B x T), B = R * D chains,
 //       region-major (chain = (r-1) * D + d): a filter output such as S_SMOOTH;  D  draws per region;  q  1 .. 16
@@ -224,6 +230,37 @@ static void lasso(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void robustfit(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 7) mexErrMsgTxt("epiekf_pipeline_mex('robustfit', X, y, robust, lower, upper, max_iter): 7 inputs expected");
+    if (mxGetNumberOfDimensions(prhs[1]) != 3) mexErrMsgTxt("X must be R x n x D");
+    const mwSize *dx = mxGetDimensions(prhs[1]);
+    const mwSize R = dx[0], n = dx[1], D = dx[2];
+    want(prhs[2], R, D, "y");
+    epi_robfit_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.R = (int32_t)R; d.D = (int32_t)D; d.n = (int32_t)n;
+    d.robust = (int32_t)mxGetScalar(prhs[3]); d.lower_a = mxGetScalar(prhs[4]); d.upper_a = mxGetScalar(prhs[5]);
+    d.max_iter = (int32_t)mxGetScalar(prhs[6]);
+    const bool want_w = nlhs >= 7;
+    mxArray *a = mxCreateDoubleMatrix(R, n, mxREAL), *b = mxCreateDoubleMatrix(R, 1, mxREAL), *bi = mxCreateDoubleMatrix(R, n, mxREAL);
+    mxArray *sg = mxCreateDoubleMatrix(R, n, mxREAL), *it = mxCreateDoubleMatrix(R, n, mxREAL), *st = mxCreateDoubleMatrix(R, n, mxREAL);
+    mxArray *w = want_w ? dbl3(R, n, D) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxArray *o[7] = {a, b, bi, sg, it, st, w};
+    std::vector<int32_t> itv((size_t)(R * n)), stv((size_t)(R * n));
+    epi_robfit_outputs out;
+    memset(&out, 0, sizeof out);
+    out.a = mxGetPr(a); out.b = mxGetPr(b); out.b_item = mxGetPr(bi); out.sigma = mxGetPr(sg); out.iters = itv.data(); out.status = stv.data();
+    if (want_w) out.weights = mxGetPr(w);
+    // the ABI's [n][R] and [D][n][R] are MATLAB's R x n and R x n x D: no transposition
+    char err[256] = {0};
+    const int rc = epi_robfit_run_host(&d, mxGetPr(prhs[1]), mxGetPr(prhs[2]), &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < itv.size(); k++) { mxGetPr(it)[k] = (double)itv[k]; mxGetPr(st)[k] = (double)stv[k]; }
+    for (int k = 0; k < 7; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('ens_summary', src, D, q, population): 5 inputs expected");
@@ -399,6 +436,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "preprocess") == 0) preprocess(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "nnls") == 0) nnls(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "robustfit") == 0) robustfit(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
