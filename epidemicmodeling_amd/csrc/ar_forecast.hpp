@@ -38,6 +38,10 @@ struct ArSimArgs {
     double *S;                     // [L + H][3][B]
 };
 
+// workgroups per region of ar_simulate: ceil(D / 64), in 64 bits (D + 63 leaves int for D > 2^31 - 64, which validate accepts
+// with R = 1); the result is at most 2^25 and fits ArSimArgs::bpr
+inline int ar_blocks_per_region(int D) { return (int)(((int64_t)D + 63) / 64); }
+
 EPI_DEV size_t ar_lds_seg(int L) { return ((size_t)L + 7) & ~(size_t)7; }
 inline size_t ar_fit_lds_bytes(int L, int p) { return ((((size_t)L + 7) & ~(size_t)7) + 64 + (size_t)(p + 1) * 2 * (size_t)(L - p)) * sizeof(double); }
 inline size_t ar_sim_lds_bytes(int L, int p) { return ((((size_t)L + 7) & ~(size_t)7) + 32 + (size_t)p * 64) * sizeof(double); }

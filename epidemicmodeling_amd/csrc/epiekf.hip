@@ -3915,7 +3915,7 @@ int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const
         }
     }
     ArSimArgs g{};
-    g.L = d->L; g.p = d->p; g.H = d->H; g.R = d->R; g.D = d->D; g.Sd = d->Sd; g.bpr = (d->D + 63) / 64; g.dt = d->dt;
+    g.L = d->L; g.p = d->p; g.H = d->H; g.R = d->R; g.D = d->D; g.Sd = d->Sd; g.bpr = ar_blocks_per_region(d->D); g.dt = d->dt;
     g.seg = in->seg; g.beta = in->beta; g.s0 = in->s0; g.i0 = in->i0; g.A = A; g.nv = nv; g.z = in->z; g.drive = in->drive;
     g.drive_series = in->drive_series; g.S = out->S;
     const size_t shm = ar_sim_lds_bytes(d->L, d->p);
@@ -4006,8 +4006,7 @@ int epi_fuse_run_device(const epi_fuse_desc *d, const epi_fuse_inputs *in, const
     hipError_t e;
     FuseArgs g{};
     g.B = d->B; g.T = d->T; g.f32 = d->storage; g.form = d->form; g.p_solver = d->p_solver;
-    g.blk = (d->lane_block <= 0 || d->lane_block >= d->B) ? d->B : d->lane_block;
-    g.nblk = (d->B + g.blk - 1) / g.blk;
+    fuse_geometry(d->B, d->lane_block, &g.blk, &g.nblk);
     g.sf = in->sf; g.Pf = in->Pf; g.sb = in->sb; g.Pb = in->Pb;
     g.s_out = out->s_out; g.P_out = out->P_out; g.d2 = out->d2; g.rank = out->rank; g.status = out->status;
     if (out->status && (e = hipMemsetAsync(out->status, 0, (size_t)d->B * sizeof(int32_t), st)) != hipSuccess)
@@ -4030,8 +4029,9 @@ int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const e
     int rc = epi_fuse_validate(d, in, out, err);
     if (rc != EPI_OK) return rc;
     const size_t B = (size_t)d->B, T = (size_t)d->T, m = (size_t)d->m, none = (size_t)-1;
-    const size_t blk = (d->lane_block <= 0 || d->lane_block >= d->B) ? B : (size_t)d->lane_block;
-    const size_t Bp = (B + blk - 1) / blk * blk, es = d->storage ? 4 : 8;       // a day of a blocked array holds rows * Bp elements
+    int gblk, gnblk;
+    fuse_geometry(d->B, d->lane_block, &gblk, &gnblk);
+    const size_t Bp = (size_t)gnblk * (size_t)gblk, es = d->storage ? 4 : 8;       // a day of a blocked array holds rows * Bp elements
     HostIO io;
     const size_t o_sf = io.add_in(in->sf, T * m, es, Bp, 0, Bp), o_Pf = io.add_in(in->Pf, T * m * m, es, Bp, 0, Bp);
     const size_t o_sb = io.add_in(in->sb, T * m, es, Bp, 0, Bp), o_Pb = io.add_in(in->Pb, T * m * m, es, Bp, 0, Bp);

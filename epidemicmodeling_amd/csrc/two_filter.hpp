@@ -27,6 +27,15 @@ struct FuseArgs {
     int32_t *rank, *status;         // [T][B], [B], or NULL
 };
 
+// the layout block and the blocks per day from the descriptor's B and lane_block: blk = B (classic) for lane_block 0 or >= B,
+// nblk = ceil(B / blk), in 64 bits (B + blk - 1 leaves int for the classic layout with B > 2^30); both results fit an int
+inline void fuse_geometry(int B, int lane_block, int *blk, int *nblk)
+{
+    const int64_t b = (lane_block <= 0 || lane_block >= B) ? (int64_t)B : (int64_t)lane_block;
+    *blk = (int)b;
+    *nblk = (int)(((int64_t)B + b - 1) / b);
+}
+
 // the first pass over Pf / Pb (the upper triangles, for S): every element of it is read again by the products: cached
 EPI_DEV double fuse_ld(const void *p, size_t o, int f32)
 {

@@ -49,6 +49,9 @@ extern "C" void arf_run(const double *seg, const double *beta, const double *s0,
                         const int32_t *series, const double *A_in, const double *nv_in, int R, int D, int L, int p, int H, int Sd, int fit,
                         int nv_mode, double dt, double *S, double *A_out, double *nv_out, int32_t *status);
 
+// the launch geometry epi_arfc_run_device uses, for tests/test_ar_forecast_emu.py (this file also builds as a shared object)
+extern "C" int emu_ar_blocks_per_region(int D) { return ar_blocks_per_region(D); }
+
 template <class F, class... A> static void launch(F kernel, unsigned blocks, A... args)
 {
     for (unsigned b = 0; b < blocks; b++) {
@@ -119,7 +122,7 @@ int main()
             launch(ar_given_status, (unsigned)((R + 63) / 64), L, R, (const double *)seg.data(), st2.data());
         }
         ArSimArgs g{};
-        g.L = L; g.p = p; g.H = H; g.R = R; g.D = D; g.Sd = Sd; g.bpr = (D + 63) / 64; g.dt = 0.5;
+        g.L = L; g.p = p; g.H = H; g.R = R; g.D = D; g.Sd = Sd; g.bpr = ar_blocks_per_region(D); g.dt = 0.5;
         g.seg = seg.data(); g.beta = beta.data(); g.s0 = s0.data(); g.i0 = i0.data(); g.A = A; g.nv = nv; g.z = z.data(); g.drive = dp;
         g.drive_series = sp; g.S = S2.data();
         if (ar_sim_lds_bytes(L, p) > sizeof ar_lds) { puts("LDS budget exceeded"); return 2; }

@@ -696,6 +696,68 @@ def sampled_output(r, name, idx):
     return got.reshape(T, rows, len(idx)).cpu().numpy()
 
 
+# ---------------------------------------------------------------- the calls around the filter at their launch and offset limits
+# (tests/test_gpu_addressing_limits.py part B, tests/test_gpu_call_limits.py)
+def poisoned(shape, dtype, device):
+    """A device tensor filled with the poison pattern of its type: POISON64 (float64), POISON32 (float32), POISON_RANK (integers)."""
+    import torch
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if dtype == torch.float64:
+        t.view(torch.int64).fill_(POISON64)
+    elif dtype == torch.float32:
+        t.view(torch.int32).fill_(POISON32)
+    else:
+        t.fill_(POISON_RANK)
+    return t
+
+
+def holds_poison(t):
+    """Does any word of `t` (a tensor poisoned() made) still hold its poison pattern?"""
+    import torch
+    if t.dtype == torch.float64:
+        return bool((t.view(torch.int64) == POISON64).any())
+    if t.dtype == torch.float32:
+        return bool((t.view(torch.int32) == POISON32).any())
+    return bool((t == POISON_RANK).any())
+
+
+def need_free(device, need):
+    """Fail the test, with the numbers, if fewer than `need` bytes of device memory are free; reset the peak statistics."""
+    import pytest
+    import torch
+    torch.cuda.empty_cache()
+    free, total = torch.cuda.mem_get_info(device)
+    if free < need:
+        pytest.fail(f"needs ~{need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} of {total / 2**30:.1f} GiB are free")
+    torch.cuda.reset_peak_memory_stats(device)
+
+
+def formula_rows(L_, R, device, fn, dtype):
+    """[L_, R] tensor whose row t is fn(t * R + arange(R)), a row at a time (the hash's temporaries stay small)."""
+    import torch
+    out = torch.empty((L_, R), dtype=dtype, device=device)
+    c = torch.arange(R, dtype=torch.int64, device=device)
+    for t in range(L_):
+        out[t] = fn(c + t * R).to(dtype)
+    return out
+
+
+def crossing_regions(rows, R, bits=(31, 32), itemsize=8):
+    """Columns of a [rows, R] array on both sides of the element whose byte offset first reaches 2^bit."""
+    reg = []
+    for b in bits:
+        e = (1 << b) // itemsize
+        if e < rows * R:
+            reg += [(e % R) + d for d in (-2, -1, 0, 1)]
+    return [q for q in reg if 0 <= q < R]
+
+
+def boundary_items(unit, count):
+    """Items k * unit - 2 .. k * unit + 1 around every launch-slice boundary k * unit < count of a call that starts `unit` items
+    per launch."""
+    return [k * unit + d for k in range(1, (count - 1) // unit + 1) for d in (-2, -1, 0, 1) if 0 <= k * unit + d < count]
+
+
 # ---------------------------------------------------------------- whole-batch comparisons of the full-size runs
 # (DESIGN.md 2, "Every chain of the full-size runs").  The equality is the suite's np.array_equal(..., equal_nan=True): NaN equals
 # NaN whatever its payload, +0 equals -0, nothing else is equal that is not the same number.  words_equal() is that rule element

@@ -66,6 +66,7 @@ BAD = [
     (dict(with_in=("drive",), Sd=0), "Sd must be >= 1"),
     (dict(with_in=("drive",), Sd=5), "drive without drive_series needs Sd == R * D"),
     (dict(null_outs=("S",)), "NULL S output"),
+    (dict(R=2, D=2 ** 30), "R * D is limited to 2^31 - 1"),
 ]
 
 
@@ -83,6 +84,9 @@ def test_validate_accepts(hip_lib):
     assert _call("validate", p=32, L=288)[0] == 0
     assert _call("validate", p=32, L=49)[0] == 0
     assert _call("validate", R=2 ** 16, D=2 ** 15 - 1)[0] == 0
+    # R * D = 2^31 - 1 itself (a prime: one region of 2^31 - 1 draws, or the transpose) -- the descriptor alone, S would be 144 GiB
+    assert _call("validate", R=1, D=2 ** 31 - 1)[0] == 0
+    assert _call("validate", R=2 ** 31 - 1, D=1)[0] == 0
     assert _call("validate", fit=0, with_in=("A", "noise_var"), null_outs=("A_out", "noise_var_out", "status"))[0] == 0
     assert _call("validate", null_outs=("status",))[0] == 0
     assert _call("validate", with_in=("drive",), Sd=R_ * D_)[0] == 0

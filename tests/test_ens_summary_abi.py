@@ -77,6 +77,7 @@ def test_validate_accepts(hip_lib):
     assert _call("validate", D=4096, q=tuple(np.linspace(0.0, 1.0, 16)), storage=1)[0] == 0
     assert _call("validate", derive_newcases=1, with_pop=True, null_outs=("mean", "std", "min", "max", "quantiles"))[0] == 0
     assert _call("validate", R=(2 ** 31 - 1) // 4096, D=4096)[0] == 0
+    assert _call("validate", R=2 ** 31 - 1, D=1)[0] == 0                  # R * D = 2^31 - 1 itself (a prime: D = 1 only)
 
 
 def test_descriptor_matches_the_header(hip_lib):

@@ -540,28 +540,8 @@ def test_rt_window_and_lasso_element_count_rejections():
 
 
 # ---------------------------------------------------------------------------------- B: runs at the batch-count limits
-def _poisoned(shape, dtype, device):
-    import torch
-    t = torch.empty(shape, dtype=dtype, device=device)
-    if dtype == torch.float64:
-        t.view(torch.int64).fill_(H.POISON64)
-    else:
-        t.fill_(H.POISON_RANK)
-    return t
-
-
-def _holds_poison(t):
-    import torch
-    return bool((t.view(torch.int64) == H.POISON64).any()) if t.dtype == torch.float64 else bool((t == H.POISON_RANK).any())
-
-
-def _need_free(device, need):
-    import torch
-    torch.cuda.empty_cache()
-    free, total = torch.cuda.mem_get_info(device)
-    if free < need:
-        pytest.fail(f"needs ~{need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} of {total / 2**30:.1f} GiB are free")
-    torch.cuda.reset_peak_memory_stats(device)
+_poisoned, _holds_poison, _need_free = H.poisoned, H.holds_poison, H.need_free        # shared with tests/test_gpu_call_limits.py
+_formula_rows, _crossing_regions = H.formula_rows, H.crossing_regions
 
 
 @pytest.mark.parametrize("R,F,LL,M", [(1 << 21, 4, 12, 2), (1 << 23, 1, 4, 9)], ids=["4-starts", "2^26-table-columns"])
@@ -615,26 +595,6 @@ def test_lookahead_at_two_to_the_23_chains(gpu_device, R, F, LL, M):
     print(f"[addressing] lookahead R={R} F={F}: peak {torch.cuda.max_memory_allocated(gpu_device) / 2**30:.1f} GiB")
     del run, dw, truth, pop
     torch.cuda.empty_cache()
-
-
-def _formula_rows(L_, R, device, fn, dtype):
-    """[L_, R] tensor whose row t is fn(t * R + arange(R)), a row at a time (the hash's temporaries stay small)."""
-    import torch
-    out = torch.empty((L_, R), dtype=dtype, device=device)
-    c = torch.arange(R, dtype=torch.int64, device=device)
-    for t in range(L_):
-        out[t] = fn(c + t * R).to(dtype)
-    return out
-
-
-def _crossing_regions(rows, R, bits=(31, 32), itemsize=8):
-    """Columns of a [rows, R] array on both sides of the element whose byte offset first reaches 2^bit."""
-    reg = []
-    for b in bits:
-        e = (1 << b) // itemsize
-        if e < rows * R:
-            reg += [(e % R) + d for d in (-2, -1, 0, 1)]
-    return [q for q in reg if 0 <= q < R]
 
 
 @pytest.fixture(scope="module")

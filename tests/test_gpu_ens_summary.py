@@ -13,6 +13,9 @@ pytestmark = pytest.mark.gpu
 FILL, I32_FILL, GUARD = -98765.4321, -12345, 8
 Q16 = (0.0, 1.0, 0.5, 1.0 / 3.0, 0.025, 0.25, 0.75, 0.975, 0.01, 0.99, 0.1, 0.9, 0.2, 0.8, 2.0 / 3.0, 0.6)
 R_, T_, ROWS_ = 3, 2, 3
+# the draws per item of the shape grid: every register count NV = P / 64 of the dispatch in epi_ens_run_device (P the power of
+# two >= D) and both sides of each of its `<=` (test_the_grid_reaches_every_instantiation)
+GRID_D = [1, 2, 3, 63, 64, 65, 127, 128, 129, 256, 257, 300, 512, 513, 1000, 1024, 1025, 2000, 2048, 2049, 4095, 4096]
 
 
 def _run_device(src, R, D, q, population=None, names=None, device="cuda:0", calls=1):
@@ -70,7 +73,7 @@ def _source(D, storage, seed, R=R_, T=T_, rows=ROWS_):
 
 
 @pytest.mark.parametrize("storage", ["f64", "f32"])
-@pytest.mark.parametrize("D", [1, 2, 3, 63, 64, 65, 127, 128, 129, 1000, 1024, 4096])
+@pytest.mark.parametrize("D", GRID_D)
 def test_shape_grid_equals_reference(gpu_device, D, storage):
     src = _source(D, storage, seed=D)
     for q in ((1.0 / 3.0,), Q16):
@@ -79,8 +82,22 @@ def test_shape_grid_equals_reference(gpu_device, D, storage):
         assert (got["count"] == D).all()
 
 
+def test_the_grid_reaches_every_instantiation():
+    """what the shape grid above covers of epi_ens_run_device's dispatch (D <= 64: ens_summary<1>, <= 128: <2>, ... <= 2048:
+    <32>, else <64>): every instantiation is launched, by more than one D where the range allows, and every threshold has a D
+    on it and a D one beyond it; the planted members run NV = 8 and NV = 32 too"""
+    nv = lambda D: max(64, 1 << (D - 1).bit_length()) // 64
+    assert {nv(D) for D in GRID_D} == {1, 2, 4, 8, 16, 32, 64}
+    for edge in (64, 128, 256, 512, 1024, 2048):
+        assert edge in GRID_D and edge + 1 in GRID_D and nv(edge + 1) == 2 * nv(edge), edge
+    assert 1 in GRID_D and 4096 in GRID_D and 4095 in GRID_D                # validate's ends: 1 .. kEnsMaxD
+    for n in (8, 32):
+        assert any(nv(D) == n and D % 64 for D in GRID_D), n                # with a partly filled last register
+    assert {nv(D) for D in (64, 65, 300, 1000, 2000)} == {1, 2, 8, 16, 32}  # test_planted_members
+
+
 @pytest.mark.parametrize("storage", ["f64", "f32"])
-@pytest.mark.parametrize("D", [64, 65, 1000])
+@pytest.mark.parametrize("D", [64, 65, 300, 1000, 2000])
 def test_planted_members(gpu_device, D, storage):
     src = _source(D, storage, seed=100 + D)
     big = 300 if storage == "f64" else 30

@@ -19,6 +19,8 @@ F64_POISON, I32_POISON, GUARD = -7777.25, -12345, 64
 
 # the issue's shapes, plus D = 300: without it no shape runs the NV = 8 instantiation (256 < D <= 512)
 SHAPES = list(itertools.product((3, 4, 63, 64, 65, 129, 300, 1024), (1, 12), (1, 5, 70)))
+# both sides of every `<=` of rf_dispatch (64 | 128 | 256 | 512): 64 / 65 and 129 are above, these are the rest
+SHAPES += [(D, 1, 5) for D in (128, 256, 257, 512, 513)]
 MAIN = (1, 50, 0.0, INF)                                        # robust, max_iter, lower, upper: the reference's call
 ROTA = [(1, 1, 0.0, INF), (1, 3, -INF, INF), (0, 50, 0.0, INF), (0, 50, -INF, INF), (1, 50, -INF, INF), (1, 3, 0.0, INF),
         (1, 1, -INF, INF), (1, 50, 0.02, 0.02), (0, 3, -INF, INF), (0, 1, 0.0, INF)]
@@ -135,6 +137,11 @@ def test_the_cases_reach_every_path(ref):
                 assert (w["iters"] == 0).all()
     assert bits == RF.NONFINITE | RF.CONST | RF.SLOPE_LOST | RF.MAXITER | RF.BOUND
     assert nvs == {1, 2, 4, 8, 16} and below and at
+    days = {D for D, _, _ in SHAPES}
+    nv = lambda D: max(64, 1 << (D - 1).bit_length()) // 64
+    for edge in (64, 128, 256, 512):                             # rf_dispatch: a shape on each threshold and one beyond it
+        assert edge in days and edge + 1 in days and nv(edge + 1) == 2 * nv(edge), edge
+    assert 3 in days and 1024 in days                            # validate's ends: 3 .. kRfMaxD
     assert {s[0] for s in seen} == {0, 1} and {s[1] for s in seen} == {1, 3, 50}
     assert {(0.0, INF), (-INF, INF)} <= {s[2:] for s in seen}
     X, y = _problem(5, 12, 70)

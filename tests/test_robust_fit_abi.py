@@ -59,6 +59,7 @@ BAD = [
     (dict(null_outs=ALL), -5, "every output is NULL"),
     (dict(n=13), -8, "n is limited to 12"),
     (dict(D=1025), -8, "D is limited to 1024"),
+    (dict(R=(2 ** 31 - 1) // 3 + 1, D=3, n=1), -5, "R * D * n is limited to 2^31 - 1"),        # 2^31 + 1
 ]
 
 
@@ -74,6 +75,9 @@ def test_validate_accepts(hip_lib):
     assert _call("validate") == (0, "")
     assert _call("validate", D=3, n=12, max_iter=100000, lower_a=-float("inf"))[0] == 0
     assert _call("validate", D=1024, n=1, max_iter=1, robust=0, lower_a=0.25, upper_a=0.25)[0] == 0
+    # the largest product D >= 3 allows (2^31 - 1 is prime): 2^31 - 2, through the descriptor alone (X would be 16 GiB)
+    assert _call("validate", R=(2 ** 31 - 1) // 3, D=3, n=1)[0] == 0
+    assert _call("validate", R=(2 ** 31 - 2) // (6 * 331), D=331, n=6)[0] == 0 and (2 ** 31 - 2) % (6 * 331) == 0
     for k in ALL:                                            # every output alone is enough
         assert _call("validate", null_outs=tuple(o for o in ALL if o != k))[0] == 0
 

@@ -78,3 +78,19 @@ def test_real_filter_outputs(emu, which):
         got = _run(emu, arrs, which, w.B, w.T, form, ps, "f64", 4)
         for k, v in got.items():
             assert TF.same_bits(v, want[k]), (form, ps, k)
+
+
+GEOMETRY = [(B, lb) for B in (1, 2**30, 2**30 + 1, 2**31 - 1) for lb in sorted({0, 1, 4, B - 1, B}) if lb <= B]
+
+
+@pytest.mark.parametrize("B, lane_block", GEOMETRY)
+def test_layout_geometry_at_the_ends_of_int(emu, B, lane_block):
+    """fuse_geometry (csrc/two_filter.hpp), the function epi_fuse_run_device and epi_fuse_run_host take the layout block and
+    the blocks per day from: blk = B for lane_block 0 or B, else lane_block; nblk = ceil(B / blk).  `(B + blk - 1) / blk` in
+    int, the expression it replaces in the device entry, leaves int in the classic layout with B > 2^30 (validate accepts B up
+    to 2^31 - 1): nblk came out wrong and, with T >= 2, slot = t * nblk + cb addressed another day.  A GPU run at that B
+    needs ~77 GiB per P array, so this is a CPU test."""
+    blk, nblk = C.c_int(-7), C.c_int(-7)
+    emu.emu_fuse_geometry(C.c_int(B), C.c_int(lane_block), C.byref(blk), C.byref(nblk))
+    want = B if lane_block in (0, B) else lane_block
+    assert (blk.value, nblk.value) == (want, -(-B // want))

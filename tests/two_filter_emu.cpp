@@ -26,6 +26,9 @@ namespace epi {
 template <int M> constexpr int pinv_wg() { return 1; }
 #include "two_filter.hpp"
 }
+// the launch geometry epi_fuse_run_device / _host use, for tests/test_two_filter_emu.py
+extern "C" void emu_fuse_geometry(int B, int lane_block, int *blk, int *nblk) { epi::fuse_geometry(B, lane_block, blk, nblk); }
+
 extern "C" void emu_fuse(int m, int B, int T, int blk, int nblk, int f32, int form, int p_solver, const void *sf, const void *Pf,
                          const void *sb, const void *Pb, void *s_out, void *P_out, double *d2, int32_t *rank, int32_t *status)
 {
