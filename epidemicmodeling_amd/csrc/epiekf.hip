@@ -2008,318 +2008,8 @@ int epi_ekf_precheck_device(const epi_batch_desc *d, const epi_inputs *in, void 
 // outlives the call (idle contexts wait in a per-device pool), so that the 250 calls per region of the unchanged
 // reference caller (TrainPredictPrescribeNPI.m:421-460) do not pay 50 hipMalloc/hipFree and 50 synchronous copies each.
 }   // extern "C"
+#include "host_stage.hpp"
 namespace epi {
-constexpr size_t kStageBytes = (size_t)64 << 20;
-constexpr size_t kStageSmallBytes = (size_t)8 << 20;   // dense calls above this go straight to / from the caller's arrays (HostIO::staged)
-constexpr size_t kArenaKeepBytes = (size_t)2 << 30;   // an idle context keeps at most this much device memory
-constexpr int kPoolPerDevice = 4;                      // idle contexts kept per device (64 MiB of pinned memory each)
-struct HostCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    char *arena = nullptr; size_t arena_bytes = 0;
-    bool tuned = false;        // the arena is the fastest of several candidates (place_and_run): kept whatever its size
-    char *pinned = nullptr;
-    ~HostCtx()
-    {
-        if (device < 0) return;
-        (void)hipSetDevice(device);
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        if (arena) (void)hipFree(arena);
-        if (pinned) (void)hipHostFree(pinned);
-    }
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= arena_bytes) return hipSuccess;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        if (arena) { (void)hipFree(arena); arena = nullptr; arena_bytes = 0; tuned = false; }
-        size_t want = bytes + bytes / 4;
-        e = hipMalloc((void **)&arena, want);
-        if (e != hipSuccess) { (void)hipGetLastError(); want = bytes; e = hipMalloc((void **)&arena, want); }
-        if (e != hipSuccess) { arena = nullptr; return e; }
-        arena_bytes = want;
-        return hipSuccess;
-    }
-};
-static std::mutex g_pool_mu;
-static std::vector<HostCtx *> g_pool;     // idle contexts of all devices
-static HostCtx *ctx_acquire(int device, hipError_t *e)
-{
-    if (device < 0 || device >= kMaxDevices) { *e = hipErrorInvalidDevice; return nullptr; }
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        size_t pick = g_pool.size();               // the idle context of this device with the largest arena
-        for (size_t i = 0; i < g_pool.size(); i++)
-            if (g_pool[i]->device == device && (pick == g_pool.size() || g_pool[i]->arena_bytes > g_pool[pick]->arena_bytes)) pick = i;
-        if (pick < g_pool.size()) { HostCtx *c = g_pool[pick]; g_pool.erase(g_pool.begin() + (long)pick); *e = hipSetDevice(device); return c; }
-    }
-    if ((*e = hipSetDevice(device)) != hipSuccess) return nullptr;
-    HostCtx *c = new HostCtx();
-    c->device = device;
-    if ((*e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { c->device = -1; delete c; return nullptr; }
-    if ((*e = hipHostMalloc((void **)&c->pinned, kStageBytes, hipHostMallocDefault)) != hipSuccess) { delete c; return nullptr; }
-    return c;
-}
-// back to the pool: a device keeps at most kPoolPerDevice idle contexts, and only ONE of them an arena above kArenaKeepBytes (the
-// others hand theirs back to the device first; epi_host_pool_release frees everything).  Until round 6 every large arena was
-// returned at once -- but hipFree takes ~30 ms per GiB on these boxes (24 GiB: 730 ms; hipMalloc 0.4 ms) and the next hipMalloc
-// sometimes waits behind it for seconds: the headline sweep's host-pointer call took 16 ms or 0.7-6 s, the 9 375-chain shard with all
-// outputs 118 or 200 ms, depending on whether the previous call's arena was still being returned (profiles/r06/host_calls.json).
-static void ctx_release(HostCtx *c)
-{
-    bool big_kept = false;
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        for (HostCtx *o : g_pool) big_kept = big_kept || (o->device == c->device && o->arena_bytes > kArenaKeepBytes);
-    }
-    if (c->arena_bytes > kArenaKeepBytes && !c->tuned && big_kept) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(c->arena);
-        c->arena = nullptr; c->arena_bytes = 0;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        int same = 0;
-        for (HostCtx *o : g_pool) same += o->device == c->device;
-        if (same < kPoolPerDevice) { g_pool.push_back(c); return; }
-    }
-    delete c;
-}
-
-// Placement of a host call's arena (epi_batch_desc.placement_tries / epi_prescribe_desc.placement_tries, ABI 6).  Where the
-// allocator puts the ~14 arrays a pass streams concurrently changes the forward kernel's and the smoother's time by 5-15 %
-// (which PHYSICAL pages the allocation got: DESIGN.md 4, "Placement"); it is a property of the allocation and a host-pointer
-// caller never sees the allocation.  When a call has to allocate a NEW arena and asks for `tries` > 1: the call's own kernels
-// are run once untimed (clocks, code objects), then timed on up to `tries` candidate arenas, each allocated while the earlier
-// ones are held (so that other memory is handed out) and each for at least ~15 ms of kernels; the fastest is kept -- with the
-// complete results of its last run in it, nothing is computed again -- and stays with the pooled context whatever its size
-// (epi_host_pool_release frees it).  compute(base, ev0, ev1) enqueues upload + kernels for the arena at `base` on the
-// context's stream and records the two events (when given) around the kernels.
-template <class F>
-static int place_and_run(HostCtx *cx, size_t need, int tries, epi_placement_report *rep, F &&compute, char *err)
-{
-    if (rep) memset(rep, 0, sizeof *rep);
-    const bool fresh = need > cx->arena_bytes;
-    hipError_t e = cx->reserve(need);
-    if (e != hipSuccess) return hip_fail(err, e, "device arena");
-    if (tries <= 1 || !fresh) return compute(cx->arena, nullptr, nullptr);
-    if (tries > EPI_PLACEMENT_MAX_TRIES) tries = EPI_PLACEMENT_MAX_TRIES;
-    int rc = compute(cx->arena, nullptr, nullptr);
-    if (rc != EPI_OK) return rc;
-    if ((e = hipStreamSynchronize(cx->stream)) != hipSuccess) return hip_fail(err, e, "kernel execution (placement warm-up)");
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if ((e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) {
-        if (ev0) (void)hipEventDestroy(ev0);
-        return hip_fail(err, e, "hipEventCreate");
-    }
-    struct Cand { char *p; size_t bytes; float ms; };
-    std::vector<Cand> cands;
-    for (int i = 0; i < tries && rc == EPI_OK; i++) {
-        Cand c{cx->arena, cx->arena_bytes, 0.0f};
-        if (i > 0) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + need / 16) { (void)hipGetLastError(); break; }
-            if (hipMalloc((void **)&c.p, need) != hipSuccess) { (void)hipGetLastError(); break; }
-            c.bytes = need;
-        }
-        float acc = 0.0f;
-        int n = 0;
-        do {
-            rc = compute(c.p, ev0, ev1);
-            if (rc != EPI_OK) break;
-            if ((e = hipStreamSynchronize(cx->stream)) != hipSuccess) { rc = hip_fail(err, e, "kernel execution (placement try)"); break; }
-            float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, ev0, ev1);
-            acc += ms; n++;
-        } while (acc < 15.0f && n < 64);
-        c.ms = n ? acc / (float)n : 0.0f;
-        cands.push_back(c);
-    }
-    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-    size_t best = 0;
-    for (size_t i = 1; i < cands.size(); i++)
-        if (rc == EPI_OK && cands[i].ms < cands[best].ms) best = i;
-    if (rc != EPI_OK) best = 0;                       // an error: back to the first arena, the others are freed
-    (void)hipStreamSynchronize(cx->stream);
-    for (size_t i = 0; i < cands.size(); i++)
-        if (i != best) (void)hipFree(cands[i].p);
-    if (!cands.empty()) { cx->arena = cands[best].p; cx->arena_bytes = cands[best].bytes; }
-    cx->tuned = rc == EPI_OK && cands.size() > 1;
-    if (rep && rc == EPI_OK) {
-        rep->tries = (int32_t)cands.size(); rep->chosen = (int32_t)best;
-        for (size_t i = 0; i < cands.size(); i++) rep->ms[i] = cands[i].ms;
-    }
-    return rc;
-}
-
-// The arrays of one host call on one context: every array is `rows` rows of which this call moves a strided piece
-// (columns [col0, col0 + cols) of a row of cols_full elements) to / from a contiguous device copy.  Calls whose arrays fit
-// the pinned buffer are packed there and moved by ONE copy each way; larger ones go row block by row block.
-struct HostIO {
-    struct Piece { const char *src; char *dst; size_t rows, width, pitch, off; };
-    std::vector<Piece> ins, outs;
-    size_t off = 0, in_bytes = 0;
-    size_t align = 256;
-    size_t add_in(const void *host, size_t rows, size_t elem, size_t cols_full, size_t col0, size_t cols)
-    {
-        ins.push_back(Piece{host ? (const char *)host + col0 * elem : nullptr, nullptr, rows, cols * elem, cols_full * elem, off});
-        const size_t o = off;
-        off += (rows * cols * elem + align - 1) / align * align;
-        in_bytes = off;
-        return o;
-    }
-    size_t add_out(void *host, size_t rows, size_t elem, size_t cols_full, size_t col0, size_t cols)
-    {
-        // host == NULL: the device copy exists (kernels write it) but nothing is copied back
-        outs.push_back(Piece{nullptr, host ? (char *)host + col0 * elem : nullptr, rows, cols * elem, cols_full * elem, off});
-        const size_t o = off;
-        off += (rows * cols * elem + align - 1) / align * align;
-        return o;
-    }
-    size_t reserve(size_t bytes)       // device-only scratch inside the same arena
-    {
-        off = (off + 255) & ~(size_t)255;
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-    bool inputs_present() const
-    {
-        for (auto &p : ins) if (!p.src) return false;
-        return true;
-    }
-    // (outputs must all have been added before the first reserve() for the staged download to be one copy; the code
-    // below copies [in_bytes, out_end) where out_end is the end of the last output piece)
-    size_t out_end() const { return outs.empty() ? in_bytes : outs.back().off + outs.back().rows * outs.back().width; }
-    // A piece that covers whole rows (a call over all chains of the caller's arrays) is one contiguous range on both sides.
-    static bool dense(const Piece &p) { return p.width == p.pitch || p.rows <= 1; }
-    bool all_dense() const
-    {
-        for (auto &p : ins) if (!dense(p)) return false;
-        for (auto &p : outs) if (p.dst && !dense(p)) return false;
-        return true;
-    }
-    // Through the pinned buffer (ONE copy each way + the host's memcpy per row) or straight between the caller's arrays and
-    // the device?  Measured on the pool's boxes (profiles/pcie_probe): a copy from / to pageable memory runs at 13 GB/s for 1
-    // MiB and 54-56 GB/s from 16 MiB on, the pinned buffer at 37 / 55-57 GB/s, the host's memcpy out of it at 25 GB/s beyond
-    // the caches -- so small calls (the reference's one-chain call: 0.66 MB in 11 arrays) are packed, large dense ones are
-    // not, and strided pieces (a chain block of a multi-device call) are packed while they fit.
-    bool staged() const
-    {
-        const size_t end = out_end();
-        if (end > kStageBytes || in_bytes > kStageBytes) return false;
-        return end <= kStageSmallBytes || !all_dense();
-    }
-    static hipError_t move(char *dev, const Piece &p, bool to_device, hipStream_t st)
-    {
-        if (dense(p))
-            return to_device ? hipMemcpyAsync(dev, p.src, p.rows * p.width, hipMemcpyHostToDevice, st)
-                             : hipMemcpyAsync(p.dst, dev, p.rows * p.width, hipMemcpyDeviceToHost, st);
-        return to_device ? hipMemcpy2DAsync(dev, p.width, p.src, p.pitch, p.width, p.rows, hipMemcpyHostToDevice, st)
-                         : hipMemcpy2DAsync(p.dst, p.pitch, dev, p.width, p.width, p.rows, hipMemcpyDeviceToHost, st);
-    }
-    hipError_t upload(HostCtx *cx, char *base) const
-    {
-        if (staged()) {
-            for (auto &p : ins)
-                for (size_t r = 0; r < p.rows; r++) memcpy(cx->pinned + p.off + r * p.width, p.src + r * p.pitch, p.width);
-            return in_bytes ? hipMemcpyAsync(base, cx->pinned, in_bytes, hipMemcpyHostToDevice, cx->stream) : hipSuccess;
-        }
-        for (auto &p : ins) {
-            const hipError_t e = move(base + p.off, p, true, cx->stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    // enqueues the copies back, waits for the stream, and (staged) scatters the rows into the caller's arrays
-    hipError_t download(HostCtx *cx, const char *base) const
-    {
-        hipError_t e;
-        if (staged()) {
-            const size_t end = out_end();
-            if (end > in_bytes && (e = hipMemcpyAsync(cx->pinned + in_bytes, base + in_bytes, end - in_bytes, hipMemcpyDeviceToHost, cx->stream)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(cx->stream)) != hipSuccess) return e;
-            for (auto &p : outs)
-                if (p.dst)
-                    for (size_t r = 0; r < p.rows; r++) memcpy(p.dst + r * p.pitch, cx->pinned + p.off + r * p.width, p.width);
-            return hipSuccess;
-        }
-        // Large pieces into memory the caller has never touched (a MEX gateway's freshly created outputs, np.empty) would be
-        // faulted in page by page under the copy, by ONE thread inside the driver's pinning call: 14-17 GB/s instead of the
-        // 33-52 GB/s resident pages reach (profiles/r06/host_calls.json).  A helper thread therefore populates the destination
-        // of piece k + 1 on several threads (populate_pages) while piece k is on the wire; the copy of a piece is issued when
-        // its pages are there.  Resident pages cost a page-table walk.
-        std::vector<const Piece *> todo;
-        size_t big = 0;
-        for (auto &p : outs)
-            if (p.dst) { todo.push_back(&p); if (span_bytes(p) >= kPopulateMinBytes) big++; }
-        if (big == 0) {
-            for (const Piece *p : todo)
-                if ((e = move((char *)base + p->off, *p, false, cx->stream)) != hipSuccess) return e;
-            return hipStreamSynchronize(cx->stream);
-        }
-        std::mutex mu;
-        std::condition_variable cv;
-        size_t ready = 0;                      // pieces [0, ready) are populated
-        std::thread helper([&] {
-            for (size_t k = 0; k < todo.size(); k++) {
-                if (span_bytes(*todo[k]) >= kPopulateMinBytes) populate_pages(todo[k]->dst, span_bytes(*todo[k]), dense(*todo[k]));
-                { std::lock_guard<std::mutex> lk(mu); ready = k + 1; }
-                cv.notify_one();
-            }
-        });
-        e = hipSuccess;
-        for (size_t k = 0; k < todo.size() && e == hipSuccess; k++) {
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return ready > k; }); }
-            e = move((char *)base + todo[k]->off, *todo[k], false, cx->stream);
-        }
-        helper.join();
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(cx->stream);
-    }
-    // bytes of the caller's array a piece spans (a strided piece: first row's start to last row's end, gaps included -- they
-    // belong to the same array)
-    static size_t span_bytes(const Piece &p) { return p.rows ? (p.rows - 1) * p.pitch + p.width : 0; }
-    static constexpr size_t kPopulateMinBytes = (size_t)8 << 20;
-    // Make [p, p + bytes) resident and writable WITHOUT changing its contents: madvise(MADV_POPULATE_WRITE) per slice on up to
-    // eight threads (page-table population scales with threads; one thread zeroes fresh pages at ~10 GB/s), falling back to
-    // writing a byte of every page back to itself where the kernel does not know the advice (< 5.14; dense pieces only).
-    static void populate_pages(char *p, size_t bytes, bool whole)
-    {
-        const size_t page = 4096;
-        const uintptr_t a0 = (uintptr_t)p & ~(uintptr_t)(page - 1), a1 = ((uintptr_t)p + bytes + page - 1) & ~(uintptr_t)(page - 1);
-        const size_t pages = (a1 - a0) / page;
-        unsigned hw = std::thread::hardware_concurrency();
-        size_t nt = bytes / ((size_t)16 << 20) + 1;
-        const size_t cap = hw >= 16 ? 12 : (hw >= 4 ? hw / 2 : 1);
-        if (nt > cap) nt = cap;
-        // huge pages where the system grants them on request: 512 times fewer faults, the population is then bound by zeroing
-        if (a1 - a0 >= ((size_t)4 << 20)) (void)madvise((void *)a0, a1 - a0, MADV_HUGEPAGE);
-        auto slice = [=](size_t i) {
-            const uintptr_t b = a0 + pages * i / nt * page, e = a0 + pages * (i + 1) / nt * page;
-            if (e <= b) return;
-#ifdef MADV_POPULATE_WRITE
-            if (madvise((void *)b, e - b, MADV_POPULATE_WRITE) == 0) return;
-#else
-            if (madvise((void *)b, e - b, 23) == 0) return;
-#endif
-            // (a strided piece's gaps are other blocks' columns, which another device's copy may be writing right now: no
-            // write-back there.)  The pages at the two ends may hold bytes outside [p, p + bytes): the byte touched is inside
-            if (!whole) return;
-            for (uintptr_t q = b; q < e; q += page) {
-                uintptr_t t = q < (uintptr_t)p ? (uintptr_t)p : q;
-                if (t >= (uintptr_t)p + bytes) break;
-                volatile char *c = (volatile char *)t;
-                *c = *c;
-            }
-        };
-        std::vector<std::thread> th;
-        for (size_t i = 1; i < nt; i++) th.emplace_back(slice, i);
-        slice(0);
-        for (auto &t : th) t.join();
-    }
-};
-
 // ekf_precheck's rules on HOST arrays ([rows][pitch] doubles, columns [lo, lo + n)): may these chains take the packed
 // kernels?  Ps_init and Ps_final bit-wise symmetric (values and NaN pattern), Q_w diagonal, s_init / Ps_init / diag(Q_w)
 // finite.  The host entry points have the arrays in host memory, so the check costs no device round trip.
@@ -2386,33 +2076,32 @@ static int run_host_block(HostCtx *cx, const epi_batch_desc *d0, const epi_input
     if (d.path_hint == 0 && mi.generic && d.q_mode == 0)
         d.path_hint = host_precheck(m, mi.flipped != 0, in, Bfull, (size_t)lo, (size_t)n) ? 1 : 2;
     // outputs
-    struct O { uint32_t bit; double *host; double **dev; size_t rows; };
+    struct O { uint32_t bit; double *epi_outputs::*arr; size_t rows; };
     const size_t rU = T * d.n_npi, rS = T * m, rP = T * mm, r1 = T;
-    O olist[] = {{EPI_OUT_U_OPT, out->u_opt, &dout.u_opt, rU}, {EPI_OUT_U_OPT_SMOOTH, out->u_opt_smooth, &dout.u_opt_smooth, rU},
-                 {EPI_OUT_S_MINUS, out->S_MINUS, &dout.S_MINUS, rS}, {EPI_OUT_S_PLUS, out->S_PLUS, &dout.S_PLUS, rS},
-                 {EPI_OUT_S_SMOOTH, out->S_SMOOTH, &dout.S_SMOOTH, rS}, {EPI_OUT_P_MINUS, out->P_MINUS, &dout.P_MINUS, rP},
-                 {EPI_OUT_P_PLUS, out->P_PLUS, &dout.P_PLUS, rP}, {EPI_OUT_P_SMOOTH, out->P_SMOOTH, &dout.P_SMOOTH, rP},
-                 {EPI_OUT_K_GAIN, out->K_GAIN, &dout.K_GAIN, rS}, {EPI_OUT_INNOVATIONS, out->innovations, &dout.innovations, r1},
-                 {EPI_OUT_RHO, out->rho, &dout.rho, r1}};
+    const O olist[] = {{EPI_OUT_U_OPT, &epi_outputs::u_opt, rU}, {EPI_OUT_U_OPT_SMOOTH, &epi_outputs::u_opt_smooth, rU},
+                       {EPI_OUT_S_MINUS, &epi_outputs::S_MINUS, rS}, {EPI_OUT_S_PLUS, &epi_outputs::S_PLUS, rS},
+                       {EPI_OUT_S_SMOOTH, &epi_outputs::S_SMOOTH, rS}, {EPI_OUT_P_MINUS, &epi_outputs::P_MINUS, rP},
+                       {EPI_OUT_P_PLUS, &epi_outputs::P_PLUS, rP}, {EPI_OUT_P_SMOOTH, &epi_outputs::P_SMOOTH, rP},
+                       {EPI_OUT_K_GAIN, &epi_outputs::K_GAIN, rS}, {EPI_OUT_INNOVATIONS, &epi_outputs::innovations, r1},
+                       {EPI_OUT_RHO, &epi_outputs::rho, r1}};
     std::vector<size_t> o_out;
     for (auto &o : olist)
-        o_out.push_back(((d.out_mask & o.bit) && o.host) ? io.add_out(o.host, o.rows, 8, Bfull, lo, n) : (size_t)-1);
-    const size_t o_rank = out->pinv_rank ? io.add_out(out->pinv_rank, T, 4, Bfull, lo, n) : (size_t)-1;
+        o_out.push_back(((d.out_mask & o.bit) && out->*o.arr) ? io.add_out(out->*o.arr, o.rows, 8, Bfull, lo, n) : HostIO::kAbsent);
+    const size_t o_rank = out->pinv_rank ? io.add_out(out->pinv_rank, T, 4, Bfull, lo, n) : HostIO::kAbsent;
     // does this call run the smoother (which is where an overflowed chain is recognised)?
     const uint32_t smooth_bits = EPI_OUT_S_SMOOTH | EPI_OUT_P_SMOOTH | (mi.generic ? (uint32_t)EPI_OUT_U_OPT_SMOOTH : 0u);
     bool smooths = out->pinv_rank != nullptr || out->status != nullptr;
-    for (auto &o : olist) smooths = smooths || ((d.out_mask & o.bit & smooth_bits) && o.host);
+    for (auto &o : olist) smooths = smooths || ((d.out_mask & o.bit & smooth_bits) && out->*o.arr);
     const bool watch = smooths && mi.generic && d.q_mode == 0 && d.storage == 0 && d.phase == 0;
     std::vector<int32_t> own_status;
     int32_t *hstat = out->status ? out->status + lo : nullptr;
-    size_t o_stat = (size_t)-1;
+    size_t o_stat = HostIO::kAbsent;
     if (out->status) o_stat = io.add_out(out->status, 1, 4, Bfull, lo, n);
     else if (watch) { own_status.assign((size_t)n, 0); hstat = own_status.data(); o_stat = io.add_out(own_status.data(), 1, 4, (size_t)n, 0, n); }
     epi_batch_desc dmax = d;
     dmax.exact_nonfinite = watch ? 1 : -1;           // the workspace is sized for the second pass
     const size_t wsb = epi_ekf_workspace_bytes(&dmax);
     const size_t o_ws = io.reserve(wsb);
-    hipError_t e = hipSuccess;
     // the device-side view of the call for the arena at `base`
     auto bind = [&](char *base) {
         din.x_series = in->x_series ? (const int32_t *)(base + o_xs) : nullptr;
@@ -2425,37 +2114,24 @@ static int run_host_block(HostCtx *cx, const epi_batch_desc *d0, const epi_input
         din.s_final = (const double *)(base + o_sf); din.Ps_final = (const double *)(base + o_pf);
         din.Q = (const double *)(base + o_q);
         size_t k = 0;
-        for (auto &o : olist) { if (o_out[k] != (size_t)-1) *o.dev = (double *)(base + o_out[k]); k++; }
-        if (o_rank != (size_t)-1) dout.pinv_rank = (int32_t *)(base + o_rank);
-        if (o_stat != (size_t)-1) dout.status = (int32_t *)(base + o_stat);
+        for (auto &o : olist) dout.*o.arr = HostIO::at<double>(base, o_out[k++]);
+        dout.pinv_rank = HostIO::at<int32_t>(base, o_rank);
+        dout.status = HostIO::at<int32_t>(base, o_stat);
     };
-    // upload + kernels (place_and_run may call this for several candidate arenas; ev0 / ev1 bracket the kernels).  From the
-    // upload on, copies that read the caller's arrays / the pinned buffer may be in flight: every error return waits for the
-    // stream first, so that neither is touched after the call has returned
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
+    int rc = run_call(cx, io, d0->placement_tries, lo == 0 ? out->placement : nullptr, err, [&](char *base, hipStream_t st) {
         bind(base);
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
-        const int rc = epi_ekf_run_device(&d, &din, &dout, wsb ? base + o_ws : nullptr, wsb, cx->stream, err);
+        return epi_ekf_run_device(&d, &din, &dout, wsb ? base + o_ws : nullptr, wsb, st, err);
+    });
+    if (rc != EPI_OK || !watch) return rc;
+    bool any = false;
+    for (int c = 0; c < n; c++) any = any || (hstat[c] & 1);
+    if (any) {                                        // rare: a covariance overflowed -- the dense second pass, then the outputs again
+        char *base = cx->arena;
+        bind(base);
+        rc = epi_ekf_run_device(&dmax, &din, &dout, wsb ? base + o_ws : nullptr, wsb, cx->stream, err);
         if (rc != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return rc; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
-    };
-    {
-        const int rc = place_and_run(cx, io.off + 256, d0->placement_tries, lo == 0 ? out->placement : nullptr, compute, err);
-        if (rc != EPI_OK) return rc;
-    }
-    char *base = cx->arena;
-    bind(base);
-    if ((e = io.download(cx, base)) != hipSuccess) return hip_fail(err, e, "kernel execution / download");
-    if (watch) {
-        bool any = false;
-        for (int c = 0; c < n; c++) any = any || (hstat[c] & 1);
-        if (any) {                                    // rare: a covariance overflowed -- the dense second pass, then the outputs again
-            const int rc2 = epi_ekf_run_device(&dmax, &din, &dout, wsb ? base + o_ws : nullptr, wsb, cx->stream, err);
-            if (rc2 != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return rc2; }
-            if ((e = io.download(cx, base)) != hipSuccess) return hip_fail(err, e, "kernel execution / download (dense second pass)");
-        }
+        const hipError_t e = io.download(cx, base);
+        if (e != hipSuccess) return hip_fail(err, e, "kernel execution / download (dense second pass)");
     }
     return EPI_OK;
 }
@@ -2526,13 +2202,7 @@ static void workers_release_all()
 // runs job(r) for r = 0 .. n-1 on the workers of devices dev_of(r) and waits for all of them
 static void run_on_devices(int n, const std::function<int(int)> &dev_of, const std::function<void(int)> &job)
 {
-    if (n == 1) {                            // one block: the calling thread does it, and keeps its current device
-        int prev = 0;
-        const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-        job(0);
-        if (have_prev) (void)hipSetDevice(prev);
-        return;
-    }
+    if (n == 1) { job(0); return; }          // one block: the calling thread does it (and keeps its current device: with_ctx)
     std::mutex mu;
     std::condition_variable cv;
     int left = n;
@@ -2552,19 +2222,7 @@ int epi_ekf_run_host(const epi_batch_desc *d, const epi_inputs *in, const epi_ou
 {
     int rc = host_args_ok(d, in, out, err);
     if (rc != EPI_OK) return rc;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    rc = run_host_block(cx, d, in, out, 0, d->B, err);
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_host_block(cx, d, in, out, 0, d->B, err); });
 }
 
 static int multi_devices_ok(int n_devices, const int *device_ids, char *err)
@@ -2590,11 +2248,8 @@ int epi_ekf_run_host_multi(const epi_batch_desc *d, const epi_inputs *in, const 
     run_on_devices(n_devices, dev_of, [&](int r) {
         const int lo = r * per < d->B ? r * per : d->B, n = (lo + per <= d->B ? per : d->B - lo);
         if (n <= 0) return;
-        hipError_t e = hipSuccess;
-        HostCtx *cx = ctx_acquire(dev_of(r), &e);
-        if (!cx || e != hipSuccess) { if (cx) ctx_release(cx); rcs[(size_t)r] = hip_fail(errs[(size_t)r].data(), e, "hipSetDevice / context"); return; }
-        rcs[(size_t)r] = run_host_block(cx, d, in, out, lo, n, errs[(size_t)r].data());
-        ctx_release(cx);
+        char *er = errs[(size_t)r].data();
+        rcs[(size_t)r] = with_ctx(dev_of(r), er, [&](HostCtx *cx) { return run_host_block(cx, d, in, out, lo, n, er); });
     });
     for (int r = 0; r < n_devices; r++)
         if (rcs[(size_t)r] != EPI_OK) { set_err(err, errs[(size_t)r].data()); return rcs[(size_t)r]; }
@@ -2650,74 +2305,61 @@ static int prescribe_block(HostCtx *cx, const epi_prescribe_desc *pd, const epi_
     const size_t o_j0 = io.add_out(out->J0, 1, 8, Bfull, c0, Bd), o_j1 = io.add_out(out->J1, 1, 8, Bfull, c0, Bd);
     const size_t o_of = io.add_out(out->on_front, 1, 4, Bfull, c0, Bd), o_io = io.add_out(out->i_opt, 1, 4, R, r0, Rd);
     const size_t o_uo = io.add_out(out->u_opt, T * n, 8, R, r0, Rd), o_so = io.add_out(out->S_opt, T * 6, 8, R, r0, Rd);
-    struct O { uint32_t bit; double *host; double *epi_outputs::*dev; size_t rows; };
+    struct O { uint32_t bit; double *epi_outputs::*arr; size_t rows; };
     const epi_outputs &ex = out->extras;
-    O olist[] = {{EPI_OUT_U_OPT, ex.u_opt, &epi_outputs::u_opt, T * n}, {EPI_OUT_U_OPT_SMOOTH, ex.u_opt_smooth, &epi_outputs::u_opt_smooth, T * n},
-                 {EPI_OUT_S_MINUS, ex.S_MINUS, &epi_outputs::S_MINUS, T * 6}, {EPI_OUT_S_PLUS, ex.S_PLUS, &epi_outputs::S_PLUS, T * 6},
-                 {EPI_OUT_S_SMOOTH, ex.S_SMOOTH, &epi_outputs::S_SMOOTH, T * 6}, {EPI_OUT_P_MINUS, ex.P_MINUS, &epi_outputs::P_MINUS, T * 36},
-                 {EPI_OUT_P_PLUS, ex.P_PLUS, &epi_outputs::P_PLUS, T * 36}, {EPI_OUT_P_SMOOTH, ex.P_SMOOTH, &epi_outputs::P_SMOOTH, T * 36},
-                 {EPI_OUT_K_GAIN, ex.K_GAIN, &epi_outputs::K_GAIN, T * 6}, {EPI_OUT_INNOVATIONS, ex.innovations, &epi_outputs::innovations, T},
-                 {EPI_OUT_RHO, ex.rho, &epi_outputs::rho, T}};
+    const O olist[] = {{EPI_OUT_U_OPT, &epi_outputs::u_opt, T * n}, {EPI_OUT_U_OPT_SMOOTH, &epi_outputs::u_opt_smooth, T * n},
+                       {EPI_OUT_S_MINUS, &epi_outputs::S_MINUS, T * 6}, {EPI_OUT_S_PLUS, &epi_outputs::S_PLUS, T * 6},
+                       {EPI_OUT_S_SMOOTH, &epi_outputs::S_SMOOTH, T * 6}, {EPI_OUT_P_MINUS, &epi_outputs::P_MINUS, T * 36},
+                       {EPI_OUT_P_PLUS, &epi_outputs::P_PLUS, T * 36}, {EPI_OUT_P_SMOOTH, &epi_outputs::P_SMOOTH, T * 36},
+                       {EPI_OUT_K_GAIN, &epi_outputs::K_GAIN, T * 6}, {EPI_OUT_INNOVATIONS, &epi_outputs::innovations, T},
+                       {EPI_OUT_RHO, &epi_outputs::rho, T}};
     std::vector<size_t> o_ex;
     for (auto &o : olist) {
-        if ((pd->out_mask & o.bit) && !o.host) { set_err(err, "extras: output selected but NULL"); return EPI_ERR_BAD_ARG; }
-        o_ex.push_back((pd->out_mask & o.bit) ? io.add_out(o.host, o.rows, 8, Bfull, c0, Bd) : (size_t)-1);
+        if ((pd->out_mask & o.bit) && !(ex.*o.arr)) { set_err(err, "extras: output selected but NULL"); return EPI_ERR_BAD_ARG; }
+        o_ex.push_back((pd->out_mask & o.bit) ? io.add_out(ex.*o.arr, o.rows, 8, Bfull, c0, Bd) : HostIO::kAbsent);
     }
     // device-only: expanded per-chain rows, the series map, filter outputs that do not leave the device, workspace
     const size_t o_chain = io.reserve(nrows * Bd * 8), o_ser = io.reserve(Bd * 4);
-    const size_t o_uos = (pd->out_mask & EPI_OUT_U_OPT_SMOOTH) ? (size_t)-1 : io.reserve(T * n * Bp * 8);
-    const size_t o_ss = ((pd->out_mask & EPI_OUT_S_SMOOTH) || !out->S_opt) ? (size_t)-1 : io.reserve(T * 6 * Bp * 8);
+    const size_t o_uos = (pd->out_mask & EPI_OUT_U_OPT_SMOOTH) ? HostIO::kAbsent : io.reserve(T * n * Bp * 8);
+    const size_t o_ss = ((pd->out_mask & EPI_OUT_S_SMOOTH) || !out->S_opt) ? HostIO::kAbsent : io.reserve(T * 6 * Bp * 8);
     const size_t wsb = epi_ekf_workspace_bytes(&d);
     const size_t o_ws = io.reserve(wsb);
-    hipError_t e = hipSuccess;
-    // upload + kernels for the arena at `base` (place_and_run may call this for several candidate arenas: every call leaves the
-    // complete results in its arena); ev0 / ev1 bracket the kernels
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-    // (as in run_host_block: after upload() every error return waits for the stream)
-    if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-    if (ev0) (void)hipEventRecord(ev0, cx->stream);
-    double *chain = (double *)(base + o_chain);
-    int32_t *series = (int32_t *)(base + o_ser);
-    hipLaunchKernelGGL(sweep_expand, dim3((unsigned)((Bd + 255) / 256), 8), dim3(256), 0, cx->stream, (int)nrows, Rd, (int)P,
-                       (int)EPI_PRM_EPSILON, (const double *)(base + o_reg), (const double *)(base + o_eps), chain, series);
-    if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "sweep_expand launch"); }
-    epi_inputs din{};
-    din.x_series = series; din.u_series = series;
-    din.x = (const double *)(base + o_x); din.u = (const double *)(base + o_u); din.R_series = (const double *)(base + o_rs);
-    size_t row = 0;
-    auto take = [&](size_t nr) { const double *p = chain + row * Bd; row += nr; return p; };
-    din.prm = take(EPI_PRM_COUNT); din.s_init = take(6); din.Ps_init = take(36); din.s_final = take(6); din.Ps_final = take(36);
-    din.Q = take(36);
-    const double *sp = take(EPI_SIM_PRM_COUNT), *j0p = take(1), *j1p = take(1);
-    epi_outputs dd{};
-    {
+    return run_call(cx, io, pd->placement_tries, r0 == 0 ? out->placement : nullptr, err, [&](char *base, hipStream_t st) -> int {
+        double *chain = (double *)(base + o_chain);
+        int32_t *series = (int32_t *)(base + o_ser);
+        hipLaunchKernelGGL(sweep_expand, dim3((unsigned)((Bd + 255) / 256), 8), dim3(256), 0, st, (int)nrows, Rd, (int)P,
+                           (int)EPI_PRM_EPSILON, (const double *)(base + o_reg), (const double *)(base + o_eps), chain, series);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(err, e, "sweep_expand launch");
+        epi_inputs din{};
+        din.x_series = series; din.u_series = series;
+        din.x = (const double *)(base + o_x); din.u = (const double *)(base + o_u); din.R_series = (const double *)(base + o_rs);
+        size_t row = 0;
+        auto take = [&](size_t nr) { const double *p = chain + row * Bd; row += nr; return p; };
+        din.prm = take(EPI_PRM_COUNT); din.s_init = take(6); din.Ps_init = take(36); din.s_final = take(6); din.Ps_final = take(36);
+        din.Q = take(36);
+        const double *sp = take(EPI_SIM_PRM_COUNT), *j0p = take(1), *j1p = take(1);
+        epi_outputs dd{};
         size_t k = 0;
-        for (auto &o : olist) { if (o_ex[k] != (size_t)-1) dd.*(o.dev) = (double *)(base + o_ex[k]); k++; }
-    }
-    if (!dd.u_opt_smooth) dd.u_opt_smooth = (double *)(base + o_uos);
-    if (!dd.S_SMOOTH && out->S_opt) dd.S_SMOOTH = (double *)(base + o_ss);
-    epi_sweep_desc sd{};
-    sd.abi_version = EPIEKF_ABI_VERSION; sd.R = Rd; sd.P = (int32_t)P; sd.t_hist = pd->t_hist;
-    rc = epi_sweep_run_device(&d, &din, &dd, wsb ? base + o_ws : nullptr, wsb, &sd, sp, j0p, j1p, (double *)(base + o_j0),
-                              (double *)(base + o_j1), (int32_t *)(base + o_of), (int32_t *)(base + o_io), cx->stream, err);
-    if (rc != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return rc; }
-    struct G { double *host; const double *src; size_t off; int rows; };
-    const G gs[] = {{out->u_opt, dd.u_opt_smooth, o_uo, (int)n}, {out->S_opt, dd.S_SMOOTH, o_so, 6}};
-    for (auto &g : gs) {
-        if (!g.host) continue;
-        const size_t cnt = T * (size_t)g.rows * (size_t)Rd;
-        hipLaunchKernelGGL(sweep_gather_opt, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, cx->stream, (int)T, g.rows, Rd, (int)P,
-                           (int)blk, (int)nblk, (const int32_t *)(base + o_io), g.src, (double *)(base + g.off));
-        if ((e = hipGetLastError()) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "sweep_gather_opt launch"); }
-    }
-    if (ev1) (void)hipEventRecord(ev1, cx->stream);
-    return EPI_OK;
-    };
-    rc = place_and_run(cx, io.off + 256, pd->placement_tries, r0 == 0 ? out->placement : nullptr, compute, err);
-    if (rc != EPI_OK) return rc;
-    char *base = cx->arena;
-    if ((e = io.download(cx, base)) != hipSuccess) return hip_fail(err, e, "kernel execution / download");
-    return EPI_OK;
+        for (auto &o : olist) dd.*o.arr = HostIO::at<double>(base, o_ex[k++]);
+        if (!dd.u_opt_smooth) dd.u_opt_smooth = (double *)(base + o_uos);
+        if (!dd.S_SMOOTH && out->S_opt) dd.S_SMOOTH = (double *)(base + o_ss);
+        epi_sweep_desc sd{};
+        sd.abi_version = EPIEKF_ABI_VERSION; sd.R = Rd; sd.P = (int32_t)P; sd.t_hist = pd->t_hist;
+        const int r = epi_sweep_run_device(&d, &din, &dd, wsb ? base + o_ws : nullptr, wsb, &sd, sp, j0p, j1p, (double *)(base + o_j0),
+                                           (double *)(base + o_j1), (int32_t *)(base + o_of), (int32_t *)(base + o_io), st, err);
+        if (r != EPI_OK) return r;
+        struct G { double *host; const double *src; size_t off; int rows; };
+        const G gs[] = {{out->u_opt, dd.u_opt_smooth, o_uo, (int)n}, {out->S_opt, dd.S_SMOOTH, o_so, 6}};
+        for (auto &g : gs) {
+            if (!g.host) continue;
+            const size_t cnt = T * (size_t)g.rows * (size_t)Rd;
+            hipLaunchKernelGGL(sweep_gather_opt, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (int)T, g.rows, Rd, (int)P,
+                               (int)blk, (int)nblk, (const int32_t *)(base + o_io), g.src, (double *)(base + g.off));
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "sweep_gather_opt launch");
+        }
+        return EPI_OK;
+    });
 }
 
 int epi_sweep_prescribe_host(const epi_prescribe_desc *d, const epi_prescribe_inputs *in, const epi_prescribe_outputs *out,
@@ -2738,11 +2380,8 @@ int epi_sweep_prescribe_host(const epi_prescribe_desc *d, const epi_prescribe_in
     run_on_devices(n_devices, dev_of, [&](int r) {
         const int lo = r * per < d->R ? r * per : d->R, n = (lo + per <= d->R ? per : d->R - lo);
         if (n <= 0) return;
-        hipError_t e = hipSuccess;
-        HostCtx *cx = ctx_acquire(dev_of(r), &e);
-        if (!cx || e != hipSuccess) { if (cx) ctx_release(cx); rcs[(size_t)r] = hip_fail(errs[(size_t)r].data(), e, "hipSetDevice / context"); return; }
-        rcs[(size_t)r] = prescribe_block(cx, d, in, out, lo, n, errs[(size_t)r].data());
-        ctx_release(cx);
+        char *er = errs[(size_t)r].data();
+        rcs[(size_t)r] = with_ctx(dev_of(r), er, [&](HostCtx *cx) { return prescribe_block(cx, d, in, out, lo, n, er); });
     });
     for (int r = 0; r < n_devices; r++)
         if (rcs[(size_t)r] != EPI_OK) { set_err(err, errs[(size_t)r].data()); return rcs[(size_t)r]; }
@@ -2878,40 +2517,6 @@ int epi_sir_sim_device(int32_t B, int32_t K, double dt, const double *prm, doubl
 }
 
 // ---- host-pointer variants of the simulators and the cost (what a MEX gateway binds: matlab/epiekf_sim_mex.cpp) ----
-namespace {
-struct HostStage {   // device copies of host arrays for one call; frees everything on destruction
-    std::vector<void *> allocs;
-    std::vector<std::tuple<void *, void *, size_t>> downloads;
-    hipError_t e = hipSuccess;
-    ~HostStage() { for (void *p : allocs) (void)hipFree(p); }
-    void *in(const void *host, size_t bytes)
-    {
-        if (!host || e != hipSuccess) return nullptr;
-        void *p = nullptr;
-        if ((e = hipMalloc(&p, bytes)) != hipSuccess) return nullptr;
-        allocs.push_back(p);
-        e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
-        return p;
-    }
-    void *out(void *host, size_t bytes)
-    {
-        if (!host || e != hipSuccess) return nullptr;
-        void *p = nullptr;
-        if ((e = hipMalloc(&p, bytes)) != hipSuccess) return nullptr;
-        allocs.push_back(p);
-        downloads.emplace_back(host, p, bytes);
-        return p;
-    }
-    int finish(int rc, char *err)
-    {
-        if (rc != EPI_OK) return rc;
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        for (auto &d : downloads)
-            if (e == hipSuccess) e = hipMemcpy(std::get<0>(d), std::get<1>(d), std::get<2>(d), hipMemcpyDeviceToHost);
-        return e == hipSuccess ? EPI_OK : hip_fail(err, e, "host staging");
-    }
-};
-}  // namespace
 
 int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
                          const double *z, double *s, double *i, double *alpha, double *J0, double *J1, int device,
@@ -2919,15 +2524,13 @@ int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const d
 {
     if (!d || d->B < 1 || d->K < 1 || d->Su < 1 || d->n_npi < 1 || !u || !sp) { set_err(err, "bad simulator descriptor"); return EPI_ERR_BAD_ARG; }
     if (d->u_block != 0) { set_err(err, "u_block is a device-side layout"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
     const size_t B = d->B, K = d->K;
-    HostStage h;
+    HostStage h(device);
     const void *dus = h.in(u_series, B * 4), *du = h.in(u, K * d->n_npi * (size_t)d->Su * 8);
     const void *dsp = h.in(sp, (size_t)EPI_SIM_PRM_COUNT * B * 8), *dz = h.in(z, K * 3 * B * 8);
     void *ds = h.out(s, K * B * 8), *di = h.out(i, K * B * 8), *da = h.out(alpha, K * B * 8);
     void *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_sialpha_sim_device(d, (const int32_t *)dus, (const double *)du, (const double *)dsp, (const double *)dz,
                                            (double *)ds, (double *)di, (double *)da, (double *)d0, (double *)d1, nullptr, err), err);
 }
@@ -2936,12 +2539,10 @@ int epi_seirp_sim_host(int32_t B, int32_t K, int32_t par_steps, double dt, int32
                        const double *par, const double *init, const double *sat, double *out, int device, char *err)
 {
     if (B < 1 || K < 1 || par_steps < 1 || !par || !init || !out) { set_err(err, "bad SEIRP arguments"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
-    HostStage h;
+    HostStage h(device);
     const void *dp = h.in(par, (size_t)par_steps * 7 * B * 8), *di = h.in(init, (size_t)5 * B * 8), *ds = h.in(sat, (size_t)6 * B * 8);
     void *dout = h.out(out, (size_t)K * 5 * B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_seirp_sim_device(B, K, par_steps, dt, saturated, integrator, (const double *)dp, (const double *)di,
                                          (const double *)ds, (double *)dout, nullptr, err), err);
 }
@@ -2950,13 +2551,11 @@ int epi_si_controlled_host(int32_t B, int32_t K, int32_t Sa, double dt, const in
                            const double *prm, double *s, double *i, int device, char *err)
 {
     if (B < 1 || K < 1 || Sa < 1) { set_err(err, "bad SI_Controlled arguments"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
-    HostStage h;
+    HostStage h(device);
     const void *das = h.in(alpha_series, (size_t)B * 4), *da = h.in(alpha, (size_t)(K > 1 ? K - 1 : 1) * Sa * 8);
     const void *dp = h.in(prm, (size_t)3 * B * 8);
     void *ds = h.out(s, (size_t)K * B * 8), *di = h.out(i, (size_t)K * B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_si_controlled_device(B, K, Sa, dt, (const int32_t *)das, (const double *)da, (const double *)dp,
                                              (double *)ds, (double *)di, nullptr, err), err);
 }
@@ -2966,14 +2565,12 @@ int epi_npi_cost_host(int32_t B, int32_t T, int32_t n_npi, int32_t Su, int32_t w
                       int device, char *err)
 {
     if (B < 1 || T < 1 || n_npi < 1 || Su < 1) { set_err(err, "bad NPICost arguments"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
-    HostStage h;
+    HostStage h(device);
     const void *dus = h.in(u_series, (size_t)B * 4), *dn = h.in(newcases, (size_t)T * B * 8);
     const void *du = h.in(inputs, (size_t)T * n_npi * Su * 8);
     const void *dw = h.in(weights, (size_t)(weights_per_day ? T : 1) * n_npi * B * 8);
     void *d0 = h.out(J0, (size_t)B * 8), *d1 = h.out(J1, (size_t)B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_npi_cost_device(B, T, n_npi, Su, weights_per_day, (const int32_t *)dus, (const double *)dn,
                                         (const double *)du, (const double *)dw, (double *)d0, (double *)d1, nullptr, err), err);
 }
@@ -2981,12 +2578,10 @@ int epi_npi_cost_host(int32_t B, int32_t T, int32_t n_npi, int32_t Su, int32_t w
 int epi_sir_sim_host(int32_t B, int32_t K, double dt, const double *prm, double *out, int device, char *err)
 {
     if (B < 1 || K < 1) { set_err(err, "bad SIR arguments"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
-    HostStage h;
+    HostStage h(device);
     const void *dp = h.in(prm, (size_t)6 * B * 8);
     void *dout = h.out(out, (size_t)K * 3 * B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_sir_sim_device(B, K, dt, (const double *)dp, (double *)dout, nullptr, err), err);
 }
 
@@ -2994,10 +2589,8 @@ int epi_preprocess_host(const epi_pre_desc *d, const double *cases, const double
                         const double *ip, const epi_pre_outputs *out, int device, char *err)
 {
     if (!d || !out || d->S < 1 || d->T < 1 || d->n_npi < 0 || d->n_npi > EPI_MAX_NPI) { set_err(err, "bad preprocessing descriptor"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
     const size_t TS = (size_t)d->T * d->S * 8;
-    HostStage h;
+    HostStage h(device);
     const void *dc = h.in(cases, TS), *dd = h.in(deaths, TS), *dp = h.in(population, (size_t)d->S * 8);
     const void *dip = h.in(ip, TS * (size_t)d->n_npi);
     epi_pre_outputs dout{};
@@ -3007,9 +2600,8 @@ int epi_preprocess_host(const epi_pre_desc *d, const double *cases, const double
     dout.fatality = (double *)h.out(out->fatality, TS); dout.I0 = (double *)h.out(out->I0, (size_t)d->S * 8);
     dout.ip_filled = (double *)h.out(out->ip_filled, TS * (size_t)d->n_npi);
     const size_t wsb = epi_preprocess_workspace_bytes(d);
-    void *ws = nullptr;
-    if (wsb && h.e == hipSuccess && (h.e = hipMalloc(&ws, wsb)) == hipSuccess) h.allocs.push_back(ws);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    void *ws = wsb ? h.scratch(wsb) : nullptr;
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_preprocess_device(d, (const double *)dc, (const double *)dd, (const double *)dp, (const double *)dip, &dout,
                                           ws, wsb, nullptr, err), err);
 }
@@ -3018,14 +2610,12 @@ int epi_nnls_affine_fit_host(const epi_nnls_desc *d, const double *X, const doub
                              double *min_err, int32_t *iters, int32_t *flag, int device, char *err)
 {
     if (!d || d->S < 1 || d->D < 1 || d->n < 1 || d->n > EPI_MAX_NPI) { set_err(err, "bad NNLS descriptor"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
     const size_t S = d->S;
-    HostStage h;
+    HostStage h(device);
     const void *dX = h.in(X, (size_t)d->D * d->n * S * 8), *dy = h.in(y, (size_t)d->D * S * 8);
     void *da = h.out(a, (size_t)d->n * S * 8), *db = h.out(b, S * 8), *dm = h.out(min_err, S * 8);
     void *di = h.out(iters, S * 4), *df = h.out(flag, S * 4);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_nnls_affine_fit_device(d, (const double *)dX, (const double *)dy, (double *)da, (double *)db, (double *)dm,
                                                (int32_t *)di, (int32_t *)df, nullptr, err), err);
 }
@@ -3036,14 +2626,12 @@ int epi_random_npi_mc_host(const epi_mc_desc *d, const double *sp, const double 
 {
     if (!d || d->R < 1 || d->n_scen < 1 || d->K < 1 || d->n_npi < 1 || d->n_npi > EPI_MAX_NPI ||
         (int64_t)d->R * d->n_scen > (int64_t)1 << 30) { set_err(err, "bad Monte-Carlo scenario descriptor"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
     const size_t R = d->R, B = R * (size_t)d->n_scen, K = d->K;
-    HostStage h;
+    HostStage h(device);
     const void *dsp = h.in(sp, (size_t)EPI_SIM_PRM_COUNT * R * 8), *dum = h.in(u_min, (size_t)d->n_npi * R * 8);
     const void *dz = h.in(z, K * 3 * B * 8), *dj0 = h.in(J0_prefix, R * 8), *dj1 = h.in(J1_prefix, R * 8);
     void *du = h.out(u_out, K * (size_t)d->n_npi * B * 8), *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
-    if (h.e != hipSuccess) return hip_fail(err, h.e, "host staging");
+    if (h.failed()) return h.fail(err);
     return h.finish(epi_random_npi_mc_device(d, (const double *)dsp, (const double *)dum, (const double *)dz, (const double *)dj0,
                                              (const double *)dj1, (double *)du, (double *)d0, (double *)d1, nullptr, err), err);
 }
@@ -3096,40 +2684,19 @@ int epi_rt_expfit_run_host(const epi_rt_desc *d, const int32_t *x_series, const 
     int rc = epi_rt_expfit_validate(d, err);
     if (rc != EPI_OK) return rc;
     if (!x || !rp || !out) { set_err(err, "NULL input array"); return EPI_ERR_BAD_ARG; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
     const size_t B = d->B, T = d->T;
-    std::vector<void *> allocs;
-    auto fail = [&](hipError_t ee, const char *what) { for (void *p : allocs) (void)hipFree(p); return hip_fail(err, ee, what); };
-    auto dev_alloc = [&](size_t bytes, void **p) -> hipError_t {
-        hipError_t ee = hipMalloc(p, bytes);
-        if (ee == hipSuccess) allocs.push_back(*p);
-        return ee;
-    };
-    void *dxs = nullptr, *dx = nullptr, *drp = nullptr;
-    if (x_series) {
-        if ((e = dev_alloc(B * 4, &dxs)) != hipSuccess || (e = hipMemcpy(dxs, x_series, B * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload x_series");
-    }
-    if ((e = dev_alloc(T * d->Sx * 8, &dx)) != hipSuccess || (e = hipMemcpy(dx, x, T * d->Sx * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload x");
-    if ((e = dev_alloc((size_t)EPI_RT_PRM_COUNT * B * 8, &drp)) != hipSuccess || (e = hipMemcpy(drp, rp, (size_t)EPI_RT_PRM_COUNT * B * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload rp");
-    struct O { double *host; double **dev; size_t bytes; bool required; };
-    epi_rt_outputs dout{};
+    HostStage h(device);
+    const void *dxs = h.in(x_series, B * 4), *dx = h.in(x, T * d->Sx * 8), *drp = h.in(rp, (size_t)EPI_RT_PRM_COUNT * B * 8);
+    struct O { double *epi_rt_outputs::*arr; size_t bytes; bool required; };
     const size_t n2 = T * 2 * B * 8, n4 = T * 4 * B * 8, n1 = T * B * 8;
-    O outs[] = {{out->S_MINUS, &dout.S_MINUS, n2, true}, {out->S_PLUS, &dout.S_PLUS, n2, true}, {out->P_MINUS, &dout.P_MINUS, n4, true},
-                {out->P_PLUS, &dout.P_PLUS, n4, true}, {out->K_GAIN, &dout.K_GAIN, n2, false}, {out->S_SMOOTH, &dout.S_SMOOTH, n2, false},
-                {out->P_SMOOTH, &dout.P_SMOOTH, n4, false}, {out->innovations, &dout.innovations, n1, false}, {out->rho, &dout.rho, n1, false}};
-    for (auto &o : outs)
-        if (o.host || o.required) {   // forward quantities the caller does not want still feed the smoother
-            void *p; if ((e = dev_alloc(o.bytes, &p)) != hipSuccess) return fail(e, "hipMalloc output");
-            *o.dev = (double *)p;
-        }
-    rc = epi_rt_expfit_run_device(d, (const int32_t *)dxs, (const double *)dx, (const double *)drp, &dout, nullptr, err);
-    if (rc != EPI_OK) { for (void *p : allocs) (void)hipFree(p); return rc; }
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "kernel execution");
-    for (auto &o : outs)
-        if (o.host && (e = hipMemcpy(o.host, *o.dev, o.bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "download");
-    for (void *p : allocs) (void)hipFree(p);
-    return EPI_OK;
+    const O outs[] = {{&epi_rt_outputs::S_MINUS, n2, true}, {&epi_rt_outputs::S_PLUS, n2, true}, {&epi_rt_outputs::P_MINUS, n4, true},
+                      {&epi_rt_outputs::P_PLUS, n4, true}, {&epi_rt_outputs::K_GAIN, n2, false}, {&epi_rt_outputs::S_SMOOTH, n2, false},
+                      {&epi_rt_outputs::P_SMOOTH, n4, false}, {&epi_rt_outputs::innovations, n1, false}, {&epi_rt_outputs::rho, n1, false}};
+    epi_rt_outputs dout{};
+    for (auto &o : outs)   // forward quantities the caller does not want still feed the smoother: a device buffer, no download
+        dout.*o.arr = (double *)(out->*o.arr ? h.out(out->*o.arr, o.bytes) : (o.required ? h.scratch(o.bytes) : nullptr));
+    if (h.failed()) return h.fail(err);
+    return h.finish(epi_rt_expfit_run_device(d, (const int32_t *)dxs, (const double *)dx, (const double *)drp, &dout, nullptr, err), err);
 }
 
 static int pre_validate(const epi_pre_desc *d, int *W2, int *nfact, char *err)
@@ -3383,54 +2950,35 @@ int epi_lookahead_run_host(const epi_lookahead_desc *d, const epi_lookahead_inpu
     const size_t o_psi = io.add_in(in->Ps_init, 9, 8, R, 0, R), o_sf = io.add_in(in->s_final, 3, 8, R, 0, R);
     const size_t o_psf = io.add_in(in->Ps_final, 9, 8, R, 0, R), o_q = io.add_in(in->Q, 9, 8, R, 0, R);
     const size_t o_tr = io.add_in(in->truth, T, 8, R, 0, R), o_pop = io.add_in(in->population, 1, 8, R, 0, R);
-    double *const *stat_host[6] = {&out->mean_plus, &out->median_plus, &out->std_plus, &out->mean_smooth, &out->median_smooth, &out->std_smooth};
+    using LO = epi_lookahead_outputs;
+    double *LO::*const stats[6] = {&LO::mean_plus, &LO::median_plus, &LO::std_plus, &LO::mean_smooth, &LO::median_smooth, &LO::std_smooth};
     const size_t o_ep = io.add_out(out->est_plus, F * M, 8, R, 0, R), o_es = io.add_out(out->est_smooth, F * M, 8, R, 0, R);
     size_t o_st[6];
-    for (int k = 0; k < 6; k++) o_st[k] = io.add_out(*stat_host[k], M, 8, R, 0, R);
-    const size_t o_sp = out->S_PLUS ? io.add_out(out->S_PLUS, T * 3, 8, B, 0, B) : (size_t)-1;
-    const size_t o_ss = out->S_SMOOTH ? io.add_out(out->S_SMOOTH, T * 3, 8, B, 0, B) : (size_t)-1;
-    const size_t o_status = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : (size_t)-1;
+    for (int k = 0; k < 6; k++) o_st[k] = io.add_out(out->*stats[k], M, 8, R, 0, R);
+    const size_t o_sp = out->S_PLUS ? io.add_out(out->S_PLUS, T * 3, 8, B, 0, B) : HostIO::kAbsent;
+    const size_t o_ss = out->S_SMOOTH ? io.add_out(out->S_SMOOTH, T * 3, 8, B, 0, B) : HostIO::kAbsent;
+    const size_t o_status = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : HostIO::kAbsent;
     const size_t wsb = epi_lookahead_workspace_bytes(d);
     const size_t o_ws = io.reserve(wsb);
     // the inputs are per region: the packed kernels' conditions are checked on the host, once per region
     epi_inputs hin{};
     hin.s_init = in->s_init; hin.Ps_init = in->Ps_init; hin.s_final = in->s_final; hin.Ps_final = in->Ps_final; hin.Q = in->Q;
     const int path_hint = host_precheck(3, false, &hin, R, 0, R) ? 1 : 2;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
-        auto dp = [&](size_t o) { return (const double *)(base + o); };
-        auto op = [&](size_t o) { return o == (size_t)-1 ? nullptr : (double *)(base + o); };
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto dp = [&](size_t o) { return HostIO::at<const double>(base, o); };
         epi_lookahead_inputs din{};
         din.x = dp(o_x); din.u = dp(o_u);
         din.R_series = d->r_mode == 1 ? dp(o_rs) : nullptr; din.R_scalar = d->r_mode == 0 ? dp(o_rs) : nullptr;
         din.prm = dp(o_prm); din.s_init = dp(o_si); din.Ps_init = dp(o_psi); din.s_final = dp(o_sf); din.Ps_final = dp(o_psf);
         din.Q = dp(o_q); din.truth = dp(o_tr); din.population = dp(o_pop);
         epi_lookahead_outputs dout{};
-        dout.est_plus = op(o_ep); dout.est_smooth = op(o_es);
-        dout.mean_plus = op(o_st[0]); dout.median_plus = op(o_st[1]); dout.std_plus = op(o_st[2]);
-        dout.mean_smooth = op(o_st[3]); dout.median_smooth = op(o_st[4]); dout.std_smooth = op(o_st[5]);
-        dout.S_PLUS = op(o_sp); dout.S_SMOOTH = op(o_ss);
-        dout.status = o_status == (size_t)-1 ? nullptr : (int32_t *)(base + o_status);
-        const int r = la_enqueue(d, &din, &dout, base + o_ws, wsb, path_hint, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        dout.est_plus = HostIO::at<double>(base, o_ep); dout.est_smooth = HostIO::at<double>(base, o_es);
+        for (int k = 0; k < 6; k++) dout.*stats[k] = HostIO::at<double>(base, o_st[k]);
+        dout.S_PLUS = HostIO::at<double>(base, o_sp); dout.S_SMOOTH = HostIO::at<double>(base, o_ss);
+        dout.status = HostIO::at<int32_t>(base, o_status);
+        return la_enqueue(d, &din, &dout, base + o_ws, wsb, path_hint, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, d->placement_tries, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, d->placement_tries, nullptr, err, enqueue); });
 }
 
 // ---- the sliding-window growth-rate estimators (Tools/Rt_ExpFitLogLinReg.m, Rt_ExpFitGenRatios.m, Rt_ExpFitNonlinLS.m) ----
@@ -3513,40 +3061,21 @@ int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const e
     const size_t R = (size_t)d->R, T = (size_t)d->L;
     HostIO io;
     const size_t o_x = io.add_in(new_cases, T, 8, R, 0, R);
-    double *const *f64[12] = {&out->llr_Rt, &out->llr_A, &out->llr_Lambda, &out->llr_ExpFit, &out->gr_Rt, &out->gr_Lambda,
-                              &out->gr_RtSmoothed, &out->gr_LambdaSmoothed, &out->nls_Rt, &out->nls_A, &out->nls_Lambda, &out->nls_ExpFit};
-    int32_t *const *i32[2] = {&out->nls_status, &out->nls_iters};
+    using RO = epi_rtwin_outputs;
+    const HostIO::Opt<RO, double> f64[12] = {{&RO::llr_Rt, T}, {&RO::llr_A, T}, {&RO::llr_Lambda, T}, {&RO::llr_ExpFit, T},
+                                             {&RO::gr_Rt, T}, {&RO::gr_Lambda, T}, {&RO::gr_RtSmoothed, T}, {&RO::gr_LambdaSmoothed, T},
+                                             {&RO::nls_Rt, T}, {&RO::nls_A, T}, {&RO::nls_Lambda, T}, {&RO::nls_ExpFit, T}};
+    const HostIO::Opt<RO, int32_t> i32[2] = {{&RO::nls_status, T}, {&RO::nls_iters, T}};
     size_t o_f[12], o_i[2];
-    for (int k = 0; k < 12; k++) o_f[k] = *f64[k] ? io.add_out(*f64[k], T, 8, R, 0, R) : (size_t)-1;
-    for (int k = 0; k < 2; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], T, 4, R, 0, R) : (size_t)-1;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+    io.add_opt(*out, f64, o_f, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
         epi_rtwin_outputs dout{};
-        double **df[12] = {&dout.llr_Rt, &dout.llr_A, &dout.llr_Lambda, &dout.llr_ExpFit, &dout.gr_Rt, &dout.gr_Lambda,
-                           &dout.gr_RtSmoothed, &dout.gr_LambdaSmoothed, &dout.nls_Rt, &dout.nls_A, &dout.nls_Lambda, &dout.nls_ExpFit};
-        int32_t **di[2] = {&dout.nls_status, &dout.nls_iters};
-        for (int k = 0; k < 12; k++) *df[k] = o_f[k] == (size_t)-1 ? nullptr : (double *)(base + o_f[k]);
-        for (int k = 0; k < 2; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
-        const int r = epi_rtwin_run_device(d, (const double *)(base + o_x), &dout, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        HostIO::bind_opt(dout, f64, o_f, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_rtwin_run_device(d, (const double *)(base + o_x), &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 // ---- REGRESSION_TYPE = 'LASSO': lasso(X, y, 'CV', K) per region (TrainPredictPrescribeNPI.m:254-290) ----
@@ -3620,42 +3149,22 @@ int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y
     }
     HostIO io;
     const size_t o_X = io.add_in(X, D * n, 8, R, 0, R), o_y = io.add_in(y, D, 8, R, 0, R);
-    const size_t o_f = d->K >= 2 ? io.add_in(fold, D, 4, R, 0, R) : (size_t)-1;
-    double *const *f64[7] = {&out->a, &out->b, &out->lambda, &out->B, &out->intercept, &out->mse, &out->se};
-    const size_t f64_rows[7] = {n, 1, NL, NL * n, NL, NL, NL};
-    int32_t *const *i32[5] = {&out->df, &out->iters, &out->idx_min_mse, &out->idx_1se, &out->status};
-    const size_t i32_rows[5] = {NL, NL, 1, 1, 1};
+    const size_t o_f = d->K >= 2 ? io.add_in(fold, D, 4, R, 0, R) : HostIO::kAbsent;
+    using LO = epi_lasso_outputs;
+    const HostIO::Opt<LO, double> f64[7] = {{&LO::a, n}, {&LO::b, 1}, {&LO::lambda, NL}, {&LO::B, NL * n}, {&LO::intercept, NL},
+                                            {&LO::mse, NL}, {&LO::se, NL}};
+    const HostIO::Opt<LO, int32_t> i32[5] = {{&LO::df, NL}, {&LO::iters, NL}, {&LO::idx_min_mse, 1}, {&LO::idx_1se, 1}, {&LO::status, 1}};
     size_t o_d[7], o_i[5];
-    for (int k = 0; k < 7; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], f64_rows[k], 8, R, 0, R) : (size_t)-1;
-    for (int k = 0; k < 5; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], i32_rows[k], 4, R, 0, R) : (size_t)-1;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
         epi_lasso_outputs dout{};
-        double **df[7] = {&dout.a, &dout.b, &dout.lambda, &dout.B, &dout.intercept, &dout.mse, &dout.se};
-        int32_t **di[5] = {&dout.df, &dout.iters, &dout.idx_min_mse, &dout.idx_1se, &dout.status};
-        for (int k = 0; k < 7; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
-        for (int k = 0; k < 5; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
-        const int r = epi_lasso_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y),
-                                           o_f == (size_t)-1 ? nullptr : (const int32_t *)(base + o_f), &dout, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_lasso_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), HostIO::at<const int32_t>(base, o_f),
+                                    &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 // ---- REGRESSION_TYPE = 'NONNEGATIVELS-ELEMENT-WISE': a robust bounded affine fit per (NPI, region) (TrainPredictPrescribeNPI.m:279-292) ----
@@ -3725,39 +3234,19 @@ int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double 
     const size_t R = (size_t)d->R, D = (size_t)d->D, n = (size_t)d->n;
     HostIO io;
     const size_t o_X = io.add_in(X, D * n, 8, R, 0, R), o_y = io.add_in(y, D, 8, R, 0, R);
-    double *const *f64[5] = {&out->a, &out->b_item, &out->sigma, &out->weights, &out->b};
-    const size_t f64_rows[5] = {n, n, n, D * n, 1};
-    int32_t *const *i32[2] = {&out->iters, &out->status};
+    using RO = epi_robfit_outputs;
+    const HostIO::Opt<RO, double> f64[5] = {{&RO::a, n}, {&RO::b_item, n}, {&RO::sigma, n}, {&RO::weights, D * n}, {&RO::b, 1}};
+    const HostIO::Opt<RO, int32_t> i32[2] = {{&RO::iters, n}, {&RO::status, n}};
     size_t o_d[5], o_i[2];
-    for (int k = 0; k < 5; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], f64_rows[k], 8, R, 0, R) : (size_t)-1;
-    for (int k = 0; k < 2; k++) o_i[k] = *i32[k] ? io.add_out(*i32[k], n, 4, R, 0, R) : (size_t)-1;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
         epi_robfit_outputs dout{};
-        double **df[5] = {&dout.a, &dout.b_item, &dout.sigma, &dout.weights, &dout.b};
-        int32_t **di[2] = {&dout.iters, &dout.status};
-        for (int k = 0; k < 5; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
-        for (int k = 0; k < 2; k++) *di[k] = o_i[k] == (size_t)-1 ? nullptr : (int32_t *)(base + o_i[k]);
-        const int r = epi_robfit_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), &dout, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_robfit_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 // ---- Monte-Carlo ensemble statistics over the draws of every region (BASELINE config 5) ----
@@ -3819,38 +3308,20 @@ int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *popul
     const size_t R = (size_t)d->R, B = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases);
     HostIO io;
     const size_t o_src = io.add_in(src, T * (size_t)d->rows, d->storage ? 4 : 8, B, 0, B);
-    const size_t o_pop = d->derive_newcases ? io.add_in(population, 1, 8, R, 0, R) : (size_t)-1;
-    double *const *f64[5] = {&out->mean, &out->std, &out->min, &out->max, &out->quantiles};
+    const size_t o_pop = d->derive_newcases ? io.add_in(population, 1, 8, R, 0, R) : HostIO::kAbsent;
+    using EO = epi_ens_outputs;
+    const HostIO::Opt<EO, double> f64[5] = {{&EO::mean, T * ro}, {&EO::std, T * ro}, {&EO::min, T * ro}, {&EO::max, T * ro},
+                                            {&EO::quantiles, T * ro * (size_t)d->n_q}};
     size_t o_d[5];
-    for (int k = 0; k < 5; k++) o_d[k] = *f64[k] ? io.add_out(*f64[k], T * ro * (k == 4 ? (size_t)d->n_q : 1), 8, R, 0, R) : (size_t)-1;
+    io.add_opt(*out, f64, o_d, R);
     const size_t o_cnt = io.add_out(out->count, T * ro, 4, R, 0, R);
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+    auto enqueue = [&](char *base, hipStream_t st) {
         epi_ens_outputs dout{};
-        double **df[5] = {&dout.mean, &dout.std, &dout.min, &dout.max, &dout.quantiles};
-        for (int k = 0; k < 5; k++) *df[k] = o_d[k] == (size_t)-1 ? nullptr : (double *)(base + o_d[k]);
+        HostIO::bind_opt(dout, f64, o_d, base);
         dout.count = (int32_t *)(base + o_cnt);
-        const int r = epi_ens_run_device(d, base + o_src, o_pop == (size_t)-1 ? nullptr : (const double *)(base + o_pop), &dout,
-                                         cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        return epi_ens_run_device(d, base + o_src, HostIO::at<const double>(base, o_pop), &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 // ---- the autoregressive alpha forecaster, R regions x D draws (Tools/PrescribeNPI.m:204-215) ----
@@ -3933,7 +3404,7 @@ int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const e
 {
     int rc = epi_arfc_validate(d, in, out, err);
     if (rc != EPI_OK) return rc;
-    const size_t R = (size_t)d->R, B = R * (size_t)d->D, K = (size_t)d->L + (size_t)d->H, none = (size_t)-1;
+    const size_t R = (size_t)d->R, B = R * (size_t)d->D, K = (size_t)d->L + (size_t)d->H, none = HostIO::kAbsent;
     HostIO io;
     const size_t o_seg = io.add_in(in->seg, (size_t)d->L, 8, R, 0, R);
     const size_t o_beta = io.add_in(in->beta, 1, 8, R, 0, R), o_s0 = io.add_in(in->s0, 1, 8, R, 0, R), o_i0 = io.add_in(in->i0, 1, 8, R, 0, R);
@@ -3946,36 +3417,18 @@ int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const e
     const size_t o_Ao = io.add_out(out->A_out, (size_t)d->p, 8, R, 0, R);          // device copies exist even when not wanted
     const size_t o_nvo = io.add_out(out->noise_var_out, 1, 8, R, 0, R);
     const size_t o_st = io.add_out(out->status, 1, 4, R, 0, R);
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
-        auto dp = [&](size_t o) { return o == none ? nullptr : (const double *)(base + o); };
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto dp = [&](size_t o) { return HostIO::at<const double>(base, o); };
         epi_arfc_inputs din{};
         din.seg = dp(o_seg); din.beta = dp(o_beta); din.s0 = dp(o_s0); din.i0 = dp(o_i0); din.z = dp(o_z); din.drive = dp(o_drv);
-        din.drive_series = o_ser == none ? nullptr : (const int32_t *)(base + o_ser);
+        din.drive_series = HostIO::at<const int32_t>(base, o_ser);
         din.A = dp(o_A); din.noise_var = dp(o_nv);
         epi_arfc_outputs dout{};
         dout.S = (double *)(base + o_S); dout.A_out = (double *)(base + o_Ao); dout.noise_var_out = (double *)(base + o_nvo);
         dout.status = (int32_t *)(base + o_st);
-        const int r = epi_arfc_run_device(d, &din, &dout, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        return epi_arfc_run_device(d, &din, &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 // ---- the forward-backward filter fusion, one item per (chain, day) (Tools/TrainPredictPrescribeNPI.m:464-478) ----
@@ -4028,7 +3481,7 @@ int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const e
 {
     int rc = epi_fuse_validate(d, in, out, err);
     if (rc != EPI_OK) return rc;
-    const size_t B = (size_t)d->B, T = (size_t)d->T, m = (size_t)d->m, none = (size_t)-1;
+    const size_t B = (size_t)d->B, T = (size_t)d->T, m = (size_t)d->m, none = HostIO::kAbsent;
     int gblk, gnblk;
     fuse_geometry(d->B, d->lane_block, &gblk, &gnblk);
     const size_t Bp = (size_t)gnblk * (size_t)gblk, es = d->storage ? 4 : 8;       // a day of a blocked array holds rows * Bp elements
@@ -4040,44 +3493,23 @@ int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const e
     const size_t o_d2 = out->d2 ? io.add_out(out->d2, T, 8, B, 0, B) : none;
     const size_t o_rk = out->rank ? io.add_out(out->rank, T, 4, B, 0, B) : none;
     const size_t o_st = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : none;
-    hipError_t e = hipSuccess;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;       // the calling thread keeps its current device
-    HostCtx *cx = ctx_acquire(device, &e);
-    if (!cx || e != hipSuccess) {
-        if (cx) ctx_release(cx);
-        if (have_prev) (void)hipSetDevice(prev);
-        return hip_fail(err, e, "hipSetDevice / context");
-    }
-    auto compute = [&](char *base, hipEvent_t ev0, hipEvent_t ev1) -> int {
-        if ((e = io.upload(cx, base)) != hipSuccess) { (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "upload"); }
-        if (ev0) (void)hipEventRecord(ev0, cx->stream);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
         // the padding lanes of a blocked output are never written by the kernel: the host entry returns them as zeros, not as
         // arena bytes (include/epiekf.h says so)
+        hipError_t e;
         if (Bp != B) {
-            if (o_s != none && (e = hipMemsetAsync(base + o_s, 0, T * m * Bp * es, cx->stream)) != hipSuccess) {
-                (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "hipMemsetAsync of s_out");
-            }
-            if (o_P != none && (e = hipMemsetAsync(base + o_P, 0, T * m * m * Bp * es, cx->stream)) != hipSuccess) {
-                (void)hipStreamSynchronize(cx->stream); return hip_fail(err, e, "hipMemsetAsync of P_out");
-            }
+            if (o_s != none && (e = hipMemsetAsync(base + o_s, 0, T * m * Bp * es, st)) != hipSuccess) return hip_fail(err, e, "hipMemsetAsync of s_out");
+            if (o_P != none && (e = hipMemsetAsync(base + o_P, 0, T * m * m * Bp * es, st)) != hipSuccess) return hip_fail(err, e, "hipMemsetAsync of P_out");
         }
         epi_fuse_inputs din{};
         din.sf = base + o_sf; din.Pf = base + o_Pf; din.sb = base + o_sb; din.Pb = base + o_Pb;
         epi_fuse_outputs dout{};
-        dout.s_out = o_s == none ? nullptr : base + o_s; dout.P_out = o_P == none ? nullptr : base + o_P;
-        dout.d2 = o_d2 == none ? nullptr : (double *)(base + o_d2);
-        dout.rank = o_rk == none ? nullptr : (int32_t *)(base + o_rk); dout.status = o_st == none ? nullptr : (int32_t *)(base + o_st);
-        const int r = epi_fuse_run_device(d, &din, &dout, cx->stream, err);
-        if (r != EPI_OK) { (void)hipStreamSynchronize(cx->stream); return r; }
-        if (ev1) (void)hipEventRecord(ev1, cx->stream);
-        return EPI_OK;
+        dout.s_out = HostIO::at<char>(base, o_s); dout.P_out = HostIO::at<char>(base, o_P);
+        dout.d2 = HostIO::at<double>(base, o_d2);
+        dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_st);
+        return epi_fuse_run_device(d, &din, &dout, st, err);
     };
-    rc = place_and_run(cx, io.off + 256, 0, nullptr, compute, err);
-    if (rc == EPI_OK && (e = io.download(cx, cx->arena)) != hipSuccess) rc = hip_fail(err, e, "kernel execution / download");
-    ctx_release(cx);
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }
 
 }  // extern "C"

@@ -211,9 +211,9 @@ def lapack_reading_worker(job):
     return out
 
 
-def host_call(w, devices=None, outputs=None, extras=True, shape=0, out=None, timing=None, placement_tries=0, report=None):
-    """Workload `w` through the HOST-pointer C ABI (classic layout, numpy arrays [T][rows][B]): epi_ekf_run_host on device
-    0, or -- devices = list of device ids -- epi_ekf_run_host_multi with one chain block per entry.  Returns dict of arrays.
+def host_call(w, devices=None, outputs=None, extras=True, shape=0, out=None, timing=None, placement_tries=0, report=None, device=0):
+    """Workload `w` through the HOST-pointer C ABI (classic layout, numpy arrays [T][rows][B]): epi_ekf_run_host on `device`,
+    or -- devices = list of device ids -- epi_ekf_run_host_multi with one chain block per entry.  Returns dict of arrays.
     `out`: the dict a previous call returned (its arrays are written again instead of allocating and NaN-filling new ones);
     `timing`: a list that gets the seconds the C call itself took appended; `placement_tries` / `report` (a list that gets
     {"tries", "chosen", "ms"} appended): epi_batch_desc.placement_tries and the epi_placement_report the call fills."""
@@ -255,7 +255,7 @@ def host_call(w, devices=None, outputs=None, extras=True, shape=0, out=None, tim
     err = C.create_string_buffer(256)
     t0 = time.perf_counter()
     if devices is None:
-        rc = _lib.lib().epi_ekf_run_host(C.byref(d), C.byref(ins), C.byref(outs), 0, err)
+        rc = _lib.lib().epi_ekf_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
     else:
         ids = (C.c_int * len(devices))(*devices)
         rc = _lib.lib().epi_ekf_run_host_multi(C.byref(d), C.byref(ins), C.byref(outs), len(devices), ids, err)
