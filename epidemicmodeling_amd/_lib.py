@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "epi_arfc_validate", "epi_arfc_run_device", "epi_arfc_run_host",
     "epi_fuse_validate", "epi_fuse_run_device", "epi_fuse_run_host",
     "epi_robfit_validate", "epi_robfit_run_device", "epi_robfit_run_host",
+    "epi_ratemap_validate", "epi_ratemap_run_device", "epi_ratemap_run_host",
 ]
 
 
@@ -219,6 +220,70 @@ def robfit_out_names(outputs):
     if not names:
         raise ValueError("no output requested")
     return names
+
+
+class RatemapDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "n", "R", "E", "K", "n_lags")] + [("lags", C.c_int32 * 3)] + \
+        [(n, C.c_int32) for n in ("fit", "effect_lag")] + \
+        [(n, C.c_double) for n in ("ridge", "lambda_threshold", "reduction_effect")]
+
+
+RATEMAP_IN_NAMES = ("ip", "y", "new_smoothed", "extra", "lambda_in", "n_train")
+RATEMAP_OUT_NAMES = ("map", "x_mx", "y_filled", "lambda_hat", "new_cases_est", "tracker", "status")
+RATEMAP_OUT_I32 = ("status",)
+RATEMAP_STATUS_BITS = {"leading_nan": 1, "not_pd": 2, "nonfinite": 4}
+
+
+class RatemapInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RATEMAP_IN_NAMES]
+
+
+class RatemapOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RATEMAP_OUT_NAMES]
+
+
+def ratemap_shapes(T, n, R, E, K, n_lags):
+    """shape of every output of epi_ratemap_run_*"""
+    F = n * (1 + n_lags) + E
+    return {"map": (K, F, R), "x_mx": (F, R), "y_filled": (T, R), "lambda_hat": (K, T, R), "new_cases_est": (K, T, R),
+            "tracker": (T, R), "status": (K, R)}
+
+
+def make_ratemap_desc(T, n, R, E, K, lags=(3, 5, 7), fit=1, effect_lag=3, ridge=1e-6, lambda_threshold=0.1,
+                      reduction_effect=0.01) -> RatemapDesc:
+    lags = [int(v) for v in lags]
+    if len(lags) > 3:
+        raise ValueError("at most 3 lags")
+    d = RatemapDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.n, d.R, d.E, d.K, d.n_lags, d.fit, d.effect_lag = int(T), int(n), int(R), int(E), int(K), len(lags), int(fit), int(effect_lag)
+    for i, v in enumerate(lags):
+        d.lags[i] = v
+    d.ridge, d.lambda_threshold, d.reduction_effect = float(ridge), float(lambda_threshold), float(reduction_effect)
+    return d
+
+
+def ratemap_out_names(outputs, fit, have_y):
+    """the validated list of output names (default: all that the call can give)"""
+    if outputs is None:
+        names = [k for k in RATEMAP_OUT_NAMES if (fit or k != "map") and (have_y or k != "y_filled")]
+    else:
+        names = list(outputs)
+    bad = [k for k in names if k not in RATEMAP_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    if not names:
+        raise ValueError("no output requested")
+    return names
+
+
+def ratemap_n_train(n_train, K=None):
+    """n_train as the int32 HOST array the call reads (a list of MATLAB-style train ends 1 .. T)"""
+    import numpy as np
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(n_train)), dtype=np.int32)
+    if a.ndim != 1 or a.size < 1 or (K is not None and a.size != K):
+        raise ValueError("n_train must be a list of K train ends")
+    return a
 
 
 class EnsDesc(C.Structure):
@@ -470,6 +535,13 @@ def lib():
         h.epi_robfit_run_device.argtypes = robfit_args + [C.c_void_p, C.c_char_p]
         h.epi_robfit_run_host.restype = C.c_int
         h.epi_robfit_run_host.argtypes = robfit_args + [C.c_int, C.c_char_p]
+        ratemap_args = [C.POINTER(RatemapDesc), C.POINTER(RatemapInputs), C.POINTER(RatemapOutputs)]
+        h.epi_ratemap_validate.restype = C.c_int
+        h.epi_ratemap_validate.argtypes = ratemap_args + [C.c_char_p]
+        h.epi_ratemap_run_device.restype = C.c_int
+        h.epi_ratemap_run_device.argtypes = ratemap_args + [C.c_void_p, C.c_char_p]
+        h.epi_ratemap_run_host.restype = C.c_int
+        h.epi_ratemap_run_host.argtypes = ratemap_args + [C.c_int, C.c_char_p]
         ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
         h.epi_ens_validate.restype = C.c_int
         h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]

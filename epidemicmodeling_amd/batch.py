@@ -872,6 +872,53 @@ def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter
     return out
 
 
+def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags=(3, 5, 7), ridge=1e-6, lambda_threshold=0.1,
+             reduction_effect=0.01, effect_lag=3, outputs=None, device="cuda:0"):
+    """The NPI-to-growth-rate predictor of testScripts/test04FullFeatureExtMLpipeline.m (:292-404, :418-431, :576-642) for
+    every region and every train end in one device call (epi_ratemap_run_device): the growth rate y [T, R]
+    (NaN / Inf filled forward) regressed on [ip, ip lagged by each of `lags`, extra] (ip [T, n, R] N/A-filled, extra
+    [T, E, R] caller-made columns), every column divided by its max(abs) over all T days, over the days 1 .. n_train[k] with
+    (X'X + ridge I) m = X'y; lambda_hat = [y(1:n_train); X m] clipped to +-lambda_threshold on the test days;
+    new_cases_est = [new_smoothed(1:n_train); new_smoothed(n_train) exp(cumsum(lambda_hat test days))]; tracker: the
+    policy-variation increments per region.  With lambda_in [K, T, R] instead of y nothing is fitted: lambda_in is
+    lambda_hat (LASSO's or the AR model's prediction) and goes through the same clip and rebuild.
+    n_train: a list of K train ends (MATLAB's numTimeStepsTrain, 1 .. T), read on the host.
+    outputs: names out of map [K, F, R], x_mx [F, R], y_filled [T, R], lambda_hat, new_cases_est [K, T, R], tracker [T, R],
+    status [K, R] (int32, a set of _lib.RATEMAP_STATUS_BITS; default: all that apply).  Returns a dict of torch tensors.
+    Enqueued on the current stream without a host synchronisation."""
+    dev = torch.device(device)
+    t = lambda v: None if v is None else (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
+    ip, ns, y, extra, lambda_in = t(ip), t(new_smoothed), t(y), t(extra), t(lambda_in)
+    if ip.dim() != 3 or ns.dim() != 2 or ns.shape != (ip.shape[0], ip.shape[2]):
+        raise ValueError("ip must be [T, n, R] and new_smoothed [T, R]")
+    T, n, R = ip.shape
+    nt = _lib.ratemap_n_train(n_train)
+    K = int(nt.size)
+    fit = lambda_in is None
+    if fit and y is None:
+        raise ValueError("y (to fit) or lambda_in (to skip the fit) is needed")
+    if (y is not None and y.shape != (T, R)) or (extra is not None and (extra.dim() != 3 or extra.shape[0] != T or extra.shape[2] != R)) \
+            or (lambda_in is not None and lambda_in.shape != (K, T, R)):
+        raise ValueError("y must be [T, R], extra [T, E, R] and lambda_in [K, T, R]")
+    E = 0 if extra is None else int(extra.shape[1])
+    names = _lib.ratemap_out_names(outputs, fit, y is not None)
+    d = _lib.make_ratemap_desc(T, n, R, E, K, lags, int(fit), effect_lag, ridge, lambda_threshold, reduction_effect)
+    shapes = _lib.ratemap_shapes(T, n, R, E, K, d.n_lags)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.RATEMAP_OUT_I32 else torch.float64, device=dev)
+           for k in _lib.RATEMAP_OUT_NAMES if k in names}
+    ins = _lib.RatemapInputs()
+    ins.ip, ins.y, ins.new_smoothed, ins.extra, ins.lambda_in = _ptr(ip), _ptr(y), _ptr(ns), _ptr(extra), _ptr(lambda_in)
+    ins.n_train = nt.ctypes.data
+    outs = _lib.RatemapOutputs()
+    for k in _lib.RATEMAP_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_ratemap_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
     """Monte-Carlo ensemble statistics in one device call (epi_ens_run_device): src [T, rows, B] or [T, B]
     (float32 or float64, on the device) is an output array of B = R * D chains in the classic layout, region-major (chain =

@@ -831,6 +831,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "ar_forecast.hpp"
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
+#include "rate_map.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3245,6 +3246,131 @@ int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double 
         HostIO::bind_opt(dout, f64, o_d, base);
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_robfit_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), &dout, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- the NPI-to-growth-rate predictor per (train end, region) (test04FullFeatureExtMLpipeline.m:292-404, :418-431, :576-642) ----
+int epi_ratemap_validate(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->n < 1) { set_err(err, "n must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->E < 0) { set_err(err, "E must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (d->K < 1) { set_err(err, "K must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->n_lags < 0) { set_err(err, "n_lags must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (d->fit != 0 && d->fit != 1) { set_err(err, "fit must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->effect_lag < 0) { set_err(err, "effect_lag must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (!(d->ridge >= 0.0) || d->ridge == (double)INFINITY) { set_err(err, "ridge must be finite and >= 0"); return EPI_ERR_BAD_ARG; }
+    if (!(d->lambda_threshold >= 0.0)) { set_err(err, "lambda_threshold must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (!(fabs(d->reduction_effect) < (double)INFINITY)) { set_err(err, "reduction_effect must be finite"); return EPI_ERR_BAD_ARG; }
+    if (d->n > kRmMaxN) { set_err(err, "n is limited to 24"); return EPI_ERR_UNSUPPORTED; }
+    if (d->n_lags > kRmMaxLags) { set_err(err, "n_lags is limited to 3"); return EPI_ERR_UNSUPPORTED; }
+    if (d->E > kRmMaxE) { set_err(err, "E is limited to 8"); return EPI_ERR_UNSUPPORTED; }
+    const int64_t F = (int64_t)d->n * (1 + d->n_lags) + d->E;
+    if (F > kRmMaxF) { set_err(err, "F = n (1 + n_lags) + E is limited to 96 (the triangle of G is factored in LDS)"); return EPI_ERR_UNSUPPORTED; }
+    for (int l = 0; l < d->n_lags; l++)
+        if (d->lags[l] < 1 || d->lags[l] >= d->T) { set_err(err, "every lag must lie in 1 .. T - 1"); return EPI_ERR_BAD_ARG; }
+    const int64_t lim = (int64_t)1 << 31, T = d->T, R = d->R, K = d->K;
+    if (K * R >= lim) { set_err(err, "K * R must stay below 2^31"); return EPI_ERR_BAD_ARG; }
+    if (T * d->n * R >= lim || T * d->E * R >= lim || K * F * R >= lim || (double)K * (double)T * (double)R >= (double)lim) {
+        set_err(err, "every array's element count must stay below 2^31"); return EPI_ERR_BAD_ARG;
+    }
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->ip || !in->new_smoothed || !in->n_train) { set_err(err, "NULL ip / new_smoothed / n_train"); return EPI_ERR_BAD_ARG; }
+    if (d->E > 0 && !in->extra) { set_err(err, "E > 0 needs extra"); return EPI_ERR_BAD_ARG; }
+    if (d->fit && !in->y) { set_err(err, "fit = 1 needs y"); return EPI_ERR_BAD_ARG; }
+    if (!d->fit && !in->lambda_in) { set_err(err, "fit = 0 needs lambda_in"); return EPI_ERR_BAD_ARG; }
+    if (!out->map && !out->x_mx && !out->y_filled && !out->lambda_hat && !out->new_cases_est && !out->tracker && !out->status) {
+        set_err(err, "every output is NULL"); return EPI_ERR_BAD_ARG;
+    }
+    if (!d->fit && out->map) { set_err(err, "map needs fit = 1"); return EPI_ERR_BAD_ARG; }
+    if (out->y_filled && !in->y) { set_err(err, "y_filled needs y"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->K; k++)
+        if (in->n_train[k] < 1 || in->n_train[k] > d->T) { set_err(err, "every n_train must lie in 1 .. T"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+static hipError_t rm_dispatch(const RmArgs &g, unsigned blocks, hipStream_t st)
+{
+    const int per_lane = ((g.F + 1) * (g.F + 2) / 2 - 1 + kRmThreads - 1) / kRmThreads;    // entries of G and c a lane owns
+    if (!g.fit || per_lane <= 1) return rm_launch_items<1>(g, blocks, st);
+    if (per_lane <= 2) return rm_launch_items<2>(g, blocks, st);
+    if (per_lane <= 5) return rm_launch_items<5>(g, blocks, st);
+    if (per_lane <= 10) return rm_launch_items<10>(g, blocks, st);
+    return rm_launch_items<19>(g, blocks, st);
+}
+
+int epi_ratemap_run_device(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out,
+                           void *stream, char *err)
+{
+    int rc = epi_ratemap_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    RmArgs g{};
+    g.T = d->T; g.n = d->n; g.R = d->R; g.E = d->E; g.n_lags = d->n_lags; g.fit = d->fit; g.effect_lag = d->effect_lag;
+    g.F = d->n * (1 + d->n_lags) + d->E;
+    for (int l = 0; l < d->n_lags; l++) g.lags[l] = d->lags[l];
+    g.ridge = d->ridge; g.thr = d->lambda_threshold; g.red = d->reduction_effect;
+    g.ip = in->ip; g.y = in->y; g.ns = in->new_smoothed; g.extra = in->extra; g.lambda_in = in->lambda_in;
+    g.map = out->map; g.x_mx = out->x_mx; g.y_filled = out->y_filled; g.lambda_hat = out->lambda_hat; g.est = out->new_cases_est;
+    g.tracker = out->tracker; g.status = out->status;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (out->x_mx || out->y_filled || out->tracker) {
+        for (int64_t r0 = 0; r0 < d->R; r0 += kRmLaunchItems) {        // one workgroup per region
+            g.item0 = (long long)r0;
+            const unsigned nr = (unsigned)(d->R - r0 < kRmLaunchItems ? d->R - r0 : kRmLaunchItems);
+            hipLaunchKernelGGL(ratemap_region, dim3(nr), dim3(kRmThreads), 0, st, g);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ratemap_region launch");
+        }
+    }
+    if (out->map || out->lambda_hat || out->new_cases_est || out->status) {
+        for (int k0 = 0; k0 < d->K; k0 += kRmTrainEnds) {              // a launch carries up to 64 train ends by value
+            const int kc = d->K - k0 < kRmTrainEnds ? d->K - k0 : kRmTrainEnds;
+            g.k0 = k0;
+            for (int kk = 0; kk < kc; kk++) g.nt[kk] = in->n_train[k0 + kk];
+            const int64_t items = (int64_t)kc * d->R;
+            for (int64_t i0 = 0; i0 < items; i0 += kRmLaunchItems) {   // one workgroup per item, in slices (rate_map.hpp)
+                g.item0 = (long long)i0;
+                const unsigned ni = (unsigned)(items - i0 < kRmLaunchItems ? items - i0 : kRmLaunchItems);
+                if ((e = rm_dispatch(g, ni, st)) != hipSuccess) return hip_fail(err, e, "ratemap_items launch");
+            }
+        }
+    }
+    return EPI_OK;
+}
+
+int epi_ratemap_run_host(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out,
+                         int device, char *err)
+{
+    int rc = epi_ratemap_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t T = (size_t)d->T, n = (size_t)d->n, R = (size_t)d->R, E = (size_t)d->E, K = (size_t)d->K;
+    const size_t F = n * (size_t)(1 + d->n_lags) + E, none = HostIO::kAbsent;
+    HostIO io;
+    const size_t o_ip = io.add_in(in->ip, T * n, 8, R, 0, R), o_ns = io.add_in(in->new_smoothed, T, 8, R, 0, R);
+    const size_t o_y = in->y ? io.add_in(in->y, T, 8, R, 0, R) : none;
+    const size_t o_ex = d->E > 0 ? io.add_in(in->extra, T * E, 8, R, 0, R) : none;
+    const size_t o_li = d->fit ? none : io.add_in(in->lambda_in, K * T, 8, R, 0, R);
+    using MO = epi_ratemap_outputs;
+    const HostIO::Opt<MO, double> f64[6] = {{&MO::map, K * F}, {&MO::x_mx, F}, {&MO::y_filled, T}, {&MO::lambda_hat, K * T},
+                                            {&MO::new_cases_est, K * T}, {&MO::tracker, T}};
+    const HostIO::Opt<MO, int32_t> i32[1] = {{&MO::status, K}};
+    size_t o_d[6], o_i[1];
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        epi_ratemap_inputs din{};
+        din.ip = (const double *)(base + o_ip); din.new_smoothed = (const double *)(base + o_ns);
+        din.y = HostIO::at<const double>(base, o_y); din.extra = HostIO::at<const double>(base, o_ex);
+        din.lambda_in = HostIO::at<const double>(base, o_li);
+        din.n_train = in->n_train;                                     // host memory in both entry points
+        epi_ratemap_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_ratemap_run_device(d, &din, &dout, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

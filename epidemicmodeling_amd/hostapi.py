@@ -206,6 +206,42 @@ def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter
     return out
 
 
+def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags=(3, 5, 7), ridge=1e-6, lambda_threshold=0.1,
+             reduction_effect=0.01, effect_lag=3, outputs=None, device=0):
+    """epi_ratemap_run_host: the NPI-to-growth-rate predictor of batch.rate_map on NumPy arrays (synchronous).
+    ip [T, n, R], new_smoothed [T, R], y [T, R] or lambda_in [K, T, R], extra [T, E, R].  Returns the dict of batch.rate_map
+    as NumPy arrays."""
+    keep = []
+    ip, ns = np.asarray(ip, dtype=np.float64), np.asarray(new_smoothed, dtype=np.float64)
+    if ip.ndim != 3 or ns.shape != (ip.shape[0], ip.shape[2]):
+        raise ValueError("ip must be [T, n, R] and new_smoothed [T, R]")
+    T, n, R = ip.shape
+    nt = _lib.ratemap_n_train(n_train)
+    K = int(nt.size)
+    fit = lambda_in is None
+    if fit and y is None:
+        raise ValueError("y (to fit) or lambda_in (to skip the fit) is needed")
+    if (y is not None and np.shape(y) != (T, R)) or (extra is not None and (np.ndim(extra) != 3 or np.shape(extra)[0] != T or np.shape(extra)[2] != R)) \
+            or (lambda_in is not None and np.shape(lambda_in) != (K, T, R)):
+        raise ValueError("y must be [T, R], extra [T, E, R] and lambda_in [K, T, R]")
+    E = 0 if extra is None else int(np.shape(extra)[1])
+    names = _lib.ratemap_out_names(outputs, fit, y is not None)
+    d = _lib.make_ratemap_desc(T, n, R, E, K, lags, int(fit), effect_lag, ridge, lambda_threshold, reduction_effect)
+    shapes = _lib.ratemap_shapes(T, n, R, E, K, d.n_lags)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.RATEMAP_OUT_I32 else np.float64)
+           for k in _lib.RATEMAP_OUT_NAMES if k in names}
+    ins = _lib.RatemapInputs()
+    ins.ip, ins.y, ins.new_smoothed, ins.extra, ins.lambda_in = _f(ip, keep), _f(y, keep), _f(ns, keep), _f(extra, keep), _f(lambda_in, keep)
+    ins.n_train = nt.ctypes.data
+    outs = _lib.RatemapOutputs()
+    for k in _lib.RATEMAP_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_ratemap_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
     """epi_ens_run_host: the Monte-Carlo ensemble statistics of batch.ensemble_summary on NumPy arrays (synchronous).
     src [T, rows, B] or [T, B], float32 or float64 (anything else is converted to float64), B = R * D region-major.

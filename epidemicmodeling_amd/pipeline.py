@@ -305,6 +305,51 @@ def growth_rates(cases, population, wlen=7, generation_period=3, causal=1, forec
     return out
 
 
+GROWTH_TARGETS = ("llr_Lambda", "gr_Lambda", "gr_LambdaSmoothed", "nls_Lambda")
+
+
+def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lags=(3, 5, 7), target="llr_Lambda", extra=None,
+                    ridge=1e-6, lambda_threshold=0.1, reduction_effect=0.01, effect_lag=3, wlen=7, generation_period=3, causal=1,
+                    time_unit=1.0, device="cuda:0"):
+    """The phase-I predictor of testScripts/test04FullFeatureExtMLpipeline.m (:160-195 the features, :292-404 the linear map,
+    :418-431 the policy tracker, :576-642 the clip and the rebuild) for ALL regions and every train / test split:
+
+      cumulative cases, plans --batch.preprocess (W = wlen)--> new_smoothed, ip_filled
+      --batch.rt_window--> the growth-rate estimates; `target` picks the regressand (the script: Lambda_LogLinReg, :299)
+      --batch.rate_map--> map, lambda_hat, new_cases_est per (train end, region), tracker per region
+
+    cases [T, S] cumulative counts (NaN = missing), population [S], ip [T, n, S] (NaN = N/A).  Give predict_ahead (days, one
+    number or a list: numTimeStepsTrain = T - predict_ahead, :293) or n_train (train ends 1 .. T).  extra [T, E, S]: further
+    caller-made columns (test05's ones, test01's cumsum columns).
+    Returns a dict: new_smoothed, ip_filled, the rt_window outputs, n_train [K], every batch.rate_map output, and the error of
+    new_cases_est against new_smoothed over the test days: err [K, T, S] (NaN on the training days), mae and rmse [K, S]
+    (NaN for an item without test days or with a failure status)."""
+    if target not in GROWTH_TARGETS:
+        raise ValueError(f"target must be one of {GROWTH_TARGETS}")
+    if (predict_ahead is None) == (n_train is None):
+        raise ValueError("give predict_ahead or n_train, not both")
+    T = np.shape(cases)[0]
+    nt = np.atleast_1d(np.asarray(n_train if predict_ahead is None else T - np.atleast_1d(np.asarray(predict_ahead)))).astype(np.int64)
+    N = np.asarray(population, dtype=np.float64)
+    pre = batch.preprocess(cases, N, ip=ip, W=wlen, min_cases=synth.MIN_CASES, first_num_days=7,
+                           outputs=("new_smoothed", "ip_filled"), device=device)
+    ns, ipf = pre["new_smoothed"], pre["ip_filled"]
+    rw = batch.rt_window(ns, wlen, time_unit, causal, generation_period, ("LogLinReg", "GenRatios", "NonlinLS"), device=device)
+    rm = batch.rate_map(ipf, ns, nt, y=rw[target], extra=extra, lags=lags, ridge=ridge, lambda_threshold=lambda_threshold,
+                        reduction_effect=reduction_effect, effect_lag=effect_lag, device=device)
+    out = {"new_smoothed": ns.cpu().numpy(), "ip_filled": ipf.cpu().numpy(), "n_train": nt.astype(np.int32), "target": target}
+    out.update({k: v.cpu().numpy() for k, v in rw.items()})
+    out.update({k: v.cpu().numpy() for k, v in rm.items()})
+    test = np.arange(T)[None, :, None] >= nt[:, None, None]                  # [K, T, 1]
+    err = np.where(test, out["new_cases_est"] - out["new_smoothed"][None], np.nan)
+    cnt = (T - nt).astype(np.float64)[:, None]
+    with np.errstate(all="ignore"):
+        out["err"] = err
+        out["mae"] = np.where(cnt > 0, np.where(test, np.abs(err), 0.0).sum(axis=1) / cnt, np.nan)
+        out["rmse"] = np.where(cnt > 0, np.sqrt(np.where(test, err * err, 0.0).sum(axis=1) / cnt), np.nan)
+    return out
+
+
 def monte_carlo_eks(w, n_regions, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, storage="f32", outputs=("S_SMOOTH",),
                     device="cuda:0"):
     """BASELINE config 5 end to end: the Monte-Carlo smoother on a region-major workload (chain = region * n_draws + draw,

@@ -796,6 +796,70 @@ int epi_robfit_run_device(const epi_robfit_desc *d, const double *X, const doubl
 int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double *y, const epi_robfit_outputs *out,
                         int device, char *err);
 
+/* ---- The NPI-to-growth-rate predictor of testScripts/test04FullFeatureExtMLpipeline.m (:292-404, :418-431, :576-642; the
+ * same block in test01FitExponential.m:150-178, test03ExpfitVsIPRegression.m:147-196, test05DirectNewCasesLearning.m:160-186),
+ * for every region and every train / test split in ONE call.  One item = (train end k, region r):
+ *   target fill   y(jj) NaN / Inf takes y(jj-1), jj = 2 .. T; a NaN y(1) gives LEADING_NAN (the reference fails on it)
+ *   features      [IP, lagged(lags[0]), .., extra], F = n (1 + n_lags) + E columns; a lagged block is 0 on its first lag days
+ *   normalisation x_mx = max(abs(column)) over ALL T days, NaN ignored, 0 -> 1
+ *   linear map    (X'X + ridge I) m = X'y over the days 1 .. n_train[k], by unblocked lower Cholesky (a pivot <= 0 or
+ *                 non-finite gives NOT_PD; MATLAB's backslash would change its factorisation there, which is not restated)
+ *   prediction    lambda_hat = [y(1:n_train); X(n_train+1:T, :) m], clipped to +-lambda_threshold on the test days only
+ *   rebuild       new_cases_est = [new_smoothed(1:n_train); new_smoothed(n_train) exp(cumsum(lambda_hat(n_train+1:T)))]
+ *   tracker       per region: a rise of the mean plan on day ii subtracts reduction_effect from the days
+ *                 min(ii + effect_lag, T) .. T, a fall adds it
+ * fit = 0 skips the features and the map and takes lambda_in as lambda_hat: LASSO's and the AR model's predictions go
+ * through the same clip and rebuild (:586-598, :635-642).  The operation order is DESIGN.md §4.11; the kernels,
+ * tests/rate_map_ref.c and tests/rate_map_ref.py share it bit for bit.  Arrays are region-fastest.
+ * An item with LEADING_NAN or NOT_PD has that bit alone and NaN map / lambda_hat / new_cases_est; otherwise NONFINITE says
+ * that an element of its map, lambda_hat or new_cases_est is Inf or NaN.
+ * epi_ratemap_run_device takes DEVICE pointers -- except n_train, which is a HOST array like the descriptor: validate reads
+ * it and the launches carry it by value -- and enqueues on `stream` (no host synchronisation, no allocation);
+ * epi_ratemap_run_host takes HOST pointers and runs on a pooled context of `device`. */
+enum {
+    EPI_RATEMAP_LEADING_NAN = 1, /* y(1) is NaN: NaN outputs */
+    EPI_RATEMAP_NOT_PD = 2,      /* a Cholesky pivot <= 0 or non-finite: NaN outputs */
+    EPI_RATEMAP_NONFINITE = 4    /* a non-finite input reached a result, or a result overflowed */
+};
+typedef struct epi_ratemap_desc {
+    int32_t abi_version;
+    int32_t T;                   /* days, >= 1 */
+    int32_t n;                   /* NPIs, 1 .. 24 */
+    int32_t R;                   /* regions, >= 1 */
+    int32_t E;                   /* caller-made extra columns, 0 .. 8 */
+    int32_t K;                   /* train ends, >= 1; K * R < 2^31 */
+    int32_t n_lags;              /* lagged copies of the plans, 0 .. 3; F = n (1 + n_lags) + E <= 96 */
+    int32_t lags[3];             /* 1 <= lag < T (the reference: 3, 5, 7) */
+    int32_t fit;                 /* 1: the linear map; 0: lambda_in is lambda_hat */
+    int32_t effect_lag;          /* >= 0 (the reference: 3) */
+    double ridge;                /* >= 0, finite (1e-6) */
+    double lambda_threshold;     /* >= 0 (0.1) */
+    double reduction_effect;     /* finite (0.01) */
+} epi_ratemap_desc;
+typedef struct epi_ratemap_inputs {
+    const double *ip;            /* [T][n][R], N/A-filled (epi_preprocess's ip_filled) */
+    const double *y;             /* [T][R] the growth rate; needed with fit = 1 or for y_filled */
+    const double *new_smoothed;  /* [T][R] */
+    const double *extra;         /* [T][E][R]; NULL with E = 0 */
+    const double *lambda_in;     /* [K][T][R]; needed with fit = 0 */
+    const int32_t *n_train;      /* [K], HOST memory in both entry points: 1 <= n_train[k] <= T */
+} epi_ratemap_inputs;
+typedef struct epi_ratemap_outputs {    /* each may be NULL, but not all of them */
+    double *map;                        /* [K][F][R] in the normalised columns' units; fit = 1 only */
+    double *x_mx;                       /* [F][R] */
+    double *y_filled;                   /* [T][R] */
+    double *lambda_hat, *new_cases_est; /* [K][T][R] */
+    double *tracker;                    /* [T][R] */
+    int32_t *status;                    /* [K][R] */
+} epi_ratemap_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor, a missing array or an element count of 2^31 or more,
+ * EPI_ERR_UNSUPPORTED for n > 24, n_lags > 3, E > 8 or F > 96 */
+int epi_ratemap_validate(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out, char *err);
+int epi_ratemap_run_device(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out,
+                           void *stream, char *err);
+int epi_ratemap_run_host(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out,
+                         int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

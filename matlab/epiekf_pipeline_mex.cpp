@@ -33,6 +33,16 @@
 //       X  R x n x D (as for 'nnls');  y  R x D;  robust  0 or 1;  lower, upper  the slope's bounds (the reference: 0, Inf);
 //       max_iter  1 .. 100000 (50).  a, b_item, sigma, iters, status  R x n (status: bits 1 non-finite, 2 constant column,
 //       4 slope lost, 8 iteration cap, 16 bound active);  b  R x 1;  weights  R x n x D (only when requested).
+//   [lambda_hat, new_cases_est, map, status, x_mx, y_filled, tracker] = epiekf_pipeline_mex('ratemap', ip, y, new_smoothed, extra,
+//           lambda_in, n_train, lags, ridge, lambda_threshold, reduction_effect, effect_lag)
+//       The NPI-to-growth-rate predictor of testScripts/test04FullFeatureExtMLpipeline.m (:292-404, :418-431, :576-642) for R
+//       regions x K train ends.  ip  R x n x T, N/A-filled;  y ([] with lambda_in)  R x T, the growth rate;
+//       new_smoothed  R x T;  extra ([] = none)  R x E x T caller-made columns;  lambda_in ([] = fit the linear map)  R x T x K:
+//       taken as lambda_hat, clipped and rebuilt;  n_train  K train ends (numTimeStepsTrain, 1 .. T);  lags  0 .. 3 lags
+//       (the reference: [3 5 7]);  ridge (1e-6), lambda_threshold (0.1), reduction_effect (0.01), effect_lag (3).
+//       lambda_hat, new_cases_est  R x T x K;  map  R x F x K, F = n (1 + numel(lags)) + E ([] without a fit);  status  R x K
+//       (bits 1 leading NaN target, 2 not positive definite, 4 non-finite);  x_mx  R x F;  y_filled  R x T ([] without y);
+//       tracker  R x T.
 //   [mean, std, min, max, quantiles, count] = epiekf_pipeline_mex('ens_summary', src, D, q, population)
 //       Monte-Carlo ensemble statistics (BASELINE config 5).  src  B x rows x T (or B x T), B = R * D chains,
 //       region-major (chain = (r-1) * D + d): a filter output such as S_SMOOTH;  D  draws per region;  q  1 .. 16
@@ -261,6 +271,67 @@ static void robustfit(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void ratemap(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 12)
+        mexErrMsgTxt("epiekf_pipeline_mex('ratemap', ip, y, new_smoothed, extra, lambda_in, n_train, lags, ridge, lambda_threshold, "
+                     "reduction_effect, effect_lag): 12 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    const mwSize *dx = mxGetDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1])) mexErrMsgTxt("ip must be R x n x T");
+    const mwSize R = dx[0], n = dx[1], T = nd == 3 ? dx[2] : 1;
+    const bool fit = mxIsEmpty(prhs[5]), have_y = !mxIsEmpty(prhs[2]);
+    if (have_y) want(prhs[2], R, T, "y");
+    want(prhs[3], R, T, "new_smoothed");
+    const mwSize K = mxGetNumberOfElements(prhs[6]), NL = mxGetNumberOfElements(prhs[7]);
+    if (K < 1) mexErrMsgTxt("n_train must hold at least one train end");
+    if (NL > 3) mexErrMsgTxt("lags holds at most 3 lags");
+    mwSize E = 0;
+    if (!mxIsEmpty(prhs[4])) {
+        const mwSize ne = mxGetNumberOfDimensions(prhs[4]);
+        const mwSize *de = mxGetDimensions(prhs[4]);
+        if (ne > 3 || de[0] != R || (ne == 3 ? de[2] : 1) != T) mexErrMsgTxt("extra must be R x E x T");
+        E = de[1];
+    }
+    if (!fit) {
+        const mwSize nl = mxGetNumberOfDimensions(prhs[5]);
+        const mwSize *dl = mxGetDimensions(prhs[5]);
+        if (nl > 3 || dl[0] != R || dl[1] != T || (nl == 3 ? dl[2] : 1) != K) mexErrMsgTxt("lambda_in must be R x T x K");
+    }
+    epi_ratemap_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.n = (int32_t)n; d.R = (int32_t)R; d.E = (int32_t)E; d.K = (int32_t)K;
+    d.n_lags = (int32_t)NL; d.fit = fit ? 1 : 0;
+    for (mwSize l = 0; l < NL; l++) d.lags[l] = (int32_t)mxGetPr(prhs[7])[l];
+    d.ridge = mxGetScalar(prhs[8]); d.lambda_threshold = mxGetScalar(prhs[9]); d.reduction_effect = mxGetScalar(prhs[10]);
+    d.effect_lag = (int32_t)mxGetScalar(prhs[11]);
+    std::vector<int32_t> nt((size_t)K), stv((size_t)(R * K));
+    for (mwSize k = 0; k < K; k++) nt[k] = (int32_t)mxGetPr(prhs[6])[k];
+    const mwSize F = n * (1 + NL) + E;
+    mxArray *lh = dbl3(R, T, K), *es = dbl3(R, T, K), *mp = fit ? dbl3(R, F, K) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxArray *st = mxCreateDoubleMatrix(R, K, mxREAL), *xm = mxCreateDoubleMatrix(R, F, mxREAL);
+    mxArray *yf = have_y ? mxCreateDoubleMatrix(R, T, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL), *tr = mxCreateDoubleMatrix(R, T, mxREAL);
+    mxArray *o[7] = {lh, es, mp, st, xm, yf, tr};
+    epi_ratemap_inputs in;
+    memset(&in, 0, sizeof in);
+    in.ip = mxGetPr(prhs[1]); in.y = opt(prhs[2]); in.new_smoothed = mxGetPr(prhs[3]); in.extra = opt(prhs[4]); in.lambda_in = opt(prhs[5]);
+    in.n_train = nt.data();
+    epi_ratemap_outputs out;
+    memset(&out, 0, sizeof out);
+    out.lambda_hat = mxGetPr(lh); out.new_cases_est = mxGetPr(es); out.status = stv.data();
+    if (fit) out.map = mxGetPr(mp);
+    if (nlhs >= 5) out.x_mx = mxGetPr(xm);
+    if (nlhs >= 6 && have_y) out.y_filled = mxGetPr(yf);
+    if (nlhs >= 7) out.tracker = mxGetPr(tr);
+    // the ABI's [K][T][R], [K][F][R], [F][R] and [T][R] are MATLAB's R x T x K, R x F x K, R x F and R x T: no transposition
+    char err[256] = {0};
+    const int rc = epi_ratemap_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < stv.size(); k++) mxGetPr(st)[k] = (double)stv[k];
+    for (int k = 0; k < 7; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('ens_summary', src, D, q, population): 5 inputs expected");
@@ -437,6 +508,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "nnls") == 0) nnls(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "robustfit") == 0) robustfit(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "ratemap") == 0) ratemap(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
