@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "epi_fuse_validate", "epi_fuse_run_device", "epi_fuse_run_host",
     "epi_robfit_validate", "epi_robfit_run_device", "epi_robfit_run_host",
     "epi_ratemap_validate", "epi_ratemap_run_device", "epi_ratemap_run_host",
+    "epi_mldiv_validate", "epi_mldiv_run_device", "epi_mldiv_run_host",
 ]
 
 
@@ -283,6 +284,58 @@ def ratemap_n_train(n_train, K=None):
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(n_train)), dtype=np.int32)
     if a.ndim != 1 or a.size < 1 or (K is not None and a.size != K):
         raise ValueError("n_train must be a list of K train ends")
+    return a
+
+
+class MldivDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "D", "F", "R", "K")] + [("tol_scale", C.c_double)]
+
+
+MLDIV_IN_NAMES = ("X", "y", "n_rows")
+MLDIV_OUT_NAMES = ("m", "rank", "perm", "rdiag", "resid", "fitted", "status")
+MLDIV_OUT_I32 = ("rank", "perm", "status")
+MLDIV_STATUS_BITS = {"rank_deficient": 1, "nonfinite_input": 2, "nonfinite": 4}
+MLDIV_MAX_F, MLDIV_MAX_ELEMS = 96, 20000
+
+
+class MldivInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MLDIV_IN_NAMES]
+
+
+class MldivOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MLDIV_OUT_NAMES]
+
+
+def mldiv_shapes(D, F, R, K):
+    """shape of every output of epi_mldiv_run_*"""
+    return {"m": (K, F, R), "rank": (K, R), "perm": (K, F, R), "rdiag": (K, F, R), "resid": (K, R), "fitted": (K, D, R),
+            "status": (K, R)}
+
+
+def make_mldiv_desc(D, F, R, K, tol_scale=1.0) -> MldivDesc:
+    d = MldivDesc()
+    d.abi_version = ABI_VERSION
+    d.D, d.F, d.R, d.K, d.tol_scale = int(D), int(F), int(R), int(K), float(tol_scale)
+    return d
+
+
+def mldiv_out_names(outputs):
+    """the validated list of output names (default: all)"""
+    names = list(MLDIV_OUT_NAMES) if outputs is None else list(outputs)
+    bad = [k for k in names if k not in MLDIV_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    if not names:
+        raise ValueError("no output requested")
+    return names
+
+
+def mldiv_n_rows(n_rows, D):
+    """n_rows as the int32 HOST array the call reads (default: all D rows)"""
+    import numpy as np
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(D if n_rows is None else n_rows)), dtype=np.int32)
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError("n_rows must be a list of K row counts")
     return a
 
 
@@ -542,6 +595,13 @@ def lib():
         h.epi_ratemap_run_device.argtypes = ratemap_args + [C.c_void_p, C.c_char_p]
         h.epi_ratemap_run_host.restype = C.c_int
         h.epi_ratemap_run_host.argtypes = ratemap_args + [C.c_int, C.c_char_p]
+        mldiv_args = [C.POINTER(MldivDesc), C.POINTER(MldivInputs), C.POINTER(MldivOutputs)]
+        h.epi_mldiv_validate.restype = C.c_int
+        h.epi_mldiv_validate.argtypes = mldiv_args + [C.c_char_p]
+        h.epi_mldiv_run_device.restype = C.c_int
+        h.epi_mldiv_run_device.argtypes = mldiv_args + [C.c_void_p, C.c_char_p]
+        h.epi_mldiv_run_host.restype = C.c_int
+        h.epi_mldiv_run_host.argtypes = mldiv_args + [C.c_int, C.c_char_p]
         ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
         h.epi_ens_validate.restype = C.c_int
         h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]

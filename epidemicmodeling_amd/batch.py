@@ -919,6 +919,41 @@ def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags
     return out
 
 
+def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device="cuda:0"):
+    """MATLAB's rectangular backslash m = X(1:n_rows, :) \\ y(1:n_rows) of test01FitExponential.m:159, test03 :169 and test05
+    :185 for every region and every row count in one device call (epi_mldiv_run_device): Householder QR
+    with column pivoting on X [D, F, R] itself (F <= 96, max(n_rows) (F + 1) <= 20000), the rank by
+    |R(j,j)| > tol_scale max(n_rows, F) eps |R(1,1)| (tol_scale = 1 is the rule of MATLAB's lscov.m), the basic solution;
+    fitted = X m over all D rows, so the rows beyond n_rows are the prediction.  y [D, R].
+    n_rows: a list of K row counts 1 .. D, read on the host (default: [D]).
+    outputs: names out of m [K, F, R], rank [K, R], perm [K, F, R] (0-based, pivot order), rdiag [K, F, R], resid [K, R],
+    fitted [K, D, R], status [K, R] (int32, a set of _lib.MLDIV_STATUS_BITS; default: all).  Returns a dict of torch tensors.
+    Enqueued on the current stream without a host synchronisation."""
+    dev = torch.device(device)
+    t = lambda v: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
+    X, y = t(X), t(y)
+    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.mldiv_out_names(outputs)
+    d = _lib.make_mldiv_desc(D, F, R, K, tol_scale)
+    shapes = _lib.mldiv_shapes(D, F, R, K)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.MLDIV_OUT_I32 else torch.float64, device=dev)
+           for k in _lib.MLDIV_OUT_NAMES if k in names}
+    ins = _lib.MldivInputs()
+    ins.X, ins.y, ins.n_rows = _ptr(X), _ptr(y), nr.ctypes.data
+    outs = _lib.MldivOutputs()
+    for k in _lib.MLDIV_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_mldiv_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
     """Monte-Carlo ensemble statistics in one device call (epi_ens_run_device): src [T, rows, B] or [T, B]
     (float32 or float64, on the device) is an output array of B = R * D chains in the classic layout, region-major (chain =

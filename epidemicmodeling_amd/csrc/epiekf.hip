@@ -832,6 +832,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
 #include "rate_map.hpp"
+#include "mldivide.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3371,6 +3372,97 @@ int epi_ratemap_run_host(const epi_ratemap_desc *d, const epi_ratemap_inputs *in
         HostIO::bind_opt(dout, f64, o_d, base);
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_ratemap_run_device(d, &din, &dout, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- MATLAB's rectangular backslash per (row count, region) (test01FitExponential.m:159, test03 :169, test05 :185) ----
+int epi_mldiv_validate(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1) { set_err(err, "D must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->F < 1) { set_err(err, "F must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->K < 1) { set_err(err, "K must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (!(d->tol_scale >= 0.0) || d->tol_scale == (double)INFINITY) { set_err(err, "tol_scale must be finite and >= 0"); return EPI_ERR_BAD_ARG; }
+    if (d->F > kMlMaxF) { set_err(err, "F is limited to 96"); return EPI_ERR_UNSUPPORTED; }
+    const int64_t lim = (int64_t)1 << 31, D = d->D, F = d->F, R = d->R, K = d->K;
+    if (K * R >= lim) { set_err(err, "K * R must stay below 2^31"); return EPI_ERR_BAD_ARG; }
+    if (D * F * R >= lim || K * F * R >= lim || (double)K * (double)D * (double)R >= (double)lim) {
+        set_err(err, "every array's element count must stay below 2^31"); return EPI_ERR_BAD_ARG;
+    }
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->X || !in->y || !in->n_rows) { set_err(err, "NULL X / y / n_rows"); return EPI_ERR_BAD_ARG; }
+    if (!out->m && !out->rank && !out->perm && !out->rdiag && !out->resid && !out->fitted && !out->status) {
+        set_err(err, "every output is NULL"); return EPI_ERR_BAD_ARG;
+    }
+    for (int k = 0; k < d->K; k++)
+        if (in->n_rows[k] < 1 || in->n_rows[k] > d->D) { set_err(err, "every n_rows must lie in 1 .. D"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->K; k++)
+        if ((int64_t)in->n_rows[k] * (F + 1) > kMlMaxElems) {
+            set_err(err, "max(n_rows) * (F + 1) is limited to 20000 (the item's matrix is factored in LDS)"); return EPI_ERR_UNSUPPORTED;
+        }
+    return EPI_OK;
+}
+
+int epi_mldiv_run_device(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out,
+                         void *stream, char *err)
+{
+    int rc = epi_mldiv_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    MlArgs g{};
+    g.D = d->D; g.F = d->F; g.R = d->R; g.tol_scale = d->tol_scale;
+    g.X = in->X; g.y = in->y;
+    g.m = out->m; g.rank = out->rank; g.perm = out->perm; g.rdiag = out->rdiag; g.resid = out->resid; g.fitted = out->fitted;
+    g.status = out->status;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    for (int k0 = 0; k0 < d->K; k0 += kMlRowCounts) {                  // a launch carries up to 64 row counts by value
+        const int kc = d->K - k0 < kMlRowCounts ? d->K - k0 : kMlRowCounts;
+        g.k0 = k0;
+        int nmax = 1;
+        for (int kk = 0; kk < kc; kk++) {
+            g.nr[kk] = in->n_rows[k0 + kk];
+            nmax = g.nr[kk] > nmax ? g.nr[kk] : nmax;
+        }
+        const size_t shm = ml_lds_bytes(nmax, d->F);
+        if (shm > 64u * 1024u &&        // above the default dynamic-LDS limit
+            (e = hipFuncSetAttribute((const void *)mldivide_items, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess)
+            return hip_fail(err, e, "hipFuncSetAttribute");
+        const int64_t items = (int64_t)kc * d->R;
+        for (int64_t i0 = 0; i0 < items; i0 += kMlLaunchItems) {       // one workgroup per item, in slices (mldivide.hpp)
+            g.item0 = (long long)i0;
+            const unsigned ni = (unsigned)(items - i0 < kMlLaunchItems ? items - i0 : kMlLaunchItems);
+            hipLaunchKernelGGL(mldivide_items, dim3(ni), dim3(kMlThreads), shm, st, g);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "mldivide_items launch");
+        }
+    }
+    return EPI_OK;
+}
+
+int epi_mldiv_run_host(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out,
+                       int device, char *err)
+{
+    int rc = epi_mldiv_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t D = (size_t)d->D, F = (size_t)d->F, R = (size_t)d->R, K = (size_t)d->K;
+    HostIO io;
+    const size_t o_X = io.add_in(in->X, D * F, 8, R, 0, R), o_y = io.add_in(in->y, D, 8, R, 0, R);
+    using MO = epi_mldiv_outputs;
+    const HostIO::Opt<MO, double> f64[4] = {{&MO::m, K * F}, {&MO::rdiag, K * F}, {&MO::resid, K}, {&MO::fitted, K * D}};
+    const HostIO::Opt<MO, int32_t> i32[3] = {{&MO::rank, K}, {&MO::perm, K * F}, {&MO::status, K}};
+    size_t o_d[4], o_i[3];
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        epi_mldiv_inputs din{};
+        din.X = (const double *)(base + o_X); din.y = (const double *)(base + o_y);
+        din.n_rows = in->n_rows;                                       // host memory in both entry points
+        epi_mldiv_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_mldiv_run_device(d, &din, &dout, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

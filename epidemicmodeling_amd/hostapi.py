@@ -242,6 +242,32 @@ def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags
     return out
 
 
+def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device=0):
+    """epi_mldiv_run_host: MATLAB's rectangular backslash of batch.mldivide on NumPy arrays (synchronous).
+    X [D, F, R], y [D, R].  Returns the dict of batch.mldivide as NumPy arrays."""
+    keep = []
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 3 or np.shape(y) != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.mldiv_out_names(outputs)
+    d = _lib.make_mldiv_desc(D, F, R, K, tol_scale)
+    shapes = _lib.mldiv_shapes(D, F, R, K)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.MLDIV_OUT_I32 else np.float64)
+           for k in _lib.MLDIV_OUT_NAMES if k in names}
+    ins = _lib.MldivInputs()
+    ins.X, ins.y, ins.n_rows = _f(X, keep), _f(y, keep), nr.ctypes.data
+    outs = _lib.MldivOutputs()
+    for k in _lib.MLDIV_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_mldiv_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
     """epi_ens_run_host: the Monte-Carlo ensemble statistics of batch.ensemble_summary on NumPy arrays (synchronous).
     src [T, rows, B] or [T, B], float32 or float64 (anything else is converted to float64), B = R * D region-major.

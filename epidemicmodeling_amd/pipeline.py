@@ -306,11 +306,26 @@ def growth_rates(cases, population, wlen=7, generation_period=3, causal=1, forec
 
 
 GROWTH_TARGETS = ("llr_Lambda", "gr_Lambda", "gr_LambdaSmoothed", "nls_Lambda")
+GROWTH_SOLVERS = ("ridge", "backslash")
+
+
+def backslash_features(ip_filled, lags, extra=None):
+    """[ip_filled, its copies lagged by each of `lags` (zero on their first lag days), extra] as one device tensor [T, F, S]:
+    rate_map's feature matrix before the normalisation"""
+    T = ip_filled.shape[0]
+    blocks = [ip_filled]
+    for lag in lags:
+        b = torch.zeros_like(ip_filled)
+        b[int(lag):] = ip_filled[:T - int(lag)]
+        blocks.append(b)
+    if extra is not None:
+        blocks.append(extra)
+    return torch.cat(blocks, dim=1).contiguous()
 
 
 def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lags=(3, 5, 7), target="llr_Lambda", extra=None,
                     ridge=1e-6, lambda_threshold=0.1, reduction_effect=0.01, effect_lag=3, wlen=7, generation_period=3, causal=1,
-                    time_unit=1.0, device="cuda:0"):
+                    time_unit=1.0, device="cuda:0", solver="ridge", normalise=False, tol_scale=1.0):
     """The phase-I predictor of testScripts/test04FullFeatureExtMLpipeline.m (:160-195 the features, :292-404 the linear map,
     :418-431 the policy tracker, :576-642 the clip and the rebuild) for ALL regions and every train / test split:
 
@@ -323,9 +338,17 @@ def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lag
     caller-made columns (test05's ones, test01's cumsum columns).
     Returns a dict: new_smoothed, ip_filled, the rt_window outputs, n_train [K], every batch.rate_map output, and the error of
     new_cases_est against new_smoothed over the test days: err [K, T, S] (NaN on the training days), mae and rmse [K, S]
-    (NaN for an item without test days or with a failure status)."""
+    (NaN for an item without test days or with a failure status).
+
+    solver="backslash" is the predictor of test01FitExponential.m:159, test03ExpfitVsIPRegression.m:169 and
+    test05DirectNewCasesLearning.m:185 instead: IPtoRateMap = X(1:train,:) \\ y(1:train) on the raw columns (normalise=True
+    divides every column by rate_map's x_mx first), no ridge, by batch.mldivide (tol_scale: its rank tolerance);
+    lambda_in = [y(1:n_train); X(n_train+1:T,:) m] then goes through batch.rate_map's clip, rebuild and tracker.  The dict
+    gains map [K, F, S] (in the units of the columns used), rank, perm, resid and mldivide_status."""
     if target not in GROWTH_TARGETS:
         raise ValueError(f"target must be one of {GROWTH_TARGETS}")
+    if solver not in GROWTH_SOLVERS:
+        raise ValueError(f"solver must be one of {GROWTH_SOLVERS}")
     if (predict_ahead is None) == (n_train is None):
         raise ValueError("give predict_ahead or n_train, not both")
     T = np.shape(cases)[0]
@@ -335,8 +358,24 @@ def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lag
                            outputs=("new_smoothed", "ip_filled"), device=device)
     ns, ipf = pre["new_smoothed"], pre["ip_filled"]
     rw = batch.rt_window(ns, wlen, time_unit, causal, generation_period, ("LogLinReg", "GenRatios", "NonlinLS"), device=device)
-    rm = batch.rate_map(ipf, ns, nt, y=rw[target], extra=extra, lags=lags, ridge=ridge, lambda_threshold=lambda_threshold,
-                        reduction_effect=reduction_effect, effect_lag=effect_lag, device=device)
+    if solver == "ridge":
+        rm = batch.rate_map(ipf, ns, nt, y=rw[target], extra=extra, lags=lags, ridge=ridge, lambda_threshold=lambda_threshold,
+                            reduction_effect=reduction_effect, effect_lag=effect_lag, device=device)
+    else:
+        if extra is not None:
+            extra = torch.as_tensor(np.ascontiguousarray(extra), dtype=torch.float64).to(ipf.device)
+        rm = batch.rate_map(ipf, ns, nt, y=rw[target], extra=extra, lags=lags, reduction_effect=reduction_effect,
+                            effect_lag=effect_lag, outputs=("x_mx", "y_filled", "tracker"), device=device)
+        X = backslash_features(ipf, lags, extra)
+        if normalise:
+            X = X / rm["x_mx"][None]
+        ml = batch.mldivide(X, rm["y_filled"], n_rows=nt, tol_scale=tol_scale, outputs=("m", "rank", "perm", "resid", "fitted", "status"),
+                            device=device)
+        train = torch.arange(T, device=ipf.device)[None, :, None] < torch.as_tensor(nt, device=ipf.device)[:, None, None]
+        lambda_in = torch.where(train, rm["y_filled"][None], ml["fitted"])
+        rm.update(batch.rate_map(ipf, ns, nt, lambda_in=lambda_in, lambda_threshold=lambda_threshold, outputs=("lambda_hat", "new_cases_est", "status"),
+                                 device=device))
+        rm.update({"map": ml["m"], "rank": ml["rank"], "perm": ml["perm"], "resid": ml["resid"], "mldivide_status": ml["status"]})
     out = {"new_smoothed": ns.cpu().numpy(), "ip_filled": ipf.cpu().numpy(), "n_train": nt.astype(np.int32), "target": target}
     out.update({k: v.cpu().numpy() for k, v in rw.items()})
     out.update({k: v.cpu().numpy() for k, v in rm.items()})

@@ -860,6 +860,59 @@ int epi_ratemap_run_device(const epi_ratemap_desc *d, const epi_ratemap_inputs *
 int epi_ratemap_run_host(const epi_ratemap_desc *d, const epi_ratemap_inputs *in, const epi_ratemap_outputs *out,
                          int device, char *err);
 
+/* ---- MATLAB's rectangular backslash m = X \ y of testScripts/test01FitExponential.m:159, test03ExpfitVsIPRegression.m:169 and
+ * test05DirectNewCasesLearning.m:185 (IPtoRateMap = X(1:train,:) \ y(1:train), the raw columns, no ridge), for every region
+ * and every row count in ONE call.  One item = (row count k, region r) and uses the rows 1 .. n_rows[k] of X [D][F][R], y [D][R]:
+ *   factorisation Householder QR with column pivoting of [X y], unblocked: the pivot is the remaining column of the largest
+ *                 partial norm (ties: the lowest original index), the norms downdated as in LAPACK's dlaqp2 with its
+ *                 recomputation safeguard at sqrt(eps), the reflectors in dlarfg's convention
+ *   rank          the leading j with |R(j,j)| > tol_scale max(n_rows, F) eps |R(1,1)|: the rule MATLAB's lscov.m states; the
+ *                 backslash's own tolerance is not documented, so tol_scale is an input (1 gives lscov's)
+ *   solution      the basic one: m(perm(1:rank)) = R(1:rank,1:rank) \ (Q'y)(1:rank), every other entry +0
+ *   fitted        X m over ALL D rows: the rows beyond n_rows[k] are the prediction
+ * Every sum over rows is 8 interleaved fma chains (row i in chain i mod 8) added in ascending order, whatever the launch.  The
+ * operation order is DESIGN.md §4.12; the kernel, tests/mldivide_ref.c and tests/mldivide_ref.py share it bit for bit.
+ * n_rows < F and n_rows == F run the same route (for a square matrix MATLAB itself goes through LU: not this path).
+ * Arrays are region-fastest.  An item with NONFINITE_INPUT has that bit alone, rank -1, perm 0 .. F-1 and NaN m / rdiag / resid /
+ * fitted; otherwise RANK_DEFICIENT (MATLAB warns there; the outputs are valid) and NONFINITE may both be set.
+ * epi_mldiv_run_device takes DEVICE pointers -- except n_rows, which is a HOST array like the descriptor: validate reads it
+ * and the launches carry it by value -- and enqueues on `stream` (no host synchronisation, no allocation);
+ * epi_mldiv_run_host takes HOST pointers and runs on a pooled context of `device`. */
+enum {
+    EPI_MLDIV_RANK_DEFICIENT = 1,  /* rank < min(n_rows, F) */
+    EPI_MLDIV_NONFINITE_INPUT = 2, /* a NaN or Inf in the used rows of X or y: NaN outputs, rank -1 */
+    EPI_MLDIV_NONFINITE = 4        /* an element of m, rdiag, resid or fitted is Inf or NaN */
+};
+typedef struct epi_mldiv_desc {
+    int32_t abi_version;
+    int32_t D;                   /* rows of X and y, >= 1 */
+    int32_t F;                   /* columns, 1 .. 96 */
+    int32_t R;                   /* regions, >= 1 */
+    int32_t K;                   /* row counts, >= 1; K * R < 2^31 */
+    double tol_scale;            /* finite, >= 0 (1: lscov's rule) */
+} epi_mldiv_desc;
+typedef struct epi_mldiv_inputs {
+    const double *X;             /* [D][F][R] */
+    const double *y;             /* [D][R] */
+    const int32_t *n_rows;       /* [K], HOST memory in both entry points: 1 <= n_rows[k] <= D, max(n_rows) (F + 1) <= 20000 */
+} epi_mldiv_inputs;
+typedef struct epi_mldiv_outputs {      /* each may be NULL, but not all of them */
+    double *m;                          /* [K][F][R] */
+    int32_t *rank;                      /* [K][R] */
+    int32_t *perm;                      /* [K][F][R]: the 0-based original column index in pivot order */
+    double *rdiag;                      /* [K][F][R]: the signed R(j,j), +0 beyond min(n_rows, F) */
+    double *resid;                      /* [K][R]: the 2-norm of (Q'y)(rank+1 : n_rows) */
+    double *fitted;                     /* [K][D][R] */
+    int32_t *status;                    /* [K][R] */
+} epi_mldiv_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor, a missing array, an n_rows outside 1 .. D or an element count of 2^31
+ * or more, EPI_ERR_UNSUPPORTED for F > 96 or max(n_rows) (F + 1) > 20000 (the item's matrix stays in LDS) */
+int epi_mldiv_validate(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out, char *err);
+int epi_mldiv_run_device(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out,
+                         void *stream, char *err);
+int epi_mldiv_run_host(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out,
+                       int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

@@ -43,6 +43,13 @@
 //       lambda_hat, new_cases_est  R x T x K;  map  R x F x K, F = n (1 + numel(lags)) + E ([] without a fit);  status  R x K
 //       (bits 1 leading NaN target, 2 not positive definite, 4 non-finite);  x_mx  R x F;  y_filled  R x T ([] without y);
 //       tracker  R x T.
+//   [m, rank, perm, rdiag, resid, fitted, status] = epiekf_pipeline_mex('mldivide', X, y, n_rows, tol_scale)
+//       MATLAB's rectangular backslash X(1:n_rows(k),:) \ y(1:n_rows(k)) of test01FitExponential.m:159, test03 :169 and test05
+//       :185 for R regions x K row counts: Householder QR with column pivoting, the rank by
+//       abs(R(j,j)) > tol_scale * max(n_rows, F) * eps * abs(R(1,1)) (tol_scale 1: lscov's rule), the basic solution.
+//       X  R x F x D (F <= 96, max(n_rows) * (F + 1) <= 20000);  y  R x D;  n_rows  K row counts 1 .. D ([] = D);  tol_scale (1).
+//       m, rdiag  R x F x K;  perm  R x F x K, 1-based column numbers in pivot order;  rank, resid, status  R x K (status: bits
+//       1 rank deficient, 2 non-finite input, 4 non-finite result);  fitted  R x D x K, X * m over all D rows.
 //   [mean, std, min, max, quantiles, count] = epiekf_pipeline_mex('ens_summary', src, D, q, population)
 //       Monte-Carlo ensemble statistics (BASELINE config 5).  src  B x rows x T (or B x T), B = R * D chains,
 //       region-major (chain = (r-1) * D + d): a filter output such as S_SMOOTH;  D  draws per region;  q  1 .. 16
@@ -332,6 +339,47 @@ static void ratemap(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void mldivide(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('mldivide', X, y, n_rows, tol_scale): 5 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    const mwSize *dx = mxGetDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1])) mexErrMsgTxt("X must be R x F x D");
+    const mwSize R = dx[0], F = dx[1], D = nd == 3 ? dx[2] : 1;
+    want(prhs[2], R, D, "y");
+    const mwSize K = mxIsEmpty(prhs[3]) ? 1 : mxGetNumberOfElements(prhs[3]);
+    epi_mldiv_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.D = (int32_t)D; d.F = (int32_t)F; d.R = (int32_t)R; d.K = (int32_t)K;
+    d.tol_scale = mxIsEmpty(prhs[4]) ? 1.0 : mxGetScalar(prhs[4]);
+    std::vector<int32_t> nr((size_t)K, (int32_t)D), rkv((size_t)(R * K)), stv((size_t)(R * K)), pmv((size_t)(R * F * K));
+    if (!mxIsEmpty(prhs[3]))
+        for (mwSize k = 0; k < K; k++) nr[k] = (int32_t)mxGetPr(prhs[3])[k];
+    mxArray *m = dbl3(R, F, K), *rk = mxCreateDoubleMatrix(R, K, mxREAL), *pm = dbl3(R, F, K), *rd = dbl3(R, F, K);
+    mxArray *rs = mxCreateDoubleMatrix(R, K, mxREAL), *fi = dbl3(R, D, K), *st = mxCreateDoubleMatrix(R, K, mxREAL);
+    mxArray *o[7] = {m, rk, pm, rd, rs, fi, st};
+    epi_mldiv_inputs in;
+    memset(&in, 0, sizeof in);
+    in.X = mxGetPr(prhs[1]); in.y = mxGetPr(prhs[2]); in.n_rows = nr.data();
+    epi_mldiv_outputs out;
+    memset(&out, 0, sizeof out);
+    out.m = mxGetPr(m);
+    if (nlhs >= 2) out.rank = rkv.data();
+    if (nlhs >= 3) out.perm = pmv.data();
+    if (nlhs >= 4) out.rdiag = mxGetPr(rd);
+    if (nlhs >= 5) out.resid = mxGetPr(rs);
+    if (nlhs >= 6) out.fitted = mxGetPr(fi);
+    if (nlhs >= 7) out.status = stv.data();
+    // the ABI's [K][F][R], [K][D][R] and [K][R] are MATLAB's R x F x K, R x D x K and R x K: no transposition
+    char err[256] = {0};
+    const int rc = epi_mldiv_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) mxDestroyArray(a); fail_if(rc, err); }
+    for (size_t k = 0; k < stv.size(); k++) { mxGetPr(rk)[k] = (double)rkv[k]; mxGetPr(st)[k] = (double)stv[k]; }
+    for (size_t k = 0; k < pmv.size(); k++) mxGetPr(pm)[k] = (double)pmv[k] + 1.0;       // MATLAB's column numbers
+    for (int k = 0; k < 7; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('ens_summary', src, D, q, population): 5 inputs expected");
@@ -509,6 +557,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "lasso") == 0) lasso(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "robustfit") == 0) robustfit(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ratemap") == 0) ratemap(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "mldivide") == 0) mldivide(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
