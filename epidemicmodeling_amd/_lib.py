@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "epi_robfit_validate", "epi_robfit_run_device", "epi_robfit_run_host",
     "epi_ratemap_validate", "epi_ratemap_run_device", "epi_ratemap_run_host",
     "epi_mldiv_validate", "epi_mldiv_run_device", "epi_mldiv_run_host",
+    "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
 ]
 
 
@@ -339,6 +340,99 @@ def mldiv_n_rows(n_rows, D):
     return a
 
 
+class SvrDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "D", "F", "R", "K", "kernel", "max_iter")] + [("tol", C.c_double)]
+
+
+SVR_IN_NAMES = ("X", "y", "n_rows", "box", "epsilon", "kernel_scale")
+SVR_OUT_NAMES = ("beta", "bias", "w", "fitted", "n_iter", "gap", "n_sv", "status")
+SVR_OUT_I32 = ("n_iter", "n_sv", "status")
+SVR_STATUS_BITS = {"not_converged": 1, "bad_input": 2, "nonfinite": 4}
+SVR_KERNELS = {"linear": 0, "gaussian": 1}
+SVR_MAX_F, SVR_MAX_ROWS, SVR_MAX_ELEMS, SVR_MAX_ITER = 96, 1024, 20000, 10000000
+
+
+class SvrInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SVR_IN_NAMES]
+
+
+class SvrOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SVR_OUT_NAMES]
+
+
+def svr_shapes(D, F, R, K):
+    """shape of every output of epi_svr_run_*"""
+    return {"beta": (K, D, R), "bias": (K, R), "w": (K, F, R), "fitted": (K, D, R), "n_iter": (K, R), "gap": (K, R),
+            "n_sv": (K, R), "status": (K, R)}
+
+
+def svr_kernel(kernel):
+    if kernel not in SVR_KERNELS:
+        raise ValueError(f"kernel must be one of {tuple(SVR_KERNELS)}")
+    return SVR_KERNELS[kernel]
+
+
+def make_svr_desc(D, F, R, K, kernel="linear", tol=1e-3, max_iter=100000) -> SvrDesc:
+    d = SvrDesc()
+    d.abi_version = ABI_VERSION
+    d.D, d.F, d.R, d.K, d.kernel, d.max_iter, d.tol = int(D), int(F), int(R), int(K), svr_kernel(kernel), int(max_iter), float(tol)
+    return d
+
+
+def svr_out_names(outputs, kernel):
+    """the validated list of output names (default: all, w for the linear kernel only)"""
+    names = [k for k in SVR_OUT_NAMES if k != "w" or kernel == "linear"] if outputs is None else list(outputs)
+    bad = [k for k in names if k not in SVR_OUT_NAMES]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    if not names:
+        raise ValueError("no output requested")
+    return names
+
+
+def svr_defaults(y, kernel="linear"):
+    """fitrsvm's documented defaults for the target(s) y [n] or [n, R] (the rows the fit will use; a NaN gives NaN):
+    Epsilon = iqr(y) / 13.49, and 0.1 where the iqr is zero; BoxConstraint = iqr(y) / 1.349 for the Gaussian kernel, 1
+    otherwise; KernelScale = 1.  iqr is MATLAB's: quantile(y, .75) - quantile(y, .25) with the sorted sample at the
+    probabilities (i - 0.5) / n and linear interpolation between them.  Recalled from MATLAB's
+    documentation, not taken from the reference: a convenience, the three are inputs.
+    Returns a dict box, epsilon, kernel_scale of float64 arrays [R] (scalars for a 1-D y)."""
+    import numpy as np
+    svr_kernel(kernel)
+    a = np.asarray(y, dtype=np.float64)
+    if a.ndim not in (1, 2) or a.shape[0] < 1:
+        raise ValueError("y must be [n] or [n, R]")
+    s = np.sort(a.reshape(a.shape[0], -1), axis=0)
+    n = s.shape[0]
+
+    def quantile(p):
+        pos = p * n - 0.5                                  # 0-based position among the sorted values
+        if pos <= 0:
+            return s[0].copy()
+        if pos >= n - 1:
+            return s[n - 1].copy()
+        lo = int(np.floor(pos))
+        return s[lo] + (pos - lo) * (s[lo + 1] - s[lo])
+
+    iqr = quantile(0.75) - quantile(0.25)
+    iqr = np.where(np.isnan(s).any(axis=0), np.nan, iqr)
+    eps = np.where(iqr == 0.0, 0.1, iqr / 13.49)
+    box = iqr / 1.349 if kernel == "gaussian" else np.ones_like(iqr)
+    out = {"box": box, "epsilon": eps, "kernel_scale": np.ones_like(iqr)}
+    return {k: (float(v[0]) if a.ndim == 1 else v) for k, v in out.items()}
+
+
+def svr_region_array(v, R, name):
+    """box / epsilon / kernel_scale as a float64 array [R]: a scalar is broadcast"""
+    import numpy as np
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(R, float(a))
+    if a.shape != (R,):
+        raise ValueError(f"{name} must be a scalar or an array [R]")
+    return np.ascontiguousarray(a)
+
+
 class EnsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "n_q", "storage", "derive_newcases")] + \
         [("q", C.c_double * 16)]
@@ -602,6 +696,13 @@ def lib():
         h.epi_mldiv_run_device.argtypes = mldiv_args + [C.c_void_p, C.c_char_p]
         h.epi_mldiv_run_host.restype = C.c_int
         h.epi_mldiv_run_host.argtypes = mldiv_args + [C.c_int, C.c_char_p]
+        svr_args = [C.POINTER(SvrDesc), C.POINTER(SvrInputs), C.POINTER(SvrOutputs)]
+        h.epi_svr_validate.restype = C.c_int
+        h.epi_svr_validate.argtypes = svr_args + [C.c_char_p]
+        h.epi_svr_run_device.restype = C.c_int
+        h.epi_svr_run_device.argtypes = svr_args + [C.c_void_p, C.c_char_p]
+        h.epi_svr_run_host.restype = C.c_int
+        h.epi_svr_run_host.argtypes = svr_args + [C.c_int, C.c_char_p]
         ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
         h.epi_ens_validate.restype = C.c_int
         h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]

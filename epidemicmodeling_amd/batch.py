@@ -954,6 +954,51 @@ def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device="cuda:0"):
     return out
 
 
+def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale=None, tol=1e-3, max_iter=100000, outputs=None,
+        device="cuda:0"):
+    """The fitrsvm rows of the reference's predictor block (test05DirectNewCasesLearning.m:198-268, test04 :435-445, test03
+    :242-262): epsilon-insensitive support-vector regression on X(1:n_rows, :), y(1:n_rows) for every region and every row
+    count in one device call (epi_svr_run_device).  X [D, F, R] (F <= 96, n_rows <= 1024,
+    max(n_rows) ((F | 1) + 1) <= 20000), y [D, R].  kernel: "linear" or "gaussian" (exp(-|a - b|^2 / kernel_scale^2)).
+    LIBSVM's sequential minimal optimisation from alpha = 0 until m(alpha) - M(alpha) < tol or max_iter pair steps.
+    n_rows: a list of K row counts 1 .. D, read on the host (default: [D]).
+    box, epsilon, kernel_scale: scalars or arrays [R] (NumPy or torch); None takes _lib.svr_defaults of y(1:max(n_rows)), which
+    copies y to the host -- pass arrays to stay asynchronous.
+    outputs: names out of beta [K, D, R], bias [K, R], w [K, F, R] (linear kernel only), fitted [K, D, R] (over all D rows: the
+    rows beyond n_rows are the prediction), n_iter, gap, n_sv, status [K, R] (status: a set of _lib.SVR_STATUS_BITS; default:
+    all).  Returns a dict of torch tensors.  Enqueued on the current stream without a host synchronisation."""
+    dev = torch.device(device)
+    t = lambda v: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
+    X, y = t(X), t(y)
+    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.svr_out_names(outputs, kernel)
+    d = _lib.make_svr_desc(D, F, R, K, kernel, tol, max_iter)
+    if box is None or epsilon is None or kernel_scale is None:
+        dflt = _lib.svr_defaults(y[:max(1, min(int(nr.max()), D))].cpu().numpy(), kernel)
+        box, epsilon = dflt["box"] if box is None else box, dflt["epsilon"] if epsilon is None else epsilon
+        kernel_scale = dflt["kernel_scale"] if kernel_scale is None else kernel_scale
+    reg = lambda v, name: v.to(dev, torch.float64).contiguous() if isinstance(v, torch.Tensor) and v.shape == (R,) else t(_lib.svr_region_array(v.cpu().numpy() if isinstance(v, torch.Tensor) else v, R, name))
+    box, epsilon, kernel_scale = reg(box, "box"), reg(epsilon, "epsilon"), reg(kernel_scale, "kernel_scale")
+    shapes = _lib.svr_shapes(D, F, R, K)
+    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.SVR_OUT_I32 else torch.float64, device=dev)
+           for k in _lib.SVR_OUT_NAMES if k in names}
+    ins = _lib.SvrInputs()
+    ins.X, ins.y, ins.n_rows = _ptr(X), _ptr(y), nr.ctypes.data
+    ins.box, ins.epsilon, ins.kernel_scale = _ptr(box), _ptr(epsilon), _ptr(kernel_scale)
+    outs = _lib.SvrOutputs()
+    for k in _lib.SVR_OUT_NAMES:
+        setattr(outs, k, _ptr(out.get(k)))
+    err = C.create_string_buffer(256)
+    st = torch.cuda.current_stream(dev)
+    rc = _lib.lib().epi_svr_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
     """Monte-Carlo ensemble statistics in one device call (epi_ens_run_device): src [T, rows, B] or [T, B]
     (float32 or float64, on the device) is an output array of B = R * D chains in the classic layout, region-major (chain =

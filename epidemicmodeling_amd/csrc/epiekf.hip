@@ -833,6 +833,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "robust_fit.hpp"
 #include "rate_map.hpp"
 #include "mldivide.hpp"
+#include "svr.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -2218,6 +2219,27 @@ static void run_on_devices(int n, const std::function<int(int)> &dev_of, const s
     cv.wait(lk, [&] { return left == 0; });
 }
 }   // namespace epi
+// ---- the launches of svr.hpp (epi_svr_run_device) ----
+template <int NR, bool GAU>
+static hipError_t sv_launch_items(const SvArgs &g, unsigned blocks, size_t shm, hipStream_t st)
+{
+    hipError_t e;
+    if (shm > 64u * 1024u &&            // above the default dynamic-LDS limit
+        (e = hipFuncSetAttribute((const void *)svr_items<NR, GAU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL((svr_items<NR, GAU>), dim3(blocks), dim3(kSvThreads), shm, st, g);
+    return hipGetLastError();
+}
+
+// the rows-per-lane instantiation for the launch's largest row count
+template <bool GAU>
+static hipError_t sv_dispatch(const SvArgs &g, int nmax, unsigned blocks, size_t shm, hipStream_t st)
+{
+    if (nmax <= kSvThreads) return sv_launch_items<1, GAU>(g, blocks, shm, st);
+    if (nmax <= 2 * kSvThreads) return sv_launch_items<2, GAU>(g, blocks, shm, st);
+    return sv_launch_items<4, GAU>(g, blocks, shm, st);
+}
+
 extern "C" {
 
 int epi_ekf_run_host(const epi_batch_desc *d, const epi_inputs *in, const epi_outputs *out, int device, char *err)
@@ -3463,6 +3485,105 @@ int epi_mldiv_run_host(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, cons
         HostIO::bind_opt(dout, f64, o_d, base);
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_mldiv_run_device(d, &din, &dout, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- support-vector regression per (row count, region) (test05DirectNewCasesLearning.m:198-268, test04 :435-445, test03 :242-262) ----
+int epi_svr_validate(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1) { set_err(err, "D must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->F < 1) { set_err(err, "F must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->K < 1) { set_err(err, "K must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->kernel != EPI_SVR_LINEAR && d->kernel != EPI_SVR_GAUSSIAN) { set_err(err, "kernel must be EPI_SVR_LINEAR or EPI_SVR_GAUSSIAN"); return EPI_ERR_BAD_ARG; }
+    if (d->max_iter < 1 || d->max_iter > 10000000) { set_err(err, "max_iter must lie in 1 .. 10000000"); return EPI_ERR_BAD_ARG; }
+    if (!(d->tol > 0.0) || d->tol == (double)INFINITY) { set_err(err, "tol must be finite and > 0"); return EPI_ERR_BAD_ARG; }
+    if (d->F > kSvMaxF) { set_err(err, "F is limited to 96"); return EPI_ERR_UNSUPPORTED; }
+    const int64_t lim = (int64_t)1 << 31, D = d->D, F = d->F, R = d->R, K = d->K;
+    if (K * R >= lim) { set_err(err, "K * R must stay below 2^31"); return EPI_ERR_BAD_ARG; }
+    if (D * F * R >= lim || K * F * R >= lim || (double)K * (double)D * (double)R >= (double)lim) {
+        set_err(err, "every array's element count must stay below 2^31"); return EPI_ERR_BAD_ARG;
+    }
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->X || !in->y || !in->n_rows) { set_err(err, "NULL X / y / n_rows"); return EPI_ERR_BAD_ARG; }
+    if (!in->box || !in->epsilon || !in->kernel_scale) { set_err(err, "NULL box / epsilon / kernel_scale"); return EPI_ERR_BAD_ARG; }
+    if (!out->beta && !out->bias && !out->w && !out->fitted && !out->n_iter && !out->gap && !out->n_sv && !out->status) {
+        set_err(err, "every output is NULL"); return EPI_ERR_BAD_ARG;
+    }
+    if (out->w && d->kernel != EPI_SVR_LINEAR) { set_err(err, "w exists for the linear kernel only"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->K; k++)
+        if (in->n_rows[k] < 1 || in->n_rows[k] > d->D) { set_err(err, "every n_rows must lie in 1 .. D"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->K; k++) {
+        if (in->n_rows[k] > kSvMaxRows) { set_err(err, "n_rows is limited to 1024 (four rows a lane)"); return EPI_ERR_UNSUPPORTED; }
+        if ((int64_t)in->n_rows[k] * ((F | 1) + 1) > kSvMaxElems) {
+            set_err(err, "max(n_rows) * ((F | 1) + 1) is limited to 20000 (the item's rows stay in LDS)"); return EPI_ERR_UNSUPPORTED;
+        }
+    }
+    return EPI_OK;
+}
+
+int epi_svr_run_device(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out,
+                       void *stream, char *err)
+{
+    int rc = epi_svr_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    SvArgs g{};
+    g.D = d->D; g.F = d->F; g.R = d->R; g.max_iter = d->max_iter; g.tol = d->tol;
+    g.X = in->X; g.y = in->y; g.box = in->box; g.eps = in->epsilon; g.scale = in->kernel_scale;
+    g.beta = out->beta; g.bias = out->bias; g.w = out->w; g.fitted = out->fitted; g.gap = out->gap;
+    g.n_iter = out->n_iter; g.n_sv = out->n_sv; g.status = out->status;
+    const bool gau = d->kernel == EPI_SVR_GAUSSIAN;
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    for (int k0 = 0; k0 < d->K; k0 += kSvRowCounts) {                  // a launch carries up to 64 row counts by value
+        const int kc = d->K - k0 < kSvRowCounts ? d->K - k0 : kSvRowCounts;
+        g.k0 = k0;
+        int nmax = 1, nmin = d->D;
+        for (int kk = 0; kk < kc; kk++) {
+            g.nr[kk] = in->n_rows[k0 + kk];
+            nmax = g.nr[kk] > nmax ? g.nr[kk] : nmax;
+            nmin = g.nr[kk] < nmin ? g.nr[kk] : nmin;
+        }
+        const size_t doubles = sv_lds_doubles(nmax, nmin, d->D, d->F, gau);
+        g.lds = (int)doubles;
+        const int64_t items = (int64_t)kc * d->R;
+        for (int64_t i0 = 0; i0 < items; i0 += kSvLaunchItems) {       // one workgroup per item, in slices (svr.hpp)
+            g.item0 = (long long)i0;
+            const unsigned ni = (unsigned)(items - i0 < kSvLaunchItems ? items - i0 : kSvLaunchItems);
+            e = gau ? sv_dispatch<true>(g, nmax, ni, doubles * sizeof(double), st) : sv_dispatch<false>(g, nmax, ni, doubles * sizeof(double), st);
+            if (e != hipSuccess) return hip_fail(err, e, "svr_items launch");
+        }
+    }
+    return EPI_OK;
+}
+
+int epi_svr_run_host(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out,
+                     int device, char *err)
+{
+    int rc = epi_svr_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t D = (size_t)d->D, F = (size_t)d->F, R = (size_t)d->R, K = (size_t)d->K;
+    HostIO io;
+    const size_t o_X = io.add_in(in->X, D * F, 8, R, 0, R), o_y = io.add_in(in->y, D, 8, R, 0, R);
+    const size_t o_b = io.add_in(in->box, 1, 8, R, 0, R), o_e = io.add_in(in->epsilon, 1, 8, R, 0, R), o_s = io.add_in(in->kernel_scale, 1, 8, R, 0, R);
+    using SO = epi_svr_outputs;
+    const HostIO::Opt<SO, double> f64[5] = {{&SO::beta, K * D}, {&SO::bias, K}, {&SO::w, K * F}, {&SO::fitted, K * D}, {&SO::gap, K}};
+    const HostIO::Opt<SO, int32_t> i32[3] = {{&SO::n_iter, K}, {&SO::n_sv, K}, {&SO::status, K}};
+    size_t o_d[5], o_i[3];
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        epi_svr_inputs din{};
+        din.X = (const double *)(base + o_X); din.y = (const double *)(base + o_y);
+        din.box = (const double *)(base + o_b); din.epsilon = (const double *)(base + o_e); din.kernel_scale = (const double *)(base + o_s);
+        din.n_rows = in->n_rows;                                       // host memory in both entry points
+        epi_svr_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_svr_run_device(d, &din, &dout, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -268,6 +268,40 @@ def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device=0):
     return out
 
 
+def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale=None, tol=1e-3, max_iter=100000, outputs=None,
+        device=0):
+    """epi_svr_run_host: the support-vector regression of batch.svr on NumPy arrays (synchronous).
+    X [D, F, R], y [D, R]; box, epsilon, kernel_scale scalars or arrays [R], None for _lib.svr_defaults of y(1:max(n_rows)).
+    Returns the dict of batch.svr as NumPy arrays."""
+    keep = []
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 3 or np.shape(y) != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.svr_out_names(outputs, kernel)
+    d = _lib.make_svr_desc(D, F, R, K, kernel, tol, max_iter)
+    if box is None or epsilon is None or kernel_scale is None:
+        dflt = _lib.svr_defaults(np.asarray(y, dtype=np.float64)[:max(1, min(int(nr.max()), D))], kernel)
+        box, epsilon = dflt["box"] if box is None else box, dflt["epsilon"] if epsilon is None else epsilon
+        kernel_scale = dflt["kernel_scale"] if kernel_scale is None else kernel_scale
+    box, epsilon, kernel_scale = (_lib.svr_region_array(v, R, n) for v, n in ((box, "box"), (epsilon, "epsilon"), (kernel_scale, "kernel_scale")))
+    shapes = _lib.svr_shapes(D, F, R, K)
+    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.SVR_OUT_I32 else np.float64)
+           for k in _lib.SVR_OUT_NAMES if k in names}
+    ins = _lib.SvrInputs()
+    ins.X, ins.y, ins.n_rows = _f(X, keep), _f(y, keep), nr.ctypes.data
+    ins.box, ins.epsilon, ins.kernel_scale = box.ctypes.data, epsilon.ctypes.data, kernel_scale.ctypes.data
+    outs = _lib.SvrOutputs()
+    for k in _lib.SVR_OUT_NAMES:
+        setattr(outs, k, out[k].ctypes.data if k in out else None)
+    err = C.create_string_buffer(256)
+    rc = _lib.lib().epi_svr_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
+    _lib.check(rc, err)
+    return out
+
+
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
     """epi_ens_run_host: the Monte-Carlo ensemble statistics of batch.ensemble_summary on NumPy arrays (synchronous).
     src [T, rows, B] or [T, B], float32 or float64 (anything else is converted to float64), B = R * D region-major.

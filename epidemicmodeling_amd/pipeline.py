@@ -306,7 +306,7 @@ def growth_rates(cases, population, wlen=7, generation_period=3, causal=1, forec
 
 
 GROWTH_TARGETS = ("llr_Lambda", "gr_Lambda", "gr_LambdaSmoothed", "nls_Lambda")
-GROWTH_SOLVERS = ("ridge", "backslash")
+GROWTH_SOLVERS = ("ridge", "backslash", "svr", "svr_gaussian")
 
 
 def backslash_features(ip_filled, lags, extra=None):
@@ -325,7 +325,8 @@ def backslash_features(ip_filled, lags, extra=None):
 
 def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lags=(3, 5, 7), target="llr_Lambda", extra=None,
                     ridge=1e-6, lambda_threshold=0.1, reduction_effect=0.01, effect_lag=3, wlen=7, generation_period=3, causal=1,
-                    time_unit=1.0, device="cuda:0", solver="ridge", normalise=False, tol_scale=1.0):
+                    time_unit=1.0, device="cuda:0", solver="ridge", normalise=False, tol_scale=1.0, box=None, epsilon=None,
+                    kernel_scale=None, svr_tol=1e-3, svr_max_iter=100000):
     """The phase-I predictor of testScripts/test04FullFeatureExtMLpipeline.m (:160-195 the features, :292-404 the linear map,
     :418-431 the policy tracker, :576-642 the clip and the rebuild) for ALL regions and every train / test split:
 
@@ -344,7 +345,13 @@ def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lag
     test05DirectNewCasesLearning.m:185 instead: IPtoRateMap = X(1:train,:) \\ y(1:train) on the raw columns (normalise=True
     divides every column by rate_map's x_mx first), no ridge, by batch.mldivide (tol_scale: its rank tolerance);
     lambda_in = [y(1:n_train); X(n_train+1:T,:) m] then goes through batch.rate_map's clip, rebuild and tracker.  The dict
-    gains map [K, F, S] (in the units of the columns used), rank, perm, resid and mldivide_status."""
+    gains map [K, F, S] (in the units of the columns used), rank, perm, resid and mldivide_status.
+
+    solver="svr" / "svr_gaussian" are the fitrsvm rows of test05 :198-262, test04 :435-445 and test03 :242-262: batch.svr with
+    the linear / the Gaussian kernel on the same feature matrix (normalise as above), box / epsilon / kernel_scale scalars or
+    arrays [S], None for _lib.svr_defaults of y_filled(1:max(n_train)); svr_tol and svr_max_iter are its stopping rule.  The
+    fitted rates go through the clip and the rebuild like the backslash's.  The dict gains beta [K, T, S], bias, n_iter, gap,
+    n_sv and svr_status [K, S], and map [K, F, S] for the linear kernel."""
     if target not in GROWTH_TARGETS:
         raise ValueError(f"target must be one of {GROWTH_TARGETS}")
     if solver not in GROWTH_SOLVERS:
@@ -369,16 +376,31 @@ def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lag
         X = backslash_features(ipf, lags, extra)
         if normalise:
             X = X / rm["x_mx"][None]
-        ml = batch.mldivide(X, rm["y_filled"], n_rows=nt, tol_scale=tol_scale, outputs=("m", "rank", "perm", "resid", "fitted", "status"),
-                            device=device)
+        if solver == "backslash":
+            ml = batch.mldivide(X, rm["y_filled"], n_rows=nt, tol_scale=tol_scale, outputs=("m", "rank", "perm", "resid", "fitted", "status"),
+                                device=device)
+            extras = {"map": ml["m"], "rank": ml["rank"], "perm": ml["perm"], "resid": ml["resid"], "mldivide_status": ml["status"]}
+        else:
+            kernel = "linear" if solver == "svr" else "gaussian"
+            ml = batch.svr(X, rm["y_filled"], n_rows=nt, kernel=kernel, box=box, epsilon=epsilon, kernel_scale=kernel_scale, tol=svr_tol,
+                           max_iter=svr_max_iter, device=device)
+            extras = {k: ml[k] for k in ("beta", "bias", "n_iter", "gap", "n_sv")}
+            extras["svr_status"] = ml["status"]
+            if kernel == "linear":
+                extras["map"] = ml["w"]
         train = torch.arange(T, device=ipf.device)[None, :, None] < torch.as_tensor(nt, device=ipf.device)[:, None, None]
         lambda_in = torch.where(train, rm["y_filled"][None], ml["fitted"])
         rm.update(batch.rate_map(ipf, ns, nt, lambda_in=lambda_in, lambda_threshold=lambda_threshold, outputs=("lambda_hat", "new_cases_est", "status"),
                                  device=device))
-        rm.update({"map": ml["m"], "rank": ml["rank"], "perm": ml["perm"], "resid": ml["resid"], "mldivide_status": ml["status"]})
+        rm.update(extras)
     out = {"new_smoothed": ns.cpu().numpy(), "ip_filled": ipf.cpu().numpy(), "n_train": nt.astype(np.int32), "target": target}
     out.update({k: v.cpu().numpy() for k, v in rw.items()})
     out.update({k: v.cpu().numpy() for k, v in rm.items()})
+    return _forecast_errors(out, nt, T)
+
+
+def _forecast_errors(out, nt, T):
+    """err [K, T, S] (NaN on the training days), mae and rmse [K, S] of out["new_cases_est"] against out["new_smoothed"]"""
     test = np.arange(T)[None, :, None] >= nt[:, None, None]                  # [K, T, 1]
     err = np.where(test, out["new_cases_est"] - out["new_smoothed"][None], np.nan)
     cnt = (T - nt).astype(np.float64)[:, None]
@@ -387,6 +409,32 @@ def growth_forecast(cases, population, ip, predict_ahead=None, n_train=None, lag
         out["mae"] = np.where(cnt > 0, np.where(test, np.abs(err), 0.0).sum(axis=1) / cnt, np.nan)
         out["rmse"] = np.where(cnt > 0, np.sqrt(np.where(test, err * err, 0.0).sum(axis=1) / cnt), np.nan)
     return out
+
+
+def growth_forecast_mean(results, lambda_threshold=0.1, device="cuda:0"):
+    """The script's LambdaHatTotal = mean([LambdaHatARX; LambdaHatLinear; LambdaHatSVM; LambdaHatSVMGAU]) of
+    test05DirectNewCasesLearning.m:268 (test04 :623-624): the mean of the lambda_hat [K, T, S] of several growth_forecast
+    results (any solvers; the same cases, plans and n_train), added in the order given and divided by their number, then
+    through batch.rate_map's clip and rebuild (fit = 0).  Returns new_smoothed, ip_filled, n_train, lambda_mean (before the
+    clip), lambda_hat, new_cases_est, status, err, mae, rmse."""
+    results = list(results)
+    if not results:
+        raise ValueError("no result given")
+    first = results[0]
+    nt = np.asarray(first["n_train"]).astype(np.int64)
+    for res in results[1:]:
+        if np.shape(res["lambda_hat"]) != np.shape(first["lambda_hat"]) or not np.array_equal(res["n_train"], first["n_train"]):
+            raise ValueError("the results must share their shapes and n_train")
+    total = np.array(first["lambda_hat"], dtype=np.float64)
+    for res in results[1:]:
+        total = total + res["lambda_hat"]
+    mean = total / float(len(results))
+    rm = batch.rate_map(first["ip_filled"], first["new_smoothed"], nt, lambda_in=mean, lambda_threshold=lambda_threshold,
+                        outputs=("lambda_hat", "new_cases_est", "status"), device=device)
+    out = {"new_smoothed": np.asarray(first["new_smoothed"]), "ip_filled": np.asarray(first["ip_filled"]), "n_train": nt.astype(np.int32),
+           "lambda_mean": mean}
+    out.update({k: v.cpu().numpy() for k, v in rm.items()})
+    return _forecast_errors(out, nt, mean.shape[1])
 
 
 def monte_carlo_eks(w, n_regions, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, storage="f32", outputs=("S_SMOOTH",),

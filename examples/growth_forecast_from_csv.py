@@ -8,7 +8,13 @@ The growth rate (log-linear regression over a sliding window) is regressed on th
 by 3, 5 and 7 days over the training days, predicted over the days ahead (14, 28 and 42 here), clipped to +-0.1 and turned
 back into new cases.  Per region, split and test day the output holds the smoothed new cases, the predicted rate and the
 rebuilt new cases.  Without arguments (or with only the output path) a small synthetic tracker file is generated first
-(there is no data set in this repository)."""
+(there is no data set in this repository).
+
+    python examples/growth_forecast_from_csv.py --solver svr ...      # ridge (default), backslash, svr, svr_gaussian or mean
+
+`--solver svr` / `svr_gaussian` take the fitrsvm rows of the reference's scripts (support-vector regression with the linear /
+the Gaussian kernel on the normalised columns, fitrsvm's default hyper-parameters); `--solver mean` is the scripts' average
+of the ridge map and the two support-vector rows."""
 import os
 import sys
 import tempfile
@@ -26,18 +32,27 @@ AHEAD = (14, 28, 42)
 
 
 def main():
-    if len(sys.argv) >= 6:
-        data, pops, start, end, dst = sys.argv[1:6]
+    argv, solver = list(sys.argv[1:]), "ridge"
+    if "--solver" in argv:
+        i = argv.index("--solver")
+        solver = argv[i + 1]
+        del argv[i:i + 2]
+    if solver not in pipeline.GROWTH_SOLVERS + ("mean",):
+        raise SystemExit(f"--solver must be one of {pipeline.GROWTH_SOLVERS + ('mean',)}")
+    if len(argv) >= 5:
+        data, pops, start, end, dst = argv[:5]
     else:
         tmp = tempfile.mkdtemp()
         data, pops, start, end = synthetic_files(tmp)
-        dst = sys.argv[1] if len(sys.argv) == 2 else os.path.join(tmp, "growth_forecast.csv")
+        dst = argv[0] if len(argv) == 1 else os.path.join(tmp, "growth_forecast.csv")
     d = dataio.read_oxcgrt(data, start, end)
     N = dataio.read_populations(pops, d["geo_ids"])
     keep = np.flatnonzero(np.isfinite(N) & np.isfinite(d["cases"]).any(axis=0))
     T = d["cases"].shape[0]
     ahead = [a for a in AHEAD if a < T - 8]
-    out = pipeline.growth_forecast(d["cases"][:, keep], N[keep], d["ip"][:, :, keep], predict_ahead=ahead)
+    run = lambda sv: pipeline.growth_forecast(d["cases"][:, keep], N[keep], d["ip"][:, :, keep], predict_ahead=ahead, solver=sv,
+                                              normalise=sv != "ridge")
+    out = pipeline.growth_forecast_mean([run(sv) for sv in ("ridge", "svr", "svr_gaussian")]) if solver == "mean" else run(solver)
     rows = []
     for i, k in enumerate(keep):
         for j, nt in enumerate(out["n_train"]):

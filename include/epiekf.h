@@ -913,6 +913,70 @@ int epi_mldiv_run_device(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, co
 int epi_mldiv_run_host(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, const epi_mldiv_outputs *out,
                        int device, char *err);
 
+/* ---- The two fitrsvm rows of the phase-I predictor block (testScripts/test05DirectNewCasesLearning.m:198-268,
+ * test04FullFeatureExtMLpipeline.m:435-445, :623-624, test03ExpfitVsIPRegression.m:242-262): epsilon-insensitive support-vector
+ * regression with a linear or a Gaussian kernel, for every region and every row count in ONE call.  One item = (row count k,
+ * region r) fits the rows 1 .. n_rows[k] of X [D][F][R], y [D][R] and predicts all D rows:
+ *   kernel        linear: K(a,b) = a.b; Gaussian: K(a,b) = exp(-|a - b|^2 / kernel_scale^2), both over f ascending by fma
+ *   problem       LIBSVM's 2n-variable form: alpha_1..n, alpha*_1..n in [0, box], signs +1 / -1, linear term eps - y / eps + y
+ *   solver        sequential minimal optimisation from alpha = 0: i the maximal violator, j by the second-order rule, a
+ *                 non-positive curvature replaced by 1e-12, ties to the lowest index, LIBSVM's clipped two-variable step,
+ *                 no shrinking; it stops when m(alpha) - M(alpha) < tol or after max_iter steps (NOT_CONVERGED: the outputs
+ *                 are the iterate reached)
+ *   bias          LIBSVM's rule: minus the mean of y_i G_i over the free variables, the midpoint of the bounds without one
+ *   fitted        linear: x_t . w + bias with w = sum_i beta_i x_i; Gaussian: sum_i beta_i K(x_t, x_i) + bias; over ALL D rows:
+ *                 the rows beyond n_rows[k] are the prediction
+ * MATLAB's own solver stops at a gap tolerance of its own and its bias rule is not documented: this is the documented QP, not
+ * fitrsvm's bits.  BoxConstraint, Epsilon and KernelScale are per-region inputs ('auto' and the hyper-parameter optimiser are
+ * not here).  The operation order is DESIGN.md §4.13; the kernel, tests/svr_ref.c and tests/svr_ref.py share it bit for bit.
+ * Arrays are region-fastest.  An item with BAD_INPUT has that bit alone, n_iter 0, n_sv 0 and NaN beta / bias / w / fitted / gap.
+ * epi_svr_run_device takes DEVICE pointers -- except n_rows, which is a HOST array like the descriptor: validate reads it and
+ * the launches carry it by value -- and enqueues on `stream` (no host synchronisation, no allocation); epi_svr_run_host takes
+ * HOST pointers and runs on a pooled context of `device`. */
+enum {
+    EPI_SVR_NOT_CONVERGED = 1,   /* max_iter steps were taken and the gap is still >= tol */
+    EPI_SVR_BAD_INPUT = 2,       /* a NaN or Inf in the used rows of X or y, or box / epsilon / kernel_scale outside its range */
+    EPI_SVR_NONFINITE = 4        /* an element of beta, bias, w, fitted or gap is Inf or NaN */
+};
+enum { EPI_SVR_LINEAR = 0, EPI_SVR_GAUSSIAN = 1 };
+typedef struct epi_svr_desc {
+    int32_t abi_version;
+    int32_t D;                   /* rows of X and y, >= 1 */
+    int32_t F;                   /* columns, 1 .. 96 */
+    int32_t R;                   /* regions, >= 1 */
+    int32_t K;                   /* row counts, >= 1; K * R < 2^31 */
+    int32_t kernel;              /* EPI_SVR_LINEAR or EPI_SVR_GAUSSIAN */
+    int32_t max_iter;            /* 1 .. 10 000 000 */
+    double tol;                  /* > 0, finite */
+} epi_svr_desc;
+typedef struct epi_svr_inputs {
+    const double *X;             /* [D][F][R] */
+    const double *y;             /* [D][R] */
+    const int32_t *n_rows;       /* [K], HOST memory in both entry points: 1 <= n_rows[k] <= min(D, 1024),
+                                    max(n_rows) ((F | 1) + 1) <= 20000 */
+    const double *box;           /* [R]: finite, > 0 */
+    const double *epsilon;       /* [R]: finite, >= 0 */
+    const double *kernel_scale;  /* [R]: finite, > 0 (read for both kernels) */
+} epi_svr_inputs;
+typedef struct epi_svr_outputs {        /* each may be NULL, but not all of them */
+    double *beta;                       /* [K][D][R]: alpha - alpha* on the rows used, +0 beyond them */
+    double *bias;                       /* [K][R] */
+    double *w;                          /* [K][F][R]: linear kernel only (must be NULL for the Gaussian kernel) */
+    double *fitted;                     /* [K][D][R] */
+    int32_t *n_iter;                    /* [K][R]: the pair steps taken */
+    double *gap;                        /* [K][R]: m(alpha) - M(alpha) of the iterate returned */
+    int32_t *n_sv;                      /* [K][R]: the rows with beta != 0 */
+    int32_t *status;                    /* [K][R] */
+} epi_svr_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for a bad descriptor, a missing array, w with the Gaussian kernel, an n_rows outside 1 .. D
+ * or an element count of 2^31 or more, EPI_ERR_UNSUPPORTED for F > 96, n_rows > 1024 or max(n_rows) ((F | 1) + 1) > 20000 (the
+ * item's rows stay in LDS, at the odd stride F | 1, with beta beside them) */
+int epi_svr_validate(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out, char *err);
+int epi_svr_run_device(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out,
+                       void *stream, char *err);
+int epi_svr_run_host(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_svr_outputs *out,
+                     int device, char *err);
+
 /* ---- Tools/Rt_ExpFitEKF.m:1 -- 2-state exponential-fit EKF/EKS over the new-case counts, order 1 or 2 ----
  * [S_MINUS, S_PLUS, P_MINUS, P_PLUS, K_GAIN, S_SMOOTH, P_SMOOTH, innovations, rho] =
  *     Rt_ExpFitEKF(x, s_init, params, w_bar, v_bar, Ps_init, Q_w, R_v, beta, gamma, inv_monitor_len, order)

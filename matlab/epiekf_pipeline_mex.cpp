@@ -50,6 +50,13 @@
 //       X  R x F x D (F <= 96, max(n_rows) * (F + 1) <= 20000);  y  R x D;  n_rows  K row counts 1 .. D ([] = D);  tol_scale (1).
 //       m, rdiag  R x F x K;  perm  R x F x K, 1-based column numbers in pivot order;  rank, resid, status  R x K (status: bits
 //       1 rank deficient, 2 non-finite input, 4 non-finite result);  fitted  R x D x K, X * m over all D rows.
+//   [beta, bias, w, fitted, n_iter, gap, n_sv, status] = epiekf_pipeline_mex('svr', X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter)
+//       The fitrsvm rows of test05DirectNewCasesLearning.m:198-268, test04 :435-445 and test03 :242-262 for R regions x K row
+//       counts: epsilon-insensitive support-vector regression by LIBSVM's sequential minimal optimisation.
+//       X  R x F x D (F <= 96, n_rows <= 1024, max(n_rows) * (bitor(F, 1) + 1) <= 20000);  y  R x D;  n_rows  K row counts 1 .. D
+//       ([] = D);  kernel  0 linear, 1 Gaussian;  box, epsilon, kernel_scale  a scalar or R values;  tol ([] = 1e-3);  max_iter
+//       ([] = 100000).  beta, fitted  R x D x K;  w  R x F x K ([] for the Gaussian kernel);  bias, n_iter, gap, n_sv, status
+//       R x K (status: bits 1 not converged, 2 bad input, 4 non-finite result).
 //   [mean, std, min, max, quantiles, count] = epiekf_pipeline_mex('ens_summary', src, D, q, population)
 //       Monte-Carlo ensemble statistics (BASELINE config 5).  src  B x rows x T (or B x T), B = R * D chains,
 //       region-major (chain = (r-1) * D + d): a filter output such as S_SMOOTH;  D  draws per region;  q  1 .. 16
@@ -76,6 +83,7 @@
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
 // Build on a MATLAB host:  mex -I../include epiekf_pipeline_mex.cpp -L../epidemicmodeling_amd -lepiekf
+#include <stdio.h>
 #include <string.h>
 #include <limits>
 #include <vector>
@@ -380,6 +388,65 @@ static void mldivide(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void svr(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('svr', X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter): 10 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    const mwSize *dx = mxGetDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1])) mexErrMsgTxt("X must be R x F x D");
+    const mwSize R = dx[0], F = dx[1], D = nd == 3 ? dx[2] : 1;
+    want(prhs[2], R, D, "y");
+    const mwSize K = mxIsEmpty(prhs[3]) ? 1 : mxGetNumberOfElements(prhs[3]);
+    epi_svr_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.D = (int32_t)D; d.F = (int32_t)F; d.R = (int32_t)R; d.K = (int32_t)K;
+    d.kernel = mxIsEmpty(prhs[4]) ? EPI_SVR_LINEAR : (int32_t)mxGetScalar(prhs[4]);
+    d.tol = mxIsEmpty(prhs[8]) ? 1e-3 : mxGetScalar(prhs[8]);
+    d.max_iter = mxIsEmpty(prhs[9]) ? 100000 : (int32_t)mxGetScalar(prhs[9]);
+    std::vector<double> reg[3];
+    static const char *const names[3] = {"box", "epsilon", "kernel_scale"};
+    for (int q = 0; q < 3; q++) {                                       // a scalar is broadcast over the regions
+        const mxArray *a = prhs[5 + q];
+        const mwSize ne = mxGetNumberOfElements(a);
+        if (ne != 1 && ne != R) {
+            char msg[64];
+            snprintf(msg, sizeof msg, "%s must be a scalar or R values", names[q]);
+            mexErrMsgTxt(msg);
+        }
+        reg[q].resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) reg[q][r] = mxGetPr(a)[ne == 1 ? 0 : r];
+    }
+    const bool lin = d.kernel == EPI_SVR_LINEAR;
+    std::vector<int32_t> nr((size_t)K, (int32_t)D), niv((size_t)(R * K)), nsv((size_t)(R * K)), stv((size_t)(R * K));
+    if (!mxIsEmpty(prhs[3]))
+        for (mwSize k = 0; k < K; k++) nr[k] = (int32_t)mxGetPr(prhs[3])[k];
+    mxArray *be = dbl3(R, D, K), *bi = mxCreateDoubleMatrix(R, K, mxREAL), *w = lin ? dbl3(R, F, K) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxArray *fi = dbl3(R, D, K), *ni = mxCreateDoubleMatrix(R, K, mxREAL), *gp = mxCreateDoubleMatrix(R, K, mxREAL);
+    mxArray *ns = mxCreateDoubleMatrix(R, K, mxREAL), *st = mxCreateDoubleMatrix(R, K, mxREAL);
+    mxArray *o[8] = {be, bi, w, fi, ni, gp, ns, st};
+    epi_svr_inputs in;
+    memset(&in, 0, sizeof in);
+    in.X = mxGetPr(prhs[1]); in.y = mxGetPr(prhs[2]); in.n_rows = nr.data();
+    in.box = reg[0].data(); in.epsilon = reg[1].data(); in.kernel_scale = reg[2].data();
+    epi_svr_outputs out;
+    memset(&out, 0, sizeof out);
+    out.beta = mxGetPr(be);
+    if (nlhs >= 2) out.bias = mxGetPr(bi);
+    if (nlhs >= 3 && lin) out.w = mxGetPr(w);
+    if (nlhs >= 4) out.fitted = mxGetPr(fi);
+    if (nlhs >= 5) out.n_iter = niv.data();
+    if (nlhs >= 6) out.gap = mxGetPr(gp);
+    if (nlhs >= 7) out.n_sv = nsv.data();
+    if (nlhs >= 8) out.status = stv.data();
+    // the ABI's [K][D][R], [K][F][R] and [K][R] are MATLAB's R x D x K, R x F x K and R x K: no transposition
+    char err[256] = {0};
+    const int rc = epi_svr_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) mxDestroyArray(a); fail_if(rc, err); }
+    for (size_t k = 0; k < stv.size(); k++) { mxGetPr(ni)[k] = (double)niv[k]; mxGetPr(ns)[k] = (double)nsv[k]; mxGetPr(st)[k] = (double)stv[k]; }
+    for (int k = 0; k < 8; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 5) mexErrMsgTxt("epiekf_pipeline_mex('ens_summary', src, D, q, population): 5 inputs expected");
@@ -558,6 +625,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "robustfit") == 0) robustfit(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ratemap") == 0) ratemap(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mldivide") == 0) mldivide(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "svr") == 0) svr(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
