@@ -1,0 +1,175 @@
+"""The one call path of the batched family calls (_lib.FAMILIES), shared by batch (torch tensors on a stream) and hostapi
+(NumPy arrays, a device ordinal).  No torch here: what differs between the two entry points is asked of a backend,
+
+    f64(v) / i32(v)    the input as a contiguous float64 / int32 array where the call reads it (None stays None); the
+                       backend keeps it alive
+    empty(shape, dt)   an uninitialised output, dt one of np.float64 / np.int32 / np.float32
+    ptr(a)             the address of such an array (None stays None)
+    kind, tail()       "run_device" and the stream, or "run_host" and the device ordinal
+    resident(v)        v already lies where the call reads it (a torch tensor for the device entry; never for the host's)
+    host(v)            v as something NumPy reads
+    checks_folds       lasso_cv checks a host-side partition before the call
+
+batch.DeviceBackend and hostapi.HostBackend.  Every family's call ends in run_family; the six families whose two entry
+points are the same function have their body here, written against a backend."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def run_family(fam, be, desc, args, shapes, names, f32=()):
+    """Allocate the outputs `names` of family `fam` (a key of _lib.FAMILIES) from `shapes` -- int32 where the family says so,
+    float32 for those in `f32`, else float64 --, bind them (the others stay NULL), call epi_<fam>_<be.kind>(desc, *args,
+    outputs, be.tail(), err) and check its status.  Returns the dict of outputs in the order of the family's names."""
+    f = _lib.FAMILIES[fam]
+    out = {k: be.empty(shapes[k], np.int32 if k in f.out_i32 else (np.float32 if k in f32 else np.float64))
+           for k in f.out_names if k in names}
+    outs = f.args[-1]._type_()                      # the family's outputs structure
+    for k, v in out.items():
+        setattr(outs, k, be.ptr(v))
+    err = C.create_string_buffer(256)
+    rc = getattr(_lib.lib(), f"epi_{fam}_{be.kind}")(C.byref(desc), *args, C.byref(outs), be.tail(), err)
+    _lib.check(rc, err)
+    return out
+
+
+def _rtwin_names(methods, status=True):
+    bits = _lib.rtwin_methods(methods)
+    names = []
+    if bits & 1:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("llr_")]
+    if bits & 2:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("gr_")]
+    if bits & 4:
+        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("nls_")] + (list(_lib.RTWIN_OUT_I32) if status else [])
+    return bits, names
+
+
+def rt_window(be, new_cases, wlen, time_unit, causal, generation_period, methods):
+    x = be.f64(new_cases)
+    if x.ndim != 2:
+        raise ValueError("new_cases must be [L, R]")
+    L_, R = x.shape
+    bits, names = _rtwin_names(methods)
+    d = _lib.make_rtwin_desc(R, L_, wlen, time_unit, causal, generation_period, bits)
+    return run_family("rtwin", be, d, [be.ptr(x)], dict.fromkeys(names, (L_, R)), names)
+
+
+def lasso_folds(D, K, R, seed=0):
+    """A cross-validation partition for lasso_cv: fold [D, R] int32 in 0 .. K-1.  Every region gets its own random
+    permutation of the D days (np.random.default_rng(seed), regions in order); the fold sizes are those of cvpartition's
+    KFold: the first D mod K folds get ceil(D / K) days, the rest floor(D / K).  Deterministic for a given seed."""
+    D, K, R = int(D), int(K), int(R)
+    if not 2 <= K <= D:
+        raise ValueError("lasso_folds needs 2 <= K <= D")
+    rng = np.random.default_rng(seed)
+    sizes = np.full(K, D // K)
+    sizes[:D % K] += 1
+    label = np.repeat(np.arange(K, dtype=np.int32), sizes)
+    fold = np.empty((D, R), dtype=np.int32)
+    for r in range(R):
+        fold[rng.permutation(D), r] = label
+    return fold
+
+
+def check_lasso_folds(fold, K):
+    """ValueError unless fold [D, R] holds only 0 .. K-1 and leaves no fold empty in any region"""
+    f = np.asarray(fold)
+    if f.ndim != 2 or f.min() < 0 or f.max() >= K:
+        raise ValueError("folds must be [D, R] with values in 0 .. K-1")
+    for r in range(f.shape[1]):
+        if np.bincount(f[:, r], minlength=K).min() == 0:
+            raise ValueError(f"region {r}: a fold is empty")
+
+
+def lasso_cv(be, X, y, K, folds, seed, num_lambda, lambda_ratio, rel_tol, max_iter):
+    X, y = be.f64(X), be.f64(y)
+    if X.ndim != 3 or y.ndim != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    K = int(K)
+    f = None
+    if K >= 2:
+        if folds is None:
+            folds = lasso_folds(D, K, R, seed)
+        if be.checks_folds and not be.resident(folds):
+            check_lasso_folds(folds, K)
+        f = be.i32(folds)
+    d = _lib.make_lasso_desc(R, D, n, K, num_lambda, lambda_ratio, rel_tol, max_iter)
+    shapes = _lib.lasso_shapes(R, D, n, K, num_lambda)
+    out = run_family("lasso", be, d, [be.ptr(X), be.ptr(y), be.ptr(f)], shapes, shapes)
+    return {k: out[k] for k in shapes}              # the path's outputs first, the cross-validation's behind them
+
+
+def robust_affine_fit(be, X, y, robust, lower, upper, max_iter, outputs):
+    X, y = be.f64(X), be.f64(y)
+    if X.ndim != 3 or y.ndim != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, n, R] and y [D, R]")
+    D, n, R = X.shape
+    names = _lib.robfit_out_names(outputs)
+    d = _lib.make_robfit_desc(R, D, n, int(bool(robust)), max_iter, lower, upper)
+    return run_family("robfit", be, d, [be.ptr(X), be.ptr(y)], _lib.robfit_shapes(R, D, n), names)
+
+
+def rate_map(be, ip, new_smoothed, n_train, y, extra, lambda_in, lags, ridge, lambda_threshold, reduction_effect, effect_lag,
+             outputs):
+    ip, ns, y, extra, lambda_in = be.f64(ip), be.f64(new_smoothed), be.f64(y), be.f64(extra), be.f64(lambda_in)
+    if ip.ndim != 3 or ns.ndim != 2 or ns.shape != (ip.shape[0], ip.shape[2]):
+        raise ValueError("ip must be [T, n, R] and new_smoothed [T, R]")
+    T, n, R = ip.shape
+    nt = _lib.ratemap_n_train(n_train)
+    K = int(nt.size)
+    fit = lambda_in is None
+    if fit and y is None:
+        raise ValueError("y (to fit) or lambda_in (to skip the fit) is needed")
+    if (y is not None and y.shape != (T, R)) or (extra is not None and (extra.ndim != 3 or extra.shape[0] != T or extra.shape[2] != R)) \
+            or (lambda_in is not None and lambda_in.shape != (K, T, R)):
+        raise ValueError("y must be [T, R], extra [T, E, R] and lambda_in [K, T, R]")
+    E = 0 if extra is None else int(extra.shape[1])
+    names = _lib.ratemap_out_names(outputs, fit, y is not None)
+    d = _lib.make_ratemap_desc(T, n, R, E, K, lags, int(fit), effect_lag, ridge, lambda_threshold, reduction_effect)
+    ins = _lib.RatemapInputs()
+    ins.ip, ins.y, ins.new_smoothed, ins.extra, ins.lambda_in = be.ptr(ip), be.ptr(y), be.ptr(ns), be.ptr(extra), be.ptr(lambda_in)
+    ins.n_train = nt.ctypes.data
+    return run_family("ratemap", be, d, [C.byref(ins)], _lib.ratemap_shapes(T, n, R, E, K, d.n_lags), names)
+
+
+def mldivide(be, X, y, n_rows, tol_scale, outputs):
+    X, y = be.f64(X), be.f64(y)
+    if X.ndim != 3 or y.ndim != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.mldiv_out_names(outputs)
+    d = _lib.make_mldiv_desc(D, F, R, K, tol_scale)
+    ins = _lib.MldivInputs()
+    ins.X, ins.y, ins.n_rows = be.ptr(X), be.ptr(y), nr.ctypes.data
+    return run_family("mldiv", be, d, [C.byref(ins)], _lib.mldiv_shapes(D, F, R, K), names)
+
+
+def svr(be, X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, outputs):
+    X, y = be.f64(X), be.f64(y)
+    if X.ndim != 3 or y.ndim != 2 or y.shape != (X.shape[0], X.shape[2]):
+        raise ValueError("X must be [D, F, R] and y [D, R]")
+    D, F, R = X.shape
+    nr = _lib.mldiv_n_rows(n_rows, D)
+    K = int(nr.size)
+    names = _lib.svr_out_names(outputs, kernel)
+    d = _lib.make_svr_desc(D, F, R, K, kernel, tol, max_iter)
+    if box is None or epsilon is None or kernel_scale is None:
+        dflt = _lib.svr_defaults(be.host(y[:max(1, min(int(nr.max()), D))]), kernel)
+        box, epsilon = dflt["box"] if box is None else box, dflt["epsilon"] if epsilon is None else epsilon
+        kernel_scale = dflt["kernel_scale"] if kernel_scale is None else kernel_scale
+
+    def reg(v, name):                               # an array [R] that is already resident is taken as it is
+        return be.f64(v if be.resident(v) and v.shape == (R,) else _lib.svr_region_array(be.host(v), R, name))
+
+    ins = _lib.SvrInputs()
+    ins.X, ins.y, ins.n_rows = be.ptr(X), be.ptr(y), nr.ctypes.data
+    ins.box, ins.epsilon, ins.kernel_scale = be.ptr(reg(box, "box")), be.ptr(reg(epsilon, "epsilon")), be.ptr(reg(kernel_scale, "kernel_scale"))
+    return run_family("svr", be, d, [C.byref(ins)], _lib.svr_shapes(D, F, R, K), names)

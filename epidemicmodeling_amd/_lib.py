@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -138,6 +139,17 @@ class LookaheadOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LA_OUT_NAMES]
 
 
+def out_names(all_names, outputs, default):
+    """the validated list of output names of a family call: `outputs`, or `default` when it is None"""
+    names = list(default if outputs is None else outputs)
+    bad = [k for k in names if k not in all_names]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}")
+    if not names:
+        raise ValueError("no output requested")
+    return names
+
+
 class RtwinDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "L", "wlen", "causal", "generation_period", "methods")] + \
         [("time_unit", C.c_double)]
@@ -215,13 +227,7 @@ def make_robfit_desc(R, D, n, robust=1, max_iter=50, lower_a=0.0, upper_a=float(
 
 def robfit_out_names(outputs):
     """the validated list of output names (default: all but weights)"""
-    names = [k for k in ROBFIT_OUT_NAMES if k != "weights"] if outputs is None else list(outputs)
-    bad = [k for k in names if k not in ROBFIT_OUT_NAMES]
-    if bad:
-        raise ValueError(f"unknown outputs {bad}")
-    if not names:
-        raise ValueError("no output requested")
-    return names
+    return out_names(ROBFIT_OUT_NAMES, outputs, [k for k in ROBFIT_OUT_NAMES if k != "weights"])
 
 
 class RatemapDesc(C.Structure):
@@ -267,21 +273,11 @@ def make_ratemap_desc(T, n, R, E, K, lags=(3, 5, 7), fit=1, effect_lag=3, ridge=
 
 def ratemap_out_names(outputs, fit, have_y):
     """the validated list of output names (default: all that the call can give)"""
-    if outputs is None:
-        names = [k for k in RATEMAP_OUT_NAMES if (fit or k != "map") and (have_y or k != "y_filled")]
-    else:
-        names = list(outputs)
-    bad = [k for k in names if k not in RATEMAP_OUT_NAMES]
-    if bad:
-        raise ValueError(f"unknown outputs {bad}")
-    if not names:
-        raise ValueError("no output requested")
-    return names
+    return out_names(RATEMAP_OUT_NAMES, outputs, [k for k in RATEMAP_OUT_NAMES if (fit or k != "map") and (have_y or k != "y_filled")])
 
 
 def ratemap_n_train(n_train, K=None):
     """n_train as the int32 HOST array the call reads (a list of MATLAB-style train ends 1 .. T)"""
-    import numpy as np
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(n_train)), dtype=np.int32)
     if a.ndim != 1 or a.size < 1 or (K is not None and a.size != K):
         raise ValueError("n_train must be a list of K train ends")
@@ -322,18 +318,11 @@ def make_mldiv_desc(D, F, R, K, tol_scale=1.0) -> MldivDesc:
 
 def mldiv_out_names(outputs):
     """the validated list of output names (default: all)"""
-    names = list(MLDIV_OUT_NAMES) if outputs is None else list(outputs)
-    bad = [k for k in names if k not in MLDIV_OUT_NAMES]
-    if bad:
-        raise ValueError(f"unknown outputs {bad}")
-    if not names:
-        raise ValueError("no output requested")
-    return names
+    return out_names(MLDIV_OUT_NAMES, outputs, MLDIV_OUT_NAMES)
 
 
 def mldiv_n_rows(n_rows, D):
     """n_rows as the int32 HOST array the call reads (default: all D rows)"""
-    import numpy as np
     a = np.ascontiguousarray(np.atleast_1d(np.asarray(D if n_rows is None else n_rows)), dtype=np.int32)
     if a.ndim != 1 or a.size < 1:
         raise ValueError("n_rows must be a list of K row counts")
@@ -381,13 +370,7 @@ def make_svr_desc(D, F, R, K, kernel="linear", tol=1e-3, max_iter=100000) -> Svr
 
 def svr_out_names(outputs, kernel):
     """the validated list of output names (default: all, w for the linear kernel only)"""
-    names = [k for k in SVR_OUT_NAMES if k != "w" or kernel == "linear"] if outputs is None else list(outputs)
-    bad = [k for k in names if k not in SVR_OUT_NAMES]
-    if bad:
-        raise ValueError(f"unknown outputs {bad}")
-    if not names:
-        raise ValueError("no output requested")
-    return names
+    return out_names(SVR_OUT_NAMES, outputs, [k for k in SVR_OUT_NAMES if k != "w" or kernel == "linear"])
 
 
 def svr_defaults(y, kernel="linear"):
@@ -397,7 +380,6 @@ def svr_defaults(y, kernel="linear"):
     probabilities (i - 0.5) / n and linear interpolation between them.  Recalled from MATLAB's
     documentation, not taken from the reference: a convenience, the three are inputs.
     Returns a dict box, epsilon, kernel_scale of float64 arrays [R] (scalars for a 1-D y)."""
-    import numpy as np
     svr_kernel(kernel)
     a = np.asarray(y, dtype=np.float64)
     if a.ndim not in (1, 2) or a.shape[0] < 1:
@@ -424,7 +406,6 @@ def svr_defaults(y, kernel="linear"):
 
 def svr_region_array(v, R, name):
     """box / epsilon / kernel_scale as a float64 array [R]: a scalar is broadcast"""
-    import numpy as np
     a = np.asarray(v, dtype=np.float64)
     if a.ndim == 0:
         a = np.full(R, float(a))
@@ -537,6 +518,23 @@ def make_fuse_desc(m, B, T, form, p_solver=0, lane_block=0, storage=0) -> FuseDe
     return d
 
 
+# A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
+# (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
+Family = namedtuple("Family", "prefix desc args out_names out_i32")
+FAMILY_TAILS = {"validate": [C.c_char_p], "run_device": [C.c_void_p, C.c_char_p], "run_host": [C.c_int, C.c_char_p]}
+FAMILIES = {f.prefix: f for f in (
+    Family("rtwin", RtwinDesc, [C.c_void_p, C.POINTER(RtwinOutputs)], RTWIN_OUT_NAMES, RTWIN_OUT_I32),
+    Family("lasso", LassoDesc, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LassoOutputs)], LASSO_OUT_NAMES, LASSO_OUT_I32),
+    Family("robfit", RobfitDesc, [C.c_void_p, C.c_void_p, C.POINTER(RobfitOutputs)], ROBFIT_OUT_NAMES, ROBFIT_OUT_I32),
+    Family("ratemap", RatemapDesc, [C.POINTER(RatemapInputs), C.POINTER(RatemapOutputs)], RATEMAP_OUT_NAMES, RATEMAP_OUT_I32),
+    Family("mldiv", MldivDesc, [C.POINTER(MldivInputs), C.POINTER(MldivOutputs)], MLDIV_OUT_NAMES, MLDIV_OUT_I32),
+    Family("svr", SvrDesc, [C.POINTER(SvrInputs), C.POINTER(SvrOutputs)], SVR_OUT_NAMES, SVR_OUT_I32),
+    Family("ens", EnsDesc, [C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)], ENS_OUT_NAMES, ("count",)),
+    Family("arfc", ArfcDesc, [C.POINTER(ArfcInputs), C.POINTER(ArfcOutputs)], ARFC_OUT_NAMES, ("status",)),
+    Family("fuse", FuseDesc, [C.POINTER(FuseInputs), C.POINTER(FuseOutputs)], FUSE_OUT_NAMES, ("rank", "status")),
+)}
+
+
 class NnlsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "S", "D", "n", "max_iters")]
 
@@ -569,161 +567,69 @@ def lib():
                               "(python -c 'import __graft_entry__ as g; g.build()'); there is no CPU fallback")
         _preload_torch_hip_runtime()
         h = C.CDLL(LIB_PATH)
-        h.epi_abi_version.restype = C.c_int
-        h.epi_status_string.restype = C.c_char_p
         h.epi_status_string.argtypes = [C.c_int]
-        h.epi_model_dim.restype = C.c_int
         h.epi_model_dim.argtypes = [C.c_int]
-        h.epi_ekf_validate.restype = C.c_int
         h.epi_ekf_validate.argtypes = [C.POINTER(BatchDesc), C.c_char_p]
-        h.epi_ekf_workspace_bytes.restype = C.c_size_t
         h.epi_ekf_workspace_bytes.argtypes = [C.POINTER(BatchDesc)]
-        h.epi_ekf_precheck_device.restype = C.c_int
         h.epi_ekf_precheck_device.argtypes = [C.POINTER(BatchDesc), C.POINTER(Inputs), C.c_void_p, C.POINTER(C.c_int),
                                               C.c_char_p]
-        h.epi_ekf_preferred_lane_block.restype = C.c_int
         h.epi_ekf_preferred_lane_block.argtypes = [C.POINTER(BatchDesc)]
-        h.epi_ekf_run_device.restype = C.c_int
         h.epi_ekf_run_device.argtypes = [C.POINTER(BatchDesc), C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p,
                                          C.c_size_t, C.c_void_p, C.c_char_p]
-        h.epi_ekf_time_stages_device.restype = C.c_int
         h.epi_ekf_time_stages_device.argtypes = [C.POINTER(BatchDesc), C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p,
                                                  C.c_size_t, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_char_p]
-        h.epi_ekf_run_host.restype = C.c_int
         h.epi_ekf_run_host.argtypes = [C.POINTER(BatchDesc), C.POINTER(Inputs), C.POINTER(Outputs), C.c_int,
                                        C.c_char_p]
-        h.epi_sialpha_sim_device.restype = C.c_int
         h.epi_sialpha_sim_device.argtypes = [C.POINTER(SimDesc)] + [C.c_void_p] * 9 + [C.c_void_p, C.c_char_p]
-        h.epi_sialpha_score_device.restype = C.c_int
         h.epi_sialpha_score_device.argtypes = [C.POINTER(SimDesc)] + [C.c_void_p] * 11 + [C.c_void_p, C.c_char_p]
-        h.epi_seirp_sim_device.restype = C.c_int
         h.epi_seirp_sim_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
-        h.epi_random_npi_mc_device.restype = C.c_int
         h.epi_random_npi_mc_device.argtypes = [C.POINTER(McDesc)] + [C.c_void_p] * 8 + [C.c_void_p, C.c_char_p]
-        h.epi_pareto_front_device.restype = C.c_int
         h.epi_pareto_front_device.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_void_p, C.c_char_p]
-        h.epi_npi_cost_device.restype = C.c_int
         h.epi_npi_cost_device.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 6 + [C.c_void_p, C.c_char_p]
-        h.epi_sialpha_sim_host.restype = C.c_int
         h.epi_sialpha_sim_host.argtypes = [C.POINTER(SimDesc)] + [C.c_void_p] * 9 + [C.c_int, C.c_char_p]
-        h.epi_seirp_sim_host.restype = C.c_int
         h.epi_seirp_sim_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p]
-        h.epi_si_controlled_device.restype = C.c_int
         h.epi_si_controlled_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p, C.c_char_p]
-        h.epi_si_controlled_host.restype = C.c_int
         h.epi_si_controlled_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 5 + [C.c_int, C.c_char_p]
-        h.epi_npi_cost_host.restype = C.c_int
         h.epi_npi_cost_host.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 6 + [C.c_int, C.c_char_p]
-        h.epi_rt_expfit_validate.restype = C.c_int
         h.epi_rt_expfit_validate.argtypes = [C.POINTER(RtDesc), C.c_char_p]
-        h.epi_rt_expfit_run_device.restype = C.c_int
         h.epi_rt_expfit_run_device.argtypes = [C.POINTER(RtDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtOutputs),
                                                C.c_void_p, C.c_char_p]
-        h.epi_rt_expfit_run_host.restype = C.c_int
         h.epi_rt_expfit_run_host.argtypes = [C.POINTER(RtDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtOutputs),
                                              C.c_int, C.c_char_p]
-        h.epi_preprocess_workspace_bytes.restype = C.c_size_t
         h.epi_preprocess_workspace_bytes.argtypes = [C.POINTER(PreDesc)]
-        h.epi_preprocess_device.restype = C.c_int
         h.epi_preprocess_device.argtypes = [C.POINTER(PreDesc)] + [C.c_void_p] * 4 + [C.POINTER(PreOutputs), C.c_void_p,
                                                                                         C.c_size_t, C.c_void_p, C.c_char_p]
-        h.epi_nnls_affine_fit_device.restype = C.c_int
         h.epi_nnls_affine_fit_device.argtypes = [C.POINTER(NnlsDesc)] + [C.c_void_p] * 7 + [C.c_void_p, C.c_char_p]
-        h.epi_calib_copy_f64_device.restype = C.c_int
         h.epi_calib_copy_f64_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
-        h.epi_ekf_run_host_multi.restype = C.c_int
         h.epi_ekf_run_host_multi.argtypes = [C.POINTER(BatchDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_char_p]
-        h.epi_host_pool_release.restype = None
-        h.epi_sweep_run_device.restype = C.c_int
         h.epi_sweep_run_device.argtypes = [C.POINTER(BatchDesc), C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_size_t,
                                            C.POINTER(SweepDesc)] + [C.c_void_p] * 7 + [C.c_void_p, C.c_char_p]
-        h.epi_sweep_prescribe_host.restype = C.c_int
         h.epi_sweep_prescribe_host.argtypes = [C.POINTER(PrescribeDesc), C.POINTER(PrescribeInputs), C.POINTER(PrescribeOutputs),
                                                C.c_int, C.POINTER(C.c_int), C.c_char_p]
-        h.epi_sir_sim_device.restype = C.c_int
         h.epi_sir_sim_device.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
-        h.epi_sir_sim_host.restype = C.c_int
         h.epi_sir_sim_host.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p]
-        h.epi_preprocess_host.restype = C.c_int
         h.epi_preprocess_host.argtypes = [C.POINTER(PreDesc)] + [C.c_void_p] * 4 + [C.POINTER(PreOutputs), C.c_int, C.c_char_p]
-        h.epi_nnls_affine_fit_host.restype = C.c_int
         h.epi_nnls_affine_fit_host.argtypes = [C.POINTER(NnlsDesc)] + [C.c_void_p] * 7 + [C.c_int, C.c_char_p]
-        h.epi_random_npi_mc_host.restype = C.c_int
         h.epi_random_npi_mc_host.argtypes = [C.POINTER(McDesc)] + [C.c_void_p] * 8 + [C.c_int, C.c_char_p]
-        h.epi_lookahead_validate.restype = C.c_int
         h.epi_lookahead_validate.argtypes = [C.POINTER(LookaheadDesc), C.c_char_p]
-        h.epi_lookahead_workspace_bytes.restype = C.c_size_t
         h.epi_lookahead_workspace_bytes.argtypes = [C.POINTER(LookaheadDesc)]
-        h.epi_lookahead_run_device.restype = C.c_int
         h.epi_lookahead_run_device.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
-        h.epi_lookahead_run_host.restype = C.c_int
         h.epi_lookahead_run_host.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
                                              C.c_int, C.c_char_p]
-        h.epi_rtwin_validate.restype = C.c_int
-        h.epi_rtwin_validate.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_char_p]
-        h.epi_rtwin_run_device.restype = C.c_int
-        h.epi_rtwin_run_device.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_void_p, C.c_char_p]
-        h.epi_rtwin_run_host.restype = C.c_int
-        h.epi_rtwin_run_host.argtypes = [C.POINTER(RtwinDesc), C.c_void_p, C.POINTER(RtwinOutputs), C.c_int, C.c_char_p]
-        lasso_args = [C.POINTER(LassoDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LassoOutputs)]
-        h.epi_lasso_validate.restype = C.c_int
-        h.epi_lasso_validate.argtypes = lasso_args + [C.c_char_p]
-        h.epi_lasso_run_device.restype = C.c_int
-        h.epi_lasso_run_device.argtypes = lasso_args + [C.c_void_p, C.c_char_p]
-        h.epi_lasso_run_host.restype = C.c_int
-        h.epi_lasso_run_host.argtypes = lasso_args + [C.c_int, C.c_char_p]
-        robfit_args = [C.POINTER(RobfitDesc), C.c_void_p, C.c_void_p, C.POINTER(RobfitOutputs)]
-        h.epi_robfit_validate.restype = C.c_int
-        h.epi_robfit_validate.argtypes = robfit_args + [C.c_char_p]
-        h.epi_robfit_run_device.restype = C.c_int
-        h.epi_robfit_run_device.argtypes = robfit_args + [C.c_void_p, C.c_char_p]
-        h.epi_robfit_run_host.restype = C.c_int
-        h.epi_robfit_run_host.argtypes = robfit_args + [C.c_int, C.c_char_p]
-        ratemap_args = [C.POINTER(RatemapDesc), C.POINTER(RatemapInputs), C.POINTER(RatemapOutputs)]
-        h.epi_ratemap_validate.restype = C.c_int
-        h.epi_ratemap_validate.argtypes = ratemap_args + [C.c_char_p]
-        h.epi_ratemap_run_device.restype = C.c_int
-        h.epi_ratemap_run_device.argtypes = ratemap_args + [C.c_void_p, C.c_char_p]
-        h.epi_ratemap_run_host.restype = C.c_int
-        h.epi_ratemap_run_host.argtypes = ratemap_args + [C.c_int, C.c_char_p]
-        mldiv_args = [C.POINTER(MldivDesc), C.POINTER(MldivInputs), C.POINTER(MldivOutputs)]
-        h.epi_mldiv_validate.restype = C.c_int
-        h.epi_mldiv_validate.argtypes = mldiv_args + [C.c_char_p]
-        h.epi_mldiv_run_device.restype = C.c_int
-        h.epi_mldiv_run_device.argtypes = mldiv_args + [C.c_void_p, C.c_char_p]
-        h.epi_mldiv_run_host.restype = C.c_int
-        h.epi_mldiv_run_host.argtypes = mldiv_args + [C.c_int, C.c_char_p]
-        svr_args = [C.POINTER(SvrDesc), C.POINTER(SvrInputs), C.POINTER(SvrOutputs)]
-        h.epi_svr_validate.restype = C.c_int
-        h.epi_svr_validate.argtypes = svr_args + [C.c_char_p]
-        h.epi_svr_run_device.restype = C.c_int
-        h.epi_svr_run_device.argtypes = svr_args + [C.c_void_p, C.c_char_p]
-        h.epi_svr_run_host.restype = C.c_int
-        h.epi_svr_run_host.argtypes = svr_args + [C.c_int, C.c_char_p]
-        ens_args = [C.POINTER(EnsDesc), C.c_void_p, C.c_void_p, C.POINTER(EnsOutputs)]
-        h.epi_ens_validate.restype = C.c_int
-        h.epi_ens_validate.argtypes = ens_args + [C.c_char_p]
-        h.epi_ens_run_device.restype = C.c_int
-        h.epi_ens_run_device.argtypes = ens_args + [C.c_void_p, C.c_char_p]
-        h.epi_ens_run_host.restype = C.c_int
-        h.epi_ens_run_host.argtypes = ens_args + [C.c_int, C.c_char_p]
-        arfc_args = [C.POINTER(ArfcDesc), C.POINTER(ArfcInputs), C.POINTER(ArfcOutputs)]
-        h.epi_arfc_validate.restype = C.c_int
-        h.epi_arfc_validate.argtypes = arfc_args + [C.c_char_p]
-        h.epi_arfc_run_device.restype = C.c_int
-        h.epi_arfc_run_device.argtypes = arfc_args + [C.c_void_p, C.c_char_p]
-        h.epi_arfc_run_host.restype = C.c_int
-        h.epi_arfc_run_host.argtypes = arfc_args + [C.c_int, C.c_char_p]
-        fuse_args = [C.POINTER(FuseDesc), C.POINTER(FuseInputs), C.POINTER(FuseOutputs)]
-        h.epi_fuse_validate.restype = C.c_int
-        h.epi_fuse_validate.argtypes = fuse_args + [C.c_char_p]
-        h.epi_fuse_run_device.restype = C.c_int
-        h.epi_fuse_run_device.argtypes = fuse_args + [C.c_void_p, C.c_char_p]
-        h.epi_fuse_run_host.restype = C.c_int
-        h.epi_fuse_run_host.argtypes = fuse_args + [C.c_int, C.c_char_p]
+        for f in FAMILIES.values():
+            for kind, tail in FAMILY_TAILS.items():
+                getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail
+        own = ("epi_status_string", "epi_host_pool_release", "epi_ekf_workspace_bytes", "epi_preprocess_workspace_bytes",
+               "epi_lookahead_workspace_bytes")
+        h.epi_status_string.restype = C.c_char_p
+        h.epi_host_pool_release.restype = None
+        h.epi_ekf_workspace_bytes.restype = h.epi_preprocess_workspace_bytes.restype = h.epi_lookahead_workspace_bytes.restype = C.c_size_t
+        for name in ABI_SYMBOLS:                    # every other symbol returns an int
+            if name not in own:
+                getattr(h, name).restype = C.c_int
         if h.epi_abi_version() != ABI_VERSION:
             raise ImportError("libepiekf.so ABI version mismatch")
         _lib = h

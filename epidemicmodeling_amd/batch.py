@@ -10,8 +10,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 from . import layout as L
+from ._call import _rtwin_names, check_lasso_folds, lasso_folds  # noqa: F401  (their home is _call; public here)
 
 OUT_NAMES = ["u_opt", "u_opt_smooth", "S_MINUS", "S_PLUS", "S_SMOOTH", "P_MINUS", "P_PLUS", "P_SMOOTH",
              "K_GAIN", "innovations", "rho"]
@@ -26,6 +27,45 @@ def out_mask_of(names) -> int:
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class DeviceBackend:
+    """The device entry points' side of a family call (_call): inputs become contiguous tensors on `device`, outputs are
+    allocated there, the call is enqueued on `stream` (default: the device's current stream)."""
+    kind, checks_folds = "run_device", True
+    _DTYPES = {np.float64: torch.float64, np.int32: torch.int32, np.float32: torch.float32}
+
+    def __init__(self, device, stream=None):
+        self.device, self.stream, self.keep = torch.device(device), stream, []
+
+    def _put(self, v, dtype):
+        if v is not None:
+            v = v.to(self.device, dtype).contiguous()
+            self.keep.append(v)
+        return v
+
+    def f64(self, v):
+        return self._put(v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64),
+                         torch.float64)
+
+    def i32(self, v):
+        return self._put(v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)),
+                         torch.int32)
+
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=self._DTYPES[dtype], device=self.device)
+
+    ptr = staticmethod(_ptr)
+
+    def resident(self, v):
+        return isinstance(v, torch.Tensor)
+
+    def host(self, v):
+        return v.cpu().numpy() if isinstance(v, torch.Tensor) else v
+
+    def tail(self):
+        st = torch.cuda.current_stream(self.device) if self.stream is None else self.stream
+        return C.c_void_p(st.cuda_stream)
 
 
 class DeviceWorkload:
@@ -740,18 +780,6 @@ def lookahead_host(w, truth, population, F, M=60, device=0, chains=False, shape=
     return out
 
 
-def _rtwin_names(methods, status=True):
-    bits = _lib.rtwin_methods(methods)
-    names = []
-    if bits & 1:
-        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("llr_")]
-    if bits & 2:
-        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("gr_")]
-    if bits & 4:
-        names += [n for n in _lib.RTWIN_OUT_F64 if n.startswith("nls_")] + (list(_lib.RTWIN_OUT_I32) if status else [])
-    return bits, names
-
-
 def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, methods=("LogLinReg", "GenRatios", "NonlinLS"),
               device="cuda:0"):
     """Tools/Rt_ExpFitLogLinReg.m, Rt_ExpFitGenRatios.m and Rt_ExpFitNonlinLS.m over every column of new_cases [L, R] (days x
@@ -760,50 +788,7 @@ def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, 
     llr_{Rt, A, Lambda, ExpFit}, gr_{Rt, Lambda, RtSmoothed, LambdaSmoothed}, nls_{Rt, A, Lambda, ExpFit} and the int32
     nls_status / nls_iters (status codes in _lib.RTWIN_STATUS), for the methods asked.  Enqueued on the current stream (where
     the input copy and the outputs are allocated) without a host synchronisation."""
-    dev = torch.device(device)
-    x = new_cases if isinstance(new_cases, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(new_cases), dtype=torch.float64)
-    x = x.to(dev, torch.float64).contiguous()
-    if x.dim() != 2:
-        raise ValueError("new_cases must be [L, R]")
-    L_, R = x.shape
-    bits, names = _rtwin_names(methods)
-    d = _lib.make_rtwin_desc(R, L_, wlen, time_unit, causal, generation_period, bits)
-    out = {n: torch.empty((L_, R), dtype=torch.int32 if n in _lib.RTWIN_OUT_I32 else torch.float64, device=dev) for n in names}
-    outs = _lib.RtwinOutputs()
-    for n in _lib.RTWIN_OUT_NAMES:
-        setattr(outs, n, _ptr(out.get(n)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_rtwin_run_device(C.byref(d), _ptr(x), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
-
-
-def lasso_folds(D, K, R, seed=0):
-    """A cross-validation partition for lasso_cv: fold [D, R] int32 in 0 .. K-1.  Every region gets its own random
-    permutation of the D days (np.random.default_rng(seed), regions in order); the fold sizes are those of cvpartition's
-    KFold: the first D mod K folds get ceil(D / K) days, the rest floor(D / K).  Deterministic for a given seed."""
-    D, K, R = int(D), int(K), int(R)
-    if not 2 <= K <= D:
-        raise ValueError("lasso_folds needs 2 <= K <= D")
-    rng = np.random.default_rng(seed)
-    sizes = np.full(K, D // K)
-    sizes[:D % K] += 1
-    label = np.repeat(np.arange(K, dtype=np.int32), sizes)
-    fold = np.empty((D, R), dtype=np.int32)
-    for r in range(R):
-        fold[rng.permutation(D), r] = label
-    return fold
-
-
-def check_lasso_folds(fold, K):
-    """ValueError unless fold [D, R] holds only 0 .. K-1 and leaves no fold empty in any region"""
-    f = np.asarray(fold)
-    if f.ndim != 2 or f.min() < 0 or f.max() >= K:
-        raise ValueError("folds must be [D, R] with values in 0 .. K-1")
-    for r in range(f.shape[1]):
-        if np.bincount(f[:, r], minlength=K).min() == 0:
-            raise ValueError(f"region {r}: a fold is empty")
+    return _call.rt_window(DeviceBackend(device), new_cases, wlen, time_unit, causal, generation_period, methods)
 
 
 def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4, max_iter=100000,
@@ -815,32 +800,7 @@ def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, 
     with K >= 2, mse, se [NL, R], idx_min_mse, idx_1se [R] (0-based), a [n, R] = B at idx_min_mse, b [R] its intercept.
     Enqueued on the current stream without a host synchronisation (a folds tensor already on the device is not checked
     here: a bad partition gives its regions status bad_folds)."""
-    dev = torch.device(device)
-    t = lambda v: v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)
-    X, y = t(X).to(dev, torch.float64).contiguous(), t(y).to(dev, torch.float64).contiguous()
-    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, n, R] and y [D, R]")
-    D, n, R = X.shape
-    K = int(K)
-    f = None
-    if K >= 2:
-        if folds is None:
-            folds = lasso_folds(D, K, R, seed)
-        if not isinstance(folds, torch.Tensor):
-            check_lasso_folds(folds, K)
-            folds = torch.as_tensor(np.ascontiguousarray(folds, dtype=np.int32))
-        f = folds.to(dev, torch.int32).contiguous()
-    d = _lib.make_lasso_desc(R, D, n, K, num_lambda, lambda_ratio, rel_tol, max_iter)
-    out = {k: torch.empty(sh, dtype=torch.int32 if k in _lib.LASSO_OUT_I32 else torch.float64, device=dev)
-           for k, sh in _lib.lasso_shapes(R, D, n, K, num_lambda).items()}
-    outs = _lib.LassoOutputs()
-    for k in _lib.LASSO_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_lasso_run_device(C.byref(d), _ptr(X), _ptr(y), _ptr(f), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    return _call.lasso_cv(DeviceBackend(device), X, y, K, folds, seed, num_lambda, lambda_ratio, rel_tol, max_iter)
 
 
 def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter=50, outputs=None, device="cuda:0"):
@@ -851,25 +811,7 @@ def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter
     outputs: names out of a, b_item, sigma, iters, status [n, R], weights [D, n, R], b [R] (default: all but weights).
     Returns a dict of torch tensors (iters, status int32; status is a set of _lib.ROBFIT_STATUS_BITS).  Enqueued on the
     current stream without a host synchronisation."""
-    dev = torch.device(device)
-    t = lambda v: v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)
-    X, y = t(X).to(dev, torch.float64).contiguous(), t(y).to(dev, torch.float64).contiguous()
-    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, n, R] and y [D, R]")
-    D, n, R = X.shape
-    names = _lib.robfit_out_names(outputs)
-    d = _lib.make_robfit_desc(R, D, n, int(bool(robust)), max_iter, lower, upper)
-    shapes = _lib.robfit_shapes(R, D, n)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.ROBFIT_OUT_I32 else torch.float64, device=dev)
-           for k in _lib.ROBFIT_OUT_NAMES if k in names}
-    outs = _lib.RobfitOutputs()
-    for k in _lib.ROBFIT_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_robfit_run_device(C.byref(d), _ptr(X), _ptr(y), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    return _call.robust_affine_fit(DeviceBackend(device), X, y, robust, lower, upper, max_iter, outputs)
 
 
 def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags=(3, 5, 7), ridge=1e-6, lambda_threshold=0.1,
@@ -886,37 +828,8 @@ def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags
     outputs: names out of map [K, F, R], x_mx [F, R], y_filled [T, R], lambda_hat, new_cases_est [K, T, R], tracker [T, R],
     status [K, R] (int32, a set of _lib.RATEMAP_STATUS_BITS; default: all that apply).  Returns a dict of torch tensors.
     Enqueued on the current stream without a host synchronisation."""
-    dev = torch.device(device)
-    t = lambda v: None if v is None else (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
-    ip, ns, y, extra, lambda_in = t(ip), t(new_smoothed), t(y), t(extra), t(lambda_in)
-    if ip.dim() != 3 or ns.dim() != 2 or ns.shape != (ip.shape[0], ip.shape[2]):
-        raise ValueError("ip must be [T, n, R] and new_smoothed [T, R]")
-    T, n, R = ip.shape
-    nt = _lib.ratemap_n_train(n_train)
-    K = int(nt.size)
-    fit = lambda_in is None
-    if fit and y is None:
-        raise ValueError("y (to fit) or lambda_in (to skip the fit) is needed")
-    if (y is not None and y.shape != (T, R)) or (extra is not None and (extra.dim() != 3 or extra.shape[0] != T or extra.shape[2] != R)) \
-            or (lambda_in is not None and lambda_in.shape != (K, T, R)):
-        raise ValueError("y must be [T, R], extra [T, E, R] and lambda_in [K, T, R]")
-    E = 0 if extra is None else int(extra.shape[1])
-    names = _lib.ratemap_out_names(outputs, fit, y is not None)
-    d = _lib.make_ratemap_desc(T, n, R, E, K, lags, int(fit), effect_lag, ridge, lambda_threshold, reduction_effect)
-    shapes = _lib.ratemap_shapes(T, n, R, E, K, d.n_lags)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.RATEMAP_OUT_I32 else torch.float64, device=dev)
-           for k in _lib.RATEMAP_OUT_NAMES if k in names}
-    ins = _lib.RatemapInputs()
-    ins.ip, ins.y, ins.new_smoothed, ins.extra, ins.lambda_in = _ptr(ip), _ptr(y), _ptr(ns), _ptr(extra), _ptr(lambda_in)
-    ins.n_train = nt.ctypes.data
-    outs = _lib.RatemapOutputs()
-    for k in _lib.RATEMAP_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_ratemap_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    return _call.rate_map(DeviceBackend(device), ip, new_smoothed, n_train, y, extra, lambda_in, lags, ridge, lambda_threshold,
+                          reduction_effect, effect_lag, outputs)
 
 
 def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device="cuda:0"):
@@ -929,29 +842,7 @@ def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device="cuda:0"):
     outputs: names out of m [K, F, R], rank [K, R], perm [K, F, R] (0-based, pivot order), rdiag [K, F, R], resid [K, R],
     fitted [K, D, R], status [K, R] (int32, a set of _lib.MLDIV_STATUS_BITS; default: all).  Returns a dict of torch tensors.
     Enqueued on the current stream without a host synchronisation."""
-    dev = torch.device(device)
-    t = lambda v: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
-    X, y = t(X), t(y)
-    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, F, R] and y [D, R]")
-    D, F, R = X.shape
-    nr = _lib.mldiv_n_rows(n_rows, D)
-    K = int(nr.size)
-    names = _lib.mldiv_out_names(outputs)
-    d = _lib.make_mldiv_desc(D, F, R, K, tol_scale)
-    shapes = _lib.mldiv_shapes(D, F, R, K)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.MLDIV_OUT_I32 else torch.float64, device=dev)
-           for k in _lib.MLDIV_OUT_NAMES if k in names}
-    ins = _lib.MldivInputs()
-    ins.X, ins.y, ins.n_rows = _ptr(X), _ptr(y), nr.ctypes.data
-    outs = _lib.MldivOutputs()
-    for k in _lib.MLDIV_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_mldiv_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    return _call.mldivide(DeviceBackend(device), X, y, n_rows, tol_scale, outputs)
 
 
 def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale=None, tol=1e-3, max_iter=100000, outputs=None,
@@ -967,36 +858,7 @@ def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale
     outputs: names out of beta [K, D, R], bias [K, R], w [K, F, R] (linear kernel only), fitted [K, D, R] (over all D rows: the
     rows beyond n_rows are the prediction), n_iter, gap, n_sv, status [K, R] (status: a set of _lib.SVR_STATUS_BITS; default:
     all).  Returns a dict of torch tensors.  Enqueued on the current stream without a host synchronisation."""
-    dev = torch.device(device)
-    t = lambda v: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64)).to(dev, torch.float64).contiguous()
-    X, y = t(X), t(y)
-    if X.dim() != 3 or y.dim() != 2 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, F, R] and y [D, R]")
-    D, F, R = X.shape
-    nr = _lib.mldiv_n_rows(n_rows, D)
-    K = int(nr.size)
-    names = _lib.svr_out_names(outputs, kernel)
-    d = _lib.make_svr_desc(D, F, R, K, kernel, tol, max_iter)
-    if box is None or epsilon is None or kernel_scale is None:
-        dflt = _lib.svr_defaults(y[:max(1, min(int(nr.max()), D))].cpu().numpy(), kernel)
-        box, epsilon = dflt["box"] if box is None else box, dflt["epsilon"] if epsilon is None else epsilon
-        kernel_scale = dflt["kernel_scale"] if kernel_scale is None else kernel_scale
-    reg = lambda v, name: v.to(dev, torch.float64).contiguous() if isinstance(v, torch.Tensor) and v.shape == (R,) else t(_lib.svr_region_array(v.cpu().numpy() if isinstance(v, torch.Tensor) else v, R, name))
-    box, epsilon, kernel_scale = reg(box, "box"), reg(epsilon, "epsilon"), reg(kernel_scale, "kernel_scale")
-    shapes = _lib.svr_shapes(D, F, R, K)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in _lib.SVR_OUT_I32 else torch.float64, device=dev)
-           for k in _lib.SVR_OUT_NAMES if k in names}
-    ins = _lib.SvrInputs()
-    ins.X, ins.y, ins.n_rows = _ptr(X), _ptr(y), nr.ctypes.data
-    ins.box, ins.epsilon, ins.kernel_scale = _ptr(box), _ptr(epsilon), _ptr(kernel_scale)
-    outs = _lib.SvrOutputs()
-    for k in _lib.SVR_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_svr_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    return _call.svr(DeviceBackend(device), X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, outputs)
 
 
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, stream=None):
@@ -1034,18 +896,10 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
     bad = [k for k in names if k not in _lib.ENS_OUT_NAMES]
     if bad:
         raise ValueError(f"unknown outputs {bad}")
-    err = C.create_string_buffer(256)
     shapes = _lib.ens_shapes(T, rows, R, d.n_q, d.derive_newcases)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "count" else torch.float64, device=dev)
-           for k in _lib.ENS_OUT_NAMES if k == "count" or k in names}
+    out = _call.run_family("ens", DeviceBackend(dev, stream), d, [_ptr(src), _ptr(pop)], shapes, names + ["count"])
     if src.dim() == 2:
         out = {k: v.squeeze(-2) for k, v in out.items()}
-    outs = _lib.EnsOutputs()
-    for k in _lib.ENS_OUT_NAMES:
-        setattr(outs, k, _ptr(out.get(k)))
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    rc = _lib.lib().epi_ens_run_device(C.byref(d), _ptr(src), _ptr(pop), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
     return out
 
 
@@ -1109,15 +963,7 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     ins = _lib.ArfcInputs()
     for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, ser, A, noise_var)):
         setattr(ins, k, _ptr(v))
-    err = C.create_string_buffer(256)
-    shapes = _lib.arfc_shapes(R, D, L, p, H)
-    out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "status" else torch.float64, device=dev) for k in _lib.ARFC_OUT_NAMES}
-    outs = _lib.ArfcOutputs()
-    for k in _lib.ARFC_OUT_NAMES:
-        setattr(outs, k, _ptr(out[k]))
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    rc = _lib.lib().epi_arfc_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
+    out = _call.run_family("arfc", DeviceBackend(dev, stream), d, [C.byref(ins)], _lib.arfc_shapes(R, D, L, p, H), _lib.ARFC_OUT_NAMES)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
 
 
@@ -1179,16 +1025,9 @@ def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, lane_block=0, outputs=FUSE_OU
     d = _lib.make_fuse_desc(m, B, T, form, p_solver=p_solver, lane_block=blk, storage=int(sf.dtype == torch.float32))
     shapes = _lib.fuse_shapes(m, B, T, blk)
     abi = {"s": "s_out", "P": "P_out", "d2": "d2", "rank": "rank", "status": "status"}
-    dt = {"s": sf.dtype, "P": sf.dtype, "d2": torch.float64, "rank": torch.int32, "status": torch.int32}
-    out = {k: torch.empty(shapes[abi[k]], dtype=dt[k], device=dev) for k in outputs}
     ins = _lib.FuseInputs()
     for k, v in zip(_lib.FUSE_IN_NAMES, (sf, Pf, sb, Pb)):
         setattr(ins, k, _ptr(v))
-    outs = _lib.FuseOutputs()
-    for k in outputs:
-        setattr(outs, abi[k], _ptr(out[k]))
-    err = C.create_string_buffer(256)
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    rc = _lib.lib().epi_fuse_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(st.cuda_stream), err)
-    _lib.check(rc, err)
-    return out
+    out = _call.run_family("fuse", DeviceBackend(dev, stream), d, [C.byref(ins)], shapes, [abi[k] for k in outputs],
+                           f32=("s_out", "P_out") if sf.dtype == torch.float32 else ())
+    return {k: out[abi[k]] for k in outputs}

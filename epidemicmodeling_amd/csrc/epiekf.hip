@@ -932,6 +932,27 @@ static int hip_fail(char *err, hipError_t e, const char *what)
     return EPI_ERR_HIP;
 }
 
+// [launch slices] -- host code only; tests/launch_slices_test.cpp compiles the lines between the two markers on their own
+// A grid holds at most `cap` workgroups: launch(i0, ni) for every slice [i0, i0 + ni) of [0, items) in order, until one fails.
+template <class F>
+static hipError_t for_slices(int64_t items, int64_t cap, F &&launch)
+{
+    for (int64_t i0 = 0; i0 < items; i0 += cap) {
+        const hipError_t e = launch(i0, (unsigned)(items - i0 < cap ? items - i0 : cap));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// A launch carries at most N counts by value: src[k0 .. k0 + kc) goes into the launch arguments' array, kc = min(K - k0, N).
+template <int N>
+static int copy_counts(int (&dst)[N], const int32_t *src, int k0, int K)
+{
+    const int kc = K - k0 < N ? K - k0 : N;
+    for (int kk = 0; kk < kc; kk++) dst[kk] = src[k0 + kk];
+    return kc;
+}
+// [/launch slices]
+
 struct WsLayout { size_t s_minus, s_plus, p_minus, p_plus, x, rank, flag, innov, hand_s, hand_p, hand_i, only, status, total; };
 static int lane_block_of(const epi_batch_desc *d) { return (d->lane_block <= 0 || d->lane_block >= d->B) ? d->B : d->lane_block; }
 static size_t padded_chains(const epi_batch_desc *d)
@@ -3234,18 +3255,18 @@ int epi_robfit_run_device(const epi_robfit_desc *d, const double *X, const doubl
     hipError_t e;
     if (out->a || out->b_item || out->sigma || out->iters || out->status || out->weights) {
         const int64_t items = (int64_t)d->n * d->R;
-        for (int64_t i0 = 0; i0 < items; i0 += kRfLaunchItems) {   // one 64-lane workgroup per item, in slices (robust_fit.hpp)
+        e = for_slices(items, kRfLaunchItems, [&](int64_t i0, unsigned ni) {    // one 64-lane workgroup per item, in slices (robust_fit.hpp)
             g.item0 = (long long)i0;
-            const unsigned ni = (unsigned)(items - i0 < kRfLaunchItems ? items - i0 : kRfLaunchItems);
-            if ((e = rf_dispatch(g, ni, false, st)) != hipSuccess) return hip_fail(err, e, "robfit_items launch");
-        }
+            return rf_dispatch(g, ni, false, st);
+        });
+        if (e != hipSuccess) return hip_fail(err, e, "robfit_items launch");
     }
     if (out->b) {
-        for (int64_t r0 = 0; r0 < d->R; r0 += kRfLaunchItems) {    // one 64-lane workgroup per region, behind the items
+        e = for_slices(d->R, kRfLaunchItems, [&](int64_t r0, unsigned nr) {     // one 64-lane workgroup per region, behind the items
             g.item0 = (long long)r0;
-            const unsigned nr = (unsigned)(d->R - r0 < kRfLaunchItems ? d->R - r0 : kRfLaunchItems);
-            if ((e = rf_dispatch(g, nr, true, st)) != hipSuccess) return hip_fail(err, e, "robfit_intercept launch");
-        }
+            return rf_dispatch(g, nr, true, st);
+        });
+        if (e != hipSuccess) return hip_fail(err, e, "robfit_intercept launch");
     }
     return EPI_OK;
 }
@@ -3342,24 +3363,22 @@ int epi_ratemap_run_device(const epi_ratemap_desc *d, const epi_ratemap_inputs *
     const hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     if (out->x_mx || out->y_filled || out->tracker) {
-        for (int64_t r0 = 0; r0 < d->R; r0 += kRmLaunchItems) {        // one workgroup per region
+        e = for_slices(d->R, kRmLaunchItems, [&](int64_t r0, unsigned nr) {     // one workgroup per region
             g.item0 = (long long)r0;
-            const unsigned nr = (unsigned)(d->R - r0 < kRmLaunchItems ? d->R - r0 : kRmLaunchItems);
             hipLaunchKernelGGL(ratemap_region, dim3(nr), dim3(kRmThreads), 0, st, g);
-            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ratemap_region launch");
-        }
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return hip_fail(err, e, "ratemap_region launch");
     }
     if (out->map || out->lambda_hat || out->new_cases_est || out->status) {
         for (int k0 = 0; k0 < d->K; k0 += kRmTrainEnds) {              // a launch carries up to 64 train ends by value
-            const int kc = d->K - k0 < kRmTrainEnds ? d->K - k0 : kRmTrainEnds;
+            const int kc = copy_counts(g.nt, in->n_train, k0, d->K);
             g.k0 = k0;
-            for (int kk = 0; kk < kc; kk++) g.nt[kk] = in->n_train[k0 + kk];
-            const int64_t items = (int64_t)kc * d->R;
-            for (int64_t i0 = 0; i0 < items; i0 += kRmLaunchItems) {   // one workgroup per item, in slices (rate_map.hpp)
+            e = for_slices((int64_t)kc * d->R, kRmLaunchItems, [&](int64_t i0, unsigned ni) {   // one workgroup per item, in slices (rate_map.hpp)
                 g.item0 = (long long)i0;
-                const unsigned ni = (unsigned)(items - i0 < kRmLaunchItems ? items - i0 : kRmLaunchItems);
-                if ((e = rm_dispatch(g, ni, st)) != hipSuccess) return hip_fail(err, e, "ratemap_items launch");
-            }
+                return rm_dispatch(g, ni, st);
+            });
+            if (e != hipSuccess) return hip_fail(err, e, "ratemap_items launch");
         }
     }
     return EPI_OK;
@@ -3441,24 +3460,20 @@ int epi_mldiv_run_device(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, co
     const hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     for (int k0 = 0; k0 < d->K; k0 += kMlRowCounts) {                  // a launch carries up to 64 row counts by value
-        const int kc = d->K - k0 < kMlRowCounts ? d->K - k0 : kMlRowCounts;
+        const int kc = copy_counts(g.nr, in->n_rows, k0, d->K);
         g.k0 = k0;
         int nmax = 1;
-        for (int kk = 0; kk < kc; kk++) {
-            g.nr[kk] = in->n_rows[k0 + kk];
-            nmax = g.nr[kk] > nmax ? g.nr[kk] : nmax;
-        }
+        for (int kk = 0; kk < kc; kk++) nmax = g.nr[kk] > nmax ? g.nr[kk] : nmax;
         const size_t shm = ml_lds_bytes(nmax, d->F);
         if (shm > 64u * 1024u &&        // above the default dynamic-LDS limit
             (e = hipFuncSetAttribute((const void *)mldivide_items, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess)
             return hip_fail(err, e, "hipFuncSetAttribute");
-        const int64_t items = (int64_t)kc * d->R;
-        for (int64_t i0 = 0; i0 < items; i0 += kMlLaunchItems) {       // one workgroup per item, in slices (mldivide.hpp)
+        e = for_slices((int64_t)kc * d->R, kMlLaunchItems, [&](int64_t i0, unsigned ni) {       // one workgroup per item, in slices (mldivide.hpp)
             g.item0 = (long long)i0;
-            const unsigned ni = (unsigned)(items - i0 < kMlLaunchItems ? items - i0 : kMlLaunchItems);
             hipLaunchKernelGGL(mldivide_items, dim3(ni), dim3(kMlThreads), shm, st, g);
-            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "mldivide_items launch");
-        }
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return hip_fail(err, e, "mldivide_items launch");
     }
     return EPI_OK;
 }
@@ -3539,23 +3554,20 @@ int epi_svr_run_device(const epi_svr_desc *d, const epi_svr_inputs *in, const ep
     const hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     for (int k0 = 0; k0 < d->K; k0 += kSvRowCounts) {                  // a launch carries up to 64 row counts by value
-        const int kc = d->K - k0 < kSvRowCounts ? d->K - k0 : kSvRowCounts;
+        const int kc = copy_counts(g.nr, in->n_rows, k0, d->K);
         g.k0 = k0;
         int nmax = 1, nmin = d->D;
         for (int kk = 0; kk < kc; kk++) {
-            g.nr[kk] = in->n_rows[k0 + kk];
             nmax = g.nr[kk] > nmax ? g.nr[kk] : nmax;
             nmin = g.nr[kk] < nmin ? g.nr[kk] : nmin;
         }
         const size_t doubles = sv_lds_doubles(nmax, nmin, d->D, d->F, gau);
         g.lds = (int)doubles;
-        const int64_t items = (int64_t)kc * d->R;
-        for (int64_t i0 = 0; i0 < items; i0 += kSvLaunchItems) {       // one workgroup per item, in slices (svr.hpp)
+        e = for_slices((int64_t)kc * d->R, kSvLaunchItems, [&](int64_t i0, unsigned ni) {       // one workgroup per item, in slices (svr.hpp)
             g.item0 = (long long)i0;
-            const unsigned ni = (unsigned)(items - i0 < kSvLaunchItems ? items - i0 : kSvLaunchItems);
-            e = gau ? sv_dispatch<true>(g, nmax, ni, doubles * sizeof(double), st) : sv_dispatch<false>(g, nmax, ni, doubles * sizeof(double), st);
-            if (e != hipSuccess) return hip_fail(err, e, "svr_items launch");
-        }
+            return gau ? sv_dispatch<true>(g, nmax, ni, doubles * sizeof(double), st) : sv_dispatch<false>(g, nmax, ni, doubles * sizeof(double), st);
+        });
+        if (e != hipSuccess) return hip_fail(err, e, "svr_items launch");
     }
     return EPI_OK;
 }
@@ -3622,20 +3634,18 @@ int epi_ens_run_device(const epi_ens_desc *d, const void *src, const double *pop
     for (int k = 0; k < d->n_q; k++) g.q[k] = d->q[k];
     g.mean = out->mean; g.std = out->std; g.mn = out->min; g.mx = out->max; g.quant = out->quantiles; g.count = out->count;
     const int64_t items = (int64_t)d->T * g.rows_out * d->R;
-    for (int64_t i0 = 0; i0 < items; i0 += kEnsLaunchItems) {      // one 64-lane workgroup per item, in slices (ens_summary.hpp)
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = for_slices(items, kEnsLaunchItems, [&](int64_t i0, unsigned ni) {      // one 64-lane workgroup per item, in slices (ens_summary.hpp)
         g.item0 = (long long)i0;
-        const unsigned ni = (unsigned)(items - i0 < kEnsLaunchItems ? items - i0 : kEnsLaunchItems);
-        const hipStream_t st = (hipStream_t)stream;
-        hipError_t e;
-        if (d->D <= 64) e = ens_launch<1>(g, ni, st);              // registers per lane: P / 64, P the power of two >= D
-        else if (d->D <= 128) e = ens_launch<2>(g, ni, st);
-        else if (d->D <= 256) e = ens_launch<4>(g, ni, st);
-        else if (d->D <= 512) e = ens_launch<8>(g, ni, st);
-        else if (d->D <= 1024) e = ens_launch<16>(g, ni, st);
-        else if (d->D <= 2048) e = ens_launch<32>(g, ni, st);
-        else e = ens_launch<64>(g, ni, st);
-        if (e != hipSuccess) return hip_fail(err, e, "ens_summary launch");
-    }
+        if (d->D <= 64) return ens_launch<1>(g, ni, st);           // registers per lane: P / 64, P the power of two >= D
+        if (d->D <= 128) return ens_launch<2>(g, ni, st);
+        if (d->D <= 256) return ens_launch<4>(g, ni, st);
+        if (d->D <= 512) return ens_launch<8>(g, ni, st);
+        if (d->D <= 1024) return ens_launch<16>(g, ni, st);
+        if (d->D <= 2048) return ens_launch<32>(g, ni, st);
+        return ens_launch<64>(g, ni, st);
+    });
+    if (e != hipSuccess) return hip_fail(err, e, "ens_summary launch");
     return EPI_OK;
 }
 

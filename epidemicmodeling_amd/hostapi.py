@@ -7,11 +7,48 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from . import layout as L
 
 
+class HostBackend:
+    """The host entry points' side of a family call (_call): inputs become contiguous NumPy arrays, which it keeps alive,
+    outputs are NumPy arrays, the library stages both through device `device` and returns when the results are back."""
+    kind, checks_folds = "run_host", False
+
+    def __init__(self, device):
+        self.device, self.keep = int(device), []
+
+    def _put(self, v, dtype):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=dtype)
+            self.keep.append(v)
+        return v
+
+    def f64(self, v):
+        return self._put(v, np.float64)
+
+    def i32(self, v):
+        return self._put(v, np.int32)
+
+    def empty(self, shape, dtype):
+        return np.empty(shape, dtype=dtype)
+
+    def ptr(self, a):
+        return None if a is None else a.ctypes.data
+
+    def resident(self, v):
+        return False
+
+    def host(self, v):
+        return v
+
+    def tail(self):
+        return self.device
+
+
 def _f(a, keep):
+    """the flat-argument calls' inputs: the address of `a` as a contiguous float64 array, kept alive in `keep`"""
     if a is None:
         return None
     a = np.ascontiguousarray(a, dtype=np.float64)
@@ -139,71 +176,19 @@ def rt_window(new_cases, wlen, time_unit=1.0, causal=1, generation_period=None, 
               device=0):
     """epi_rtwin_run_host: the three sliding-window growth-rate estimators over new_cases [L, R] (NumPy in and out,
     synchronous).  Returns the dict of batch.rt_window as NumPy arrays."""
-    keep = []
-    x = np.asarray(new_cases, dtype=np.float64)
-    if x.ndim != 2:
-        raise ValueError("new_cases must be [L, R]")
-    L_, R = x.shape
-    bits = _lib.rtwin_methods(methods)
-    names = [n for n, b in zip(_lib.RTWIN_OUT_NAMES, [1] * 4 + [2] * 4 + [4] * 6) if bits & b]
-    d = _lib.make_rtwin_desc(R, L_, wlen, time_unit, causal, generation_period, bits)
-    out = {n: np.empty((L_, R), dtype=np.int32 if n in _lib.RTWIN_OUT_I32 else np.float64) for n in names}
-    outs = _lib.RtwinOutputs()
-    for n in _lib.RTWIN_OUT_NAMES:
-        setattr(outs, n, out[n].ctypes.data if n in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_rtwin_run_host(C.byref(d), _f(x, keep), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.rt_window(HostBackend(device), new_cases, wlen, time_unit, causal, generation_period, methods)
 
 
 def lasso_cv(X, y, K=50, folds=None, seed=0, num_lambda=100, lambda_ratio=1e-4, rel_tol=1e-4, max_iter=100000, device=0):
     """epi_lasso_run_host: lasso(X, y, 'CV', K) for every region (NumPy in and out, synchronous).  X [D, n, R], y [D, R],
     folds [D, R] (default batch.lasso_folds(D, K, R, seed)).  Returns the dict of batch.lasso_cv as NumPy arrays."""
-    from .batch import lasso_folds
-    keep = []
-    X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
-    if X.ndim != 3 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, n, R] and y [D, R]")
-    D, n, R = X.shape
-    K = int(K)
-    f = None
-    if K >= 2:
-        f = np.ascontiguousarray(lasso_folds(D, K, R, seed) if folds is None else folds, dtype=np.int32)
-        keep.append(f)
-    d = _lib.make_lasso_desc(R, D, n, K, num_lambda, lambda_ratio, rel_tol, max_iter)
-    out = {k: np.empty(sh, dtype=np.int32 if k in _lib.LASSO_OUT_I32 else np.float64)
-           for k, sh in _lib.lasso_shapes(R, D, n, K, num_lambda).items()}
-    outs = _lib.LassoOutputs()
-    for k in _lib.LASSO_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_lasso_run_host(C.byref(d), _f(X, keep), _f(y, keep), None if f is None else f.ctypes.data,
-                                       C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.lasso_cv(HostBackend(device), X, y, K, folds, seed, num_lambda, lambda_ratio, rel_tol, max_iter)
 
 
 def robust_affine_fit(X, y, robust=True, lower=0.0, upper=float("inf"), max_iter=50, outputs=None, device=0):
     """epi_robfit_run_host: the element-wise robust regression of batch.robust_affine_fit on NumPy arrays (synchronous).
     X [D, n, R], y [D, R].  Returns the dict of batch.robust_affine_fit as NumPy arrays."""
-    keep = []
-    X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
-    if X.ndim != 3 or y.shape != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, n, R] and y [D, R]")
-    D, n, R = X.shape
-    names = _lib.robfit_out_names(outputs)
-    d = _lib.make_robfit_desc(R, D, n, int(bool(robust)), max_iter, lower, upper)
-    shapes = _lib.robfit_shapes(R, D, n)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.ROBFIT_OUT_I32 else np.float64)
-           for k in _lib.ROBFIT_OUT_NAMES if k in names}
-    outs = _lib.RobfitOutputs()
-    for k in _lib.ROBFIT_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_robfit_run_host(C.byref(d), _f(X, keep), _f(y, keep), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.robust_affine_fit(HostBackend(device), X, y, robust, lower, upper, max_iter, outputs)
 
 
 def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags=(3, 5, 7), ridge=1e-6, lambda_threshold=0.1,
@@ -211,61 +196,14 @@ def rate_map(ip, new_smoothed, n_train, y=None, extra=None, lambda_in=None, lags
     """epi_ratemap_run_host: the NPI-to-growth-rate predictor of batch.rate_map on NumPy arrays (synchronous).
     ip [T, n, R], new_smoothed [T, R], y [T, R] or lambda_in [K, T, R], extra [T, E, R].  Returns the dict of batch.rate_map
     as NumPy arrays."""
-    keep = []
-    ip, ns = np.asarray(ip, dtype=np.float64), np.asarray(new_smoothed, dtype=np.float64)
-    if ip.ndim != 3 or ns.shape != (ip.shape[0], ip.shape[2]):
-        raise ValueError("ip must be [T, n, R] and new_smoothed [T, R]")
-    T, n, R = ip.shape
-    nt = _lib.ratemap_n_train(n_train)
-    K = int(nt.size)
-    fit = lambda_in is None
-    if fit and y is None:
-        raise ValueError("y (to fit) or lambda_in (to skip the fit) is needed")
-    if (y is not None and np.shape(y) != (T, R)) or (extra is not None and (np.ndim(extra) != 3 or np.shape(extra)[0] != T or np.shape(extra)[2] != R)) \
-            or (lambda_in is not None and np.shape(lambda_in) != (K, T, R)):
-        raise ValueError("y must be [T, R], extra [T, E, R] and lambda_in [K, T, R]")
-    E = 0 if extra is None else int(np.shape(extra)[1])
-    names = _lib.ratemap_out_names(outputs, fit, y is not None)
-    d = _lib.make_ratemap_desc(T, n, R, E, K, lags, int(fit), effect_lag, ridge, lambda_threshold, reduction_effect)
-    shapes = _lib.ratemap_shapes(T, n, R, E, K, d.n_lags)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.RATEMAP_OUT_I32 else np.float64)
-           for k in _lib.RATEMAP_OUT_NAMES if k in names}
-    ins = _lib.RatemapInputs()
-    ins.ip, ins.y, ins.new_smoothed, ins.extra, ins.lambda_in = _f(ip, keep), _f(y, keep), _f(ns, keep), _f(extra, keep), _f(lambda_in, keep)
-    ins.n_train = nt.ctypes.data
-    outs = _lib.RatemapOutputs()
-    for k in _lib.RATEMAP_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_ratemap_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.rate_map(HostBackend(device), ip, new_smoothed, n_train, y, extra, lambda_in, lags, ridge, lambda_threshold,
+                          reduction_effect, effect_lag, outputs)
 
 
 def mldivide(X, y, n_rows=None, tol_scale=1.0, outputs=None, device=0):
     """epi_mldiv_run_host: MATLAB's rectangular backslash of batch.mldivide on NumPy arrays (synchronous).
     X [D, F, R], y [D, R].  Returns the dict of batch.mldivide as NumPy arrays."""
-    keep = []
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim != 3 or np.shape(y) != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, F, R] and y [D, R]")
-    D, F, R = X.shape
-    nr = _lib.mldiv_n_rows(n_rows, D)
-    K = int(nr.size)
-    names = _lib.mldiv_out_names(outputs)
-    d = _lib.make_mldiv_desc(D, F, R, K, tol_scale)
-    shapes = _lib.mldiv_shapes(D, F, R, K)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.MLDIV_OUT_I32 else np.float64)
-           for k in _lib.MLDIV_OUT_NAMES if k in names}
-    ins = _lib.MldivInputs()
-    ins.X, ins.y, ins.n_rows = _f(X, keep), _f(y, keep), nr.ctypes.data
-    outs = _lib.MldivOutputs()
-    for k in _lib.MLDIV_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_mldiv_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.mldivide(HostBackend(device), X, y, n_rows, tol_scale, outputs)
 
 
 def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale=None, tol=1e-3, max_iter=100000, outputs=None,
@@ -273,33 +211,7 @@ def svr(X, y, n_rows=None, kernel="linear", box=None, epsilon=None, kernel_scale
     """epi_svr_run_host: the support-vector regression of batch.svr on NumPy arrays (synchronous).
     X [D, F, R], y [D, R]; box, epsilon, kernel_scale scalars or arrays [R], None for _lib.svr_defaults of y(1:max(n_rows)).
     Returns the dict of batch.svr as NumPy arrays."""
-    keep = []
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim != 3 or np.shape(y) != (X.shape[0], X.shape[2]):
-        raise ValueError("X must be [D, F, R] and y [D, R]")
-    D, F, R = X.shape
-    nr = _lib.mldiv_n_rows(n_rows, D)
-    K = int(nr.size)
-    names = _lib.svr_out_names(outputs, kernel)
-    d = _lib.make_svr_desc(D, F, R, K, kernel, tol, max_iter)
-    if box is None or epsilon is None or kernel_scale is None:
-        dflt = _lib.svr_defaults(np.asarray(y, dtype=np.float64)[:max(1, min(int(nr.max()), D))], kernel)
-        box, epsilon = dflt["box"] if box is None else box, dflt["epsilon"] if epsilon is None else epsilon
-        kernel_scale = dflt["kernel_scale"] if kernel_scale is None else kernel_scale
-    box, epsilon, kernel_scale = (_lib.svr_region_array(v, R, n) for v, n in ((box, "box"), (epsilon, "epsilon"), (kernel_scale, "kernel_scale")))
-    shapes = _lib.svr_shapes(D, F, R, K)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k in _lib.SVR_OUT_I32 else np.float64)
-           for k in _lib.SVR_OUT_NAMES if k in names}
-    ins = _lib.SvrInputs()
-    ins.X, ins.y, ins.n_rows = _f(X, keep), _f(y, keep), nr.ctypes.data
-    ins.box, ins.epsilon, ins.kernel_scale = box.ctypes.data, epsilon.ctypes.data, kernel_scale.ctypes.data
-    outs = _lib.SvrOutputs()
-    for k in _lib.SVR_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_svr_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
-    return out
+    return _call.svr(HostBackend(device), X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, outputs)
 
 
 def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=None, device=0):
@@ -316,9 +228,9 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
     if src.shape[-1] != R * D:
         raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
     T, rows = src.shape[0], (1 if src.ndim == 2 else src.shape[1])
-    keep = []
-    pop = _f(population, keep)
-    if population is not None and keep[0].shape != (R,):
+    be = HostBackend(device)
+    pop = be.f64(population)
+    if pop is not None and pop.shape != (R,):
         raise ValueError("population must be [R]")
     d = _lib.make_ens_desc(T, rows, R, D, q, storage=1 if src.dtype == np.float32 else 0, derive_newcases=int(population is not None))
     names = [k for k in _lib.ENS_OUT_NAMES if k != "count"] if outputs is None else list(outputs)
@@ -326,14 +238,7 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
     if bad:
         raise ValueError(f"unknown outputs {bad}")
     shapes = _lib.ens_shapes(T, rows, R, d.n_q, d.derive_newcases)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k == "count" else np.float64)
-           for k in _lib.ENS_OUT_NAMES if k == "count" or k in names}
-    outs = _lib.EnsOutputs()
-    for k in _lib.ENS_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data if k in out else None)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_ens_run_host(C.byref(d), src.ctypes.data, pop, C.byref(outs), int(device), err)
-    _lib.check(rc, err)
+    out = _call.run_family("ens", be, d, [be.ptr(src), be.ptr(pop)], shapes, names + ["count"])
     if src.ndim == 2:
         out = {k: v.reshape(v.shape[:-2] + v.shape[-1:]) for k, v in out.items()}
     return out
@@ -346,7 +251,7 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     and noise_var [R] (both or neither).  Returns the dict of batch.ar_forecast as NumPy arrays."""
     if (A is None) != (noise_var is None):
         raise ValueError("A and noise_var are given together (the given-model mode) or not at all")
-    keep = []
+    be = HostBackend(device)
     seg = np.ascontiguousarray(seg, dtype=np.float64)
     if seg.ndim != 2:
         raise ValueError("seg must be [L, R]")
@@ -373,16 +278,9 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     d = _lib.make_arfc_desc(R, D, Ls, p, H, dt, fit=int(A is None), nv_mode=nv_mode, Sd=Sd)
     ins = _lib.ArfcInputs()
     for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, None, A, noise_var)):
-        setattr(ins, k, _f(v, keep))
-    ins.drive_series = None if ser is None else ser.ctypes.data
-    err = C.create_string_buffer(256)
-    shapes = _lib.arfc_shapes(R, D, Ls, p, H)
-    out = {k: np.empty(shapes[k], dtype=np.int32 if k == "status" else np.float64) for k in _lib.ARFC_OUT_NAMES}
-    outs = _lib.ArfcOutputs()
-    for k in _lib.ARFC_OUT_NAMES:
-        setattr(outs, k, out[k].ctypes.data)
-    rc = _lib.lib().epi_arfc_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
+        setattr(ins, k, be.ptr(be.f64(v)))
+    ins.drive_series = be.ptr(ser)
+    out = _call.run_family("arfc", be, d, [C.byref(ins)], _lib.arfc_shapes(R, D, Ls, p, H), _lib.ARFC_OUT_NAMES)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
 
 
@@ -408,17 +306,12 @@ def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, outputs=("s", "P", "d2", "ran
     d = _lib.make_fuse_desc(m, B, T, form, p_solver=p_solver, lane_block=0, storage=int(dt == np.float32))
     shapes = _lib.fuse_shapes(m, B, T, 0)
     abi = {"s": "s_out", "P": "P_out", "d2": "d2", "rank": "rank", "status": "status"}
-    odt = {"s": dt, "P": dt, "d2": np.float64, "rank": np.int32, "status": np.int32}
-    out = {k: np.empty(shapes[abi[k]], dtype=odt[k]) for k in outputs}
     ins = _lib.FuseInputs()
     for k, v in zip(_lib.FUSE_IN_NAMES, arrs):
         setattr(ins, k, v.ctypes.data)
-    outs = _lib.FuseOutputs()
-    for k in outputs:
-        setattr(outs, abi[k], out[k].ctypes.data)
-    err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_fuse_run_host(C.byref(d), C.byref(ins), C.byref(outs), int(device), err)
-    _lib.check(rc, err)
+    out = _call.run_family("fuse", HostBackend(device), d, [C.byref(ins)], shapes, [abi[k] for k in outputs],
+                           f32=("s_out", "P_out") if dt == np.float32 else ())
+    out = {k: out[abi[k]] for k in outputs}
     if single:
         out = {k: (v if k == "status" else v[..., 0]) for k, v in out.items()}
     return out
