@@ -1,7 +1,8 @@
 """The one call path of the batched family calls (_lib.FAMILIES), shared by batch (torch tensors on a stream) and hostapi
 (NumPy arrays, a device ordinal).  No torch here: what differs between the two entry points is asked of a backend,
 
-    f64(v) / i32(v)    the input as a contiguous float64 / int32 array where the call reads it (None stays None); the
+    f64(v) / i32(v) / f32(v)
+                       the input as a contiguous float64 / int32 / float32 array where the call reads it (None stays None); the
                        backend keeps it alive
     empty(shape, dt)   an uninitialised output, dt one of np.float64 / np.int32 / np.float32
     ptr(a)             the address of such an array (None stays None)
@@ -19,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import layout as L
 
 
 def run_family(fam, be, desc, args, shapes, names, f32=()):
@@ -173,3 +175,80 @@ def svr(be, X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, out
     ins.X, ins.y, ins.n_rows = be.ptr(X), be.ptr(y), nr.ctypes.data
     ins.box, ins.epsilon, ins.kernel_scale = be.ptr(reg(box, "box")), be.ptr(reg(epsilon, "epsilon")), be.ptr(reg(kernel_scale, "kernel_scale"))
     return run_family("svr", be, d, [C.byref(ins)], _lib.svr_shapes(D, F, R, K), names)
+
+
+def run_loglik(be, desc, ins, shapes, names):
+    """The call helper of the innovation likelihood, which is no family (its device entry takes a workspace): allocate the
+    outputs `names`, and for the device entry the workspace epi_loglik_workspace_bytes asks for, through the backend; call
+    epi_loglik_<be.kind> and check its status.  Returns the dict of outputs in the ABI's order."""
+    h = _lib.lib()
+    out = {k: be.empty(shapes[k], np.int32 if k in _lib.LOGLIK_OUT_I32 else np.float64) for k in _lib.LOGLIK_OUT_NAMES if k in names}
+    outs = _lib.LoglikOutputs()
+    for k, v in out.items():
+        setattr(outs, k, be.ptr(v))
+    err = C.create_string_buffer(256)
+    if be.kind == "run_device":
+        n = C.c_size_t(0)
+        _lib.check(h.epi_loglik_workspace_bytes(C.byref(desc), C.byref(n), err), err)
+        ws = be.empty(((max(n.value, 8) + 7) // 8,), np.float64)
+        rc = h.epi_loglik_run_device(C.byref(desc), C.byref(ins), C.byref(outs), be.ptr(ws), n.value, be.tail(), err)
+    else:
+        rc = h.epi_loglik_run_host(C.byref(desc), C.byref(ins), C.byref(outs), be.tail(), err)
+    _lib.check(rc, err)
+    return out
+
+
+def innovation_likelihood(be, S_MINUS, P_MINUS, innovations, x, prm, model, R_series, R_scalar, x_series, L_, obs_type, k0, k1,
+                          lane_block, B, G, outputs):
+    f32 = all(str(v.dtype).endswith("float32") for v in (S_MINUS, P_MINUS, innovations))
+    put = be.f32 if f32 else be.f64
+    sm, pm, inn = put(S_MINUS), put(P_MINUS), put(innovations)
+    if model not in L.MODEL_DIM:
+        raise ValueError(f"unknown model {model!r}")
+    m, blk = L.MODEL_DIM[model], int(lane_block)
+    if sm.ndim == 3 and pm.ndim == 3:
+        T, rows, nB = sm.shape
+        if 0 < blk < nB:
+            raise ValueError("lane_block given with classic [T, rows, B] arrays")
+        if B is not None and int(B) != nB:
+            raise ValueError("B does not match the arrays")
+        B, blk, Bp = nB, 0, nB
+    elif sm.ndim == 4 and pm.ndim == 4:
+        T, nblk, rows, bl = sm.shape
+        if bl != blk:
+            raise ValueError("chain-blocked arrays [T, nblk, rows, blk] need lane_block = blk")
+        B = nblk * blk if B is None else int(B)
+        if nblk != (B + blk - 1) // blk or blk >= B:
+            raise ValueError("B does not match nblk blocks of lane_block chains")
+        Bp = nblk * blk
+    else:
+        raise ValueError("S_MINUS / P_MINUS must be [T, m, B] / [T, m*m, B] or [T, nblk, m, blk] / [T, nblk, m*m, blk]")
+    if rows != m or tuple(pm.shape) != tuple(sm.shape[:-2]) + (m * m, sm.shape[-1]):
+        raise ValueError(f"{model} has m = {m}: S_MINUS must hold m rows and P_MINUS m*m")
+    if tuple(inn.shape) != (T, Bp):
+        raise ValueError("innovations must be [T, B] ([T, nblk * blk] for chain-blocked arrays)")
+    x, prm = be.f64(x), be.f64(prm)
+    if x.ndim != 2 or x.shape[0] != T:
+        raise ValueError("x must be [T, Sx]")
+    Sx = int(x.shape[1])
+    if tuple(prm.shape) != (L.PRM_COUNT, B):
+        raise ValueError("prm must be [PRM_COUNT, B]")
+    if (R_series is None) == (R_scalar is None):
+        raise ValueError("exactly one of R_series / R_scalar is needed")
+    R_series, R_scalar, x_series = be.f64(R_series), be.f64(R_scalar), be.i32(x_series)
+    if R_series is not None and tuple(R_series.shape) != (T, Sx):
+        raise ValueError("R_series must be [T, Sx]")
+    if R_scalar is not None and tuple(R_scalar.shape) != (B,):
+        raise ValueError("R_scalar must be [B]")
+    if x_series is not None and tuple(x_series.shape) != (B,):
+        raise ValueError("x_series must be [B]")
+    if x_series is None and Sx != B:
+        raise ValueError("without x_series, x must be [T, B]")
+    names = _lib.loglik_out_names(outputs, G)
+    d = _lib.make_loglik_desc(model, B, T, L_, obs_type, int(R_series is not None), Sx, blk, int(f32), k0, k1, G)
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_loglik_validate(C.byref(d), err), err)      # before anything is allocated from G
+    ins = _lib.LoglikInputs()
+    for k, v in zip(_lib.LOGLIK_IN_NAMES, (sm, pm, inn, x, R_series, R_scalar, x_series, prm)):
+        setattr(ins, k, be.ptr(v))
+    return run_loglik(be, d, ins, _lib.loglik_shapes(B, T, G), names)

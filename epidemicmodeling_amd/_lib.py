@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "epi_ratemap_validate", "epi_ratemap_run_device", "epi_ratemap_run_host",
     "epi_mldiv_validate", "epi_mldiv_run_device", "epi_mldiv_run_host",
     "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
+    "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
 ]
 
 
@@ -518,6 +519,53 @@ def make_fuse_desc(m, B, T, form, p_solver=0, lane_block=0, storage=0) -> FuseDe
     return d
 
 
+class LoglikDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "model", "B", "T", "L", "obs_type", "r_mode", "Sx", "lane_block", "storage",
+                                          "k0", "k1", "G", "reserved")]
+
+
+LOGLIK_IN_NAMES = ("S_MINUS", "P_MINUS", "innovations", "x", "R_series", "R_scalar", "x_series", "prm")
+LOGLIK_OUT_NAMES = ("loglik", "nis_mean", "n_valid", "status", "S", "nis", "R_used", "best", "best_loglik")
+LOGLIK_OUT_I32 = ("n_valid", "status", "best")
+LOGLIK_BAD_DAY, LOGLIK_ROUNDED_REPLAY = 1, 4          # bits of status
+
+
+class LoglikInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LOGLIK_IN_NAMES]
+
+
+class LoglikOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LOGLIK_OUT_NAMES]
+
+
+def loglik_shapes(B, T, G=0):
+    B, T, G = int(B), int(T), int(G)
+    sh = {k: (B,) for k in ("loglik", "nis_mean", "n_valid", "status")}
+    sh.update({k: (T, B) for k in ("S", "nis", "R_used")})
+    sh.update({k: (B // G if G > 0 else 0,) for k in ("best", "best_loglik")})
+    return sh
+
+
+def loglik_out_names(outputs, G=0):
+    """None -> the four per-chain outputs, and the two of the selection with G > 0; else the names given, in the ABI's order"""
+    if outputs is None:
+        return list(LOGLIK_OUT_NAMES[:4]) + (list(LOGLIK_OUT_NAMES[7:]) if int(G) > 0 else [])
+    for k in outputs:
+        if k not in LOGLIK_OUT_NAMES:
+            raise ValueError(f"unknown output {k!r}")
+    return [k for k in LOGLIK_OUT_NAMES if k in outputs]
+
+
+def make_loglik_desc(model, B, T, L_, obs_type, r_mode, Sx, lane_block=0, storage=0, k0=0, k1=None, G=0) -> LoglikDesc:
+    d = LoglikDesc()
+    d.abi_version = ABI_VERSION
+    d.model = L.MODEL_IDS[model] if isinstance(model, str) else int(model)
+    d.B, d.T, d.L, d.r_mode, d.Sx = int(B), int(T), int(L_), int(r_mode), int(Sx)
+    d.obs_type = L.OBS_IDS.get(obs_type, 99) if isinstance(obs_type, str) else int(obs_type)
+    d.lane_block, d.storage, d.k0, d.k1, d.G, d.reserved = int(lane_block), int(storage), int(k0), 0 if k1 is None else int(k1), int(G), 0
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -619,6 +667,12 @@ def lib():
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_lookahead_run_host.argtypes = [C.POINTER(LookaheadDesc), C.POINTER(LookaheadInputs), C.POINTER(LookaheadOutputs),
                                              C.c_int, C.c_char_p]
+        h.epi_loglik_validate.argtypes = [C.POINTER(LoglikDesc), C.c_char_p]
+        h.epi_loglik_workspace_bytes.argtypes = [C.POINTER(LoglikDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_loglik_run_device.argtypes = [C.POINTER(LoglikDesc), C.POINTER(LoglikInputs), C.POINTER(LoglikOutputs),
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_loglik_run_host.argtypes = [C.POINTER(LoglikDesc), C.POINTER(LoglikInputs), C.POINTER(LoglikOutputs),
+                                          C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

@@ -52,6 +52,10 @@ class DeviceBackend:
         return self._put(v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v, dtype=np.int32)),
                          torch.int32)
 
+    def f32(self, v):
+        return self._put(v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)),
+                         torch.float32)
+
     def empty(self, shape, dtype):
         return torch.empty(shape, dtype=self._DTYPES[dtype], device=self.device)
 
@@ -1031,3 +1035,37 @@ def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, lane_block=0, outputs=FUSE_OU
     out = _call.run_family("fuse", DeviceBackend(dev, stream), d, [C.byref(ins)], shapes, [abi[k] for k in outputs],
                            f32=("s_out", "P_out") if sf.dtype == torch.float32 else ())
     return {k: out[abi[k]] for k in outputs}
+
+
+def innovation_likelihood(S_MINUS, P_MINUS, innovations, x, prm, model, R_series=None, R_scalar=None, x_series=None, L=21,
+                          obs_type="NEWCASES", k0=0, k1=None, lane_block=0, B=None, G=0, outputs=None, stream=None):
+    """The Gaussian innovation log-likelihood of every chain from what a filter run left on the device (epi_loglik_run_device,
+    DESIGN.md §4.14): per observed day of the window k0 <= k < k1 (filter steps; k1 = None: T) the innovation variance
+    S = C P- C' + gamma R(k) -- the denominator the filter divided by, bit for bit -- and
+        loglik = -1/2 sum (log S + e^2 / S + log 2 pi),   nis_mean = mean of e^2 / S.
+    It is the likelihood of the EKF's linearisation: with the state clamps and gamma != 1 a score for comparing candidates of
+    one region (Q_w, R_v, gamma, beta), not a calibrated probability.
+    S_MINUS [T, m, B], P_MINUS [T, m*m, B], innovations [T, B] device tensors of `model`'s run, all float64 or all float32 --
+    or, with lane_block = an EkfRunner's `blk`, its chain-blocked outputs [T, nblk, rows, blk] / [T, nblk * blk] as they lie
+    (nothing is unblocked or copied) with B = the number of chains.  x [T, Sx], R_series [T, Sx] or R_scalar [B], x_series [B]
+    or None, prm [PRM_COUNT, B] and L, obs_type are the filter's own inputs.  With R_scalar the filter's adaptive R(k) is
+    replayed from the stored innovations (from float32 ones: bit 2, _lib.LOGLIK_ROUNDED_REPLAY, of the status of every chain
+    with beta != 1).  A day whose S is not a normal positive number or whose innovation is not finite is left out and sets
+    bit 0 (_lib.LOGLIK_BAD_DAY).
+    outputs: any of "loglik", "nis_mean" [B] float64, "n_valid", "status" [B] int32, "S", "nis", "R_used" [T, B] float64 by day
+    (NaN where the day does not count; R_used = R(k) on every day), and with G > 0 (B = regions x G chains, region-major)
+    "best" [B / G] int32 (the lowest index of the largest loglik among the candidates without a bad day and with n_valid > 0,
+    or -1) and "best_loglik" (or NaN).  Default: the four per-chain ones, plus the selection with G > 0.  Returns a dict of
+    device tensors.  Enqueued on `stream` (default: the current stream) without a host synchronisation."""
+    for name, v in (("S_MINUS", S_MINUS), ("P_MINUS", P_MINUS), ("innovations", innovations)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+        if not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not (S_MINUS.dtype == P_MINUS.dtype == innovations.dtype) or S_MINUS.dtype not in (torch.float64, torch.float32):
+        raise ValueError("S_MINUS, P_MINUS, innovations must all be float64 or all float32")
+    dev = S_MINUS.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.innovation_likelihood(DeviceBackend(dev, st), S_MINUS, P_MINUS, innovations, x, prm, model, R_series, R_scalar,
+                                           x_series, L, obs_type, k0, k1, lane_block, B, G, outputs)

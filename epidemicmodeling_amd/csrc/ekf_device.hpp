@@ -142,6 +142,31 @@ EPI_DEV double epi_exp(double x)
     const double r = epi_reduce_ln2(x, &k);
     return ldexp(1.0 + epi_expm1_reduced(r), (int)k);
 }
+// ---- log with a fixed operation order -----------------------------------------------------------------------------
+// x = 2^k m with m in [sqrt(1/2), sqrt(2)), f = m - 1 (exact), s = f / (2 + f); log(1 + f) = f - hfsq + s (hfsq + R(s^2))
+// with the degree-14 minimax polynomial R of the classic public-domain fdlibm log (error < 1 ulp).  No fma: the same text
+// compiled with -ffp-contract=off rounds identically on the device and in tests/rt_window_ref.c.
+EPI_DEV double epi_log(double x)
+{
+    if (x != x) return x;
+    if (x < 0.0) return __builtin_nan("");
+    if (x == 0.0) return -(double)INFINITY;
+    if (x == (double)INFINITY) return x;
+    int e;
+    double m = frexp(x, &e);                                  // m in [0.5, 1)
+    if (m < 0.70710678118654752440) { m = m + m; e = e - 1; }
+    const double f = m - 1.0;
+    const double k = (double)e;
+    const double s = f / (2.0 + f);
+    const double z = s * s, w = z * z;
+    const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
+    const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 +
+                                                                                           w * 1.479819860511658591e-01)));
+    const double R = t2 + t1;
+    const double hfsq = 0.5 * f * f;
+    return k * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + k * 1.90821492927058770002e-10)) - f);
+}
+
 EPI_DEV double epi_tanh(double x)
 {
     if (x != x) return x;

@@ -834,6 +834,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "rate_map.hpp"
 #include "mldivide.hpp"
 #include "svr.hpp"
+#include "loglik.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -3857,6 +3858,177 @@ int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const e
         dout.d2 = HostIO::at<double>(base, o_d2);
         dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_st);
         return epi_fuse_run_device(d, &din, &dout, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- the Gaussian innovation log-likelihood of every chain, from the arrays a filter run left (loglik.hpp) ----
+// the workspace: the block sums [nb32][B] (term, q: double; n, bad: int32), the per-chain loglik / n_valid / status the selection
+// reads when the caller does not want them, and for r_mode 0 R(k) [T][B]; every piece starts at a multiple of 256 bytes
+struct LlWs { size_t term, q, n, bad, ll, nv, st, rk, bytes; };
+static LlWs ll_workspace(const epi_loglik_desc *d)
+{
+    const size_t B = (size_t)d->B, nb = ((size_t)d->T + kLlBlock - 1) / kLlBlock;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    LlWs w{};
+    size_t o = 0;
+    w.term = o; o += up(nb * B * 8);
+    w.q = o; o += up(nb * B * 8);
+    w.n = o; o += up(nb * B * 4);
+    w.bad = o; o += up(nb * B * 4);
+    w.ll = o; o += up(B * 8);
+    w.nv = o; o += up(B * 4);
+    w.st = o; o += up(B * 4);
+    w.rk = o; if (d->r_mode == 0) o += up((size_t)d->T * B * 8);
+    w.bytes = o;
+    return w;
+}
+
+int epi_loglik_validate(const epi_loglik_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->model < 0 || d->model > EPI_MODEL_NEWCASE6_CODEGEN) { set_err(err, "unknown model"); return EPI_ERR_BAD_ARG; }
+    const ModelInfo &mi = MODEL_TABLE[d->model];
+    if (!mi.obs_fixed && d->obs_type != EPI_OBS_NEWCASES && d->obs_type != EPI_OBS_TOTALCASES) {
+        set_err(err, "unknown observation type");
+        return EPI_ERR_OBS_TYPE;
+    }
+    if (d->B < 1) { set_err(err, "B must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->L < 1) { set_err(err, "L must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->Sx < 1) { set_err(err, "Sx must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode != 0 && d->r_mode != 1) { set_err(err, "r_mode must be 0 (R_scalar) or 1 (R_series)"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k1 < 0 || d->k1 > d->T || d->k0 >= (d->k1 ? d->k1 : d->T)) {
+        set_err(err, "the window must satisfy 0 <= k0 < k1 <= T (k1 = 0: T)");
+        return EPI_ERR_BAD_ARG;
+    }
+    if (d->G < 0 || (d->G > 0 && d->B % d->G != 0)) { set_err(err, "G must be 0 or divide B"); return EPI_ERR_BAD_ARG; }
+    if (d->lane_block < 0 || d->lane_block > d->B) { set_err(err, "lane_block must lie in 0 .. B (0 or B: the classic [T][rows][B])"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->reserved != 0) { set_err(err, "reserved must be 0"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode == 0 && (size_t)2 * d->L * kWave * sizeof(double) > 64u * 1024u) { set_err(err, "L too large for the replay's windows in LDS (max 64)"); return EPI_ERR_UNSUPPORTED; }
+    if (((int64_t)d->B + 255) / 256 * 256 * (((int64_t)d->T + kLlBlock - 1) / kLlBlock) >= ((int64_t)1 << 31) || ((int64_t)d->T + kLlBlock - 1) / kLlBlock > 65535) {
+        set_err(err, "B * ceil(T / 32) is limited to 2^31 - 1 (one launch covers every block of every chain)");
+        return EPI_ERR_UNSUPPORTED;
+    }
+    return EPI_OK;
+}
+
+int epi_loglik_workspace_bytes(const epi_loglik_desc *d, size_t *bytes, char *err)
+{
+    int rc = epi_loglik_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = ll_workspace(d).bytes;
+    return EPI_OK;
+}
+
+// the pointer checks, shared by the device and the host entry
+static int ll_check_arrays(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, char *err)
+{
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->S_MINUS || !in->P_MINUS || !in->innovations || !in->x || !in->prm) { set_err(err, "NULL S_MINUS / P_MINUS / innovations / x / prm"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode == 1 && !in->R_series) { set_err(err, "r_mode 1 needs R_series"); return EPI_ERR_BAD_ARG; }
+    if (d->r_mode == 0 && !in->R_scalar) { set_err(err, "r_mode 0 needs R_scalar"); return EPI_ERR_BAD_ARG; }
+    if (!in->x_series && d->Sx != d->B) { set_err(err, "x_series is NULL: Sx must equal B"); return EPI_ERR_BAD_ARG; }
+    if (!out->loglik && !out->nis_mean && !out->S && !out->nis && !out->R_used) {
+        set_err(err, "no output requested: at least one of loglik / nis_mean / S / nis / R_used");
+        return EPI_ERR_BAD_ARG;
+    }
+    if ((out->best || out->best_loglik) && d->G <= 0) { set_err(err, "best / best_loglik need G > 0"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_loglik_run_device(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_loglik_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = ll_check_arrays(d, in, out, err)) != EPI_OK) return rc;
+    const LlWs w = ll_workspace(d);
+    if (!ws || ws_bytes < w.bytes) { set_err(err, "workspace too small (epi_loglik_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    const ModelInfo &mi = MODEL_TABLE[d->model];
+    char *base = (char *)ws;
+    LlArgs a{};
+    a.B = d->B; a.T = d->T; a.L = d->L; a.Sx = d->Sx; a.r_mode = d->r_mode; a.f32 = d->storage; a.flip = mi.flipped;
+    a.generic = mi.generic; a.obs_type = mi.obs_fixed ? EPI_OBS_NEWCASES : d->obs_type;
+    a.k0 = d->k0; a.k1 = d->k1 ? d->k1 : d->T; a.G = d->G; a.m = mi.m; a.nb32 = (d->T + kLlBlock - 1) / kLlBlock;
+    ll_geometry(d->B, d->lane_block, &a.blk, &a.nblk);
+    a.S_MINUS = in->S_MINUS; a.P_MINUS = in->P_MINUS; a.innov = in->innovations;
+    a.x = in->x; a.R_series = in->R_series; a.R_scalar = in->R_scalar; a.prm = in->prm; a.x_series = in->x_series;
+    a.Rk = out->R_used ? out->R_used : (d->r_mode == 0 ? (double *)(base + w.rk) : nullptr);
+    a.part_term = (double *)(base + w.term); a.part_q = (double *)(base + w.q);
+    a.part_n = (int32_t *)(base + w.n); a.part_bad = (int32_t *)(base + w.bad);
+    a.loglik = out->loglik ? out->loglik : (double *)(base + w.ll);
+    a.nis_mean = out->nis_mean;
+    a.n_valid = out->n_valid ? out->n_valid : (int32_t *)(base + w.nv);
+    a.status = out->status ? out->status : (int32_t *)(base + w.st);
+    a.S = out->S; a.nis = out->nis; a.best = out->best; a.best_loglik = out->best_loglik;
+    const unsigned tiles = (unsigned)(((int64_t)d->B + 255) / 256);
+    if (d->r_mode == 0) {
+        hipLaunchKernelGGL(ll_replay, dim3((unsigned)(((int64_t)d->B + kWave - 1) / kWave)), dim3(kWave),
+                           (size_t)2 * d->L * kWave * sizeof(double), st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ll_replay launch");
+    }
+    const bool sums = out->loglik || out->nis_mean || out->n_valid || out->status || out->best || out->best_loglik;
+    if (sums || out->S || out->nis || (d->r_mode == 1 && out->R_used)) {
+        hipLaunchKernelGGL(ll_blocks, dim3(tiles, (unsigned)a.nb32), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ll_blocks launch");
+    }
+    if (sums) {
+        hipLaunchKernelGGL(ll_chains, dim3(tiles), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ll_chains launch");
+    }
+    if (out->best || out->best_loglik) {
+        hipLaunchKernelGGL(ll_select, dim3((unsigned)(((int64_t)(d->B / d->G) + 255) / 256)), dim3(256), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ll_select launch");
+    }
+    return EPI_OK;
+}
+
+int epi_loglik_run_host(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, int device, char *err)
+{
+    int rc = epi_loglik_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = ll_check_arrays(d, in, out, err)) != EPI_OK) return rc;
+    const size_t B = (size_t)d->B, T = (size_t)d->T, Sx = (size_t)d->Sx, m = (size_t)MODEL_TABLE[d->model].m, none = HostIO::kAbsent;
+    int gblk, gnblk;
+    ll_geometry(d->B, d->lane_block, &gblk, &gnblk);
+    const size_t Bp = (size_t)gnblk * (size_t)gblk, es = d->storage ? 4 : 8;
+    HostIO io;
+    const size_t o_sm = io.add_in(in->S_MINUS, T * m, es, Bp, 0, Bp), o_pm = io.add_in(in->P_MINUS, T * m * m, es, Bp, 0, Bp);
+    const size_t o_in = io.add_in(in->innovations, T, es, Bp, 0, Bp), o_x = io.add_in(in->x, T, 8, Sx, 0, Sx);
+    const size_t o_rs = d->r_mode == 1 ? io.add_in(in->R_series, T, 8, Sx, 0, Sx) : none;
+    const size_t o_rv = d->r_mode == 0 ? io.add_in(in->R_scalar, 1, 8, B, 0, B) : none;
+    const size_t o_xs = in->x_series ? io.add_in(in->x_series, 1, 4, B, 0, B) : none;
+    const size_t o_prm = io.add_in(in->prm, (size_t)EPI_PRM_COUNT, 8, B, 0, B);
+    const size_t Rg = d->G > 0 ? B / (size_t)d->G : 0;
+    const size_t o_ll = out->loglik ? io.add_out(out->loglik, 1, 8, B, 0, B) : none;
+    const size_t o_nm = out->nis_mean ? io.add_out(out->nis_mean, 1, 8, B, 0, B) : none;
+    const size_t o_nv = out->n_valid ? io.add_out(out->n_valid, 1, 4, B, 0, B) : none;
+    const size_t o_st = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : none;
+    const size_t o_S = out->S ? io.add_out(out->S, T, 8, B, 0, B) : none;
+    const size_t o_ni = out->nis ? io.add_out(out->nis, T, 8, B, 0, B) : none;
+    const size_t o_ru = out->R_used ? io.add_out(out->R_used, T, 8, B, 0, B) : none;
+    const size_t o_b = out->best ? io.add_out(out->best, 1, 4, Rg, 0, Rg) : none;
+    const size_t o_bl = out->best_loglik ? io.add_out(out->best_loglik, 1, 8, Rg, 0, Rg) : none;
+    const size_t wsb = ll_workspace(d).bytes;
+    const size_t o_ws = io.reserve(wsb);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_loglik_inputs din{};
+        din.S_MINUS = base + o_sm; din.P_MINUS = base + o_pm; din.innovations = base + o_in;
+        din.x = HostIO::at<const double>(base, o_x); din.R_series = HostIO::at<const double>(base, o_rs);
+        din.R_scalar = HostIO::at<const double>(base, o_rv); din.x_series = HostIO::at<const int32_t>(base, o_xs);
+        din.prm = HostIO::at<const double>(base, o_prm);
+        epi_loglik_outputs dout{};
+        dout.loglik = HostIO::at<double>(base, o_ll); dout.nis_mean = HostIO::at<double>(base, o_nm);
+        dout.n_valid = HostIO::at<int32_t>(base, o_nv); dout.status = HostIO::at<int32_t>(base, o_st);
+        dout.S = HostIO::at<double>(base, o_S); dout.nis = HostIO::at<double>(base, o_ni); dout.R_used = HostIO::at<double>(base, o_ru);
+        dout.best = HostIO::at<int32_t>(base, o_b); dout.best_loglik = HostIO::at<double>(base, o_bl);
+        return epi_loglik_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -31,6 +31,9 @@ class HostBackend:
     def i32(self, v):
         return self._put(v, np.int32)
 
+    def f32(self, v):
+        return self._put(v, np.float32)
+
     def empty(self, shape, dtype):
         return np.empty(shape, dtype=dtype)
 
@@ -315,3 +318,11 @@ def two_filter(sf, Pf, sb, Pb, form=1, p_solver=0, outputs=("s", "P", "d2", "ran
     if single:
         out = {k: (v if k == "status" else v[..., 0]) for k, v in out.items()}
     return out
+
+
+def innovation_likelihood(S_MINUS, P_MINUS, innovations, x, prm, model, R_series=None, R_scalar=None, x_series=None, L=21,
+                          obs_type="NEWCASES", k0=0, k1=None, lane_block=0, B=None, G=0, outputs=None, device=0):
+    """epi_loglik_run_host: batch.innovation_likelihood on NumPy arrays (synchronous): the same arguments, and the same keys,
+    order, dtypes and bits.  S_MINUS, P_MINUS, innovations all float32 = float storage, anything else is taken as float64."""
+    return _call.innovation_likelihood(HostBackend(device), *(np.asarray(v) for v in (S_MINUS, P_MINUS, innovations)), x, prm,
+                                       model, R_series, R_scalar, x_series, L, obs_type, k0, k1, lane_block, B, G, outputs)

@@ -530,3 +530,83 @@ def two_filter_smooth(w, form=1, backward="minus", storage="f64", device="cuda:0
     fused = batch.two_filter(rf.out[names_f[0]], rf.out[names_f[1]], rb.out[names_b[0]], rb.out[names_b[1]], form=form,
                              p_solver=p_solver, lane_block=0 if rf.blk == w.B else rf.blk, B=w.B)
     return {"forward": rf, "backward": rb, "fused": fused, "lane_block": rf.blk, "B": w.B}
+
+
+def filter_likelihood(w, k0=0, k1=None, storage="f64", lane_block="auto", shape=0, device="cuda:0", G=0, outputs=None):
+    """Run the filter of `w` (a synth.Workload of any of the six models) and score every chain with
+    batch.innovation_likelihood: an EkfRunner with the outputs S_MINUS, P_MINUS, innovations, then the likelihood call on
+    runner.out[...] as they lie -- chain-blocked or classic, float64 or float32 (storage "f32"); nothing is unblocked or
+    copied back in between.  k0, k1: the window of filter steps that counts (k1 = None: T).  G, outputs: as
+    batch.innovation_likelihood.  Returns (runner, dict of device tensors).  No host synchronisation."""
+    dw = batch.DeviceWorkload(w, device)
+    r = batch.EkfRunner(dw, ["S_MINUS", "P_MINUS", "innovations"], lane_block=lane_block, shape=shape, storage=storage)
+    r.run()
+    res = batch.innovation_likelihood(r.out["S_MINUS"], r.out["P_MINUS"], r.out["innovations"], dw.x, dw.prm, w.model,
+                                      R_series=dw.R_series, R_scalar=dw.R_scalar, x_series=dw.x_series, L=w.L, obs_type=w.obs_type,
+                                      k0=k0, k1=k1, lane_block=0 if r.blk == w.B else r.blk, B=w.B, G=G, outputs=outputs)
+    return r, res
+
+
+def likelihood_grid(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None):
+    """The workload of R x G chains, region-major, that runs every chain ("region") of `w` under G candidate noise settings:
+    G = the Cartesian product q_scale x r_scale x gamma_ekf x beta_ekf in that order, the last axis fastest.  Q_w is scaled per
+    chain by q_scale; R_v by r_scale (R_scalar per chain; R_series -- and x beside it -- once per r_scale value, addressed
+    through x_series); the prm rows GAMMA_EKF / BETA_EKF are replaced per chain (None: every region keeps its own, the table
+    holds NaN there); u is shared through u_series.  Returns (workload, table [G, 4] of (q_scale, r_scale, gamma_ekf,
+    beta_ekf) per candidate)."""
+    import itertools
+    if np.ndim(w.Q) != 2:
+        raise ValueError("likelihood_grid scales a constant Q_w [m*m, B]")
+    qs, rs = [float(v) for v in np.atleast_1d(q_scale)], [float(v) for v in np.atleast_1d(r_scale)]
+    gs = [np.nan] if gamma_ekf is None else [float(v) for v in np.atleast_1d(gamma_ekf)]
+    bs = [np.nan] if beta_ekf is None else [float(v) for v in np.atleast_1d(beta_ekf)]
+    combos = list(itertools.product(range(len(qs)), range(len(rs)), range(len(gs)), range(len(bs))))
+    G, R = len(combos), w.B
+    table = np.array([[qs[a], rs[b], gs[c], bs[d]] for a, b, c, d in combos], dtype=np.float64).reshape(G, 4)
+    reg = np.repeat(np.arange(R), G)                      # the region of every chain
+    cand = np.tile(np.arange(G), R)
+    rep = lambda a: np.ascontiguousarray(a[..., reg])
+    prm = rep(w.prm)
+    if gamma_ekf is not None:
+        prm[L.PRM_GAMMA_EKF] = table[cand, 2]
+    if beta_ekf is not None:
+        prm[L.PRM_BETA_EKF] = table[cand, 3]
+    xs0 = np.arange(R) if w.x_series is None else np.asarray(w.x_series, dtype=np.int64)
+    us0 = np.arange(R) if w.u_series is None else np.asarray(w.u_series, dtype=np.int64)
+    ri = np.array([b for _, b, _, _ in combos], dtype=np.int64)[cand]      # index into r_scale of every chain
+    if w.R_series is not None:
+        x = np.ascontiguousarray(np.concatenate([w.x] * len(rs), axis=1))
+        R_series = np.ascontiguousarray(np.concatenate([w.R_series * v for v in rs], axis=1))
+        x_series, R_scalar = (ri * w.Sx + xs0[reg]).astype(np.int32), None
+    else:
+        x, R_series = w.x, None
+        x_series, R_scalar = xs0[reg].astype(np.int32), np.ascontiguousarray(w.R_scalar[reg] * table[cand, 1])
+    gw = synth.Workload(model=w.model, T=w.T, n_npi=w.n_npi, x=x, u=w.u, R_series=R_series, R_scalar=R_scalar, x_series=x_series,
+                        u_series=us0[reg].astype(np.int32), prm=prm, s_init=rep(w.s_init), Ps_init=rep(w.Ps_init),
+                        s_final=rep(w.s_final), Ps_final=rep(w.Ps_final), Q=np.ascontiguousarray(rep(w.Q) * table[cand, 0]),
+                        L=w.L, order=w.order, obs_type=w.obs_type, meta=dict(w.meta))
+    return gw, table
+
+
+def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None, burn_in=0, storage="f64", lane_block="auto",
+                shape=0, device="cuda:0"):
+    """Choose the filter's noise settings per region by likelihood: likelihood_grid(w, ...) run as one batch of R x G chains by
+    filter_likelihood with k0 = burn_in (the first burn_in filter steps, where Ps_init still dominates, do not count), and per
+    region the candidate with the largest log-likelihood.
+    What this is: the Gaussian innovation likelihood of the EKF's linearisation, sum over the observed days of
+    -1/2 (log S + e^2 / S + log 2 pi) with S the innovation variance the filter itself divided by.  What it is not: with the
+    state clamps and a fading memory gamma != 1 the innovations are not those of an exact Gaussian model, so the number is a
+    score for comparing candidates of ONE region on the same data and window -- not a calibrated probability, and not
+    comparable between regions or windows.
+    Returns {"loglik" [R, G], "n_valid" [R, G], "status" [R, G], "best" [R] int32 (-1: no usable candidate), "best_loglik" [R],
+    "chosen" [R, 4] (q_scale, r_scale, gamma_ekf, beta_ekf of the best candidate; NaN for best = -1 and for an axis left at
+    None), "table" [G, 4], "runner", "workload"}, tensors on the device.  No host synchronisation."""
+    gw, table = likelihood_grid(w, q_scale, r_scale, gamma_ekf, beta_ekf)
+    G, R = table.shape[0], w.B
+    r, res = filter_likelihood(gw, k0=burn_in, storage=storage, lane_block=lane_block, shape=shape, device=device, G=G)
+    tab = torch.as_tensor(table, dtype=torch.float64).to(res["best"].device)
+    best = res["best"].to(torch.int64)
+    chosen = tab[best.clamp(min=0)]
+    chosen = torch.where((best < 0)[:, None], torch.full_like(chosen, float("nan")), chosen)
+    return {"loglik": res["loglik"].view(R, G), "n_valid": res["n_valid"].view(R, G), "status": res["status"].view(R, G),
+            "best": res["best"], "best_loglik": res["best_loglik"], "chosen": chosen, "table": tab, "runner": r, "workload": gw}

@@ -1105,6 +1105,81 @@ int epi_npi_cost_host(int32_t B, int32_t T, int32_t n_npi, int32_t Su, int32_t w
                       const double *newcases, const double *inputs, const double *weights, double *J0, double *J1,
                       int device, char *err);
 
+/* ---- The Gaussian innovation log-likelihood of every chain, from the arrays a filter run left on the device ----
+ * Not a script of the reference: it hand-picks Q_w, R_v, gamma and beta (Tools/TrainPredictPrescribeNPI.m:12-22, :229-240);
+ * this is the number that lets a batch of regions x candidates choose them.  It is the likelihood of the EKF's linearisation;
+ * with the state clamps and gamma != 1 it is a score for comparing candidates of one region, not a calibrated probability.
+ * Definition (pinned; restated in tests/loglik_ref.c).  Chain c, filter step k, day t = k (t = T-1-k for the
+ * two *_BWD models), window k0 <= k < k1 (k1 = 0: T):
+ *   C        ObsJacobian of S_MINUS(t), rows 0..2 (NEWCASES: s1 s2, s0 s2, s0 s1; TOTALCASES: -1, 0, 0)
+ *   CP(j)    = C0 P(0,j), then fma(C1, P(1,j), .), fma(C2, P(2,j), .), j = 0..2, P = the upper-left 3 x 3 of P_MINUS(t), all nine
+ *              elements read (entry (i, j) in row i + m j); CPC' = CP0 C0, fma(CP1, C1, .), fma(CP2, C2, .): the dense filter's
+ *              order, whose 6-state terms with C(3..5) = 0 add nothing for a finite P
+ *   S        = CPC' + gamma R(k), gamma = prm[EPI_PRM_GAMMA_EKF][c]: the denominator the filter divided by
+ *   R(k)     r_mode 1: R_series[k][x_series[c]].  r_mode 0: the filter's own recursion from R_scalar[c], replayed from k = 0
+ *              (whatever the window) over the stored innovations and the NaN mask of x: two L-sample windows summed newest
+ *              first, mu = sum / cnt, cc = (e - mu)^2, and on a step with beta != 1 and x(t) observed (generic models: and
+ *              k < T-1) R(k+1) = beta R(k) + (1 - beta) (sumC / cnt) -- NewCase models: beta R(k) + (1 - beta) sumC / cnt;
+ *              on every other step the generic models fall back to R_scalar[c], the NewCase models keep R(k)
+ *   valid    x(t) is not NaN and k0 <= k < k1.  bad: valid, and S NaN / infinite / below DBL_MIN or the innovation non-finite;
+ *              a bad day enters no sum and sets bit 0 of status[c].  good: valid and not bad
+ *   per good day   q = e e / S;  term = log(S) + q  (the library's fixed-order log)
+ *   sums     in blocks of 32 filter steps aligned at k = 0: each block from 0.0 over its good days in ascending k, then the
+ *              block sums from 0.0 in ascending block order (term, q and the count alike)
+ *   n_valid  the number of good days;  loglik = -0.5 (sum_term + n_valid * 1.8378770664093453);  nis_mean = sum_q / n_valid
+ *              (NaN for n_valid = 0)
+ *   status   bit 0: a bad day;  bit 2: storage 1, r_mode 0 and beta != 1 -- R replayed from rounded innovations
+ *   S, nis, R_used [T][B] by DAY: S of every valid day (NaN otherwise), nis = q of every good day (NaN otherwise), R_used =
+ *              R(k) of every day
+ *   G > 0    B = regions x G chains, region-major: best[r] = the lowest candidate index of the largest loglik among the
+ *              candidates with status bit 0 clear and n_valid > 0, or -1;  best_loglik[r] = that value, or NaN
+ * Layout: S_MINUS (m rows), P_MINUS (m*m rows), innovations (one row) as epi_ekf_run_* left them: element (t, row, c) at
+ *   ((t * nblk + c / blk) * rows + row) * blk + c % blk, blk = lane_block (0 or B: the classic [T][rows][B]), doubles (storage
+ *   0) or floats (storage 1, widened on load; all arithmetic is double).  Padding lanes are never read.  x [T][Sx] and R_series
+ *   [T][Sx] (indexed by filter step) are the filter's inputs, x_series [B] or NULL (chain c reads column c), R_scalar [B], prm
+ *   [EPI_PRM_COUNT][B] as the filter got it (rows EPI_PRM_GAMMA_EKF and EPI_PRM_BETA_EKF are read).
+ * Every output may be NULL; at least one of loglik / nis_mean / S / nis / R_used is required, best / best_loglik need G > 0. */
+typedef struct epi_loglik_desc {
+    int32_t abi_version;
+    int32_t model;               /* epi_model */
+    int32_t B, T;                /* chains, days */
+    int32_t L;                   /* the filter's inv_monitor_len (r_mode 0: the replay's window) */
+    int32_t obs_type;            /* epi_obs_type (ignored by EPI_MODEL_NEWCASE6_CODEGEN, as by the filter) */
+    int32_t r_mode;              /* 1 = R_series, 0 = R_scalar with the adaptive recursion */
+    int32_t Sx;                  /* columns of x / R_series */
+    int32_t lane_block;          /* 0 or B: classic; else chains per layout block */
+    int32_t storage;             /* 0 = double, 1 = float (S_MINUS, P_MINUS, innovations) */
+    int32_t k0, k1;              /* window of filter steps, k1 = 0: T */
+    int32_t G;                   /* candidates per region (divides B) for best / best_loglik, or 0 */
+    int32_t reserved;            /* 0 */
+} epi_loglik_desc;
+typedef struct epi_loglik_inputs {
+    const void *S_MINUS, *P_MINUS, *innovations;
+    const double *x;
+    const double *R_series, *R_scalar;   /* the one r_mode names */
+    const int32_t *x_series;             /* [B] or NULL */
+    const double *prm;
+} epi_loglik_inputs;
+typedef struct epi_loglik_outputs {
+    double *loglik, *nis_mean;           /* [B] */
+    int32_t *n_valid, *status;           /* [B] */
+    double *S, *nis, *R_used;            /* [T][B] */
+    int32_t *best;                       /* [B / G] */
+    double *best_loglik;                 /* [B / G] */
+} epi_loglik_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG with a message for anything outside the limits, EPI_ERR_OBS_TYPE for an unknown observation
+ * type, EPI_ERR_UNSUPPORTED for an L whose two windows do not fit the LDS or B * ceil(T / 32) of 2^31 or more */
+int epi_loglik_validate(const epi_loglik_desc *d, char *err);
+/* bytes of device workspace epi_loglik_run_device needs (the block sums; r_mode 0: R(k) [T][B]) */
+int epi_loglik_workspace_bytes(const epi_loglik_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; up to four kernels enqueued on `stream`: no host synchronisation, no allocation, no second stream.
+ * EPI_ERR_WORKSPACE for a workspace below epi_loglik_workspace_bytes */
+int epi_loglik_run_device(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_loglik_run_host(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, int device,
+                        char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

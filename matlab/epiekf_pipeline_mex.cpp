@@ -79,6 +79,13 @@
 //       reference's choice.  form  0 = the reference's two lines as written (p_solver 0: S \ C by LU, 1: pinv(S) * C),
 //       1 = the information form Pf X Pb, symmetrised (p_solver 0); both required.  S_FRW_BCK  m x T;  P_FRW_BCK  m x m x T;
 //       d2  1 x T, (S_f - S_b)' pinv(P_f + P_b) (S_f - S_b);  rank  1 x T, the rank pinv kept (-1: a non-finite day, NaN).
+//   [loglik, nis_mean, n_valid, status, S, nis, R_used] = epiekf_pipeline_mex('loglik', model_id, S_MINUS, P_MINUS, innovations, x, R_v, prm, L, obs_type, k_first, k_last)
+//       The Gaussian innovation log-likelihood of one chain from a filter run's outputs, the arguments in the
+//       order of epi_loglik_inputs.  model_id, obs_type  as epiekf_mex takes them;  S_MINUS  m x T;  P_MINUS  m x m x T;
+//       innovations, x  1 x T;  R_v  1 x T (a series, by filter step) or a scalar (the filter's adaptive R is replayed);  prm
+//       the filter's parameter vector (EPI_PRM_COUNT entries);  L  inv_monitor_len;  k_first, k_last ([] = 1, T)  the filter steps
+//       that count, ONE-based and inclusive.  loglik, nis_mean, n_valid, status  scalars;  S, nis, R_used  1 x T by day (NaN where
+//       the day does not count).
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -586,6 +593,57 @@ static void fuse(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void loglik(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 12) mexErrMsgTxt("epiekf_pipeline_mex('loglik', model_id, S_MINUS, P_MINUS, innovations, x, R_v, prm, L, obs_type, k_first, k_last): 12 inputs expected");
+    for (int k = 1; k <= 9; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("model_id ... obs_type must be non-empty double arrays");
+    const int model = (int)mxGetScalar(prhs[1]);
+    const int mm = epi_model_dim(model);
+    if (mm < 0) mexErrMsgTxt("unknown model id");
+    const mwSize m = (mwSize)mm;
+    if (mxGetNumberOfDimensions(prhs[2]) != 2 || mxGetM(prhs[2]) != m) mexErrMsgTxt("S_MINUS must be m x T");
+    const mwSize T = mxGetN(prhs[2]);
+    {
+        const mwSize nd = mxGetNumberOfDimensions(prhs[3]);
+        const mwSize *dm = mxGetDimensions(prhs[3]);
+        if (nd < 2 || nd > 3 || dm[0] != m || dm[1] != m || (nd == 3 ? dm[2] : 1) != T) mexErrMsgTxt("P_MINUS must be m x m x T");
+    }
+    if (mxGetNumberOfElements(prhs[4]) != T || mxGetNumberOfElements(prhs[5]) != T) mexErrMsgTxt("innovations and x must be 1 x T");
+    const mwSize nr = mxGetNumberOfElements(prhs[6]);
+    if (nr != 1 && nr != T) mexErrMsgTxt("R_v must be 1 x T or a scalar");
+    if (mxGetNumberOfElements(prhs[7]) != EPI_PRM_COUNT) mexErrMsgTxt("prm must hold EPI_PRM_COUNT entries");
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[10])) kf = mxGetScalar(prhs[10]);
+    if (!mxIsEmpty(prhs[11])) kl = mxGetScalar(prhs[11]);
+    if (!(kf >= 1.0 && kl >= kf && kl <= (double)T) || kf != (double)(int32_t)kf || kl != (double)(int32_t)kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= k_last <= T");
+    epi_loglik_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.model = model; d.B = 1; d.T = (int32_t)T; d.L = (int32_t)mxGetScalar(prhs[8]);
+    d.obs_type = (int32_t)mxGetScalar(prhs[9]); d.r_mode = (nr == T && T > 1) ? 1 : 0; d.Sx = 1;
+    d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    epi_loglik_inputs in;
+    memset(&in, 0, sizeof in);
+    // the ABI's [T][m][1], [T][m*m][1] (entry (i, j) in row i + m j) are MATLAB's m x T, m x m x T: no transposition
+    in.S_MINUS = mxGetPr(prhs[2]); in.P_MINUS = mxGetPr(prhs[3]); in.innovations = mxGetPr(prhs[4]); in.x = mxGetPr(prhs[5]);
+    if (d.r_mode) in.R_series = mxGetPr(prhs[6]); else in.R_scalar = mxGetPr(prhs[6]);
+    in.prm = mxGetPr(prhs[7]);
+    mxArray *o[7];
+    for (int k = 0; k < 7; k++) o[k] = mxCreateDoubleMatrix(1, k < 4 ? 1 : T, mxREAL);
+    int32_t nv = 0, st = 0;
+    epi_loglik_outputs out;
+    memset(&out, 0, sizeof out);
+    out.loglik = mxGetPr(o[0]); out.nis_mean = mxGetPr(o[1]); out.n_valid = &nv; out.status = &st;
+    out.S = mxGetPr(o[4]); out.nis = mxGetPr(o[5]); out.R_used = mxGetPr(o[6]);
+    char err[256] = {0};
+    const int rc = epi_loglik_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) mxDestroyArray(a); fail_if(rc, err); }
+    mxGetPr(o[2])[0] = (double)nv; mxGetPr(o[3])[0] = (double)st;
+    for (int k = 0; k < 7; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -629,6 +687,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "ens_summary") == 0) ens_summary(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "loglik") == 0) loglik(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
