@@ -177,25 +177,30 @@ def svr(be, X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, out
     return run_family("svr", be, d, [C.byref(ins)], _lib.svr_shapes(D, F, R, K), names)
 
 
-def run_loglik(be, desc, ins, shapes, names):
-    """The call helper of the innovation likelihood, which is no family (its device entry takes a workspace): allocate the
-    outputs `names`, and for the device entry the workspace epi_loglik_workspace_bytes asks for, through the backend; call
-    epi_loglik_<be.kind> and check its status.  Returns the dict of outputs in the ABI's order."""
+def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, names):
+    """The call helper of the calls whose device entry takes a workspace (epi_<prefix>_workspace_bytes / _run_device /
+    _run_host), which are no families: allocate the outputs `names`, and for the device entry the workspace, through the
+    backend; bind them into the outputs structure `outs`, call and check the status.  Returns the dict of outputs in the ABI's
+    order."""
     h = _lib.lib()
-    out = {k: be.empty(shapes[k], np.int32 if k in _lib.LOGLIK_OUT_I32 else np.float64) for k in _lib.LOGLIK_OUT_NAMES if k in names}
-    outs = _lib.LoglikOutputs()
+    out = {k: be.empty(shapes[k], np.int32 if k in out_i32 else np.float64) for k in out_names if k in names}
     for k, v in out.items():
         setattr(outs, k, be.ptr(v))
     err = C.create_string_buffer(256)
     if be.kind == "run_device":
         n = C.c_size_t(0)
-        _lib.check(h.epi_loglik_workspace_bytes(C.byref(desc), C.byref(n), err), err)
+        _lib.check(getattr(h, f"epi_{prefix}_workspace_bytes")(C.byref(desc), C.byref(n), err), err)
         ws = be.empty(((max(n.value, 8) + 7) // 8,), np.float64)
-        rc = h.epi_loglik_run_device(C.byref(desc), C.byref(ins), C.byref(outs), be.ptr(ws), n.value, be.tail(), err)
+        rc = getattr(h, f"epi_{prefix}_run_device")(C.byref(desc), C.byref(ins), C.byref(outs), be.ptr(ws), n.value, be.tail(), err)
     else:
-        rc = h.epi_loglik_run_host(C.byref(desc), C.byref(ins), C.byref(outs), be.tail(), err)
+        rc = getattr(h, f"epi_{prefix}_run_host")(C.byref(desc), C.byref(ins), C.byref(outs), be.tail(), err)
     _lib.check(rc, err)
     return out
+
+
+def run_loglik(be, desc, ins, shapes, names):
+    """The innovation likelihood's call: run_with_workspace with its names"""
+    return run_with_workspace("loglik", be, desc, ins, _lib.LoglikOutputs(), _lib.LOGLIK_OUT_NAMES, _lib.LOGLIK_OUT_I32, shapes, names)
 
 
 def innovation_likelihood(be, S_MINUS, P_MINUS, innovations, x, prm, model, R_series, R_scalar, x_series, L_, obs_type, k0, k1,
@@ -252,3 +257,34 @@ def innovation_likelihood(be, S_MINUS, P_MINUS, innovations, x, prm, model, R_se
     for k, v in zip(_lib.LOGLIK_IN_NAMES, (sm, pm, inn, x, R_series, R_scalar, x_series, prm)):
         setattr(ins, k, be.ptr(v))
     return run_loglik(be, d, ins, _lib.loglik_shapes(B, T, G), names)
+
+
+def npi_plan(be, sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter, max_halvings, tol, outputs):
+    sp, u_min, eps = be.f64(sp), be.f64(u_min), be.f64(eps)
+    if sp.ndim != 2 or sp.shape[0] != _lib.PLAN_SIM_PRM_COUNT:
+        raise ValueError("sp must be [48, R] (pipeline.scoring_region_inputs)")
+    R = int(sp.shape[1])
+    if u_min.ndim != 2 or u_min.shape[1] != R:
+        raise ValueError("u_min must be [n, R]")
+    if eps.ndim != 1:
+        raise ValueError("eps must be [P]")
+    n, P, H = int(u_min.shape[0]), int(eps.shape[0]), int(horizon)
+    u_fixed, u_init, J0_prefix, J1_prefix = be.f64(u_fixed), be.f64(u_init), be.f64(J0_prefix), be.f64(J1_prefix)
+    if u_fixed is not None and tuple(u_fixed.shape) != (H, n, R):
+        raise ValueError("u_fixed must be [H, n, R]")
+    if u_init is not None and tuple(u_init.shape) != (H, n, R * P):
+        raise ValueError("u_init must be [H, n, R * P]")
+    if int(prefix_days) > 0 and (J0_prefix is None or J1_prefix is None):
+        raise ValueError("prefix_days > 0 needs J0_prefix and J1_prefix")
+    for v in (J0_prefix, J1_prefix):
+        if v is not None and tuple(v.shape) != (R,):
+            raise ValueError("J0_prefix / J1_prefix must be [R]")
+    names = _lib.plan_out_names(outputs)
+    d = _lib.make_plan_desc(R, P, H, n, prefix_days, max_iter, max_halvings, tol)
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_plan_validate(C.byref(d), err), err)        # before anything is allocated from the sizes
+    ins = _lib.PlanInputs()
+    for k, v in zip(_lib.PLAN_IN_NAMES, (sp, u_min, eps, u_fixed, u_init, J0_prefix, J1_prefix)):
+        setattr(ins, k, be.ptr(v))
+    return run_with_workspace("plan", be, d, ins, _lib.PlanOutputs(), _lib.PLAN_OUT_NAMES, _lib.PLAN_OUT_I32,
+                              _lib.plan_shapes(R, P, H, n, max_iter), names)

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "epi_mldiv_validate", "epi_mldiv_run_device", "epi_mldiv_run_host",
     "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
     "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
+    "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
 ]
 
 
@@ -566,6 +567,51 @@ def make_loglik_desc(model, B, T, L_, obs_type, r_mode, Sx, lane_block=0, storag
     return d
 
 
+class PlanDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "P", "H", "n_npi", "prefix_days", "max_iter", "max_halvings")] + [
+        ("tol", C.c_double)]
+
+
+PLAN_IN_NAMES = ("sp", "u_min", "eps", "u_fixed", "u_init", "J0_prefix", "J1_prefix")
+PLAN_OUT_NAMES = ("plan", "J0", "J1", "F", "gap", "iters", "halvings", "status", "states", "mu", "F_trace")
+PLAN_OUT_I32 = ("iters", "halvings", "status")
+PLAN_OPTIONAL = ("states", "mu", "F_trace")
+PLAN_SIM_PRM_COUNT = 48                                 # EPI_SIM_PRM_COUNT
+PLAN_STOP_CAP, PLAN_STOP_SEARCH, PLAN_STOP_NONFINITE = 1, 2, 4      # bits of status
+
+
+class PlanInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PLAN_IN_NAMES]
+
+
+class PlanOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PLAN_OUT_NAMES]
+
+
+def plan_shapes(R, P, H, n, max_iter):
+    B, H, n = int(R) * int(P), int(H), int(n)
+    sh = {k: (B,) for k in ("J0", "J1", "F", "gap", "iters", "halvings", "status")}
+    sh.update(plan=(H, n, B), states=(H, 3, B), mu=(H, 3, B), F_trace=(int(max_iter), B))
+    return sh
+
+
+def plan_out_names(outputs):
+    """None -> the eight required outputs; else those and the optional ones named ("states", "mu", "F_trace"), in the ABI's order"""
+    extra = () if outputs is None else tuple(outputs)
+    for k in extra:
+        if k not in PLAN_OUT_NAMES:
+            raise ValueError(f"unknown output {k!r}")
+    return [k for k in PLAN_OUT_NAMES if k not in PLAN_OPTIONAL or k in extra]
+
+
+def make_plan_desc(R, P, H, n_npi, prefix_days=0, max_iter=64, max_halvings=30, tol=1e-9) -> PlanDesc:
+    d = PlanDesc()
+    d.abi_version = ABI_VERSION
+    d.R, d.P, d.H, d.n_npi, d.prefix_days = int(R), int(P), int(H), int(n_npi), int(prefix_days)
+    d.max_iter, d.max_halvings, d.tol = int(max_iter), int(max_halvings), float(tol)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -673,6 +719,11 @@ def lib():
                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_loglik_run_host.argtypes = [C.POINTER(LoglikDesc), C.POINTER(LoglikInputs), C.POINTER(LoglikOutputs),
                                           C.c_int, C.c_char_p]
+        h.epi_plan_validate.argtypes = [C.POINTER(PlanDesc), C.c_char_p]
+        h.epi_plan_workspace_bytes.argtypes = [C.POINTER(PlanDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_plan_run_device.argtypes = [C.POINTER(PlanDesc), C.POINTER(PlanInputs), C.POINTER(PlanOutputs),
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_plan_run_host.argtypes = [C.POINTER(PlanDesc), C.POINTER(PlanInputs), C.POINTER(PlanOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

@@ -1069,3 +1069,23 @@ def innovation_likelihood(S_MINUS, P_MINUS, innovations, x, prm, model, R_series
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.innovation_likelihood(DeviceBackend(dev, st), S_MINUS, P_MINUS, innovations, x, prm, model, R_series, R_scalar,
                                            x_series, L, obs_type, k0, k1, lane_block, B, G, outputs)
+
+
+def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None, J1_prefix=None, prefix_days=0, max_iter=64,
+             max_halvings=30, tol=1e-9, outputs=None, device="cuda:0"):
+    """The direct optimal-NPI planner: a deterministic, well-conditioned optimal plan for every (region, cost weight) chain in
+    one device call (epi_plan_run_device).  It solves the Pontryagin problem of the prescription path in its
+    stable direction: the horizon simulated forward (the scoring tail's own day), the exact adjoint of the clamped Euler map
+    backward from zero, Frank-Wolfe steps u + theta (u* - u) to the bang-bang vertex u* the reference's switching function
+    names, theta = 1, 1/2, ... until F = (1 - eps) sum s i alpha + eps sum w'u drops.  It returns a stationary point with its
+    Frank-Wolfe gap, not a certificate of global optimality.
+    sp [48, R] (pipeline.scoring_region_inputs), u_min [n, R], eps [P] cost weights, horizon H days.  Chain c = region * P + l.
+    u_fixed [H, n, R]: NaN = free, a number = held at it (the sweep's convention).  u_init [H, n, R * P]: the starting plan of the
+    free entries (default u_min).  J0_prefix, J1_prefix [R] with prefix_days: NPICost's historic sums, as for random_npi_mc.
+    Returns a dict of device tensors: plan [H, n, B], J0, J1, F, gap [B] float64, iters, halvings, status [B] int32 (status 0:
+    gap <= tol |F|; _lib.PLAN_STOP_CAP: max_iter adjoint passes without it; _lib.PLAN_STOP_SEARCH: no descending step;
+    _lib.PLAN_STOP_NONFINITE: F not finite), and those of outputs = ("states", "mu", "F_trace") asked for: states, mu [H, 3, B]
+    of the plan returned, F_trace [max_iter, B] (NaN beyond iters; strictly decreasing).  Enqueued on the current stream
+    without a host synchronisation."""
+    return _call.npi_plan(DeviceBackend(device), sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter,
+                          max_halvings, tol, outputs)

@@ -1011,4 +1011,48 @@ EPI_DEV void mrdivide(const double (&Bm)[M * M], const double (&A)[M * M], doubl
         for (int i = 0; i < M; i++) X[IXM(i, j)] = Y[IXM(j, i)];
 }
 
+// ---- the forward simulator's day and the running NPICost sums (the simulators, the scoring tail, the Monte-Carlo and the planner) ----
+// Tools/SIalpha_Controlled.m:24-28 (+ NPICost.m:6-10 fused when J0/J1 are requested)
+struct SimPrm {
+    double alpha_min, alpha_max, gamma, b, beta, dt, s_std, i_std, a_std;
+    double ga[kNpi], um[kNpi], w[kNpi];   // gamma*a(k), u_max(k), NPICost weights(k)
+};
+// column `c` of an [EPI_SIM_PRM_COUNT][n] parameter block
+EPI_DEV void load_sim_prm(SimPrm &p, const double *__restrict__ sp, int n, int c, double &s, double &i, double &al)
+{
+    auto g = [&](int f) { return sp[(size_t)f * n + c]; };
+    s = g(EPI_SIM_S0); i = g(EPI_SIM_I0); al = g(EPI_SIM_ALPHA0);
+    p.alpha_min = g(EPI_SIM_ALPHA_MIN); p.alpha_max = g(EPI_SIM_ALPHA_MAX); p.gamma = g(EPI_SIM_GAMMA);
+    p.b = g(EPI_SIM_B); p.beta = g(EPI_SIM_BETA); p.dt = g(EPI_SIM_DT);
+    p.s_std = g(EPI_SIM_S_STD); p.i_std = g(EPI_SIM_I_STD); p.a_std = g(EPI_SIM_ALPHA_STD);
+#pragma unroll
+    for (int k = 0; k < kNpi; k++) { p.ga[k] = p.gamma * g(EPI_SIM_A + k); p.um[k] = g(EPI_SIM_U_MAX + k); p.w[k] = g(EPI_SIM_W + k); }
+}
+// one day of SIalpha_Controlled.m:25-27 (entries of uk beyond n_npi are 0 and a(k) there is 0)
+EPI_DEV void sialpha_step(const SimPrm &p, const double (&uk)[kNpi], double z1, double z2, double z3, double &s, double &i,
+                          double &al)
+{
+    double dot = p.ga[0] * (p.um[0] - uk[0]);
+#pragma unroll
+    for (int k = 1; k < kNpi; k++) dot = fma(p.ga[k], p.um[k] - uk[k], dot);
+    const double sn = fmax(0.0, fmin(1.0, s - p.dt * (al * s * i + z1 * p.s_std)));
+    const double in = fmax(0.0, fmin(1.0, i + p.dt * (al * s * i - p.beta * i + z2 * p.i_std)));
+    const double an = fmax(p.alpha_min, fmin(p.alpha_max, al + p.dt * (-p.gamma * al + p.gamma * p.b + dot + z3 * p.a_std)));
+    s = sn; i = in; al = an;
+}
+// running sums of NPICost.m:6-10 over one more day: mean(newcases) and mean(weights(:).*inputs(:)) in column-major
+// order (NPI index fastest); `first` = this is the very first day of the span (sum starts with the term itself)
+EPI_DEV void npicost_accumulate(const SimPrm &p, const double (&uk)[kNpi], int n_npi, bool first, double s, double i, double al,
+                                double &acc0, double &acc1)
+{
+    const double nc = s * i * al;
+    acc0 = first ? nc : acc0 + nc;
+#pragma unroll
+    for (int k = 0; k < kNpi; k++)
+        if (k < n_npi) {
+            const double term = p.w[k] * uk[k];
+            acc1 = (first && k == 0) ? term : acc1 + term;
+        }
+}
+
 }  // namespace epi

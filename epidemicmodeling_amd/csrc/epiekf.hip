@@ -732,48 +732,7 @@ __global__ __launch_bounds__(kWave) void eks_bwd(const KArgs a)
 // ---------------------------------------------------------------------------
 // forward simulators
 // ---------------------------------------------------------------------------
-// Tools/SIalpha_Controlled.m:24-28 (+ NPICost.m:6-10 fused when J0/J1 are requested)
-struct SimPrm {
-    double alpha_min, alpha_max, gamma, b, beta, dt, s_std, i_std, a_std;
-    double ga[kNpi], um[kNpi], w[kNpi];   // gamma*a(k), u_max(k), NPICost weights(k)
-};
-// column `c` of an [EPI_SIM_PRM_COUNT][n] parameter block
-EPI_DEV void load_sim_prm(SimPrm &p, const double *__restrict__ sp, int n, int c, double &s, double &i, double &al)
-{
-    auto g = [&](int f) { return sp[(size_t)f * n + c]; };
-    s = g(EPI_SIM_S0); i = g(EPI_SIM_I0); al = g(EPI_SIM_ALPHA0);
-    p.alpha_min = g(EPI_SIM_ALPHA_MIN); p.alpha_max = g(EPI_SIM_ALPHA_MAX); p.gamma = g(EPI_SIM_GAMMA);
-    p.b = g(EPI_SIM_B); p.beta = g(EPI_SIM_BETA); p.dt = g(EPI_SIM_DT);
-    p.s_std = g(EPI_SIM_S_STD); p.i_std = g(EPI_SIM_I_STD); p.a_std = g(EPI_SIM_ALPHA_STD);
-#pragma unroll
-    for (int k = 0; k < kNpi; k++) { p.ga[k] = p.gamma * g(EPI_SIM_A + k); p.um[k] = g(EPI_SIM_U_MAX + k); p.w[k] = g(EPI_SIM_W + k); }
-}
-// one day of SIalpha_Controlled.m:25-27 (entries of uk beyond n_npi are 0 and a(k) there is 0)
-EPI_DEV void sialpha_step(const SimPrm &p, const double (&uk)[kNpi], double z1, double z2, double z3, double &s, double &i,
-                          double &al)
-{
-    double dot = p.ga[0] * (p.um[0] - uk[0]);
-#pragma unroll
-    for (int k = 1; k < kNpi; k++) dot = fma(p.ga[k], p.um[k] - uk[k], dot);
-    const double sn = fmax(0.0, fmin(1.0, s - p.dt * (al * s * i + z1 * p.s_std)));
-    const double in = fmax(0.0, fmin(1.0, i + p.dt * (al * s * i - p.beta * i + z2 * p.i_std)));
-    const double an = fmax(p.alpha_min, fmin(p.alpha_max, al + p.dt * (-p.gamma * al + p.gamma * p.b + dot + z3 * p.a_std)));
-    s = sn; i = in; al = an;
-}
-// running sums of NPICost.m:6-10 over one more day: mean(newcases) and mean(weights(:).*inputs(:)) in column-major
-// order (NPI index fastest); `first` = this is the very first day of the span (sum starts with the term itself)
-EPI_DEV void npicost_accumulate(const SimPrm &p, const double (&uk)[kNpi], int n_npi, bool first, double s, double i, double al,
-                                double &acc0, double &acc1)
-{
-    const double nc = s * i * al;
-    acc0 = first ? nc : acc0 + nc;
-#pragma unroll
-    for (int k = 0; k < kNpi; k++)
-        if (k < n_npi) {
-            const double term = p.w[k] * uk[k];
-            acc1 = (first && k == 0) ? term : acc1 + term;
-        }
-}
+// SimPrm, load_sim_prm, sialpha_step and npicost_accumulate live in ekf_device.hpp (npi_plan.hpp is compiled for the host with them)
 
 __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const int32_t *__restrict__ u_series,
                                                    const double *__restrict__ u, const double *__restrict__ sp,
@@ -835,6 +794,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "mldivide.hpp"
 #include "svr.hpp"
 #include "loglik.hpp"
+#include "npi_plan.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -4029,6 +3989,133 @@ int epi_loglik_run_host(const epi_loglik_desc *d, const epi_loglik_inputs *in, c
         dout.S = HostIO::at<double>(base, o_S); dout.nis = HostIO::at<double>(base, o_ni); dout.R_used = HostIO::at<double>(base, o_ru);
         dout.best = HostIO::at<int32_t>(base, o_b); dout.best_loglik = HostIO::at<double>(base, o_bl);
         return epi_loglik_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- the direct optimal-NPI planner: one lane per (region, cost weight) chain (npi_plan.hpp) ----
+// the workspace: the second plan [H][n][B], the states of side 1 (and of side 0 when the caller does not want them) [H][3][B],
+// the vertex / held masks [H][B] uint32; every piece starts at a multiple of 256 bytes
+struct PlanWs { size_t u1, x1, x0, mask, bytes; };
+static PlanWs plan_workspace(const epi_plan_desc *d, bool want_states)
+{
+    const size_t B = (size_t)d->R * (size_t)d->P, H = (size_t)d->H;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    PlanWs w{};
+    size_t o = 0;
+    w.u1 = o; o += up(H * (size_t)d->n_npi * B * 8);
+    w.x1 = o; o += up(H * 3 * B * 8);
+    w.x0 = o; if (!want_states) o += up(H * 3 * B * 8);
+    w.mask = o; o += up(H * B * 4);
+    w.bytes = o;
+    return w;
+}
+
+int epi_plan_validate(const epi_plan_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1 || d->P < 1) { set_err(err, "R and P must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->H < 1) { set_err(err, "H must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->n_npi < 1 || d->n_npi > kNpi) { set_err(err, "n_npi must lie in 1 .. 12"); return EPI_ERR_BAD_ARG; }
+    if (d->prefix_days < 0) { set_err(err, "prefix_days must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (d->max_iter < 1 || d->max_iter > kPlanMaxIter) { set_err(err, "max_iter must lie in 1 .. 255"); return EPI_ERR_BAD_ARG; }
+    if (d->max_halvings < 0 || d->max_halvings > kPlanMaxHalvings) { set_err(err, "max_halvings must lie in 0 .. 30"); return EPI_ERR_BAD_ARG; }
+    if (!(d->tol >= 0.0 && d->tol <= 1.7976931348623157e308)) { set_err(err, "tol must be finite and >= 0"); return EPI_ERR_BAD_ARG; }
+    const int64_t B = (int64_t)d->R * d->P, lim = (int64_t)1 << 31, rows = d->n_npi > 3 ? d->n_npi : 3;
+    if (B >= lim || (int64_t)d->H * rows >= lim || (int64_t)d->H * rows * B >= lim || (int64_t)d->max_iter * B >= lim) {
+        set_err(err, "R * P, H * max(n_npi, 3) * R * P and max_iter * R * P are limited to 2^31 - 1 (the call is one launch)");
+        return EPI_ERR_UNSUPPORTED;
+    }
+    return EPI_OK;
+}
+
+int epi_plan_workspace_bytes(const epi_plan_desc *d, size_t *bytes, char *err)
+{
+    int rc = epi_plan_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = plan_workspace(d, false).bytes;               // the larger of the two cases: the caller may size it before choosing outputs
+    return EPI_OK;
+}
+
+// the pointer checks, shared by the device and the host entry
+static int plan_check_arrays(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, char *err)
+{
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->sp || !in->u_min || !in->eps) { set_err(err, "NULL sp / u_min / eps"); return EPI_ERR_BAD_ARG; }
+    if (d->prefix_days > 0 && (!in->J0_prefix || !in->J1_prefix)) { set_err(err, "prefix_days > 0 needs J0_prefix and J1_prefix"); return EPI_ERR_BAD_ARG; }
+    if (!out->plan || !out->J0 || !out->J1 || !out->F || !out->gap || !out->iters || !out->halvings || !out->status) {
+        set_err(err, "NULL plan / J0 / J1 / F / gap / iters / halvings / status");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+int epi_plan_run_device(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, void *ws, size_t ws_bytes,
+                        void *stream, char *err)
+{
+    int rc = epi_plan_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = plan_check_arrays(d, in, out, err)) != EPI_OK) return rc;
+    const PlanWs w = plan_workspace(d, out->states != nullptr);
+    if (!ws || ws_bytes < w.bytes) { set_err(err, "workspace too small (epi_plan_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    char *base = (char *)ws;
+    PlanArgs a{};
+    a.R = d->R; a.P = d->P; a.H = d->H; a.n = d->n_npi; a.max_iter = d->max_iter; a.max_halvings = d->max_halvings;
+    a.prefix_days = d->prefix_days; a.tol = d->tol;
+    a.sp = in->sp; a.u_min = in->u_min; a.eps = in->eps; a.u_fixed = in->u_fixed; a.u_init = in->u_init;
+    a.J0_prefix = in->J0_prefix; a.J1_prefix = in->J1_prefix;
+    a.ub[0] = out->plan; a.ub[1] = (double *)(base + w.u1);
+    a.xb[0] = out->states ? out->states : (double *)(base + w.x0); a.xb[1] = (double *)(base + w.x1);
+    a.want_states = out->states != nullptr;
+    a.mask = (uint32_t *)(base + w.mask);
+    a.J0 = out->J0; a.J1 = out->J1; a.F = out->F; a.gap = out->gap;
+    a.iters = out->iters; a.halvings = out->halvings; a.status = out->status;
+    a.mu = out->mu; a.F_trace = out->F_trace;
+    const int64_t B = (int64_t)d->R * d->P;
+    hipLaunchKernelGGL(plan_solve, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(err, e, "plan_solve launch");
+    return EPI_OK;
+}
+
+int epi_plan_run_host(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, int device, char *err)
+{
+    int rc = epi_plan_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = plan_check_arrays(d, in, out, err)) != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, P = (size_t)d->P, B = R * P, H = (size_t)d->H, n = (size_t)d->n_npi, none = HostIO::kAbsent;
+    const bool pre = d->prefix_days > 0;
+    HostIO io;
+    const size_t o_sp = io.add_in(in->sp, (size_t)EPI_SIM_PRM_COUNT, 8, R, 0, R), o_um = io.add_in(in->u_min, n, 8, R, 0, R);
+    const size_t o_eps = io.add_in(in->eps, 1, 8, P, 0, P);
+    const size_t o_uf = in->u_fixed ? io.add_in(in->u_fixed, H * n, 8, R, 0, R) : none;
+    const size_t o_ui = in->u_init ? io.add_in(in->u_init, H * n, 8, B, 0, B) : none;
+    const size_t o_j0p = pre ? io.add_in(in->J0_prefix, 1, 8, R, 0, R) : none, o_j1p = pre ? io.add_in(in->J1_prefix, 1, 8, R, 0, R) : none;
+    const size_t o_plan = io.add_out(out->plan, H * n, 8, B, 0, B);
+    const size_t o_j0 = io.add_out(out->J0, 1, 8, B, 0, B), o_j1 = io.add_out(out->J1, 1, 8, B, 0, B);
+    const size_t o_F = io.add_out(out->F, 1, 8, B, 0, B), o_gap = io.add_out(out->gap, 1, 8, B, 0, B);
+    const size_t o_it = io.add_out(out->iters, 1, 4, B, 0, B), o_hv = io.add_out(out->halvings, 1, 4, B, 0, B);
+    const size_t o_st = io.add_out(out->status, 1, 4, B, 0, B);
+    const size_t o_x = out->states ? io.add_out(out->states, H * 3, 8, B, 0, B) : none;
+    const size_t o_mu = out->mu ? io.add_out(out->mu, H * 3, 8, B, 0, B) : none;
+    const size_t o_ft = out->F_trace ? io.add_out(out->F_trace, (size_t)d->max_iter, 8, B, 0, B) : none;
+    const size_t wsb = plan_workspace(d, out->states != nullptr).bytes;
+    const size_t o_ws = io.reserve(wsb);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_plan_inputs din{};
+        din.sp = HostIO::at<const double>(base, o_sp); din.u_min = HostIO::at<const double>(base, o_um);
+        din.eps = HostIO::at<const double>(base, o_eps); din.u_fixed = HostIO::at<const double>(base, o_uf);
+        din.u_init = HostIO::at<const double>(base, o_ui);
+        din.J0_prefix = HostIO::at<const double>(base, o_j0p); din.J1_prefix = HostIO::at<const double>(base, o_j1p);
+        epi_plan_outputs dout{};
+        dout.plan = HostIO::at<double>(base, o_plan); dout.J0 = HostIO::at<double>(base, o_j0); dout.J1 = HostIO::at<double>(base, o_j1);
+        dout.F = HostIO::at<double>(base, o_F); dout.gap = HostIO::at<double>(base, o_gap);
+        dout.iters = HostIO::at<int32_t>(base, o_it); dout.halvings = HostIO::at<int32_t>(base, o_hv);
+        dout.status = HostIO::at<int32_t>(base, o_st);
+        dout.states = HostIO::at<double>(base, o_x); dout.mu = HostIO::at<double>(base, o_mu); dout.F_trace = HostIO::at<double>(base, o_ft);
+        return epi_plan_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

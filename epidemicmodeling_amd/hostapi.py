@@ -326,3 +326,11 @@ def innovation_likelihood(S_MINUS, P_MINUS, innovations, x, prm, model, R_series
     order, dtypes and bits.  S_MINUS, P_MINUS, innovations all float32 = float storage, anything else is taken as float64."""
     return _call.innovation_likelihood(HostBackend(device), *(np.asarray(v) for v in (S_MINUS, P_MINUS, innovations)), x, prm,
                                        model, R_series, R_scalar, x_series, L, obs_type, k0, k1, lane_block, B, G, outputs)
+
+
+def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None, J1_prefix=None, prefix_days=0, max_iter=64,
+             max_halvings=30, tol=1e-9, outputs=None, device=0):
+    """epi_plan_run_host: batch.npi_plan on NumPy arrays (synchronous): the same arguments, and the same keys, order, dtypes
+    and bits."""
+    return _call.npi_plan(HostBackend(device), sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter,
+                          max_halvings, tol, outputs)

@@ -162,14 +162,24 @@ def _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression
 
 
 def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regression_days=60, npi_weights=None,
-              W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0):
+              W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0, planner="sweep", plan_max_iter=64,
+              plan_max_halvings=30, plan_tol=1e-9):
     """Run the chain above.  cases/deaths [T,S] cumulative counts (NaN = missing), population [S], ip [T,n,S] (NaN = N/A).
     regression = "nonnegls" (REGRESSION_TYPE 'NONNEGATIVELS', the default) or "lasso" ('LASSO': lasso(X, y, 'CV', cv_folds),
     folds drawn from cv_seed in round 1 and cv_seed + 1 in round 2; the coefficients may be negative) or "elementwise"
     (REGRESSION_TYPE 'NONNEGATIVELS-ELEMENT-WISE': a robust fit of alpha against every NPI on its own, slope >= 0,
     DESIGN.md §4.10; it needs num_regression_days >= 3).
+    planner = "sweep" (the default: the reference's 6-state SIAlphaModelEKFOptControlled sweep, whose smoothed costates pick
+    the plan) or "direct": the plan of every (region, cost weight) comes from batch.npi_plan (states forward,
+    adjoint backward, up to plan_max_iter Frank-Wolfe steps to gap <= plan_tol |F|), scored by NPICost over [historic, horizon]
+    like the sweep's and put through the same Pareto selection.  Over a long history the sweep's plan is rounding noise
+    (DESIGN.md §2); the direct planner's is not.
     Returns a dict with every intermediate and `prescription` [horizon, n, S]: the smoothed optimal plan of each region's
-    Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps]."""
+    Pareto optimum (`I_opt`), plus `front` [S, n_eps] and (J0, J1) [S, n_eps].  With planner = "direct" there are no sweep
+    keys (`sweep`, `x_sweep`, `R_sweep`, `u_sweep`, `sweep_region`); instead `plan` [horizon, n, S * n_eps] (a device tensor),
+    `plan_F`, `plan_gap` [S, n_eps] float64, `plan_iters`, `plan_halvings`, `plan_status` [S, n_eps] int32 (batch.npi_plan)."""
+    if planner not in ("sweep", "direct"):
+        raise ValueError('planner must be "sweep" or "direct"')
     T, S = cases.shape
     n = ip.shape[1]
     N = np.asarray(population, dtype=np.float64)
@@ -184,8 +194,11 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
     Sf = _alpha_smooth(workload3(xh, Rh, u_fixed, N, I0, fit2["a"], fit2["b"]), device)
     hist = Sf[:T]                                                                      # s/i/alpha_historic (:355-357)
     out.update(R_mean=R_mean, historic=hist)
-    # Pareto sweep over the cost weights
     eps_grid = synth.epsilon_grid(n_eps)
+    if planner == "direct":
+        return _prescribe_direct(out, hist, u, u_fixed, fit2, u_max, npi_weights, eps_grid, horizon, I0, X, device, plan_max_iter,
+                                 plan_max_halvings, plan_tol)
+    # Pareto sweep over the cost weights
     u_nan = np.concatenate([u, np.full((horizon, n, S), np.nan)])
     w6 = workload6(xh, Rh, u_nan, N, I0, fit2["a"], fit2["b"], eps_grid)
     dw = batch.DeviceWorkload(w6, device)
@@ -216,6 +229,32 @@ def prescribe(cases, deaths, population, ip, horizon=30, n_eps=50, num_regressio
                J0=sc["J0"].cpu().numpy().reshape(S, n_eps), J1=sc["J1"].cpu().numpy().reshape(S, n_eps),
                front=front.cpu().numpy(), i_opt=i_opt_h, sweep=w6,
                prescription=best.cpu().numpy())
+    return out
+
+
+def _prescribe_direct(out, hist, u, u_fixed, fit2, u_max, npi_weights, eps_grid, horizon, I0, X, device, max_iter, max_halvings, tol):
+    """prescribe's tail with planner = "direct": batch.npi_plan from the end-of-history state, then the sweep's own Pareto
+    selection over the call's (J0, J1)"""
+    T, n, S = u.shape
+    n_eps = eps_grid.shape[0]
+    wts = np.ones((n, S)) if npi_weights is None else np.asarray(npi_weights, dtype=np.float64)
+    sp_region = scoring_region_inputs(hist[T - 1], fit2["a"], fit2["b"], u_max, wts)
+    J0p_region = np.cumsum(hist[:, 0] * hist[:, 1] * hist[:, 2], axis=0)[-1]           # sequential historic sums
+    J1p_region = np.cumsum((wts[None] * u).reshape(T * n, S), axis=0)[-1]
+    u_min = np.repeat(synth.IP_MINS[:n, None], S, axis=1)
+    res = batch.npi_plan(sp_region, u_min, eps_grid, horizon, J0_prefix=J0p_region, J1_prefix=J1p_region, prefix_days=T,
+                         max_iter=max_iter, max_halvings=max_halvings, tol=tol, device=device)
+    front, i_opt = batch.pareto_front(res["J0"], res["J1"], S)
+    torch.cuda.synchronize(res["plan"].device)
+    i_opt_h = i_opt.cpu().numpy()
+    chains = np.arange(S) * n_eps + i_opt_h
+    best = res["plan"].index_select(2, torch.as_tensor(chains, device=res["plan"].device))
+    rr = np.repeat(np.arange(S), n_eps)
+    host = lambda k: res[k].cpu().numpy().reshape(S, n_eps)
+    out.update(sp_region=sp_region, J0_prefix_region=J0p_region, J1_prefix_region=J1p_region, I0=I0, u_fixed=u_fixed, X_reg=X,
+               eps_grid=eps_grid, sp=sp_region[:, rr], J0_prefix=J0p_region[rr], J1_prefix=J1p_region[rr], J0=host("J0"), J1=host("J1"),
+               front=front.cpu().numpy(), i_opt=i_opt_h, prescription=best.cpu().numpy(), plan=res["plan"], plan_F=host("F"),
+               plan_gap=host("gap"), plan_iters=host("iters"), plan_halvings=host("halvings"), plan_status=host("status"))
     return out
 
 

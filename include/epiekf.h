@@ -1180,6 +1180,70 @@ int epi_loglik_run_device(const epi_loglik_desc *d, const epi_loglik_inputs *in,
 int epi_loglik_run_host(const epi_loglik_desc *d, const epi_loglik_inputs *in, const epi_loglik_outputs *out, int device,
                         char *err);
 
+/* ---- The direct optimal-NPI planner: the prescription's Pontryagin problem solved in its stable direction ----
+ * Not a script of the reference: its sweep integrates the costates forward (SIAlphaModelEKFOptControlled.m:70-72), where they
+ * grow like (1 + gamma dt)^T; this call runs the states forward and the adjoint backward from zero, the scheme the demos
+ * testScripts/testSIModelOptimalControl01-03.m sketch.  It returns a stationary point of F with its Frank-Wolfe gap, not a
+ * certificate of global optimality.
+ * Definition (pinned; restated in tests/npi_plan_ref.c).  Chain c = region * P + l, eps = eps[l], ome = 1 - eps:
+ *   forward    from (EPI_SIM_S0, _I0, _ALPHA0) of sp, per day t = 0 .. H-1 the scoring tail's day: SIalpha_Controlled's update
+ *                with zero noise (the fma chain over gamma a(k) (u_max(k) - u(k)), k ascending, and the clamps), x(t) = the
+ *                post-update (s, i, alpha), then NPICost's two running sums (s i alpha; w(k) u(k), k ascending), started from the
+ *                first term:  F = ome * sum0 + eps * sum1.  J0, J1: the same sums continued from J0_prefix / J1_prefix when
+ *                prefix_days > 0, divided by (H + prefix_days) and n_npi (H + prefix_days): epi_sialpha_score_device's values
+ *   d(t)       three flags: x(t) strictly inside its clamp (0 < s < 1, 0 < i < 1, alpha_min < alpha < alpha_max)
+ *   adjoint    t = H-1 .. 0:  mu(t) = ome (i al, s al, s i)  [t = H-1],  else  ome (..) + m  with v = d(t+1) ? mu(t+1) : 0 and
+ *                m0 = fma(A10, v1, A00 v0), m1 = fma(A11, v1, A01 v0), m2 = fma(A22, v2, fma(A12, v1, A02 v0)), A the state block
+ *                of StateJacobians at x(t) in the filter's own form: A00 = 1 - dt al i, A01 = -dt al s, A02 = -dt s i,
+ *                A10 = dt i al, A11 = 1 + dt (s al - beta), A12 = dt s i, A22 = 1 - dt gamma (products left to right)
+ *   gradient   g(k,t) = eps w(k) - dt (gamma a(k)) mu2(t) if d2(t), else eps w(k);  vertex u*(k,t) = u_min(k) if g > 0, else
+ *                u_max(k) (the reference's tie rule);  held entries (u_fixed not NaN) keep their value and enter no sum
+ *   gap        from 0.0, days descending, k ascending over the free entries: gap = gap + g (u - u*)
+ *   iteration  F of the starting plan (free entries: u_init, or u_min without it); then repeat: F non-finite -> stop, status
+ *                bit 2 (gap and mu NaN); F_trace[iters] = F, iters += 1, adjoint pass; gap <= tol |F| -> stop, status 0;
+ *                iters == max_iter -> stop, bit 0; for j = 0 .. max_halvings, theta = 2^-j: the trial plan u + theta (u* - u)
+ *                element by element, a full forward pass of it, accepted if F_trial < F (its plan, states and sums become the
+ *                current ones), else halvings += 1; none accepted -> stop, bit 1.
+ *   so the plan returned is always the one gap and mu belong to, F_trace is strictly decreasing, and F, J0, J1 are what the
+ *   scoring tail gives for the plan returned.  F_trace beyond iters is NaN.
+ * Layout: sp [EPI_SIM_PRM_COUNT][R] (pipeline.scoring_region_inputs), u_min [n_npi][R], eps [P], u_fixed [H][n_npi][R] or NULL
+ *   (NaN = free), u_init [H][n_npi][R*P] or NULL, J0_prefix / J1_prefix [R] (needed for prefix_days > 0).  plan [H][n_npi][R*P],
+ *   states and mu [H][3][R*P], F_trace [max_iter][R*P]; the rest [R*P].  states, mu and F_trace may be NULL. */
+typedef struct epi_plan_desc {
+    int32_t abi_version;
+    int32_t R, P;                /* regions, cost weights: B = R * P chains */
+    int32_t H;                   /* horizon in days, >= 1 */
+    int32_t n_npi;               /* 1 .. EPI_MAX_NPI */
+    int32_t prefix_days;         /* >= 0 */
+    int32_t max_iter;            /* 1 .. 255 */
+    int32_t max_halvings;        /* 0 .. 30 */
+    double tol;                  /* >= 0, finite */
+} epi_plan_desc;
+typedef struct epi_plan_inputs {
+    const double *sp, *u_min, *eps;
+    const double *u_fixed, *u_init;          /* or NULL */
+    const double *J0_prefix, *J1_prefix;     /* [R]; read for prefix_days > 0 */
+} epi_plan_inputs;
+typedef struct epi_plan_outputs {
+    double *plan;                            /* [H][n_npi][B] */
+    double *J0, *J1, *F, *gap;               /* [B] */
+    int32_t *iters, *halvings, *status;      /* [B] */
+    double *states, *mu;                     /* [H][3][B] or NULL */
+    double *F_trace;                         /* [max_iter][B] or NULL */
+} epi_plan_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG with a message for R, P, H < 1, n_npi outside 1 .. 12, prefix_days < 0, max_iter outside
+ * 1 .. 255, max_halvings outside 0 .. 30, a negative or non-finite tol; EPI_ERR_UNSUPPORTED where R * P, H * max(n_npi, 3) * R * P
+ * or max_iter * R * P reaches 2^31 (the call is not cut into launches) */
+int epi_plan_validate(const epi_plan_desc *d, char *err);
+/* bytes of device workspace epi_plan_run_device needs (the second plan, the states of both sides, the vertex masks) */
+int epi_plan_workspace_bytes(const epi_plan_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; one kernel enqueued on `stream`: no host synchronisation, no allocation.  EPI_ERR_BAD_ARG for a NULL
+ * required array, EPI_ERR_WORKSPACE for a workspace below epi_plan_workspace_bytes */
+int epi_plan_run_device(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, void *ws, size_t ws_bytes,
+                        void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_plan_run_host(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -86,6 +86,13 @@
 //       the filter's parameter vector (EPI_PRM_COUNT entries);  L  inv_monitor_len;  k_first, k_last ([] = 1, T)  the filter steps
 //       that count, ONE-based and inclusive.  loglik, nis_mean, n_valid, status  scalars;  S, nis, R_used  1 x T by day (NaN where
 //       the day does not count).
+//   [plan, J0, J1, F, gap, iters, halvings, status, states, mu, F_trace] = epiekf_pipeline_mex('plan', sp, u_min, eps, H, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter, max_halvings, tol)
+//       The direct optimal-NPI planner: for every (region, cost weight) the horizon's plan from the states run
+//       forward and the adjoint run backward, Frank-Wolfe steps with backtracking; a stationary point with its gap.  sp  R x 48;
+//       u_min  R x n_npi;  eps  P cost weights;  H  days;  u_fixed ([] = all free)  R x n_npi x H, NaN = free;  u_init ([] =
+//       u_min)  (P*R) x n_npi x H;  J0_prefix, J1_prefix ([] with prefix_days 0)  R x 1.  Chain (r-1) * P + l.  plan  (P*R) x
+//       n_npi x H;  J0 .. status  P x R (status 0: gap <= tol |F|; bit 0: max_iter passes; bit 1: no descending step; bit 2:
+//       F not finite);  states, mu  (P*R) x 3 x H and F_trace  (P*R) x max_iter (NaN beyond iters), only when requested.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -644,6 +651,50 @@ static void loglik(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void plan(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('plan', sp, u_min, eps, H, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter, max_halvings, tol): 13 inputs expected");
+    for (int k = 1; k <= 4; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("sp, u_min, eps, H must be non-empty double arrays");
+    for (int k = 9; k <= 12; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("prefix_days, max_iter, max_halvings, tol must be scalars");
+    const mwSize R = mxGetM(prhs[1]), n = mxGetN(prhs[2]), P = mxGetNumberOfElements(prhs[3]);
+    want(prhs[1], R, EPI_SIM_PRM_COUNT, "sp");
+    if (mxGetM(prhs[2]) != R) mexErrMsgTxt("u_min must be R x n_npi");
+    epi_plan_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.R = (int32_t)R; d.P = (int32_t)P; d.H = (int32_t)mxGetScalar(prhs[4]); d.n_npi = (int32_t)n;
+    d.prefix_days = (int32_t)mxGetScalar(prhs[9]); d.max_iter = (int32_t)mxGetScalar(prhs[10]);
+    d.max_halvings = (int32_t)mxGetScalar(prhs[11]); d.tol = mxGetScalar(prhs[12]);
+    char err[256] = {0};
+    fail_if(epi_plan_validate(&d, err), err);
+    const mwSize B = R * P, H = (mwSize)d.H;
+    if (!mxIsEmpty(prhs[5]) && mxGetNumberOfElements(prhs[5]) != R * n * H) mexErrMsgTxt("u_fixed must be R x n_npi x H");
+    if (!mxIsEmpty(prhs[6]) && mxGetNumberOfElements(prhs[6]) != B * n * H) mexErrMsgTxt("u_init must be (P*R) x n_npi x H");
+    if (d.prefix_days > 0 && (mxGetNumberOfElements(prhs[7]) != R || mxGetNumberOfElements(prhs[8]) != R)) mexErrMsgTxt("J0_prefix, J1_prefix must have one entry per region");
+    epi_plan_inputs in;
+    memset(&in, 0, sizeof in);
+    in.sp = mxGetPr(prhs[1]); in.u_min = mxGetPr(prhs[2]); in.eps = mxGetPr(prhs[3]); in.u_fixed = opt(prhs[5]); in.u_init = opt(prhs[6]);
+    in.J0_prefix = d.prefix_days > 0 ? mxGetPr(prhs[7]) : NULL; in.J1_prefix = d.prefix_days > 0 ? mxGetPr(prhs[8]) : NULL;
+    mxArray *o[11];
+    o[0] = dbl3(B, n, H);
+    for (int k = 1; k < 8; k++) o[k] = mxCreateDoubleMatrix(P, R, mxREAL);
+    o[8] = nlhs > 8 ? dbl3(B, 3, H) : NULL;
+    o[9] = nlhs > 9 ? dbl3(B, 3, H) : NULL;
+    o[10] = nlhs > 10 ? mxCreateDoubleMatrix(B, (mwSize)d.max_iter, mxREAL) : NULL;
+    std::vector<int32_t> it(B), hv(B), st(B);
+    epi_plan_outputs out;
+    memset(&out, 0, sizeof out);
+    out.plan = mxGetPr(o[0]); out.J0 = mxGetPr(o[1]); out.J1 = mxGetPr(o[2]); out.F = mxGetPr(o[3]); out.gap = mxGetPr(o[4]);
+    out.iters = it.data(); out.halvings = hv.data(); out.status = st.data();
+    out.states = o[8] ? mxGetPr(o[8]) : NULL; out.mu = o[9] ? mxGetPr(o[9]) : NULL; out.F_trace = o[10] ? mxGetPr(o[10]) : NULL;
+    const int rc = epi_plan_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) if (a) mxDestroyArray(a); fail_if(rc, err); }
+    for (size_t c = 0; c < (size_t)B; c++) { mxGetPr(o[5])[c] = (double)it[c]; mxGetPr(o[6])[c] = (double)hv[c]; mxGetPr(o[7])[c] = (double)st[c]; }
+    for (int k = 0; k < 11; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else if (o[k]) mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -688,6 +739,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "loglik") == 0) loglik(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "plan") == 0) plan(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
