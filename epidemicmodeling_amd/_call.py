@@ -177,13 +177,14 @@ def svr(be, X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, out
     return run_family("svr", be, d, [C.byref(ins)], _lib.svr_shapes(D, F, R, K), names)
 
 
-def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, names):
+def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, names, out_f32=()):
     """The call helper of the calls whose device entry takes a workspace (epi_<prefix>_workspace_bytes / _run_device /
     _run_host), which are no families: allocate the outputs `names`, and for the device entry the workspace, through the
     backend; bind them into the outputs structure `outs`, call and check the status.  Returns the dict of outputs in the ABI's
-    order."""
+    order.  out_f32: the outputs the descriptor asks for as float32."""
     h = _lib.lib()
-    out = {k: be.empty(shapes[k], np.int32 if k in out_i32 else np.float64) for k in out_names if k in names}
+    out = {k: be.empty(shapes[k], np.int32 if k in out_i32 else (np.float32 if k in out_f32 else np.float64))
+           for k in out_names if k in names}
     for k, v in out.items():
         setattr(outs, k, be.ptr(v))
     err = C.create_string_buffer(256)
@@ -288,3 +289,66 @@ def npi_plan(be, sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix,
         setattr(ins, k, be.ptr(v))
     return run_with_workspace("plan", be, d, ins, _lib.PlanOutputs(), _lib.PLAN_OUT_NAMES, _lib.PLAN_OUT_I32,
                               _lib.plan_shapes(R, P, H, n, max_iter), names)
+
+
+def _is_f32(v):
+    return str(v.dtype).endswith("float32")
+
+
+def smoother_draws(be, S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k0, clamp, lane_block, B, out_dtype, outputs,
+                   test_launch_groups=0):
+    big = (S_PLUS, P_PLUS, S_MINUS, P_MINUS)
+    f32 = all(_is_f32(v) for v in big)
+    put = be.f32 if f32 else be.f64
+    sp, pp, sm, pm = (put(v) for v in big)
+    blk = int(lane_block)
+    if all(v.ndim == 3 for v in (sp, pp, sm, pm)):
+        T, rows, nB = sp.shape
+        if 0 < blk < nB:
+            raise ValueError("lane_block given with classic [T, rows, B] arrays")
+        if B is not None and int(B) != nB:
+            raise ValueError("B does not match the arrays")
+        B, blk = nB, 0
+    elif all(v.ndim == 4 for v in (sp, pp, sm, pm)):
+        T, nblk, rows, bl = sp.shape
+        if bl != blk:
+            raise ValueError("chain-blocked arrays [T, nblk, rows, blk] need lane_block = blk")
+        B = nblk * blk if B is None else int(B)
+        if nblk != (B + blk - 1) // blk or blk >= B:
+            raise ValueError("B does not match nblk blocks of lane_block chains")
+    else:
+        raise ValueError("S_PLUS / P_PLUS / S_MINUS / P_MINUS must be [T, rows, B] or [T, nblk, rows, blk]")
+    if rows != 3 or tuple(sm.shape) != tuple(sp.shape) or tuple(pp.shape) != tuple(sp.shape[:-2]) + (9, sp.shape[-1]) \
+            or tuple(pm.shape) != tuple(pp.shape):
+        raise ValueError("smoother draws need the 3-state model: S_PLUS, S_MINUS must hold 3 rows and P_PLUS, P_MINUS 9")
+    prm = be.f64(prm)
+    if tuple(prm.shape) != (L.PRM_COUNT, B):
+        raise ValueError("prm must be [PRM_COUNT, B]")
+    T, D, k0 = int(T), int(D), int(k0)
+    z_f32 = z is not None and _is_f32(z)
+    if out_dtype is None:
+        out_f32 = False
+    elif str(out_dtype).endswith("float32"):
+        out_f32 = True
+    elif str(out_dtype).endswith("float64"):
+        out_f32 = False
+    else:
+        raise ValueError("out_dtype must be float64 or float32")
+    d = _lib.make_sdraw_desc(B, T, D, k0, clamp, blk, int(f32), int(z_f32), int(out_f32), test_launch_groups=test_launch_groups)
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_sdraw_validate(C.byref(d), err), err)       # before anything is allocated from the sizes
+    if z is not None:
+        z = be.f32(z) if z_f32 else be.f64(z)
+        if tuple(z.shape) != (T - k0, 3, B * D):
+            raise ValueError("z must be [T - k0, 3, B * D]")
+    s_term, P_term = be.f64(s_term), be.f64(P_term)
+    if s_term is not None and tuple(s_term.shape) != (3, B):
+        raise ValueError("s_term must be [3, B]")
+    if P_term is not None and tuple(P_term.shape) != (9, B):
+        raise ValueError("P_term must be [9, B]")
+    names = _lib.out_names(_lib.SDRAW_OUT_NAMES, outputs, _lib.SDRAW_DEFAULT)
+    ins = _lib.SdrawInputs()
+    for k, v in zip(_lib.SDRAW_IN_NAMES, (sp, pp, sm, pm, prm, z, s_term, P_term)):
+        setattr(ins, k, be.ptr(v))
+    return run_with_workspace("sdraw", be, d, ins, _lib.SdrawOutputs(), _lib.SDRAW_OUT_NAMES, _lib.SDRAW_OUT_I32,
+                              _lib.sdraw_shapes(B, T, D, k0), names, out_f32=("X",) if out_f32 else ())

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
     "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
     "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
+    "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
 ]
 
 
@@ -612,6 +613,41 @@ def make_plan_desc(R, P, H, n_npi, prefix_days=0, max_iter=64, max_halvings=30, 
     return d
 
 
+class SdrawDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "model", "B", "T", "D", "k0", "clamp", "lane_block", "storage", "z_f32", "out_f32",
+                                         "test_launch_groups")]
+
+
+SDRAW_IN_NAMES = ("S_PLUS", "P_PLUS", "S_MINUS", "P_MINUS", "prm", "z", "s_term", "P_term")
+SDRAW_OUT_NAMES = ("X", "rank", "status", "J", "L")
+SDRAW_OUT_I32 = ("rank", "status")
+SDRAW_DEFAULT = ("X", "rank", "status")
+SDRAW_NONFINITE, SDRAW_RANK_DEFICIENT = 1, 2            # bits of status
+
+
+class SdrawInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SDRAW_IN_NAMES]
+
+
+class SdrawOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SDRAW_OUT_NAMES]
+
+
+def sdraw_shapes(B, T, D, k0=0):
+    B, T, D, k0 = int(B), int(T), int(D), int(k0)
+    return dict(X=(T - k0, 3, B * D), rank=(T, B), status=(B,), J=(T, 9, B), L=(T, 9, B))
+
+
+def make_sdraw_desc(B, T, D, k0=0, clamp=True, lane_block=0, storage=0, z_f32=0, out_f32=0, model="SIAlphaModelEKF",
+                    test_launch_groups=0) -> SdrawDesc:
+    d = SdrawDesc()
+    d.abi_version = ABI_VERSION
+    d.model = L.MODEL_IDS[model] if isinstance(model, str) else int(model)
+    d.B, d.T, d.D, d.k0, d.clamp, d.lane_block = int(B), int(T), int(D), int(k0), int(clamp), int(lane_block)
+    d.storage, d.z_f32, d.out_f32, d.test_launch_groups = int(storage), int(z_f32), int(out_f32), int(test_launch_groups)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -724,6 +760,11 @@ def lib():
         h.epi_plan_run_device.argtypes = [C.POINTER(PlanDesc), C.POINTER(PlanInputs), C.POINTER(PlanOutputs),
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_plan_run_host.argtypes = [C.POINTER(PlanDesc), C.POINTER(PlanInputs), C.POINTER(PlanOutputs), C.c_int, C.c_char_p]
+        h.epi_sdraw_validate.argtypes = [C.POINTER(SdrawDesc), C.c_char_p]
+        h.epi_sdraw_workspace_bytes.argtypes = [C.POINTER(SdrawDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_sdraw_run_device.argtypes = [C.POINTER(SdrawDesc), C.POINTER(SdrawInputs), C.POINTER(SdrawOutputs),
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_sdraw_run_host.argtypes = [C.POINTER(SdrawDesc), C.POINTER(SdrawInputs), C.POINTER(SdrawOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

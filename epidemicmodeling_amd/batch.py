@@ -1089,3 +1089,37 @@ def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None,
     without a host synchronisation."""
     return _call.npi_plan(DeviceBackend(device), sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter,
                           max_halvings, tol, outputs)
+
+
+def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None, P_term=None, k0=0, clamp=True, lane_block=0, B=None,
+                   out_dtype=None, outputs=("X", "rank", "status"), stream=None):
+    """Joint posterior draws of the smoothed paths by backward simulation, from what a 3-state filter run left on the device
+    (epi_sdraw_run_device): D paths per chain of the law whose mean and covariance recursions are the
+    smoother's own (GenericExtendedKalmanFilter.m:218, :223),
+        x_T = clamp(s_T + F_T z_T),   x_k = clamp((S+_k + J_k (x_{k+1} - S-_{k+1})) + F_k z_k),   k = T-1 ... k0,
+    J_k the smoother's gain, F_k the pivoted Cholesky factor of P+_k - J_k P-_{k+1} J_k'.  Path p = chain * D + draw, so X is
+    what ensemble_summary(X, B, D) takes.
+    S_PLUS, S_MINUS [T, 3, B], P_PLUS, P_MINUS [T, 9, B] device tensors of a SIAlphaModelEKF run, all float64 or all float32 --
+    or, with lane_block = an EkfRunner's `blk`, its chain-blocked outputs [T, nblk, rows, blk] as they lie (nothing is unblocked
+    or copied) with B = the number of chains.  prm [PRM_COUNT, B] the filter's own.  z [T - k0, 3, B * D] standard-normal inputs,
+    float64 or float32, or None: no noise term -- with clamp the path is then S_SMOOTH bit for bit.  s_term [3, B], P_term [9, B]:
+    the terminal law (the last day of S_SMOOTH / P_SMOOTH when s_final / Ps_final were set; default S_PLUS, P_PLUS of day T-1).
+    k0: the first day returned.  clamp: StateHardMargins on every draw (a NaN stays NaN); False: an exactly Gaussian law.
+    out_dtype: torch.float64 (default) or torch.float32 for X (the float64 result rounded once).
+    outputs: any of "X" [T - k0, 3, B * D], "rank" [T, B] int32 (columns of F kept; -1: a NaN record), "status" [B] int32 (bit 0,
+    _lib.SDRAW_NONFINITE: a non-finite input entry met -- J = 0 by the guard :211, or a NaN record; bit 1,
+    _lib.SDRAW_RANK_DEFICIENT: a rank below 3 on some day), "J", "L" [T, 9, B] float64 (entry i + 3 j; L = F, a row-permuted lower
+    triangle).  Returns a dict of device tensors.  Enqueued on `stream` (default: the current stream) without a host
+    synchronisation."""
+    for name, v in (("S_PLUS", S_PLUS), ("P_PLUS", P_PLUS), ("S_MINUS", S_MINUS), ("P_MINUS", P_MINUS)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+        if not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not (S_PLUS.dtype == P_PLUS.dtype == S_MINUS.dtype == P_MINUS.dtype) or S_PLUS.dtype not in (torch.float64, torch.float32):
+        raise ValueError("S_PLUS, P_PLUS, S_MINUS, P_MINUS must all be float64 or all float32")
+    dev = S_PLUS.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.smoother_draws(DeviceBackend(dev, st), S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k0, clamp,
+                                    lane_block, B, out_dtype, outputs)

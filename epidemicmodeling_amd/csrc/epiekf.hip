@@ -795,6 +795,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "svr.hpp"
 #include "loglik.hpp"
 #include "npi_plan.hpp"
+#include "smoother_draws.hpp"
 
 struct SeirpRates { double ae, ai, kappa, rho, beta, mu, gamma; };
 EPI_DEV void seirp_rhs(const SeirpRates &r, const double (&y)[5], double (&f)[5])
@@ -4116,6 +4117,124 @@ int epi_plan_run_host(const epi_plan_desc *d, const epi_plan_inputs *in, const e
         dout.status = HostIO::at<int32_t>(base, o_st);
         dout.states = HostIO::at<double>(base, o_x); dout.mu = HostIO::at<double>(base, o_mu); dout.F_trace = HostIO::at<double>(base, o_ft);
         return epi_plan_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- joint posterior draws of the smoothed paths: sdraw_gain, then sdraw_paths (smoother_draws.hpp) ----
+// the workspace: one record of kSdRec doubles per (day, chain)
+int epi_sdraw_validate(const epi_sdraw_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->model < 0 || d->model > EPI_MODEL_NEWCASE6_CODEGEN) { set_err(err, "unknown model"); return EPI_ERR_BAD_ARG; }
+    const ModelInfo &mi = MODEL_TABLE[d->model];
+    if (mi.m != 3) {
+        set_err(err, "smoother draws need the 3-state SIAlphaModelEKF: the 6-state costate block has no meaningful factor in fp64");
+        return EPI_ERR_UNSUPPORTED;
+    }
+    if (mi.flipped) { set_err(err, "smoother draws do not take the time-flipped models"); return EPI_ERR_UNSUPPORTED; }
+    if (d->B < 1) { set_err(err, "B must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1) { set_err(err, "D must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k0 >= d->T) { set_err(err, "k0 must lie in 0 .. T-1"); return EPI_ERR_BAD_ARG; }
+    if (d->clamp != 0 && d->clamp != 1) { set_err(err, "clamp must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->lane_block < 0 || d->lane_block > d->B) { set_err(err, "lane_block must lie in 0 .. B (0 or B: the classic [T][rows][B])"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->z_f32 != 0 && d->z_f32 != 1) { set_err(err, "z_f32 must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->out_f32 != 0 && d->out_f32 != 1) { set_err(err, "out_f32 must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->test_launch_groups < 0) { set_err(err, "test_launch_groups must be >= 0"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_sdraw_workspace_bytes(const epi_sdraw_desc *d, size_t *bytes, char *err)
+{
+    int rc = epi_sdraw_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = (size_t)d->T * (size_t)d->B * (size_t)kSdRec * sizeof(double);
+    return EPI_OK;
+}
+
+static int sdraw_check_arrays(const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, char *err)
+{
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->S_PLUS || !in->P_PLUS || !in->S_MINUS || !in->P_MINUS || !in->prm) { set_err(err, "NULL S_PLUS / P_PLUS / S_MINUS / P_MINUS / prm"); return EPI_ERR_BAD_ARG; }
+    if (!out->X && !out->rank && !out->status && !out->J && !out->L) { set_err(err, "no output requested: at least one of X / rank / status / J / L"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, void *ws, size_t ws_bytes,
+                         void *stream, char *err)
+{
+    int rc = epi_sdraw_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = sdraw_check_arrays(in, out, err)) != EPI_OK) return rc;
+    const size_t need = (size_t)d->T * (size_t)d->B * (size_t)kSdRec * sizeof(double);
+    if (!ws || ws_bytes < need) { set_err(err, "workspace too small (epi_sdraw_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    SdArgs g{};
+    g.B = d->B; g.T = d->T; g.D = d->D; g.k0 = d->k0; g.clamp = d->clamp; g.f32 = d->storage;
+    sdraw_geometry(d->B, d->lane_block, &g.blk, &g.nblk);
+    g.S_PLUS = in->S_PLUS; g.P_PLUS = in->P_PLUS; g.S_MINUS = in->S_MINUS; g.P_MINUS = in->P_MINUS;
+    g.prm = in->prm; g.s_term = in->s_term; g.P_term = in->P_term; g.z = in->z;
+    g.X = out->X; g.ws = (double *)ws; g.J = out->J; g.L = out->L; g.rank = out->rank; g.status = out->status;
+    if (out->status && (e = hipMemsetAsync(out->status, 0, (size_t)d->B * sizeof(int32_t), st)) != hipSuccess)
+        return hip_fail(err, e, "hipMemsetAsync of status");
+    const long long cap = d->test_launch_groups > 0 ? (long long)d->test_launch_groups : kSdLaunchGroups;
+    g.tiles = (unsigned)(((int64_t)d->B + pinv_wg<3>() - 1) / pinv_wg<3>());
+    const long long groups = (long long)g.tiles * d->T;          // every day, also those below k0: J, L and rank cover [T]
+    for (long long w0 = 0; w0 < groups; w0 += cap) {                  // in slices, as two_filter's
+        g.wg0 = w0;
+        const unsigned nb = (unsigned)(groups - w0 < cap ? groups - w0 : cap);
+        hipLaunchKernelGGL(sdraw_gain<3>, dim3(nb), dim3(pinv_wg<3>()), 0, st, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "sdraw_gain launch");
+    }
+    if (!out->X) return EPI_OK;
+    const long long pg = (long long)(((int64_t)d->B * d->D + kSdPathWg - 1) / kSdPathWg);
+    using PathKernel = void (*)(const SdArgs);
+    static const PathKernel kernels[3][2] = {{sdraw_paths<0, 0>, sdraw_paths<0, 1>}, {sdraw_paths<1, 0>, sdraw_paths<1, 1>},
+                                             {sdraw_paths<2, 0>, sdraw_paths<2, 1>}};
+    const PathKernel kern = kernels[!in->z ? 0 : (d->z_f32 ? 2 : 1)][d->out_f32];
+    for (long long w0 = 0; w0 < pg; w0 += cap) {
+        g.wg0 = w0;
+        const unsigned nb = (unsigned)(pg - w0 < cap ? pg - w0 : cap);
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(kSdPathWg), 0, st, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "sdraw_paths launch");
+    }
+    return EPI_OK;
+}
+
+int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err)
+{
+    int rc = epi_sdraw_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = sdraw_check_arrays(in, out, err)) != EPI_OK) return rc;
+    const size_t B = (size_t)d->B, T = (size_t)d->T, N = B * (size_t)d->D, Tk = T - (size_t)d->k0, none = HostIO::kAbsent;
+    int gblk, gnblk;
+    sdraw_geometry(d->B, d->lane_block, &gblk, &gnblk);
+    const size_t Bp = (size_t)gnblk * (size_t)gblk, es = d->storage ? 4 : 8;
+    HostIO io;
+    const size_t o_sp = io.add_in(in->S_PLUS, T * 3, es, Bp, 0, Bp), o_pp = io.add_in(in->P_PLUS, T * 9, es, Bp, 0, Bp);
+    const size_t o_sm = io.add_in(in->S_MINUS, T * 3, es, Bp, 0, Bp), o_pm = io.add_in(in->P_MINUS, T * 9, es, Bp, 0, Bp);
+    const size_t o_prm = io.add_in(in->prm, (size_t)EPI_PRM_COUNT, 8, B, 0, B);
+    const size_t o_z = in->z ? io.add_in(in->z, Tk * 3, d->z_f32 ? 4 : 8, N, 0, N) : none;
+    const size_t o_st = in->s_term ? io.add_in(in->s_term, 3, 8, B, 0, B) : none, o_pt = in->P_term ? io.add_in(in->P_term, 9, 8, B, 0, B) : none;
+    const size_t o_X = out->X ? io.add_out(out->X, Tk * 3, d->out_f32 ? 4 : 8, N, 0, N) : none;
+    const size_t o_rk = out->rank ? io.add_out(out->rank, T, 4, B, 0, B) : none, o_ss = out->status ? io.add_out(out->status, 1, 4, B, 0, B) : none;
+    const size_t o_J = out->J ? io.add_out(out->J, T * 9, 8, B, 0, B) : none, o_L = out->L ? io.add_out(out->L, T * 9, 8, B, 0, B) : none;
+    const size_t wsb = T * B * (size_t)kSdRec * sizeof(double);
+    const size_t o_ws = io.reserve(wsb);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_sdraw_inputs din{};
+        din.S_PLUS = base + o_sp; din.P_PLUS = base + o_pp; din.S_MINUS = base + o_sm; din.P_MINUS = base + o_pm;
+        din.prm = HostIO::at<const double>(base, o_prm); din.z = HostIO::at<const char>(base, o_z);
+        din.s_term = HostIO::at<const double>(base, o_st); din.P_term = HostIO::at<const double>(base, o_pt);
+        epi_sdraw_outputs dout{};
+        dout.X = HostIO::at<char>(base, o_X); dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_ss);
+        dout.J = HostIO::at<double>(base, o_J); dout.L = HostIO::at<double>(base, o_L);
+        return epi_sdraw_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -334,3 +334,13 @@ def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None,
     and bits."""
     return _call.npi_plan(HostBackend(device), sp, u_min, eps, horizon, u_fixed, u_init, J0_prefix, J1_prefix, prefix_days, max_iter,
                           max_halvings, tol, outputs)
+
+
+def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None, P_term=None, k0=0, clamp=True, lane_block=0, B=None,
+                   out_dtype=None, outputs=("X", "rank", "status"), device=0):
+    """epi_sdraw_run_host: batch.smoother_draws on NumPy arrays (synchronous): the same arguments, and the same keys, order,
+    dtypes and bits.  The four filter arrays all float32 = float storage, anything else is taken as float64; z float32 or
+    float64; out_dtype np.float64 (default) or np.float32."""
+    z = None if z is None else np.asarray(z)
+    return _call.smoother_draws(HostBackend(device), *(np.asarray(v) for v in (S_PLUS, P_PLUS, S_MINUS, P_MINUS)), prm, D, z, s_term,
+                                P_term, k0, clamp, lane_block, B, None if out_dtype is None else np.dtype(out_dtype), outputs)

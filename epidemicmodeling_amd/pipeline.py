@@ -649,3 +649,68 @@ def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None
     chosen = torch.where((best < 0)[:, None], torch.full_like(chosen, float("nan")), chosen)
     return {"loglik": res["loglik"].view(R, G), "n_valid": res["n_valid"].view(R, G), "status": res["status"].view(R, G),
             "best": res["best"], "best_loglik": res["best_loglik"], "chosen": chosen, "table": tab, "runner": r, "workload": gw}
+
+
+def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, seed=0, k0=0, storage="f64", clamp=True,
+                 device="cuda:0", lane_block="auto", z=None):
+    """The fan chart of the EKF/EKS itself: run the smoother of `w` (a synth.Workload of SIAlphaModelEKF), draw n_draws joint
+    posterior paths per chain by backward simulation (batch.smoother_draws on the runner's arrays as they lie; the terminal law is
+    the smoothed last day, so s_final / Ps_final of the workload are honoured) and summarise them over the draws of each chain
+    (batch.ensemble_summary: mean, std, min, max, quantiles at `q`; population [B] appends the new-case row ((N s) i) alpha).
+    The noise is torch.randn on the device from `seed` (or `z` [T - k0, 3, B * n_draws], to repeat a call on given draws); k0 is
+    the first day returned.  Nothing is copied back in between.
+    Returns (runner, X [T - k0, 3, B * n_draws], the summary dict, z).  No host synchronisation."""
+    if w.model != "SIAlphaModelEKF":
+        raise ValueError("smoothed_fan needs a workload of the 3-state SIAlphaModelEKF")
+    n_draws, k0 = int(n_draws), int(k0)
+    dev = torch.device(device)
+    dw = batch.DeviceWorkload(w, device)
+    r = batch.EkfRunner(dw, ["S_PLUS", "P_PLUS", "S_MINUS", "P_MINUS", "S_SMOOTH", "P_SMOOTH"], lane_block=lane_block, storage=storage)
+    r.run()
+    if z is None:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        z = torch.randn((w.T - k0, 3, w.B * n_draws), dtype=torch.float64, device=dev, generator=gen)
+    blk = 0 if r.blk == w.B else r.blk
+    ss, ps = r.out["S_SMOOTH"][-1], r.out["P_SMOOTH"][-1]          # the last day: [3, B] / [9, B], or [nblk, rows, blk]
+    if blk:
+        ss = ss.permute(1, 0, 2).reshape(3, -1)[:, :w.B]
+        ps = ps.permute(1, 0, 2).reshape(9, -1)[:, :w.B]
+    res = batch.smoother_draws(r.out["S_PLUS"], r.out["P_PLUS"], r.out["S_MINUS"], r.out["P_MINUS"], dw.prm, n_draws, z=z,
+                               s_term=ss.to(torch.float64), P_term=ps.to(torch.float64), k0=k0, clamp=clamp, lane_block=blk, B=w.B)
+    summary = batch.ensemble_summary(res["X"], w.B, n_draws, q=q, population=population)
+    summary["rank"], summary["status"] = res["rank"], res["status"]
+    return r, res["X"], summary, z
+
+
+def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975), seed=0, k0=None,
+                 storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0, device="cuda:0"):
+    """The forecast of Tools/TrainPredictPrescribeNPI.m:356-377 as a fan chart of the smoother's own joint law: the front half
+    (preprocessing, EKF round 1, regression, round 2, regression), then the forecast filter -- the observations padded with NaN
+    over `horizon` days, R_v padded with its mean (:360), the NPIs of `plan` [horizon, n, S] or, with plan = None, the last day's
+    held (the reference's "fixed" forecast, :373-375) -- and smoothed_fan on it.  k0: the first day returned (default: the start
+    of the horizon).  Returns the front half's intermediates, `workload` (the forecast filter's), `runner`, X [T + horizon - k0,
+    3, S * n_draws], `summary` (rows s, i, alpha, new cases) and z."""
+    T, S = cases.shape
+    n = ip.shape[1]
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError("horizon must be >= 1")
+    N = np.asarray(population, dtype=np.float64)
+    out = _front_half(cases, deaths, N, ip, num_regression_days, W, device, regression, cv_folds, cv_seed)
+    pre, fit2 = out["pre"], out["fit2"]
+    x, R, u = pre["x_new"], pre["R_v"], pre["ip_filled"]
+    if plan is None:
+        tail = np.repeat(u[-1:], horizon, axis=0)
+    else:
+        tail = np.asarray(plan, dtype=np.float64)
+        if tail.shape != (horizon, n, S):
+            raise ValueError("plan must be [horizon, n, S]")
+    xf = np.concatenate([x, np.full((horizon, S), np.nan)])
+    Rf = np.concatenate([R, np.repeat(R.mean(axis=0, keepdims=True), horizon, axis=0)])
+    uf = np.concatenate([u, tail])
+    wf = workload3(xf, Rf, uf, N, pre["I0"], fit2["a"], fit2["b"])
+    r, X, summary, z = smoothed_fan(wf, n_draws, q=q, population=N, seed=seed, k0=T if k0 is None else int(k0), storage=storage,
+                                    clamp=clamp, device=device)
+    out.update(workload=wf, runner=r, X=X, summary=summary, z=z)
+    return out

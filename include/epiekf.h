@@ -1244,6 +1244,72 @@ int epi_plan_run_device(const epi_plan_desc *d, const epi_plan_inputs *in, const
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_plan_run_host(const epi_plan_desc *d, const epi_plan_inputs *in, const epi_plan_outputs *out, int device, char *err);
 
+/* ---- Joint posterior draws of the smoothed paths (backward simulation), from the arrays a 3-state filter run left ----
+ * Not a script of the reference: its smoother returns the marginal law of every day (S_SMOOTH, P_SMOOTH); this call samples the
+ * joint law over days whose mean and covariance recursions are Tools/GenericExtendedKalmanFilter.m:218 and :223.
+ * Definition (pinned; restated in tests/sdraw_ref.c).  Chain c, day k, draw d, path p = c * D + d:
+ *   A_k      StateJacobians of S_PLUS(k) (SIAlphaModelEKF.m:62-76; prm rows EPI_PRM_DT, _BETA, _GAMMA)
+ *   J_k      k < T-1: (P_PLUS(k) A_k') pinv(P_MINUS(k+1)) in the smoother's own operation order (the fma chains of its products, the
+ *              library's pinv on the upper triangle of P_MINUS): the bits the smoother forms.  0 where P_MINUS(k+1) holds a NaN
+ *              or an Inf (:211), and for k = T-1
+ *   Sigma_k  = P_PLUS(k) - (J_k P_MINUS(k+1)) J_k', products written (acc = a0 b0; acc = acc + ak bk, no fma), then (Sigma +
+ *              Sigma') / 2.  Under the guard and for k = T-1: P_PLUS(k) (k = T-1: P_term when given), symmetrised the same way
+ *   F_k      the factor of Sigma_k by a right-looking Cholesky with diagonal pivoting (the first largest remaining diagonal entry),
+ *              stopped when that pivot is <= 3 eps max diag(Sigma_k) (eps = 2^-52) or not positive: column j = a(:, j) / sqrt(pivot),
+ *              trailing block a(i, c) - l(i, j) l(c, j); the remaining columns are zero and the rows return to the original
+ *              order, so F F' = Sigma up to rounding and F is a row-permuted lower triangle (nine entries).  rank = the columns kept
+ *   x_{T-1}  = clamp(s_T + F z),  s_T = s_term when given, else S_PLUS(T-1)
+ *   x_k      = clamp((S_PLUS(k) + J_k (x_{k+1} - S_MINUS(k+1))) + F_k z_k): J d first (d0 term, then fma for d1, d2: the
+ *              smoother's :218), S_PLUS added, then F z as its own sum (written products) added.  z = NULL: the noise term is
+ *              not formed, and with clamp = 1 the path is S_SMOOTH bit for bit
+ *   clamp    StateHardMargins (SIAlphaModelEKF.m:27-31; prm rows EPI_PRM_S_MIN, _I_MIN, _ALPHA_MIN, _ALPHA_MAX) applied to every draw
+ *              as :221 applies it to the mean, except that a NaN entry stays NaN.  clamp = 0: none (an exactly Gaussian law)
+ *   a non-finite entry of S_PLUS(k) / P_PLUS(k) (k = T-1: of P_term): J_k and F_k are NaN, rank -1
+ *   status   bit 0 (EPI_SDRAW_NONFINITE): a non-finite input entry met (the guard fired, or a NaN record);  bit 1
+ *              (EPI_SDRAW_RANK_DEFICIENT): a rank below 3 on some day
+ * Layout: S_PLUS, S_MINUS (3 rows), P_PLUS, P_MINUS (9 rows) as epi_ekf_run_* left them: element (t, row, c) at ((t * nblk + c /
+ *   blk) * rows + row) * blk + c % blk, blk = lane_block (0 or B: the classic [T][rows][B]), doubles (storage 0) or floats (storage
+ *   1, widened on load; all arithmetic is double).  Padding lanes are never read.  prm [EPI_PRM_COUNT][B]; s_term [3][B], P_term
+ *   [9][B] doubles or NULL.  z and X [T - k0][3][B * D], path-minor (what epi_ens_run_* takes with R = B), each double or float
+ *   (z_f32, out_f32; a float X is the double result rounded once).  J, L (= F) [T][9][B] column-major entries, rank [T][B], status
+ *   [B].  Every output may be NULL. */
+enum { EPI_SDRAW_NONFINITE = 1, EPI_SDRAW_RANK_DEFICIENT = 2 };
+typedef struct epi_sdraw_desc {
+    int32_t abi_version;
+    int32_t model;               /* EPI_MODEL_SIA3 only */
+    int32_t B, T;                /* chains, days */
+    int32_t D;                   /* draws per chain, >= 1 */
+    int32_t k0;                  /* first day returned, 0 <= k0 < T: the recursion stops there */
+    int32_t clamp;               /* 1 = StateHardMargins on every draw, 0 = none */
+    int32_t lane_block;          /* 0 or B: classic; else chains per layout block */
+    int32_t storage;             /* 0 = double, 1 = float (S_PLUS, P_PLUS, S_MINUS, P_MINUS) */
+    int32_t z_f32, out_f32;      /* element type of z / X: 0 = double, 1 = float */
+    int32_t test_launch_groups;  /* 0; > 0: workgroups per launch (the tests cut small calls into several launches with it) */
+} epi_sdraw_desc;
+typedef struct epi_sdraw_inputs {
+    const void *S_PLUS, *P_PLUS, *S_MINUS, *P_MINUS;
+    const double *prm;
+    const void *z;                       /* or NULL: the deterministic path */
+    const double *s_term, *P_term;       /* or NULL */
+} epi_sdraw_inputs;
+typedef struct epi_sdraw_outputs {
+    void *X;                             /* [T - k0][3][B * D] */
+    int32_t *rank, *status;              /* [T][B], [B] */
+    double *J, *L;                       /* [T][9][B] */
+} epi_sdraw_outputs;
+/* no GPU needed: EPI_ERR_UNSUPPORTED with a message for a model other than EPI_MODEL_SIA3 (the six-state models: their costate
+ * block has no meaningful factor in fp64; the time-flipped models), EPI_ERR_BAD_ARG for B, T, D < 1, k0 outside 0 .. T-1, a
+ * clamp, storage, z_f32 or out_f32 outside {0, 1}, a lane_block outside 0 .. B, a negative test_launch_groups */
+int epi_sdraw_validate(const epi_sdraw_desc *d, char *err);
+/* bytes of device workspace epi_sdraw_run_device needs (24 doubles per (day, chain)) */
+int epi_sdraw_workspace_bytes(const epi_sdraw_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; a memset of status and the two kernels (each cut into launches below 2^31 threads) enqueued on `stream`: no
+ * host synchronisation, no allocation.  EPI_ERR_WORKSPACE for a workspace below epi_sdraw_workspace_bytes */
+int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, void *ws, size_t ws_bytes,
+                         void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -93,6 +93,13 @@
 //       u_min)  (P*R) x n_npi x H;  J0_prefix, J1_prefix ([] with prefix_days 0)  R x 1.  Chain (r-1) * P + l.  plan  (P*R) x
 //       n_npi x H;  J0 .. status  P x R (status 0: gap <= tol |F|; bit 0: max_iter passes; bit 1: no descending step; bit 2:
 //       F not finite);  states, mu  (P*R) x 3 x H and F_trace  (P*R) x max_iter (NaN beyond iters), only when requested.
+//   [X, rank, status, J, L] = epiekf_pipeline_mex('sdraw', S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k_first, clamp)
+//       Joint posterior draws of the smoothed path of ONE 3-state chain by backward simulation.  S_PLUS, S_MINUS
+//       3 x T;  P_PLUS, P_MINUS  3 x 3 x T;  prm  the filter's parameter vector (EPI_PRM_COUNT entries);  D  draws;  z ([] = no
+//       noise: with the clamp the path is S_SMOOTH)  D x 3 x (T - k_first + 1) standard-normal inputs;  s_term, P_term ([] = S_PLUS,
+//       P_PLUS of day T)  3 x 1, 3 x 3;  k_first ([] = 1)  the first day returned, ONE-based;  clamp ([] = 1).  X  D x 3 x
+//       (T - k_first + 1);  rank  1 x T (-1: a NaN record);  status  scalar (bit 0: a non-finite input entry met, bit 1: a rank
+//       below 3);  J, L  3 x 3 x T, only when requested.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -695,6 +702,58 @@ static void plan(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else if (o[k]) mxDestroyArray(o[k]);
 }
 
+static void sdraw(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 12) mexErrMsgTxt("epiekf_pipeline_mex('sdraw', S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k_first, clamp): 12 inputs expected");
+    for (int k = 1; k <= 6; k++)
+        if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("S_PLUS ... D must be non-empty double arrays");
+    if (mxGetNumberOfDimensions(prhs[1]) != 2 || mxGetM(prhs[1]) != 3) mexErrMsgTxt("S_PLUS must be 3 x T");
+    const mwSize T = mxGetN(prhs[1]);
+    if (mxGetNumberOfDimensions(prhs[3]) != 2 || mxGetM(prhs[3]) != 3 || mxGetN(prhs[3]) != T) mexErrMsgTxt("S_MINUS must be 3 x T");
+    for (int k = 2; k <= 4; k += 2) {
+        const mwSize nd = mxGetNumberOfDimensions(prhs[k]);
+        const mwSize *dm = mxGetDimensions(prhs[k]);
+        if (nd < 2 || nd > 3 || dm[0] != 3 || dm[1] != 3 || (nd == 3 ? dm[2] : 1) != T) mexErrMsgTxt("P_PLUS, P_MINUS must be 3 x 3 x T");
+    }
+    if (mxGetNumberOfElements(prhs[5]) != EPI_PRM_COUNT) mexErrMsgTxt("prm must hold EPI_PRM_COUNT entries");
+    double kf = 1.0;
+    if (!mxIsEmpty(prhs[10])) kf = mxGetScalar(prhs[10]);
+    if (!(kf >= 1.0 && kf <= (double)T) || kf != (double)(int32_t)kf) mexErrMsgTxt("k_first must be an integer with 1 <= k_first <= T");
+    epi_sdraw_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.model = EPI_MODEL_SIA3; d.B = 1; d.T = (int32_t)T; d.D = (int32_t)mxGetScalar(prhs[6]);
+    d.k0 = (int32_t)kf - 1; d.clamp = mxIsEmpty(prhs[11]) ? 1 : (int32_t)mxGetScalar(prhs[11]);
+    char err[256] = {0};
+    fail_if(epi_sdraw_validate(&d, err), err);
+    const mwSize D = (mwSize)d.D, Tk = T - (mwSize)d.k0;
+    if (!mxIsEmpty(prhs[7]) && mxGetNumberOfElements(prhs[7]) != D * 3 * Tk) mexErrMsgTxt("z must be D x 3 x (T - k_first + 1)");
+    if (!mxIsEmpty(prhs[8]) && mxGetNumberOfElements(prhs[8]) != 3) mexErrMsgTxt("s_term must be 3 x 1");
+    if (!mxIsEmpty(prhs[9]) && mxGetNumberOfElements(prhs[9]) != 9) mexErrMsgTxt("P_term must be 3 x 3");
+    epi_sdraw_inputs in;
+    memset(&in, 0, sizeof in);
+    // the ABI's [T][3][1], [T][9][1] (entry (i, j) in row i + 3 j) are MATLAB's 3 x T, 3 x 3 x T; [T'][3][D] is D x 3 x T'
+    in.S_PLUS = mxGetPr(prhs[1]); in.P_PLUS = mxGetPr(prhs[2]); in.S_MINUS = mxGetPr(prhs[3]); in.P_MINUS = mxGetPr(prhs[4]);
+    in.prm = mxGetPr(prhs[5]); in.z = opt(prhs[7]); in.s_term = opt(prhs[8]); in.P_term = opt(prhs[9]);
+    mxArray *o[5];
+    o[0] = dbl3(D, 3, Tk);
+    o[1] = mxCreateDoubleMatrix(1, T, mxREAL);
+    o[2] = mxCreateDoubleMatrix(1, 1, mxREAL);
+    o[3] = nlhs > 3 ? dbl3(3, 3, T) : NULL;
+    o[4] = nlhs > 4 ? dbl3(3, 3, T) : NULL;
+    std::vector<int32_t> rk(T);
+    int32_t st = 0;
+    epi_sdraw_outputs out;
+    memset(&out, 0, sizeof out);
+    out.X = mxGetPr(o[0]); out.rank = rk.data(); out.status = &st;
+    out.J = o[3] ? mxGetPr(o[3]) : NULL; out.L = o[4] ? mxGetPr(o[4]) : NULL;
+    const int rc = epi_sdraw_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) if (a) mxDestroyArray(a); fail_if(rc, err); }
+    for (size_t k = 0; k < (size_t)T; k++) mxGetPr(o[1])[k] = (double)rk[k];
+    mxGetPr(o[2])[0] = (double)st;
+    for (int k = 0; k < 5; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else if (o[k]) mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
@@ -740,6 +799,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "loglik") == 0) loglik(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "plan") == 0) plan(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
