@@ -352,3 +352,51 @@ def smoother_draws(be, S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_te
         setattr(ins, k, be.ptr(v))
     return run_with_workspace("sdraw", be, d, ins, _lib.SdrawOutputs(), _lib.SDRAW_OUT_NAMES, _lib.SDRAW_OUT_I32,
                               _lib.sdraw_shapes(B, T, D, k0), names, out_f32=("X",) if out_f32 else ())
+
+
+def ensemble_score(be, src, truth, R, D, alpha, n_bins, population, truth_series, first_day, k0, k1, outputs, test_launch_items=0):
+    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+    if src.ndim not in (2, 3):
+        raise ValueError("src must be [T, rows, B] or [T, B]")
+    R, D = int(R), int(D)
+    if src.shape[-1] != R * D:
+        raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
+    T, rows = int(src.shape[0]), (1 if src.ndim == 2 else int(src.shape[1]))
+    pop = be.f64(population)
+    if pop is not None and tuple(pop.shape) != (R,):
+        raise ValueError("population must be [R]")
+    ro = rows + int(pop is not None)
+    truth = be.f64(truth)
+    if truth.ndim == 2 and src.ndim == 2:
+        truth = truth.reshape(T, 1, truth.shape[-1]) if truth.shape[0] == T else truth
+    if truth.ndim != 3 or tuple(truth.shape[:2]) != (T, ro):
+        raise ValueError(f"truth must be [T, rows', Rt] = [{T}, {ro}, Rt] ([T, Rt] for a [T, B] src)")
+    Rt = int(truth.shape[2])
+    ts, fd = be.i32(truth_series), be.i32(first_day)
+    if ts is None and Rt != R:
+        raise ValueError(f"truth holds {Rt} columns, R = {R}: pass truth_series [R]")
+    if ts is not None:
+        if tuple(ts.shape) != (R,):
+            raise ValueError("truth_series must be [R]")
+        if not be.resident(truth_series):
+            h = np.asarray(truth_series)
+            if h.min() < 0 or h.max() >= Rt:
+                raise ValueError("truth_series must hold entries in 0 .. Rt-1")
+    if fd is not None and tuple(fd.shape) != (R,):
+        raise ValueError("first_day must be [R]")
+    d = _lib.make_escore_desc(T, rows, R, D, Rt, alpha, n_bins, storage=int(_is_f32(src)), derive_newcases=int(pop is not None),
+                              k0=k0, k1=k1, test_launch_items=test_launch_items)
+    names = _lib.escore_out_names(outputs, n_bins)
+    ins = _lib.EscoreInputs()
+    for k, v in zip(_lib.ESCORE_IN_NAMES, (src, pop, truth, ts, fd)):
+        setattr(ins, k, be.ptr(v))
+    probe = _lib.EscoreOutputs()
+    for k in names:
+        setattr(probe, k, 1)                            # validate looks only at which outputs are asked for
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_escore_validate(C.byref(d), C.byref(ins), C.byref(probe), err), err)   # before anything is allocated
+    out = run_with_workspace("escore", be, d, ins, _lib.EscoreOutputs(), _lib.ESCORE_OUT_NAMES, _lib.ESCORE_OUT_I32,
+                             _lib.escore_shapes(T, rows, R, d.n_a, d.n_bins, d.derive_newcases), names)
+    if src.ndim == 2:
+        out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
+    return out

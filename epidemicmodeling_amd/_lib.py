@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
     "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
     "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
+    "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
 ]
 
 
@@ -648,6 +649,62 @@ def make_sdraw_desc(B, T, D, k0=0, clamp=True, lane_block=0, storage=0, z_f32=0,
     return d
 
 
+class EscoreDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "Rt", "n_a", "n_bins", "storage", "derive_newcases", "k0",
+                                         "k1", "test_launch_items", "reserved")] + [("alpha", C.c_double * 8)]
+
+
+ESCORE_IN_NAMES = ("src", "population", "truth", "truth_series", "first_day")
+ESCORE_ITEM_NAMES = ("crps", "wis", "ae", "width", "rank", "ties", "cover", "count")
+ESCORE_REGION_NAMES = ("crps_mean", "wis_mean", "ae_mean", "n_scored", "cover_frac", "pit_hist")
+ESCORE_OUT_NAMES = ESCORE_ITEM_NAMES + ESCORE_REGION_NAMES
+ESCORE_OUT_I32 = ("rank", "ties", "cover", "count", "n_scored", "pit_hist")
+ESCORE_DEFAULT_ALPHA = (0.5, 0.05)
+
+
+class EscoreInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ESCORE_IN_NAMES]
+
+
+class EscoreOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ESCORE_OUT_NAMES]
+
+
+def escore_shapes(T, rows, R, n_a, n_bins, derive_newcases=0):
+    """shape of every output of epi_escore_run_* (rows' = rows + derive_newcases)"""
+    ro, n_a, n_bins = int(rows) + int(derive_newcases), int(n_a), int(n_bins)
+    sh = {k: (T, ro, R) for k in ESCORE_ITEM_NAMES}
+    sh["width"] = (T, n_a, ro, R)
+    sh.update({k: (ro, R) for k in ESCORE_REGION_NAMES})
+    sh["cover_frac"], sh["pit_hist"] = (n_a, ro, R), (n_bins, ro, R)
+    return sh
+
+
+def escore_out_names(outputs, n_bins):
+    """None -> every output (pit_hist only with n_bins > 0); else the names asked for, in the ABI's order"""
+    default = [k for k in ESCORE_OUT_NAMES if k != "pit_hist" or int(n_bins) > 0]
+    names = out_names(ESCORE_OUT_NAMES, outputs, default)
+    return [k for k in ESCORE_OUT_NAMES if k in names]
+
+
+def make_escore_desc(T, rows, R, D, Rt, alpha=ESCORE_DEFAULT_ALPHA, n_bins=0, storage=0, derive_newcases=0, k0=0, k1=None,
+                     test_launch_items=0) -> EscoreDesc:
+    """storage: 0 / "f64" = double source, 1 / "f32" = float source.  More than 8 levels reach the library's own check as
+    n_a = len(alpha) (only the first 8 fit the descriptor).  k1 = None: T."""
+    d = EscoreDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.rows, d.R, d.D, d.Rt = int(T), int(rows), int(R), int(D), int(Rt)
+    alpha = [float(v) for v in np.atleast_1d(np.asarray(alpha, dtype=np.float64))]
+    d.n_a, d.n_bins = len(alpha), int(n_bins)
+    for k, v in enumerate(alpha[:8]):
+        d.alpha[k] = v
+    d.storage = {"f64": 0, "f32": 1}.get(storage, storage)
+    d.derive_newcases = int(derive_newcases)
+    d.k0, d.k1 = int(k0), int(T) if k1 is None else int(k1)
+    d.test_launch_items = int(test_launch_items)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -765,6 +822,11 @@ def lib():
         h.epi_sdraw_run_device.argtypes = [C.POINTER(SdrawDesc), C.POINTER(SdrawInputs), C.POINTER(SdrawOutputs),
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_sdraw_run_host.argtypes = [C.POINTER(SdrawDesc), C.POINTER(SdrawInputs), C.POINTER(SdrawOutputs), C.c_int, C.c_char_p]
+        h.epi_escore_validate.argtypes = [C.POINTER(EscoreDesc), C.POINTER(EscoreInputs), C.POINTER(EscoreOutputs), C.c_char_p]
+        h.epi_escore_workspace_bytes.argtypes = [C.POINTER(EscoreDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_escore_run_device.argtypes = [C.POINTER(EscoreDesc), C.POINTER(EscoreInputs), C.POINTER(EscoreOutputs),
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_escore_run_host.argtypes = [C.POINTER(EscoreDesc), C.POINTER(EscoreInputs), C.POINTER(EscoreOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

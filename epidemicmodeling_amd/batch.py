@@ -1123,3 +1123,33 @@ def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.smoother_draws(DeviceBackend(dev, st), S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k0, clamp,
                                     lane_block, B, out_dtype, outputs)
+
+
+def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, population=None, truth_series=None, first_day=None,
+                   k0=0, k1=None, outputs=None, stream=None, test_launch_items=0):
+    """Probabilistic forecast scores of a Monte-Carlo ensemble against a truth in one device call (epi_escore_run_device,
+    DESIGN.md §4.17).  src [T, rows, B] or [T, B] (float32 or float64, on the device) is what ensemble_summary takes: B = R * D
+    chains, region-major; population [R] appends the derived new-case row.  truth [T, rows', Rt] ([T, Rt] for a [T, B] src): the
+    truth of item (t, row, r) is truth[t, row, truth_series[r]] (truth_series [R] int32; None: Rt = R and column r).  NaN members
+    are absent; an item without members or with a NaN truth is not scored.
+    alpha: up to 8 levels of central intervals, each in (0, 1), strictly descending (0.5, 0.05: the 50 % and the 95 % band).
+    Per item [T, rows', R]: crps (the ensemble CRPS), wis (the weighted interval score of the median and the intervals), ae
+    (|truth - median|), rank, ties (members below / equal to the truth), cover (bit k: the truth lies in interval k), count
+    (int32), and width [T, n_a, rows', R].  Per (row, region) over the days k0 <= t < k1 (k1 = None: T) from first_day[r] on
+    (first_day [R] int32, the forecast origin of every region): crps_mean, wis_mean, ae_mean, n_scored [rows', R], cover_frac
+    [n_a, rows', R], and with n_bins > 0 (at most 32) pit_hist [n_bins, rows', R], the histogram of the non-randomised mid-rank.
+    outputs: any of these names (default: all).  Returns a dict of device tensors.  Enqueued on `stream` (default: the current
+    stream) without a host synchronisation.  A chain-blocked output (EkfRunner(lane_block=...)) is not accepted.
+    test_launch_items: the tests' launch cut (0 in production)."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a torch tensor (NumPy arrays: hostapi.ensemble_score)")
+    if src.dim() == 4:
+        raise ValueError("src is a chain-blocked tensor [T, nblk, rows, blk]; ensemble_score takes the classic layout "
+                         "[T, rows, B]: pass EkfRunner.unblocked(name).contiguous(), or run with lane_block=0")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError("src must be float32 or float64")
+    dev = src.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.ensemble_score(DeviceBackend(dev, st), src.contiguous(), truth, R, D, alpha, n_bins, population, truth_series,
+                                    first_day, k0, k1, outputs, test_launch_items)

@@ -787,6 +787,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "rt_window.hpp"
 #include "lasso.hpp"
 #include "ens_summary.hpp"
+#include "ens_score.hpp"
 #include "ar_forecast.hpp"
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
@@ -4235,6 +4236,156 @@ int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, cons
         dout.X = HostIO::at<char>(base, o_X); dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_ss);
         dout.J = HostIO::at<double>(base, o_J); dout.L = HostIO::at<double>(base, o_L);
         return epi_sdraw_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- probabilistic forecast scores of the ensembles: escore_items, then escore_regions (ens_score.hpp) ----
+static int escore_check_desc(const epi_escore_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->rows < 1) { set_err(err, "rows must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->Rt < 1) { set_err(err, "Rt must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1 || d->D > kEnsMaxD) { set_err(err, "D must lie in 1 .. 4096 (a wavefront holds the draws of an item in registers)"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->n_a < 0 || d->n_a > kEsMaxA) { set_err(err, "n_a must lie in 0 .. 8"); return EPI_ERR_BAD_ARG; }
+    if (d->n_bins < 0 || d->n_bins > kEsMaxBins) { set_err(err, "n_bins must lie in 0 .. 32"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->n_a; k++) {
+        if (!(d->alpha[k] > 0.0 && d->alpha[k] < 1.0)) { set_err(err, "every alpha must lie in (0, 1)"); return EPI_ERR_BAD_ARG; }
+        if (k && !(d->alpha[k] < d->alpha[k - 1])) { set_err(err, "alpha must be strictly descending"); return EPI_ERR_BAD_ARG; }
+    }
+    if (d->k0 < 0 || d->k1 < d->k0 || d->k1 > d->T) { set_err(err, "k0, k1 must satisfy 0 <= k0 <= k1 <= T"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases != 0 && d->derive_newcases != 1) { set_err(err, "derive_newcases must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && d->rows < 3) { set_err(err, "derive_newcases needs at least 3 rows"); return EPI_ERR_BAD_ARG; }
+    if (d->test_launch_items < 0) { set_err(err, "test_launch_items must be >= 0"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+static bool escore_wants_regions(const epi_escore_outputs *o)
+{
+    return o->crps_mean || o->wis_mean || o->ae_mean || o->n_scored || o->cover_frac || o->pit_hist;
+}
+
+int epi_escore_validate(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, char *err)
+{
+    int rc = escore_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->src) { set_err(err, "NULL src"); return EPI_ERR_BAD_ARG; }
+    if (!in->truth) { set_err(err, "NULL truth"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && !in->population) { set_err(err, "NULL population (derive_newcases)"); return EPI_ERR_BAD_ARG; }
+    if (!in->truth_series && d->Rt != d->R) { set_err(err, "without truth_series, truth must hold R columns (Rt = R)"); return EPI_ERR_BAD_ARG; }
+    if (out->pit_hist && d->n_bins < 1) { set_err(err, "pit_hist needs n_bins >= 1"); return EPI_ERR_BAD_ARG; }
+    if (!(out->crps || out->wis || out->ae || out->width || out->rank || out->ties || out->cover || out->count || escore_wants_regions(out))) {
+        set_err(err, "no output requested");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+// the workspace: crps, wis, ae (doubles), then rank, ties, cover, count (int32), each one element per item
+static size_t escore_ws_bytes(const epi_escore_desc *d)
+{
+    return (size_t)d->T * (size_t)(d->rows + d->derive_newcases) * (size_t)d->R * (3 * sizeof(double) + 4 * sizeof(int32_t));
+}
+
+int epi_escore_workspace_bytes(const epi_escore_desc *d, size_t *bytes, char *err)
+{
+    int rc = escore_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = escore_ws_bytes(d);
+    return EPI_OK;
+}
+
+int epi_escore_run_device(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_escore_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const bool regions = escore_wants_regions(out);
+    if (regions && (!ws || ws_bytes < escore_ws_bytes(d))) { set_err(err, "workspace too small (epi_escore_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    EsArgs g{};
+    g.T = d->T; g.rows = d->rows; g.rows_out = d->rows + d->derive_newcases; g.R = d->R; g.D = d->D; g.Rt = d->Rt;
+    g.n_a = d->n_a; g.n_bins = d->n_bins; g.f32 = d->storage; g.derive = d->derive_newcases; g.k0 = d->k0; g.k1 = d->k1;
+    g.src = in->src; g.population = in->population; g.truth = in->truth; g.truth_series = in->truth_series; g.first_day = in->first_day;
+    for (int k = 0; k < d->n_a; k++) {                               // the probabilities, once, in double
+        g.alpha[k] = d->alpha[k];
+        g.q_lo[k] = d->alpha[k] / 2.0;
+        g.q_hi[k] = 1.0 - d->alpha[k] / 2.0;
+    }
+    const int64_t items = (int64_t)d->T * g.rows_out * d->R;
+    g.crps = out->crps; g.wis = out->wis; g.ae = out->ae; g.width = out->width;
+    g.rank = out->rank; g.ties = out->ties; g.cover = out->cover; g.count = out->count;
+    if (regions) {                                                   // what the region pass reads and the caller did not ask for
+        double *wd = (double *)ws;
+        int32_t *wi = (int32_t *)(wd + 3 * (size_t)items);
+        if (!g.crps && out->crps_mean) g.crps = wd;
+        if (!g.wis && out->wis_mean) g.wis = wd + (size_t)items;
+        if (!g.ae && out->ae_mean) g.ae = wd + 2 * (size_t)items;
+        if (!g.rank) g.rank = wi;
+        if (!g.ties && out->pit_hist) g.ties = wi + (size_t)items;
+        if (!g.cover && out->cover_frac) g.cover = wi + 2 * (size_t)items;
+        if (!g.count && out->pit_hist) g.count = wi + 3 * (size_t)items;
+    }
+    g.crps_mean = out->crps_mean; g.wis_mean = out->wis_mean; g.ae_mean = out->ae_mean; g.n_scored = out->n_scored;
+    g.cover_frac = out->cover_frac; g.pit_hist = out->pit_hist;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t cap = d->test_launch_items > 0 ? (int64_t)d->test_launch_items : kEnsLaunchItems;
+    hipError_t e = hipSuccess;
+    for (int64_t i0 = 0; i0 < items && e == hipSuccess; i0 += cap) {  // one 64-lane workgroup per item, in slices, as sdraw's (ens_score.hpp)
+        g.item0 = (long long)i0;
+        const unsigned ni = (unsigned)(items - i0 < cap ? items - i0 : cap);
+        if (d->D <= 64) e = escore_launch<1>(g, ni, st);              // registers per lane: P / 64, P the power of two >= D
+        else if (d->D <= 128) e = escore_launch<2>(g, ni, st);
+        else if (d->D <= 256) e = escore_launch<4>(g, ni, st);
+        else if (d->D <= 512) e = escore_launch<8>(g, ni, st);
+        else if (d->D <= 1024) e = escore_launch<16>(g, ni, st);
+        else if (d->D <= 2048) e = escore_launch<32>(g, ni, st);
+        else e = escore_launch<64>(g, ni, st);
+    }
+    if (e != hipSuccess) return hip_fail(err, e, "escore_items launch");
+    if (!regions) return EPI_OK;
+    const int64_t lanes = (int64_t)g.rows_out * d->R;                // < 2^31 * 4097 / D: one launch (R * D <= INT32_MAX, rows' small)
+    hipLaunchKernelGGL(escore_regions, dim3((unsigned)((lanes + kEsRegionWg - 1) / kEsRegionWg)), dim3(kEsRegionWg), 0, st, g);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "escore_regions launch");
+    return EPI_OK;
+}
+
+int epi_escore_run_host(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, int device, char *err)
+{
+    int rc = epi_escore_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, B = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases), Rt = (size_t)d->Rt;
+    const size_t na = (size_t)d->n_a, nb = (size_t)d->n_bins, none = HostIO::kAbsent;
+    HostIO io;
+    const size_t o_src = io.add_in(in->src, T * (size_t)d->rows, d->storage ? 4 : 8, B, 0, B);
+    const size_t o_pop = d->derive_newcases ? io.add_in(in->population, 1, 8, R, 0, R) : none;
+    const size_t o_tr = io.add_in(in->truth, T * ro, 8, Rt, 0, Rt);
+    const size_t o_ts = in->truth_series ? io.add_in(in->truth_series, 1, 4, R, 0, R) : none;
+    const size_t o_fd = in->first_day ? io.add_in(in->first_day, 1, 4, R, 0, R) : none;
+    using EO = epi_escore_outputs;
+    const HostIO::Opt<EO, double> f64[8] = {{&EO::crps, T * ro}, {&EO::wis, T * ro}, {&EO::ae, T * ro}, {&EO::width, T * na * ro},
+                                            {&EO::crps_mean, ro}, {&EO::wis_mean, ro}, {&EO::ae_mean, ro}, {&EO::cover_frac, na * ro}};
+    const HostIO::Opt<EO, int32_t> i32[6] = {{&EO::rank, T * ro}, {&EO::ties, T * ro}, {&EO::cover, T * ro}, {&EO::count, T * ro},
+                                             {&EO::n_scored, ro}, {&EO::pit_hist, nb * ro}};
+    size_t o_d[8], o_i[6];
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    const size_t wsb = escore_ws_bytes(d);
+    const size_t o_ws = escore_wants_regions(out) ? io.reserve(wsb) : none;
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_escore_inputs din{};
+        din.src = base + o_src; din.population = HostIO::at<const double>(base, o_pop); din.truth = (const double *)(base + o_tr);
+        din.truth_series = HostIO::at<const int32_t>(base, o_ts); din.first_day = HostIO::at<const int32_t>(base, o_fd);
+        epi_escore_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        return epi_escore_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

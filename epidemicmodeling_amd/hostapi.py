@@ -344,3 +344,15 @@ def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None
     z = None if z is None else np.asarray(z)
     return _call.smoother_draws(HostBackend(device), *(np.asarray(v) for v in (S_PLUS, P_PLUS, S_MINUS, P_MINUS)), prm, D, z, s_term,
                                 P_term, k0, clamp, lane_block, B, None if out_dtype is None else np.dtype(out_dtype), outputs)
+
+
+def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, population=None, truth_series=None, first_day=None,
+                   k0=0, k1=None, outputs=None, device=0, test_launch_items=0):
+    """epi_escore_run_host: batch.ensemble_score on NumPy arrays (synchronous): the same arguments, and the same keys, order,
+    dtypes and bits.  A float32 src = float storage, anything else is taken as float64."""
+    src = np.asarray(src)
+    if src.ndim == 4:
+        raise ValueError("src is a chain-blocked array [T, nblk, rows, blk]; ensemble_score takes the classic layout [T, rows, B]")
+    src = np.ascontiguousarray(src, dtype=np.float32 if src.dtype == np.float32 else np.float64)
+    return _call.ensemble_score(HostBackend(device), src, truth, R, D, alpha, n_bins, population, truth_series, first_day, k0, k1,
+                                outputs, test_launch_items)

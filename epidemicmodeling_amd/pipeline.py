@@ -714,3 +714,74 @@ def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None,
                                     clamp=clamp, device=device)
     out.update(workload=wf, runner=r, X=X, summary=summary, z=z)
     return out
+
+
+def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draws=256, alpha=(0.5, 0.05), n_bins=10, seed=0,
+                storage="f64", clamp=True, num_regression_days=60, W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0,
+                z=None):
+    """The look-ahead study of forecast_quality done with fans: instead of one point estimate per day, every forecast is the
+    smoother's joint posterior law, scored against the truth by the ensemble CRPS, the weighted interval score, interval coverage
+    and the rank histogram (batch.ensemble_score).
+
+    cases / deaths [LL, S], population [S], ip [LL, n, S] over the WHOLE window; the first LL - num_forecast_days days are the
+    training window, on which the front half runs exactly as in forecast_quality.  starts: the forecast starts, each in 1 ..
+    num_forecast_days; chain c = region * len(starts) + j is region's forecast filter with its last starts[j] observations hidden
+    (ForecastQualityAssessment.m:380-393), so its origin -- the first day it has not seen -- is day LL - starts[j].  One 3-state
+    filter runs over all chains, smoothed_fan draws n_draws paths per chain from the earliest origin on, and the new-case row
+    ((N s) i) alpha of every chain is scored against new_smoothed of the whole window (the truth of forecast_quality) from the
+    chain's origin on.  Nothing is copied back between these steps.
+    Returns the front half's intermediates, pre_entire, R_full, truth [LL, S], workload (the chains'), runner, X, z, origin [B],
+    k0, `scores` (the dict of batch.ensemble_score over the days k0 .. LL-1: rows s, i, alpha carry no truth and are NaN / -1,
+    row 3 is the new cases; its per-region outputs are the per-chain aggregates), and by lead time l = day - origin, averaged over
+    the starts that reach it, crps_by_lead, wis_by_lead [max(starts), S] and cover_by_lead [n_a, max(starts), S] (torch
+    reductions over the per-item scores)."""
+    LL, S = cases.shape
+    F = int(num_forecast_days)
+    T = LL - F
+    if F < 1 or T < 2:
+        raise ValueError("num_forecast_days must be >= 1 and leave a training window of at least 2 days")
+    st = [int(v) for v in np.atleast_1d(np.asarray(starts))]
+    if not st or min(st) < 1 or max(st) > F:
+        raise ValueError("starts must hold forecast starts in 1 .. num_forecast_days")
+    J, D = len(st), int(n_draws)
+    N = np.asarray(population, dtype=np.float64)
+    out = _front_half(cases[:T], None if deaths is None else deaths[:T], N, ip[:T], num_regression_days, W, device,
+                      regression, cv_folds, cv_seed)
+    fit2, I0, R = out["fit2"], out["pre"]["I0"], out["pre"]["R_v"]
+    ent = {k: v.cpu().numpy() for k, v in batch.preprocess(cases, N, deaths, ip, W=W, min_cases=synth.MIN_CASES,
+                                                            first_num_days=7, device=device).items()}
+    R_mean = R.sum(axis=0) / T
+    R_full = np.concatenate([R, np.repeat(R_mean[None], F, 0)])
+    rr = np.repeat(np.arange(S), J)                        # the region of every chain
+    origin = (LL - np.tile(np.asarray(st), S)).astype(np.int32)
+    x = ent["x_new"][:, rr].copy()
+    x[np.arange(LL)[:, None] >= origin[None, :]] = np.nan  # the last starts[j] observations hidden
+    w = workload3(x, R_full[:, rr], ent["ip_filled"][:, :, rr], N[rr], I0[rr], fit2["a"][:, rr], fit2["b"][rr])
+    k0 = int(origin.min())
+    dev = torch.device(device)
+    r, X, _, z = smoothed_fan(w, D, q=(0.5,), population=None, seed=seed, k0=k0, storage=storage, clamp=clamp, device=device, z=z)
+    truth = ent["new_smoothed"]
+    tw = np.full((LL - k0, 4, S), np.nan)
+    tw[:, 3] = truth[k0:]
+    fd = torch.as_tensor(origin - k0, device=dev)
+    scores = batch.ensemble_score(X, torch.as_tensor(tw, device=dev), S * J, D, alpha=alpha, n_bins=n_bins, population=N[rr],
+                                  truth_series=torch.as_tensor(rr.astype(np.int32), device=dev), first_day=fd)
+    # by lead time: item (origin_c - k0 + l, row 3, c) of every chain that reaches lead l, averaged over the starts of a region
+    H = max(st)
+    lead = torch.arange(H, device=dev)[:, None]
+    day = fd.to(torch.int64)[None, :] + lead                                   # [H, B]
+    reach = day < (LL - k0)
+    dayc = day.clamp(max=LL - k0 - 1)
+    ok = reach & (scores["rank"][:, 3].gather(0, dayc) >= 0)
+    cnt = ok.view(H, S, J).sum(dim=2).to(torch.float64)
+
+    def by_lead(v):                                                              # v [LL - k0, B]
+        g = torch.where(ok, v.gather(0, dayc).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+        return g.view(H, S, J).sum(dim=2) / cnt
+    n_a = scores["width"].shape[1]
+    cover = scores["cover"][:, 3]
+    out.update(pre_entire=ent, R_mean=R_mean, R_full=R_full, truth=truth, workload=w, runner=r, X=X, z=z, origin=origin, k0=k0,
+               starts=st, scores=scores, crps_by_lead=by_lead(scores["crps"][:, 3]), wis_by_lead=by_lead(scores["wis"][:, 3]),
+               cover_by_lead=torch.stack([by_lead((cover >> k) & 1) for k in range(n_a)]) if n_a else
+               torch.empty((0, H, S), dtype=torch.float64, device=dev))
+    return out

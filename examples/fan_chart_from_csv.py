@@ -2,13 +2,18 @@
 joint posterior draws of the smoother's paths (epidemicmodeling_amd/pipeline.py: forecast_fan), for all regions of
 the file at once.
 
-    python examples/fan_chart_from_csv.py OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
+    python examples/fan_chart_from_csv.py [--score-last N] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
 
 The front half of Tools/TrainPredictPrescribeNPI.m (preprocessing, two EKF rounds, two regressions), then its forecast filter
 (:356-377: NaN observations over the horizon, the last day's NPIs held), then 256 backward-simulated paths per region and their
 quantiles per day.  The output holds one row per region and forecast day: the 2.5, 25, 50, 75 and 97.5 % quantiles and the mean of
 the daily new cases.  Without arguments (or with only the output path) a small synthetic tracker file is generated first (there is
-no data set in this repository)."""
+no data set in this repository).
+
+--score-last N holds the last N days of the window out, forecasts them from the days before, and prints how good the fans were
+(pipeline.fan_quality): per region the mean CRPS and weighted interval score of the daily new cases, the share of
+days the 50 % and the 95 % band held the truth, and the rank histogram in ten bins, with forecast starts N and N / 2 days before
+the end of the window."""
 import os
 import sys
 import tempfile
@@ -25,8 +30,27 @@ from prescribe_from_csv import synthetic_files  # noqa: E402
 Q = (0.025, 0.25, 0.5, 0.75, 0.975)
 
 
+def score_table(d, N, keep, n_last, draws):
+    """the forecast of the last n_last days of the window, scored against them: one row per region and start"""
+    starts = sorted({n_last, max(1, n_last // 2)}, reverse=True)
+    fq = pipeline.fan_quality(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], n_last, starts, n_draws=draws)
+    sc = {k: v.cpu().numpy() for k, v in fq["scores"].items()}
+    rows = []
+    for j, r in enumerate(keep):
+        for i, s in enumerate(starts):
+            c = j * len(starts) + i                       # chain = region * len(starts) + start; row 3 is the new cases
+            rows.append([d["geo_ids"][r], s, int(sc["n_scored"][3, c]), sc["crps_mean"][3, c], sc["wis_mean"][3, c], sc["ae_mean"][3, c],
+                         sc["cover_frac"][0, 3, c], sc["cover_frac"][1, 3, c], " ".join(str(v) for v in sc["pit_hist"][:, 3, c])])
+    return pd.DataFrame(rows, columns=["region", "start", "days", "crps", "wis", "abs_err", "cover50", "cover95", "pit_hist"])
+
+
 def main():
     horizon, draws = 30, 256
+    n_last = 0
+    if "--score-last" in sys.argv:
+        i = sys.argv.index("--score-last")
+        n_last = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
     if len(sys.argv) >= 6:
         data, pops, start, end, dst = sys.argv[1:6]
         horizon = int(sys.argv[6]) if len(sys.argv) > 6 else horizon
@@ -50,6 +74,9 @@ def main():
     table.to_csv(dst, index=False)
     print(f"{len(keep)} regions x {draws} draws x {horizon} days -> {dst}")
     print(table.head(12).to_string(index=False))
+    if n_last > 0:
+        print(f"the last {n_last} days held out and forecast from the days before them:")
+        print(score_table(d, N, keep, n_last, draws).to_string(index=False))
 
 
 if __name__ == "__main__":

@@ -1310,6 +1310,76 @@ int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, co
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err);
 
+/* ---- Probabilistic forecast scores of the Monte-Carlo ensembles (not a script of the reference) ----
+ * src [T][rows][B], B = R * D, region-major, double or float, and the derived row, exactly as epi_ens_run_* take them; an item is
+ * one (day t, row, region r) with its D members, NaN members absent, n the others.  The truth of the item is
+ * y = truth[(t * rows' + row) * Rt + ts], ts = truth_series ? truth_series[r] : r (entries in 0 .. Rt-1; several regions may
+ * share a column; without truth_series Rt = R).  Definition (pinned; restated in tests/escore_ref.py and tests/escore_ref.c):
+ *   rank = #{members < y}, ties = #{members == y}, count = n
+ *   x(1 .. n) the members ascending; Q(p) the quantile of epi_ens_run_* (h = n p + 0.5, k = floor(h), g = h - k; x(1) if k < 1,
+ *     x(n) if k >= n, else x(k) + g (x(k+1) - x(k)));  med = Q(0.5), l_k = Q(alpha_k / 2), u_k = Q(1 - alpha_k / 2), the two
+ *     probabilities formed once on the host in double
+ *   ae = |y - med|;  width_k = u_k - l_k;  cover bit k = (l_k <= y and y <= u_k)
+ *   IS_k = (width_k + c_k pos(l_k - y)) + c_k pos(y - u_k),  c_k = 2 / alpha_k,  pos(d) = d if d > 0 else 0
+ *   wis = (...((0.5 ae) + (alpha_0 / 2) IS_0) + ... + (alpha_{n_a-1} / 2) IS_{n_a-1}) / (n_a + 0.5)
+ *   crps = (2 / (n n)) tree(term),  term at sorted position i = 1 .. n: (x(i) - y) (((n if y < x(i) else 0) - i) + 0.5), +0.0
+ *     at the positions n+1 .. P (selected by position), P the power of two >= max(D, 64), tree() the pairwise sum of
+ *     epi_ens_run_* over the positions: the ensemble CRPS (1/n) sum |x_i - y| - (1/(2 n n)) sum sum |x_i - x_j|
+ *   n = 0 or y NaN: every floating output of the item is NaN, rank = ties = -1, cover = 0 (count = n); non-finite members
+ *     give what IEEE arithmetic gives in this order
+ * Per (row, region), over the days k0 <= t < k1 with t >= first_day[r] (0 without first_day) and rank >= 0, ascending from 0.0:
+ *   n_scored their number; crps_mean, wis_mean, ae_mean = sum / n_scored; cover_frac[k] = #{bit k set} / n_scored (NaN when
+ *   n_scored = 0); pit_hist[b] = #{days with b = min(n_bins - 1, ((2 rank + ties + 1) n_bins) / (2 (count + 1)))} in 64-bit
+ *   integer arithmetic (the bin of the non-randomised mid-rank)
+ * Outputs (each may be NULL; at least one must not be): crps, wis, ae [T][rows'][R], width [T][n_a][rows'][R], rank, ties,
+ *   cover, count [T][rows'][R] int32, crps_mean, wis_mean, ae_mean [rows'][R], n_scored [rows'][R] int32, cover_frac
+ *   [n_a][rows'][R], pit_hist [n_bins][rows'][R] int32; rows' = rows + derive_newcases */
+typedef struct epi_escore_desc {
+    int32_t abi_version;
+    int32_t T, rows, R;          /* days, rows of src, regions: each >= 1 */
+    int32_t D;                   /* draws per region, 1 .. 4096; R * D <= INT32_MAX */
+    int32_t Rt;                  /* columns of truth, >= 1 (= R without truth_series) */
+    int32_t n_a;                 /* central intervals, 0 .. 8 */
+    int32_t n_bins;              /* bins of pit_hist, 0 .. 32 (0: no histogram) */
+    int32_t storage;             /* element type of src: 0 = double, 1 = float */
+    int32_t derive_newcases;     /* 0, or 1: append the row ((N * row0) * row1) * row2 */
+    int32_t k0, k1;              /* the window of the per-region outputs, 0 <= k0 <= k1 <= T */
+    int32_t test_launch_items;   /* 0; > 0: items per launch (the tests cut small calls into several launches with it) */
+    int32_t reserved;            /* 0 */
+    double alpha[8];             /* levels, each in (0, 1), strictly descending; the first n_a are read */
+} epi_escore_desc;
+typedef struct epi_escore_inputs {
+    const void *src;                     /* [T][rows][R * D] */
+    const double *population;            /* [R] (derive_newcases) or NULL */
+    const double *truth;                 /* [T][rows'][Rt] */
+    const int32_t *truth_series;         /* [R] or NULL */
+    const int32_t *first_day;            /* [R] or NULL */
+} epi_escore_inputs;
+typedef struct epi_escore_outputs {
+    double *crps, *wis, *ae;             /* [T][rows'][R] */
+    double *width;                       /* [T][n_a][rows'][R] */
+    int32_t *rank, *ties, *cover, *count; /* [T][rows'][R] */
+    double *crps_mean, *wis_mean, *ae_mean; /* [rows'][R] */
+    int32_t *n_scored;                   /* [rows'][R] */
+    double *cover_frac;                  /* [n_a][rows'][R] */
+    int32_t *pit_hist;                   /* [n_bins][rows'][R] */
+} epi_escore_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for T, rows, R, Rt < 1, D outside 1 .. 4096, R * D > INT32_MAX, n_a outside 0 .. 8, n_bins outside
+ * 0 .. 32, an alpha outside (0, 1) or not strictly descending, k0 / k1 outside 0 <= k0 <= k1 <= T, storage or derive_newcases
+ * outside {0, 1}, derive_newcases with rows < 3 or without population, a negative test_launch_items, a NULL src / truth, Rt != R
+ * without truth_series, pit_hist with n_bins = 0, no output at all */
+int epi_escore_validate(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, char *err);
+/* bytes of device workspace epi_escore_run_device needs: the per-item arrays the per-region outputs are formed from (three
+ * doubles and four int32 per item), whichever of them the caller also asks for */
+int epi_escore_workspace_bytes(const epi_escore_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; one wavefront per item (cut into launches below 2^31 threads), then one lane per (row, region) when a
+ * per-region output is asked for, enqueued on `stream`: no host synchronisation, no allocation.  EPI_ERR_WORKSPACE for a
+ * workspace below epi_escore_workspace_bytes when a per-region output is asked for (else ws may be NULL) */
+int epi_escore_run_device(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_escore_run_host(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -100,6 +100,14 @@
 //       P_PLUS of day T)  3 x 1, 3 x 3;  k_first ([] = 1)  the first day returned, ONE-based;  clamp ([] = 1).  X  D x 3 x
 //       (T - k_first + 1);  rank  1 x T (-1: a NaN record);  status  scalar (bit 0: a non-finite input entry met, bit 1: a rank
 //       below 3);  J, L  3 x 3 x T, only when requested.
+//   [crps, wis, ae, width, rank, ties, cover, count, crps_mean, wis_mean, ae_mean, n_scored, cover_frac, pit_hist] = epiekf_pipeline_mex('escore', src, truth, D, alpha, n_bins, population, truth_series, first_day, k_first, k_last)
+//       Probabilistic forecast scores of a Monte-Carlo ensemble against a truth.  src, D, population  as
+//       'ens_summary' takes them;  truth  Rt x rows' x T (or Rt x T for a B x T src);  alpha ([] = none)  up to 8 levels of
+//       central intervals in (0, 1), strictly descending;  n_bins  0 .. 32 bins of the rank histogram;  truth_series ([] : Rt == R)
+//       R x 1, ONE-based column of truth of every region;  first_day ([] = 1)  R x 1, ONE-based first day a region is scored
+//       from;  k_first, k_last ([] = 1, T)  the days the per-region outputs run over, ONE-based and inclusive.  crps, wis, ae,
+//       rank, ties, cover, count  R x rows' x T (rank, ties -1 and NaN scores: not scored);  width  R x rows' x n_a x T;
+//       crps_mean, wis_mean, ae_mean, n_scored  R x rows';  cover_frac  R x rows' x n_a;  pit_hist  R x rows' x n_bins.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -504,6 +512,95 @@ static void ens_summary(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void escore(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 11) mexErrMsgTxt("epiekf_pipeline_mex('escore', src, truth, D, alpha, n_bins, population, truth_series, first_day, k_first, k_last): 11 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1])) mexErrMsgTxt("src must be a double array B x rows x T (or B x T)");
+    const mwSize *ds = mxGetDimensions(prhs[1]);
+    const mwSize B = ds[0], rows = nd == 3 ? ds[1] : 1, T = nd == 3 ? ds[2] : ds[1];
+    const double Dd = mxGetScalar(prhs[3]);
+    if (!(Dd >= 1.0 && Dd <= 4096.0) || (double)(mwSize)Dd != Dd || B % (mwSize)Dd != 0) mexErrMsgTxt("D must be an integer in 1 .. 4096 that divides the number of chains");
+    const mwSize D = (mwSize)Dd, R = B / D, na = mxGetNumberOfElements(prhs[4]);
+    if (na > 8) mexErrMsgTxt("alpha must hold at most 8 levels");
+    if (mxIsEmpty(prhs[5]) || !mxGetPr(prhs[5]) || mxGetNumberOfElements(prhs[5]) != 1) mexErrMsgTxt("n_bins must be a double scalar");
+    const double nbd = mxGetScalar(prhs[5]);
+    if (!(nbd >= 0.0 && nbd <= 32.0) || (double)(mwSize)nbd != nbd) mexErrMsgTxt("n_bins must be an integer in 0 .. 32");
+    const mwSize nb = (mwSize)nbd;
+    const bool derive = !mxIsEmpty(prhs[6]);
+    if (derive && mxGetNumberOfElements(prhs[6]) != R) mexErrMsgTxt("population must have one entry per region");
+    const mwSize ro = rows + (derive ? 1 : 0);
+    const mwSize ndt = mxGetNumberOfDimensions(prhs[2]);
+    if (ndt > 3 || mxIsEmpty(prhs[2]) || !mxGetPr(prhs[2])) mexErrMsgTxt("truth must be a double array Rt x rows' x T (or Rt x T)");
+    const mwSize *dt = mxGetDimensions(prhs[2]);
+    const mwSize Rt = dt[0];
+    if (nd == 3 ? !((ndt == 3 && dt[1] == ro && dt[2] == T) || (ndt == 2 && T == 1 && dt[1] == ro)) : !(ndt == 2 && dt[1] == T && ro == 1))
+        mexErrMsgTxt("truth must be Rt x rows' x T (Rt x T for a B x T src), rows' = rows + 1 with a population");
+    std::vector<int32_t> ser, fd;
+    if (!mxIsEmpty(prhs[7])) {
+        if (mxGetNumberOfElements(prhs[7]) != R) mexErrMsgTxt("truth_series must have one entry per region");
+        ser.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[7])[r];
+            if (!(v >= 1.0 && v <= (double)Rt) || (double)(mwSize)v != v) mexErrMsgTxt("truth_series must hold ONE-based columns of truth");
+            ser[(size_t)r] = (int32_t)v - 1;
+        }
+    } else if (Rt != R) {
+        mexErrMsgTxt("truth must hold one column per region (or pass truth_series)");
+    }
+    if (!mxIsEmpty(prhs[8])) {
+        if (mxGetNumberOfElements(prhs[8]) != R) mexErrMsgTxt("first_day must have one entry per region");
+        fd.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[8])[r];
+            if (!(v >= 1.0 && v <= 2147483647.0) || (double)(mwSize)v != v) mexErrMsgTxt("first_day must hold ONE-based days");
+            fd[(size_t)r] = (int32_t)v - 1;
+        }
+    }
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[9])) kf = mxGetScalar(prhs[9]);
+    if (!mxIsEmpty(prhs[10])) kl = mxGetScalar(prhs[10]);
+    if (!(kf >= 1.0 && kf <= (double)T && kl >= kf - 1.0 && kl <= (double)T) || (double)(mwSize)kf != kf || (double)(mwSize)kl != kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= T and k_first - 1 <= k_last <= T");
+    epi_escore_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.rows = (int32_t)rows; d.R = (int32_t)R; d.D = (int32_t)D; d.Rt = (int32_t)Rt;
+    d.n_a = (int32_t)na; d.n_bins = (int32_t)nb; d.storage = 0; d.derive_newcases = derive ? 1 : 0;
+    d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    for (mwSize k = 0; k < na; k++) d.alpha[k] = mxGetPr(prhs[4])[k];
+    epi_escore_inputs in;
+    memset(&in, 0, sizeof in);
+    in.src = mxGetPr(prhs[1]); in.population = derive ? mxGetPr(prhs[6]) : NULL; in.truth = mxGetPr(prhs[2]);
+    in.truth_series = ser.empty() ? NULL : ser.data(); in.first_day = fd.empty() ? NULL : fd.data();
+    // the ABI's [T][rows'][R], [T][n_a][rows'][R], [rows'][R], [n][rows'][R] are MATLAB's R x rows' x T, R x rows' x n_a x T,
+    // R x rows', R x rows' x n: no transposition
+    const mwSize d4[4] = {R, ro, na, T};
+    mxArray *o[14] = {dbl3(R, ro, T), dbl3(R, ro, T), dbl3(R, ro, T), mxCreateNumericArray(4, d4, mxDOUBLE_CLASS, mxREAL),
+                      dbl3(R, ro, T), dbl3(R, ro, T), dbl3(R, ro, T), dbl3(R, ro, T),
+                      mxCreateDoubleMatrix(R, ro, mxREAL), mxCreateDoubleMatrix(R, ro, mxREAL), mxCreateDoubleMatrix(R, ro, mxREAL),
+                      mxCreateDoubleMatrix(R, ro, mxREAL), dbl3(R, ro, na), dbl3(R, ro, nb)};
+    const size_t items = (size_t)(R * ro * T), cols = (size_t)(R * ro);
+    std::vector<int32_t> ibuf(4 * items + cols + cols * (size_t)nb + 1);
+    int32_t *irank = ibuf.data(), *ities = irank + items, *icover = ities + items, *icount = icover + items, *ins = icount + items,
+            *ipit = ins + cols;
+    epi_escore_outputs out;
+    memset(&out, 0, sizeof out);
+    out.crps = mxGetPr(o[0]); out.wis = mxGetPr(o[1]); out.ae = mxGetPr(o[2]); out.width = na ? mxGetPr(o[3]) : NULL;
+    out.rank = irank; out.ties = ities; out.cover = icover; out.count = icount;
+    out.crps_mean = mxGetPr(o[8]); out.wis_mean = mxGetPr(o[9]); out.ae_mean = mxGetPr(o[10]); out.n_scored = ins;
+    out.cover_frac = na ? mxGetPr(o[12]) : NULL; out.pit_hist = nb ? ipit : NULL;
+    char err[256] = {0};
+    const int rc = epi_escore_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    const int32_t *isrc[4] = {irank, ities, icover, icount};
+    for (int j = 0; j < 4; j++)
+        for (size_t k = 0; k < items; k++) mxGetPr(o[4 + j])[k] = (double)isrc[j][k];
+    for (size_t k = 0; k < cols; k++) mxGetPr(o[11])[k] = (double)ins[k];
+    for (size_t k = 0; k < cols * (size_t)nb; k++) mxGetPr(o[13])[k] = (double)ipit[k];
+    for (int k = 0; k < 14; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected");
@@ -800,6 +897,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "loglik") == 0) loglik(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "plan") == 0) plan(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "escore") == 0) escore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
