@@ -400,3 +400,46 @@ def ensemble_score(be, src, truth, R, D, alpha, n_bins, population, truth_series
     if src.ndim == 2:
         out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
     return out
+
+
+def path_functionals(be, src, R, D, thresholds, population, first_day, k0, k1, outputs, test_segments=0, test_launch_groups=0):
+    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+    if src.ndim not in (2, 3):
+        raise ValueError("src must be [T, rows, B] or [T, B]")
+    R, D = int(R), int(D)
+    if src.shape[-1] != R * D:
+        raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
+    T, rows = int(src.shape[0]), (1 if src.ndim == 2 else int(src.shape[1]))
+    pop = be.f64(population)
+    if pop is not None and tuple(pop.shape) != (R,):
+        raise ValueError("population must be [R]")
+    ro = rows + int(pop is not None)
+    thr = be.f64(thresholds)
+    n_thr = 0
+    if thr is not None:
+        if thr.ndim == 2 and src.ndim == 2:
+            thr = thr.reshape(thr.shape[0], 1, thr.shape[1])
+        if thr.ndim != 3 or tuple(thr.shape[1:]) != (ro, R):
+            raise ValueError(f"thresholds must be [n_thr, rows', R] = [n_thr, {ro}, {R}] ([n_thr, R] for a [T, B] src)")
+        n_thr = int(thr.shape[0])
+        if n_thr == 0:
+            thr = None
+    fd = be.i32(first_day)
+    if fd is not None and tuple(fd.shape) != (R,):
+        raise ValueError("first_day must be [R]")
+    d = _lib.make_pathfn_desc(T, rows, R, D, n_thr, storage=int(_is_f32(src)), derive_newcases=int(pop is not None), k0=k0, k1=k1,
+                              test_segments=test_segments, test_launch_groups=test_launch_groups)
+    names = _lib.pathfn_out_names(outputs, n_thr)
+    ins = _lib.PathfnInputs()
+    for k, v in zip(_lib.PATHFN_IN_NAMES, (src, pop, thr, fd)):
+        setattr(ins, k, be.ptr(v))
+    probe = _lib.PathfnOutputs()
+    for k in names:
+        setattr(probe, k, 1)                            # validate looks only at which outputs are asked for
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_pathfn_validate(C.byref(d), C.byref(ins), C.byref(probe), err), err)   # before anything is allocated
+    out = run_with_workspace("pathfn", be, d, ins, _lib.PathfnOutputs(), _lib.PATHFN_OUT_NAMES, _lib.PATHFN_OUT_I32,
+                             _lib.pathfn_shapes(rows, R, D, n_thr, d.k1 - d.k0, d.derive_newcases), names)
+    if src.ndim == 2:
+        out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
+    return out

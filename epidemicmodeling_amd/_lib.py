@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
     "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
     "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
+    "epi_pathfn_validate", "epi_pathfn_workspace_bytes", "epi_pathfn_run_device", "epi_pathfn_run_host",
 ]
 
 
@@ -705,6 +706,58 @@ def make_escore_desc(T, rows, R, D, Rt, alpha=ESCORE_DEFAULT_ALPHA, n_bins=0, st
     return d
 
 
+class PathfnDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "n_thr", "storage", "derive_newcases", "k0", "k1",
+                                         "test_segments", "test_launch_groups")]
+
+
+PATHFN_IN_NAMES = ("src", "population", "thr", "first_day")
+PATHFN_PATH_NAMES = ("peak_value", "peak_day", "min_value", "min_day", "total")
+PATHFN_THR_NAMES = ("first_cross", "days_above", "longest_run")
+PATHFN_REGION_NAMES = ("n_paths", "peak_day_hist", "n_cross", "cross_day_hist")
+PATHFN_OUT_NAMES = PATHFN_PATH_NAMES + PATHFN_THR_NAMES + ("n_valid",) + PATHFN_REGION_NAMES
+PATHFN_OUT_I32 = ("n_valid",) + PATHFN_REGION_NAMES
+PATHFN_NEED_THR = PATHFN_THR_NAMES + ("n_cross", "cross_day_hist")
+
+
+class PathfnInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PATHFN_IN_NAMES]
+
+
+class PathfnOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PATHFN_OUT_NAMES]
+
+
+def pathfn_shapes(rows, R, D, n_thr, W, derive_newcases=0):
+    """shape of every output of epi_pathfn_run_* (rows' = rows + derive_newcases, W = k1 - k0)"""
+    ro, N, n_thr, W = int(rows) + int(derive_newcases), int(R) * int(D), int(n_thr), int(W)
+    sh = {k: (ro, N) for k in PATHFN_PATH_NAMES}
+    sh.update({k: (n_thr, ro, N) for k in PATHFN_THR_NAMES})
+    sh["n_valid"] = (ro, N)
+    sh.update(n_paths=(ro, R), peak_day_hist=(W, ro, R), n_cross=(n_thr, ro, R), cross_day_hist=(W, n_thr, ro, R))
+    return sh
+
+
+def pathfn_out_names(outputs, n_thr):
+    """None -> every output (those of the thresholds only with n_thr > 0); else the names asked for, in the ABI's order"""
+    default = [k for k in PATHFN_OUT_NAMES if k not in PATHFN_NEED_THR or int(n_thr) > 0]
+    names = out_names(PATHFN_OUT_NAMES, outputs, default)
+    return [k for k in PATHFN_OUT_NAMES if k in names]
+
+
+def make_pathfn_desc(T, rows, R, D, n_thr=0, storage=0, derive_newcases=0, k0=0, k1=None, test_segments=0,
+                     test_launch_groups=0) -> PathfnDesc:
+    """storage: 0 / "f64" = double source, 1 / "f32" = float source.  k1 = None: T."""
+    d = PathfnDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.rows, d.R, d.D, d.n_thr = int(T), int(rows), int(R), int(D), int(n_thr)
+    d.storage = {"f64": 0, "f32": 1}.get(storage, storage)
+    d.derive_newcases = int(derive_newcases)
+    d.k0, d.k1 = int(k0), int(T) if k1 is None else int(k1)
+    d.test_segments, d.test_launch_groups = int(test_segments), int(test_launch_groups)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -827,6 +880,11 @@ def lib():
         h.epi_escore_run_device.argtypes = [C.POINTER(EscoreDesc), C.POINTER(EscoreInputs), C.POINTER(EscoreOutputs),
                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_escore_run_host.argtypes = [C.POINTER(EscoreDesc), C.POINTER(EscoreInputs), C.POINTER(EscoreOutputs), C.c_int, C.c_char_p]
+        h.epi_pathfn_validate.argtypes = [C.POINTER(PathfnDesc), C.POINTER(PathfnInputs), C.POINTER(PathfnOutputs), C.c_char_p]
+        h.epi_pathfn_workspace_bytes.argtypes = [C.POINTER(PathfnDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_pathfn_run_device.argtypes = [C.POINTER(PathfnDesc), C.POINTER(PathfnInputs), C.POINTER(PathfnOutputs),
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_pathfn_run_host.argtypes = [C.POINTER(PathfnDesc), C.POINTER(PathfnInputs), C.POINTER(PathfnOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

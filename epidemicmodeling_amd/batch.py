@@ -1153,3 +1153,33 @@ def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, 
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.ensemble_score(DeviceBackend(dev, st), src.contiguous(), truth, R, D, alpha, n_bins, population, truth_series,
                                     first_day, k0, k1, outputs, test_launch_items)
+
+
+def path_functionals(src, R, D, thresholds=None, population=None, first_day=None, k0=0, k1=None, outputs=None, stream=None,
+                     test_segments=0, test_launch_groups=0):
+    """Functionals of every joint path of a Monte-Carlo ensemble in one device call (epi_pathfn_run_device): one
+    streaming read of src answers when the peak is, how high, how many cases over the window, and when, for how many days and
+    for how long a threshold is exceeded.  src [T, rows, B] or [T, B] (float32 or float64, on the device) is what
+    ensemble_summary takes: B = R * D paths, region-major; population [R] appends the derived new-case row.  The window is the
+    days k0 <= t < k1 (k1 = None: T), for region r from first_day[r] on (first_day [R] int32); a NaN value is no day of its path.
+    thresholds [n_thr, rows', R] (at most 8; [n_thr, R] for a [T, B] src): a NaN entry asks nothing of that row and region.
+    Per path [rows', B], float64 (each is itself an ensemble_summary source): peak_value, peak_day (the first day of the maximum,
+    the day index of src), min_value, min_day, total (the sum in 32-day blocks); per threshold [n_thr, rows', B]: first_cross
+    (NaN: never), days_above, longest_run; n_valid (int32).  A path without a valid day is NaN throughout.  Per (row, region)
+    over the paths with a valid day, int32: n_paths [rows', R], peak_day_hist [W, rows', R] (bin t - k0), n_cross [n_thr, rows',
+    R], cross_day_hist [W, n_thr, rows', R] (W = k1 - k0, at most 4096 for a histogram).
+    outputs: any of these names (default: all).  Returns a dict of device tensors.  Enqueued on `stream` (default: the current
+    stream) without a host synchronisation.  A chain-blocked output (EkfRunner(lane_block=...)) is not accepted.
+    test_segments, test_launch_groups: the tests' time segments and launch cut (0 in production)."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a torch tensor (NumPy arrays: hostapi.path_functionals)")
+    if src.dim() == 4:
+        raise ValueError("src is a chain-blocked tensor [T, nblk, rows, blk]; path_functionals takes the classic layout "
+                         "[T, rows, B]: pass EkfRunner.unblocked(name).contiguous(), or run with lane_block=0")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError("src must be float32 or float64")
+    dev = src.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.path_functionals(DeviceBackend(dev, st), src.contiguous(), R, D, thresholds, population, first_day, k0, k1,
+                                      outputs, test_segments, test_launch_groups)

@@ -788,6 +788,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "lasso.hpp"
 #include "ens_summary.hpp"
 #include "ens_score.hpp"
+#include "path_functionals.hpp"
 #include "ar_forecast.hpp"
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
@@ -4386,6 +4387,218 @@ int epi_escore_run_host(const epi_escore_desc *d, const epi_escore_inputs *in, c
         HostIO::bind_opt(dout, f64, o_d, base);
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_escore_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- path functionals of the ensembles: pathfn_paths, pathfn_combine over time segments, pathfn_regions (path_functionals.hpp) ----
+// The segment rule (profiles/path_functionals/segments.json): a path grid of fewer wavefronts than the device has
+// SIMDs (kPfSegWaves) is cut into kPfSegMost segments of whole 32-day blocks; at 1 200 wavefronts the cut gains nothing, at 4 800 it
+// costs a third.
+constexpr long long kPfSegWaves = 1024;
+constexpr int kPfSegMost = 8;
+
+static void pathfn_geometry(const epi_pathfn_desc *d, int *nseg, int *seg_days, int *nblk)
+{
+    const int W = d->k1 - d->k0, nb = (W + kPfBlock - 1) / kPfBlock;
+    long long want = d->test_segments;
+    if (want <= 0) {
+        const long long groups = d->derive_newcases ? (long long)d->rows - 2 : (long long)d->rows;
+        const long long waves = (((long long)d->R * d->D + 63) / 64) * groups;
+        want = waves >= kPfSegWaves ? 1 : kPfSegMost;
+    }
+    if (want > nb) want = nb;
+    const int per = (int)((nb + want - 1) / want);                    // blocks of a segment
+    *nseg = (nb + per - 1) / per;                                     // no empty segment
+    *seg_days = per * kPfBlock;
+    *nblk = nb;
+}
+
+static int pathfn_check_desc(const epi_pathfn_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->rows < 1 || d->rows > 4096) { set_err(err, "rows must lie in 1 .. 4096"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1) { set_err(err, "D must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->n_thr < 0 || d->n_thr > kPfMaxThr) { set_err(err, "n_thr must lie in 0 .. 8"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k1 <= d->k0 || d->k1 > d->T) { set_err(err, "k0, k1 must satisfy 0 <= k0 < k1 <= T"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases != 0 && d->derive_newcases != 1) { set_err(err, "derive_newcases must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && d->rows < 3) { set_err(err, "derive_newcases needs at least 3 rows"); return EPI_ERR_BAD_ARG; }
+    const int nb = (d->k1 - d->k0 + kPfBlock - 1) / kPfBlock;
+    if (d->test_segments < 0 || d->test_segments > (nb < kPfMaxSeg ? nb : kPfMaxSeg)) {
+        set_err(err, "test_segments must lie in 0 .. min(ceil((k1 - k0) / 32), 1024): a segment is whole 32-day blocks");
+        return EPI_ERR_BAD_ARG;
+    }
+    if (d->test_launch_groups < 0) { set_err(err, "test_launch_groups must be >= 0"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+static bool pathfn_wants_regions(const epi_pathfn_outputs *o)
+{
+    return o->n_paths || o->peak_day_hist || o->n_cross || o->cross_day_hist;
+}
+
+int epi_pathfn_validate(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, char *err)
+{
+    int rc = pathfn_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->src) { set_err(err, "NULL src"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && !in->population) { set_err(err, "NULL population (derive_newcases)"); return EPI_ERR_BAD_ARG; }
+    if (d->n_thr > 0 && !in->thr) { set_err(err, "NULL thr (n_thr > 0)"); return EPI_ERR_BAD_ARG; }
+    if (d->n_thr == 0 && (out->first_cross || out->days_above || out->longest_run || out->n_cross || out->cross_day_hist)) {
+        set_err(err, "first_cross, days_above, longest_run, n_cross and cross_day_hist need n_thr >= 1");
+        return EPI_ERR_BAD_ARG;
+    }
+    if ((out->peak_day_hist || out->cross_day_hist) && d->k1 - d->k0 > kPfMaxW) {
+        set_err(err, "a histogram holds at most 4096 days (k1 - k0): its bins live in LDS");
+        return EPI_ERR_BAD_ARG;
+    }
+    if (!(out->peak_value || out->peak_day || out->min_value || out->min_day || out->total || out->first_cross || out->days_above ||
+          out->longest_run || out->n_valid || pathfn_wants_regions(out))) {
+        set_err(err, "no output requested");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+// the workspace in doubles, then int32: peak_day [M], first_cross [n_thr][M]; with segments p_mx, p_mn [nseg][M], p_bsum [nblk][M],
+// then p_int [nseg][3][M], p_thr [nseg][5][n_thr][M]
+static size_t pathfn_ws_bytes(const epi_pathfn_desc *d)
+{
+    int nseg, seg_days, nblk;
+    pathfn_geometry(d, &nseg, &seg_days, &nblk);
+    const size_t M = (size_t)(d->rows + d->derive_newcases) * (size_t)d->R * (size_t)d->D, nt = (size_t)d->n_thr;
+    size_t n = (1 + nt) * M * sizeof(double);
+    if (nseg > 1) n += (2 * (size_t)nseg + (size_t)nblk) * M * sizeof(double) + (size_t)nseg * (3 + 5 * nt) * M * sizeof(int32_t);
+    return n;
+}
+
+int epi_pathfn_workspace_bytes(const epi_pathfn_desc *d, size_t *bytes, char *err)
+{
+    int rc = pathfn_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = pathfn_ws_bytes(d);
+    return EPI_OK;
+}
+
+int epi_pathfn_run_device(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_pathfn_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    PfArgs g{};
+    pathfn_geometry(d, &g.nseg, &g.seg_days, &g.nblk);
+    const bool regions = pathfn_wants_regions(out);
+    if ((regions || g.nseg > 1) && (!ws || ws_bytes < pathfn_ws_bytes(d))) { set_err(err, "workspace too small (epi_pathfn_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    g.T = d->T; g.rows = d->rows; g.rows_out = d->rows + d->derive_newcases; g.R = d->R; g.D = d->D; g.n_thr = d->n_thr;
+    g.derive = d->derive_newcases; g.k0 = d->k0; g.k1 = d->k1;
+    g.src = in->src; g.population = in->population; g.thr = in->thr; g.first_day = in->first_day;
+    g.peak_value = out->peak_value; g.peak_day = out->peak_day; g.min_value = out->min_value; g.min_day = out->min_day;
+    g.total = out->total; g.first_cross = out->first_cross; g.days_above = out->days_above; g.longest_run = out->longest_run;
+    g.n_valid = out->n_valid; g.n_paths = out->n_paths; g.peak_day_hist = out->peak_day_hist; g.n_cross = out->n_cross;
+    g.cross_day_hist = out->cross_day_hist;
+    const size_t N = (size_t)d->R * (size_t)d->D, M = (size_t)g.rows_out * N, nt = (size_t)d->n_thr;
+    double *wd = (double *)ws;
+    if (!g.peak_day && (out->n_paths || out->peak_day_hist)) g.peak_day = wd;     // what the region pass reads and the caller did not ask for
+    if (!g.first_cross && (out->n_cross || out->cross_day_hist)) g.first_cross = wd + M;
+    if (g.nseg > 1) {
+        g.p_mx = wd + (1 + nt) * M;
+        g.p_mn = g.p_mx + (size_t)g.nseg * M;
+        g.p_bsum = g.p_mn + (size_t)g.nseg * M;
+        g.p_int = (int32_t *)(g.p_bsum + (size_t)g.nblk * M);
+        g.p_thr = g.p_int + (size_t)g.nseg * 3 * M;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const long long cap = d->test_launch_groups > 0 ? (long long)d->test_launch_groups : kPfLaunchGroups;
+    const long long pg = (long long)((N + kPfPathWg - 1) / kPfPathWg);
+    using PathKernel = void (*)(const PfArgs);
+    // NT: the compile-time bound on n_thr, in the buckets 0, 2 and 8 (their registers)
+#define EPI_PF_ROW(F, NT) {{pathfn_paths<F, NT, 1, 0>, pathfn_paths<F, NT, 1, 1>}, {pathfn_paths<F, NT, 4, 0>, pathfn_paths<F, NT, 4, 1>}}
+    static const PathKernel paths[2][3][2][2] = {{EPI_PF_ROW(0, 0), EPI_PF_ROW(0, 2), EPI_PF_ROW(0, 8)},
+                                                 {EPI_PF_ROW(1, 0), EPI_PF_ROW(1, 2), EPI_PF_ROW(1, 8)}};   // [storage][bucket][NR = 4][segments]
+#undef EPI_PF_ROW
+    static const PathKernel combine[3] = {pathfn_combine<0>, pathfn_combine<2>, pathfn_combine<8>};
+    const int bucket = d->n_thr == 0 ? 0 : (d->n_thr <= 2 ? 1 : 2), seg = g.nseg > 1 ? 1 : 0;
+    hipError_t e = hipSuccess;
+    // the path grid, in launches of its own loop (as sdraw's): grid.y the segments, grid.z the row groups
+    auto launch_paths = [&](PathKernel kern, int row0, int nz) {
+        const long long per = cap / ((long long)g.nseg * nz) > 0 ? cap / ((long long)g.nseg * nz) : 1;
+        g.row0 = row0;
+        for (long long w0 = 0; w0 < pg && e == hipSuccess; w0 = w0 + per) {
+            g.group0 = w0;
+            const unsigned nb = (unsigned)(pg - w0 < per ? pg - w0 : per);
+            hipLaunchKernelGGL(kern, dim3(nb, (unsigned)g.nseg, (unsigned)nz), dim3(kPfPathWg), 0, st, g);
+            e = hipGetLastError();
+        }
+    };
+    if (d->derive_newcases) {
+        launch_paths(paths[d->storage][bucket][1][seg], 0, 1);
+        if (e == hipSuccess && d->rows > 3) launch_paths(paths[d->storage][bucket][0][seg], 3, d->rows - 3);
+    } else {
+        launch_paths(paths[d->storage][bucket][0][seg], 0, d->rows);
+    }
+    if (e != hipSuccess) return hip_fail(err, e, "pathfn_paths launch");
+    if (g.nseg > 1) {
+        const long long per = cap / g.rows_out > 0 ? cap / g.rows_out : 1;
+        for (long long w0 = 0; w0 < pg; w0 = w0 + per) {
+            g.group0 = w0;
+            const unsigned nb = (unsigned)(pg - w0 < per ? pg - w0 : per);
+            hipLaunchKernelGGL(combine[bucket], dim3(nb, (unsigned)g.rows_out), dim3(kPfPathWg), 0, st, g);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "pathfn_combine launch");
+        }
+    }
+    if (!regions) return EPI_OK;
+    const long long rg = (long long)((out->n_cross || out->cross_day_hist) ? 1 + d->n_thr : 1) * g.rows_out * d->R;
+    for (long long w0 = 0; w0 < rg; w0 = w0 + cap) {
+        g.group0 = w0;
+        const unsigned nb = (unsigned)(rg - w0 < cap ? rg - w0 : cap);
+        hipLaunchKernelGGL(pathfn_regions, dim3(nb), dim3(kPfRegionWg), 0, st, g);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "pathfn_regions launch");
+    }
+    return EPI_OK;
+}
+
+int epi_pathfn_run_host(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, int device, char *err)
+{
+    int rc = epi_pathfn_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, N = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases);
+    const size_t nt = (size_t)d->n_thr, W = (size_t)(d->k1 - d->k0), none = HostIO::kAbsent;
+    HostIO io;
+    const size_t o_src = io.add_in(in->src, T * (size_t)d->rows, d->storage ? 4 : 8, N, 0, N);
+    const size_t o_pop = d->derive_newcases ? io.add_in(in->population, 1, 8, R, 0, R) : none;
+    const size_t o_thr = nt ? io.add_in(in->thr, nt * ro, 8, R, 0, R) : none;
+    const size_t o_fd = in->first_day ? io.add_in(in->first_day, 1, 4, R, 0, R) : none;
+    using PO = epi_pathfn_outputs;
+    const HostIO::Opt<PO, double> f64[8] = {{&PO::peak_value, ro}, {&PO::peak_day, ro}, {&PO::min_value, ro}, {&PO::min_day, ro},
+                                            {&PO::total, ro}, {&PO::first_cross, nt * ro}, {&PO::days_above, nt * ro},
+                                            {&PO::longest_run, nt * ro}};
+    const HostIO::Opt<PO, int32_t> i32p[1] = {{&PO::n_valid, ro}};
+    const HostIO::Opt<PO, int32_t> i32r[4] = {{&PO::n_paths, ro}, {&PO::peak_day_hist, W * ro}, {&PO::n_cross, nt * ro},
+                                              {&PO::cross_day_hist, W * nt * ro}};
+    size_t o_d[8], o_p[1], o_r[4];
+    io.add_opt(*out, f64, o_d, N);
+    io.add_opt(*out, i32p, o_p, N);
+    io.add_opt(*out, i32r, o_r, R);
+    int nseg, seg_days, nblk;
+    pathfn_geometry(d, &nseg, &seg_days, &nblk);
+    const size_t wsb = pathfn_ws_bytes(d);
+    const size_t o_ws = (pathfn_wants_regions(out) || nseg > 1) ? io.reserve(wsb) : none;
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_pathfn_inputs din{};
+        din.src = base + o_src; din.population = HostIO::at<const double>(base, o_pop); din.thr = HostIO::at<const double>(base, o_thr);
+        din.first_day = HostIO::at<const int32_t>(base, o_fd);
+        epi_pathfn_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32p, o_p, base);
+        HostIO::bind_opt(dout, i32r, o_r, base);
+        return epi_pathfn_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -356,3 +356,15 @@ def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, 
     src = np.ascontiguousarray(src, dtype=np.float32 if src.dtype == np.float32 else np.float64)
     return _call.ensemble_score(HostBackend(device), src, truth, R, D, alpha, n_bins, population, truth_series, first_day, k0, k1,
                                 outputs, test_launch_items)
+
+
+def path_functionals(src, R, D, thresholds=None, population=None, first_day=None, k0=0, k1=None, outputs=None, device=0,
+                     test_segments=0, test_launch_groups=0):
+    """epi_pathfn_run_host: batch.path_functionals on NumPy arrays (synchronous): the same arguments, and the same keys, order,
+    dtypes and bits.  A float32 src = float storage, anything else is taken as float64."""
+    src = np.asarray(src)
+    if src.ndim == 4:
+        raise ValueError("src is a chain-blocked array [T, nblk, rows, blk]; path_functionals takes the classic layout [T, rows, B]")
+    src = np.ascontiguousarray(src, dtype=np.float32 if src.dtype == np.float32 else np.float64)
+    return _call.path_functionals(HostBackend(device), src, R, D, thresholds, population, first_day, k0, k1, outputs,
+                                  test_segments, test_launch_groups)

@@ -785,3 +785,44 @@ def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draw
                cover_by_lead=torch.stack([by_lead((cover >> k) & 1) for k in range(n_a)]) if n_a else
                torch.empty((0, H, S), dtype=torch.float64, device=dev))
     return out
+
+
+OUTLOOK_SUMMARISED = ("peak_value", "peak_day", "total", "days_above", "longest_run")
+
+
+def path_outlook(X, R, D, thresholds=None, population=None, q=(0.025, 0.25, 0.5, 0.75, 0.975), k0=0, k1=None, first_day=None):
+    """What the joint draws were made for: when the peak is, how high, how many cases over the window, and with what probability a
+    threshold is exceeded by day t and for how long.  X [T, rows, R * D] are joint paths where they lie (smoothed_fan's or
+    forecast_fan's X, monte_carlo_eks', ar_forecast's); batch.path_functionals reads them once, and
+    batch.ensemble_summary turns each per-path functional into its law over the D draws of every region: nothing is copied back.
+    thresholds [n_thr, rows', R] (NaN: not asked for that row and region; None: no threshold), population [R] appends the new-case
+    row, the window is k0 <= t < k1 from first_day[r] on.
+    Returns `functionals` (the dict of batch.path_functionals), for each of peak_value, peak_day, total [rows', R] and -- with
+    thresholds -- days_above, longest_run [n_thr, rows', R] the dict of batch.ensemble_summary over the draws (mean, std, min, max,
+    count: the number of paths that have the functional; quantiles at q [rows', n_q, R] and [n_thr, n_q, rows', R]), p_peak_by_day [W, rows', R] (the probability that the
+    peak lies on or before day k0 + w) and p_cross_by_day [W, n_thr, rows', R] (that threshold j has been reached by day k0 + w):
+    the cumulative sums of the two histograms over n_paths (torch reductions)."""
+    fn = batch.path_functionals(X, R, D, thresholds=thresholds, population=population, first_day=first_day, k0=k0, k1=k1)
+    out = {"functionals": fn}
+    for k in OUTLOOK_SUMMARISED:
+        if k in fn:                                         # [rows', B] is a [T, B] source, [n_thr, rows', B] a [T, rows, B] one
+            out[k] = batch.ensemble_summary(fn[k] if fn[k].dim() > 1 else fn[k].unsqueeze(0), R, D, q=q)
+    n_paths = fn["n_paths"].to(torch.float64)
+    out["p_peak_by_day"] = fn["peak_day_hist"].cumsum(dim=0).to(torch.float64) / n_paths
+    if "cross_day_hist" in fn:
+        out["p_cross_by_day"] = fn["cross_day_hist"].cumsum(dim=0).to(torch.float64) / n_paths
+    return out
+
+
+def forecast_outlook(cases, deaths, population, ip, horizon, thresholds=None, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975),
+                     seed=0, storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0,
+                     device="cuda:0"):
+    """forecast_fan, then path_outlook over the horizon: per region the law of the peak day and height of the forecast, of the
+    cases over the horizon, and of the days above `thresholds` [n_thr, 4, S] (rows s, i, alpha, new cases; NaN: not asked).
+    Returns forecast_fan's dict with `outlook` (path_outlook's; day 0 of its histograms is the first day of the horizon)."""
+    out = forecast_fan(cases, deaths, population, ip, horizon, n_draws=n_draws, plan=plan, q=q, seed=seed, storage=storage, clamp=clamp,
+                       regression=regression, num_regression_days=num_regression_days, W=W, cv_folds=cv_folds, cv_seed=cv_seed,
+                       device=device)
+    S = cases.shape[1]
+    out["outlook"] = path_outlook(out["X"], S, int(n_draws), thresholds, population=np.asarray(population, dtype=np.float64), q=q)
+    return out

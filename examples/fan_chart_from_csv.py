@@ -2,7 +2,7 @@
 joint posterior draws of the smoother's paths (epidemicmodeling_amd/pipeline.py: forecast_fan), for all regions of
 the file at once.
 
-    python examples/fan_chart_from_csv.py [--score-last N] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
+    python examples/fan_chart_from_csv.py [--score-last N] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
 
 The front half of Tools/TrainPredictPrescribeNPI.m (preprocessing, two EKF rounds, two regressions), then its forecast filter
 (:356-377: NaN observations over the horizon, the last day's NPIs held), then 256 backward-simulated paths per region and their
@@ -13,7 +13,12 @@ no data set in this repository).
 --score-last N holds the last N days of the window out, forecasts them from the days before, and prints how good the fans were
 (pipeline.fan_quality): per region the mean CRPS and weighted interval score of the daily new cases, the share of
 days the 50 % and the 95 % band held the truth, and the rank histogram in ten bins, with forecast starts N and N / 2 days before
-the end of the window."""
+the end of the window.
+
+--threshold C (or --outlook for the peak alone) prints the outlook over the horizon from the same joint draws (pipeline.path_outlook;
+DESIGN.md 4.18): per region the median and the 95 % band of the day of the peak of the daily new cases and of its height, the median
+of the cases summed over the horizon, and with a threshold the probability that the daily new cases reach C per 100 000 inhabitants
+within the horizon, the median first day they do, and the median longest run of days at or above it."""
 import os
 import sys
 import tempfile
@@ -44,9 +49,38 @@ def score_table(d, N, keep, n_last, draws):
     return pd.DataFrame(rows, columns=["region", "start", "days", "crps", "wis", "abs_err", "cover50", "cover95", "pit_hist"])
 
 
+def outlook_table(out, d, N, keep, draws, per_100k):
+    """the forecast's path functionals, summarised over the draws: one row per region (row 3 is the new cases)"""
+    S = len(keep)
+    thr = None
+    if per_100k is not None:
+        thr = np.full((1, 4, S), np.nan)
+        thr[0, 3] = per_100k * N[keep] / 1e5
+    o = pipeline.path_outlook(out["X"], S, draws, thr, population=N[keep], q=Q)
+    g = lambda k, n: o[k][n].cpu().numpy()
+    pd_q, pv_q, tot_q = g("peak_day", "quantiles")[3], g("peak_value", "quantiles")[3], g("total", "quantiles")[3]    # [n_q, S]
+    cols = ["region", "peak_day_q2.5", "peak_day_q50", "peak_day_q97.5", "peak_q2.5", "peak_q50", "peak_q97.5", "cases_q50"]
+    rows = [[d["geo_ids"][r], pd_q[0, j] + 1, pd_q[2, j] + 1, pd_q[4, j] + 1, pv_q[0, j], pv_q[2, j], pv_q[4, j], tot_q[2, j]]
+            for j, r in enumerate(keep)]
+    if thr is not None:
+        p = o["p_cross_by_day"][-1, 0, 3].cpu().numpy()
+        first = pipeline.batch.ensemble_summary(o["functionals"]["first_cross"], S, draws, q=(0.5,))["quantiles"][0, 0, 3].cpu().numpy()
+        run = g("longest_run", "quantiles")[0, 2, 3]
+        cols += ["p_reached", "first_day_q50", "longest_run_q50"]
+        rows = [row + [p[j], first[j] + 1, run[j]] for j, row in enumerate(rows)]
+    return pd.DataFrame(rows, columns=cols)
+
+
 def main():
     horizon, draws = 30, 256
-    n_last = 0
+    n_last, outlook, per_100k = 0, False, None
+    if "--outlook" in sys.argv:
+        sys.argv.remove("--outlook")
+        outlook = True
+    if "--threshold" in sys.argv:
+        i = sys.argv.index("--threshold")
+        outlook, per_100k = True, float(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
     if "--score-last" in sys.argv:
         i = sys.argv.index("--score-last")
         n_last = int(sys.argv[i + 1])
@@ -74,6 +108,9 @@ def main():
     table.to_csv(dst, index=False)
     print(f"{len(keep)} regions x {draws} draws x {horizon} days -> {dst}")
     print(table.head(12).to_string(index=False))
+    if outlook:
+        print(f"the outlook over the {horizon} days (day 1 is the first forecast day):")
+        print(outlook_table(out, d, N, keep, draws, per_100k).to_string(index=False))
     if n_last > 0:
         print(f"the last {n_last} days held out and forecast from the days before them:")
         print(score_table(d, N, keep, n_last, draws).to_string(index=False))

@@ -1380,6 +1380,70 @@ int epi_escore_run_device(const epi_escore_desc *d, const epi_escore_inputs *in,
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_escore_run_host(const epi_escore_desc *d, const epi_escore_inputs *in, const epi_escore_outputs *out, int device, char *err);
 
+/* ---- Path functionals of the Monte-Carlo ensembles (not a script of the reference) ----
+ * src [T][rows][N], N = R * D, region-major (path p = r * D + d), double or float, and the derived row ((N_r v0) v1) v2 as row
+ * `rows`, exactly as epi_ens_run_* take them.  The window is k0 <= t < k1, W = k1 - k0.  Definition (pinned; restated in
+ * tests/pathfn_ref.py and tests/pathfn_ref.c), per path p of region r and row q:
+ *   day t is VALID if max(k0, first_day[r]) <= t < k1 (first_day 0 without the array) and the value v is not NaN; +Inf and -Inf
+ *     are values.  One IEEE double operation per written operation, no fma(); a float value is widened once.
+ *   peak_value = the maximum over the valid days, peak_day = the first t that attains it (ascending scan, update on strict >),
+ *     the absolute day index of src as a double; min_value, min_day the same with <
+ *   total: block j holds the days k0 + 32 j .. k0 + 32 j + 31 of the window; a block's sum starts at +0.0 and adds its valid
+ *     days ascending (an invalid day is dropped by a select, not added as zero); total starts at +0.0 and adds the block sums
+ *     for j ascending, every block of the window included
+ *   per threshold j, thr = thr[(j * rows' + q) * R + r]: a day is ABOVE if it is valid and v >= thr; first_cross = the first
+ *     such t (NaN: none), days_above their number, longest_run the longest run of consecutive above days (an invalid or a below
+ *     day ends a run).  A NaN thr: the three are NaN ("not asked for this row and region")
+ *   n_valid the number of valid days; n_valid = 0: every floating output of the (path, row) is NaN
+ * Per (row, region) over the paths with n_valid > 0: n_paths; peak_day_hist[t - k0] = #{paths with peak_day = t}; n_cross[j] =
+ *   #{paths with a first_cross}; cross_day_hist[t - k0][j] the same binned by first_cross.  Integer counts: no order involved.
+ * Outputs (each may be NULL; at least one must not be): peak_value, peak_day, min_value, min_day, total [rows'][N];
+ *   first_cross, days_above, longest_run [n_thr][rows'][N] (all double: each is itself a src of epi_ens_run_*); n_valid
+ *   [rows'][N] int32; n_paths [rows'][R], peak_day_hist [W][rows'][R], n_cross [n_thr][rows'][R], cross_day_hist
+ *   [W][n_thr][rows'][R] int32; rows' = rows + derive_newcases */
+typedef struct epi_pathfn_desc {
+    int32_t abi_version;
+    int32_t T, rows, R;          /* days, rows of src (1 .. 4096), regions: each >= 1 */
+    int32_t D;                   /* draws per region, >= 1; R * D <= INT32_MAX */
+    int32_t n_thr;               /* thresholds, 0 .. 8 */
+    int32_t storage;             /* element type of src: 0 = double, 1 = float */
+    int32_t derive_newcases;     /* 0, or 1: append the row ((N * row0) * row1) * row2 */
+    int32_t k0, k1;              /* the window, 0 <= k0 < k1 <= T */
+    int32_t test_segments;       /* 0: the library's rule; > 0: time segments wanted, at most min(ceil(W / 32), 1024) (the tests) */
+    int32_t test_launch_groups;  /* 0; > 0: workgroups per launch (the tests cut small calls into several launches with it) */
+} epi_pathfn_desc;
+typedef struct epi_pathfn_inputs {
+    const void *src;                     /* [T][rows][R * D] */
+    const double *population;            /* [R] (derive_newcases) or NULL */
+    const double *thr;                   /* [n_thr][rows'][R] (NULL with n_thr = 0) */
+    const int32_t *first_day;            /* [R] or NULL */
+} epi_pathfn_inputs;
+typedef struct epi_pathfn_outputs {
+    double *peak_value, *peak_day, *min_value, *min_day, *total; /* [rows'][N] */
+    double *first_cross, *days_above, *longest_run;              /* [n_thr][rows'][N] */
+    int32_t *n_valid;                    /* [rows'][N] */
+    int32_t *n_paths;                    /* [rows'][R] */
+    int32_t *peak_day_hist;              /* [W][rows'][R] */
+    int32_t *n_cross;                    /* [n_thr][rows'][R] */
+    int32_t *cross_day_hist;             /* [W][n_thr][rows'][R] */
+} epi_pathfn_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for T, R, D < 1, rows outside 1 .. 4096, R * D > INT32_MAX, n_thr outside 0 .. 8, k0 / k1 outside
+ * 0 <= k0 < k1 <= T, storage or derive_newcases outside {0, 1}, derive_newcases with rows < 3 or without population,
+ * test_segments outside 0 .. min(ceil(W / 32), 1024), a negative test_launch_groups, a NULL src, a NULL thr with n_thr > 0, a
+ * threshold output with n_thr = 0, a histogram with W > 4096 (the bins of one histogram live in LDS), no output at all */
+int epi_pathfn_validate(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, char *err);
+/* bytes of device workspace epi_pathfn_run_device needs: peak_day and first_cross for the histograms (whichever of them the
+ * caller also asks for), and with more than one time segment the segments' partial records */
+int epi_pathfn_workspace_bytes(const epi_pathfn_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; one lane per path (cut into launches of at most 2^22 workgroups), a combining pass when the days are cut into
+ * segments, then one workgroup per (histogram, row, region) when a per-region output is asked for, enqueued on `stream`: no host
+ * synchronisation, no allocation.  EPI_ERR_WORKSPACE for a workspace below epi_pathfn_workspace_bytes when the call needs one
+ * (segments or a per-region output; else ws may be NULL) */
+int epi_pathfn_run_device(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_pathfn_run_host(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -108,6 +108,13 @@
 //       from;  k_first, k_last ([] = 1, T)  the days the per-region outputs run over, ONE-based and inclusive.  crps, wis, ae,
 //       rank, ties, cover, count  R x rows' x T (rank, ties -1 and NaN scores: not scored);  width  R x rows' x n_a x T;
 //       crps_mean, wis_mean, ae_mean, n_scored  R x rows';  cover_frac  R x rows' x n_a;  pit_hist  R x rows' x n_bins.
+//   [peak_value, peak_day, min_value, min_day, total, first_cross, days_above, longest_run, n_valid, n_paths, peak_day_hist, n_cross, cross_day_hist] = epiekf_pipeline_mex('pathfn', src, D, thr, population, first_day, k_first, k_last)
+//       Functionals of every joint path of a Monte-Carlo ensemble.  src, D, population  as 'ens_summary' takes
+//       them;  thr ([] = none)  R x rows' x n_thr (R x n_thr for a B x T src), at most 8 thresholds, NaN = not asked;  first_day
+//       ([] = 1)  R x 1, ONE-based first day of every region;  k_first, k_last ([] = 1, T)  the window, ONE-based and inclusive.
+//       peak_value, min_value, total, n_valid  B x rows';  peak_day, min_day  B x rows', ONE-based days;  first_cross (ONE-based,
+//       NaN: never), days_above, longest_run  B x rows' x n_thr;  n_paths  R x rows';  peak_day_hist  R x rows' x W (W = k_last -
+//       k_first + 1, at most 4096);  n_cross  R x rows' x n_thr;  cross_day_hist  R x rows' x n_thr x W.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).
@@ -601,6 +608,85 @@ static void escore(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void pathfn(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 8) mexErrMsgTxt("epiekf_pipeline_mex('pathfn', src, D, thr, population, first_day, k_first, k_last): 8 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1])) mexErrMsgTxt("src must be a double array B x rows x T (or B x T)");
+    const mwSize *ds = mxGetDimensions(prhs[1]);
+    const mwSize B = ds[0], rows = nd == 3 ? ds[1] : 1, T = nd == 3 ? ds[2] : ds[1];
+    const double Dd = mxGetScalar(prhs[2]);
+    if (!(Dd >= 1.0 && Dd <= 2147483647.0) || (double)(mwSize)Dd != Dd || B % (mwSize)Dd != 0) mexErrMsgTxt("D must be a positive integer that divides the number of chains");
+    const mwSize D = (mwSize)Dd, R = B / D;
+    const bool derive = !mxIsEmpty(prhs[4]);
+    if (derive && mxGetNumberOfElements(prhs[4]) != R) mexErrMsgTxt("population must have one entry per region");
+    const mwSize ro = rows + (derive ? 1 : 0);
+    mwSize nt = 0;
+    if (!mxIsEmpty(prhs[3])) {
+        if (!mxGetPr(prhs[3])) mexErrMsgTxt("thr must be a double array R x rows' x n_thr (R x n_thr for a B x T src)");
+        const mwSize ndt = mxGetNumberOfDimensions(prhs[3]);
+        const mwSize *dt = mxGetDimensions(prhs[3]);
+        if (ndt > 3 || dt[0] != R || (nd == 3 ? dt[1] != ro : (ndt == 3 || ro != 1)))
+            mexErrMsgTxt("thr must be R x rows' x n_thr (R x n_thr for a B x T src), rows' = rows + 1 with a population");
+        nt = nd == 3 ? (ndt == 3 ? dt[2] : 1) : dt[1];
+        if (nt > 8) mexErrMsgTxt("thr must hold at most 8 thresholds");
+    }
+    std::vector<int32_t> fd;
+    if (!mxIsEmpty(prhs[5])) {
+        if (mxGetNumberOfElements(prhs[5]) != R) mexErrMsgTxt("first_day must have one entry per region");
+        fd.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[5])[r];
+            if (!(v >= 1.0 && v <= 2147483647.0) || (double)(mwSize)v != v) mexErrMsgTxt("first_day must hold ONE-based days");
+            fd[(size_t)r] = (int32_t)v - 1;
+        }
+    }
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[6])) kf = mxGetScalar(prhs[6]);
+    if (!mxIsEmpty(prhs[7])) kl = mxGetScalar(prhs[7]);
+    if (!(kf >= 1.0 && kf <= (double)T && kl >= kf && kl <= (double)T) || (double)(mwSize)kf != kf || (double)(mwSize)kl != kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= k_last <= T");
+    const mwSize W = (mwSize)kl - (mwSize)kf + 1;
+    if (W > 4096) mexErrMsgTxt("the window must hold at most 4096 days (the histograms)");
+    epi_pathfn_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.rows = (int32_t)rows; d.R = (int32_t)R; d.D = (int32_t)D; d.n_thr = (int32_t)nt;
+    d.storage = 0; d.derive_newcases = derive ? 1 : 0; d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    epi_pathfn_inputs in;
+    memset(&in, 0, sizeof in);
+    in.src = mxGetPr(prhs[1]); in.population = derive ? mxGetPr(prhs[4]) : NULL; in.thr = nt ? mxGetPr(prhs[3]) : NULL;
+    in.first_day = fd.empty() ? NULL : fd.data();
+    // the ABI's [rows'][N], [n_thr][rows'][N], [rows'][R], [W][rows'][R], [W][n_thr][rows'][R] are MATLAB's B x rows', B x rows' x
+    // n_thr, R x rows', R x rows' x W, R x rows' x n_thr x W: no transposition
+    const mwSize d4[4] = {R, ro, nt, W};
+    mxArray *o[13] = {mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL),
+                      mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL), dbl3(B, ro, nt), dbl3(B, ro, nt),
+                      dbl3(B, ro, nt), mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(R, ro, mxREAL), dbl3(R, ro, W),
+                      dbl3(R, ro, nt), mxCreateNumericArray(4, d4, mxDOUBLE_CLASS, mxREAL)};
+    const size_t M = (size_t)(B * ro), cols = (size_t)(R * ro);
+    const size_t ni[5] = {M, cols, cols * (size_t)W, cols * (size_t)nt, cols * (size_t)nt * (size_t)W};
+    std::vector<int32_t> ibuf(ni[0] + ni[1] + ni[2] + ni[3] + ni[4] + 1);
+    int32_t *ip[5];
+    ip[0] = ibuf.data();
+    for (int j = 1; j < 5; j++) ip[j] = ip[j - 1] + ni[j - 1];
+    epi_pathfn_outputs out;
+    memset(&out, 0, sizeof out);
+    out.peak_value = mxGetPr(o[0]); out.peak_day = mxGetPr(o[1]); out.min_value = mxGetPr(o[2]); out.min_day = mxGetPr(o[3]);
+    out.total = mxGetPr(o[4]);
+    if (nt) { out.first_cross = mxGetPr(o[5]); out.days_above = mxGetPr(o[6]); out.longest_run = mxGetPr(o[7]); out.n_cross = ip[3]; out.cross_day_hist = ip[4]; }
+    out.n_valid = ip[0]; out.n_paths = ip[1]; out.peak_day_hist = ip[2];
+    char err[256] = {0};
+    const int rc = epi_pathfn_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < M; k++) { mxGetPr(o[1])[k] += 1.0; mxGetPr(o[3])[k] += 1.0; }      // ONE-based days (NaN stays NaN)
+    for (size_t k = 0; k < M * (size_t)nt; k++) mxGetPr(o[5])[k] += 1.0;
+    const int oi[5] = {8, 9, 10, 11, 12};
+    for (int j = 0; j < 5; j++)
+        for (size_t k = 0; k < ni[j]; k++) mxGetPr(o[oi[j]])[k] = (double)ip[j][k];
+    for (int k = 0; k < 13; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected");
@@ -898,6 +984,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "plan") == 0) plan(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "escore") == 0) escore(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "pathfn") == 0) pathfn(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
