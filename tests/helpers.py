@@ -758,6 +758,58 @@ def boundary_items(unit, count):
     return [k * unit + d for k in range(1, (count - 1) // unit + 1) for d in (-2, -1, 0, 1) if 0 <= k * unit + d < count]
 
 
+def as_f64(a):
+    """an integer array of the formulas (NumPy or torch) as float64"""
+    return a.astype(np.float64) if isinstance(a, np.ndarray) else a.double()
+
+
+def hash_pos(c, k):
+    """1 .. 2^20 from stream k of the hash"""
+    return (chain_hash(c, k) >> 12) + 1
+
+
+def hash_sgn(c, k):
+    """-2^19 .. 2^19 - 1"""
+    return (chain_hash(c, k) >> 12) - (1 << 19)
+
+
+def bits_equal(g, w):
+    """bit for bit, any NaN equal to any NaN; integers: the same values"""
+    g, w = np.asarray(g), np.asarray(w)
+    if g.shape != w.shape or g.dtype != w.dtype:
+        return False
+    if g.dtype.kind != "f":
+        return bool(np.array_equal(g, w))
+    u = {4: np.uint32, 8: np.uint64}[g.dtype.itemsize]
+    ng, nw = np.isnan(g), np.isnan(w)
+    return bool(np.array_equal(ng, nw) and np.array_equal(g.view(u)[~ng], w.view(u)[~nw]))
+
+
+def both_sides(sample, items, of=lambda i: i):
+    """every launch-boundary item's region / day is in the sample"""
+    return bool(items) and {int(of(i)) for i in items} <= sample
+
+
+def poison_words(t, int_poison):
+    """how many words of output `t` still hold the poison pattern of its type (count_nonzero: no int64 copy of the mask)"""
+    import torch
+    if t.dtype == torch.float64:
+        hit = t.view(torch.int64) == POISON64
+    elif t.dtype == torch.float32:
+        hit = t.view(torch.int32) == POISON32
+    else:
+        hit = t == int_poison
+    return int(torch.count_nonzero(hit))
+
+
+def report_limits(what, t_call, t_case, device):
+    """the [limits] line of a case: the library call alone, the whole case since time.perf_counter() gave `t_case`, peak memory"""
+    import time
+    import torch
+    peak = torch.cuda.max_memory_allocated(device)
+    print(f"[limits] {what}: call {t_call:.2f} s, case {time.perf_counter() - t_case:.1f} s, peak {peak / 2**30:.1f} GiB")
+
+
 # ---------------------------------------------------------------- whole-batch comparisons of the full-size runs
 # (DESIGN.md 2, "Every chain of the full-size runs").  The equality is the suite's np.array_equal(..., equal_nan=True): NaN equals
 # NaN whatever its payload, +0 equals -0, nothing else is equal that is not the same number.  words_equal() is that rule element

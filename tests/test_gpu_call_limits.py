@@ -45,53 +45,9 @@ LAUNCH = 1 << 25            # kEnsLaunchItems, kRfLaunchItems, kArLaunchBlocks
 FUSE_LAUNCH = 1 << 23       # kFuseLaunchGroups
 
 
-def _fl(a):
-    return a.astype(np.float64) if isinstance(a, np.ndarray) else a.double()
-
-
-def _pos(c, k):
-    """1 .. 2^20 from stream k of the hash"""
-    return (H.chain_hash(c, k) >> 12) + 1
-
-
-def _sgn(c, k):
-    """-2^19 .. 2^19 - 1"""
-    return (H.chain_hash(c, k) >> 12) - (1 << 19)
-
-
-def _bits_equal(g, w):
-    """bit for bit, any NaN equal to any NaN; integers: the same values"""
-    g, w = np.asarray(g), np.asarray(w)
-    if g.shape != w.shape or g.dtype != w.dtype:
-        return False
-    if g.dtype.kind != "f":
-        return bool(np.array_equal(g, w))
-    u = {4: np.uint32, 8: np.uint64}[g.dtype.itemsize]
-    ng, nw = np.isnan(g), np.isnan(w)
-    return bool(np.array_equal(ng, nw) and np.array_equal(g.view(u)[~ng], w.view(u)[~nw]))
-
-
-def _both_sides(sample, items, of=lambda i: i):
-    """every launch-boundary item's region / day is in the sample"""
-    return bool(items) and {int(of(i)) for i in items} <= sample
-
-
-def _poison_words(t, int_poison):
-    """how many words of output `t` still hold the poison pattern of its type (count_nonzero: no int64 copy of the mask)"""
-    import torch
-    if t.dtype == torch.float64:
-        hit = t.view(torch.int64) == H.POISON64
-    elif t.dtype == torch.float32:
-        hit = t.view(torch.int32) == H.POISON32
-    else:
-        hit = t == int_poison
-    return int(torch.count_nonzero(hit))
-
-
-def _report(what, t_call, t_case, device):
-    import torch
-    peak = torch.cuda.max_memory_allocated(device)
-    print(f"[limits] {what}: call {t_call:.2f} s, case {time.perf_counter() - t_case:.1f} s, peak {peak / 2**30:.1f} GiB")
+# the small helpers this module shares with tests/test_gpu_regression_limits.py
+_fl, _pos, _sgn = H.as_f64, H.hash_pos, H.hash_sgn
+_bits_equal, _both_sides, _poison_words, _report = H.bits_equal, H.both_sides, H.poison_words, H.report_limits
 
 
 # ------------------------------------------------------------------------------------------------------------------ ens
