@@ -802,12 +802,146 @@ def poison_words(t, int_poison):
     return int(torch.count_nonzero(hit))
 
 
+def passed_bits(nbytes, bits=(31, 32, 33)):
+    """which of the byte offsets 2^bit lie inside an array of nbytes bytes"""
+    return [b for b in bits if nbytes > (1 << b)]
+
+
+def region_columns(reg, D):
+    """the columns reg[j] * D .. reg[j] * D + D - 1 of an array [rows, R * D], region after region"""
+    reg = np.asarray(reg, dtype=np.int64)
+    return (reg[:, None] * D + np.arange(D, dtype=np.int64)[None]).reshape(-1)
+
+
+def formula_sample(rows, N, cols, fn, dtype=np.float64):
+    """[rows, len(cols)]: what formula_rows(rows, N, ...) holds in the columns `cols`, evaluated by NumPy"""
+    cols = np.asarray(cols, dtype=np.int64)
+    return np.asarray(fn(np.arange(rows, dtype=np.int64)[:, None] * N + cols[None])).astype(dtype)
+
+
+def replaced(cond, value, v):
+    """v with the constant `value` where cond holds (NumPy or torch: the formulas' non-finite entries)"""
+    if isinstance(v, np.ndarray):
+        return np.where(cond, value, v)
+    import torch
+    return torch.where(cond, torch.full_like(v, value), v)
+
+
+def poisoned_words(count, device):
+    """a workspace of `count` doubles, every 64-bit word POISON64"""
+    import torch
+    t = torch.empty(int(count), dtype=torch.float64, device=device)
+    t.view(torch.int64).fill_(POISON64)
+    return t
+
+
+def selected(t, sel):
+    """the columns `sel` (a device index tensor) of the last axis of t, as NumPy"""
+    return t.index_select(t.dim() - 1, sel).cpu().numpy()
+
+
 def report_limits(what, t_call, t_case, device):
     """the [limits] line of a case: the library call alone, the whole case since time.perf_counter() gave `t_case`, peak memory"""
     import time
     import torch
     peak = torch.cuda.max_memory_allocated(device)
     print(f"[limits] {what}: call {t_call:.2f} s, case {time.perf_counter() - t_case:.1f} s, peak {peak / 2**30:.1f} GiB")
+
+
+# ---------------------------------------------------------------- the pieces the cases of tests/test_gpu_newer_call_limits.py share
+LIMIT_BITS = (31, 32, 33)
+
+
+def dyadic10(k):
+    """a formula: stream k of the hash as a dyadic value"""
+    return lambda c: as_f64(hash_pos(c, k)) * 2.0 ** -10                # (0, 1024], 20 significant bits: exact in float too
+
+
+def with_nan(fn, k, every):
+    """fn, with a NaN where stream k of the hash is a multiple of `every`"""
+    return lambda c: replaced(chain_hash(c, k) % every == 0, float("nan"), fn(c))
+
+
+def assert_passes(nbytes, passes):
+    """nbytes: {name: bytes} of EVERY array of the call; passes: {name: bits} -- every array not named stays below 2^31"""
+    assert {k: passed_bits(v, LIMIT_BITS) for k, v in nbytes.items()} == {k: list(passes.get(k, ())) for k in nbytes}, \
+        {k: passed_bits(v, LIMIT_BITS) for k, v in nbytes.items() if passed_bits(v, LIMIT_BITS)}
+
+
+def crossing_sample(rows, N, itemsize, nbytes_passes, of=lambda c: c):
+    """the regions of of(column), -1 .. +1, on both sides of every 2^bit crossing of an array seen as [rows, N]"""
+    cols = crossing_regions(rows, N, bits=LIMIT_BITS, itemsize=itemsize)
+    assert len(cols) == 4 * len(nbytes_passes), (rows, N, itemsize, cols)
+    return sorted({of(c) + d for c in cols for d in (-1, 0, 1)})
+
+
+def region_sample(R, n_spread, *more):
+    """sorted sampled regions: 0, 1, R - 2, R - 1, a spread, and the lists `more`, each of which must lie inside 0 .. R - 1 or
+    is clipped to it; asserts that the ends and the spread are held"""
+    reg, cls = extreme_sample(R, R, n_spread=n_spread, rows=())
+    reg = np.unique(np.concatenate([reg] + [np.asarray(m, dtype=np.int64) for m in more]).astype(np.int64))
+    reg = reg[(reg >= 0) & (reg < R)]
+    S = set(reg.tolist())
+    assert {0, 1, R - 2, R - 1} <= S and set(cls["spread"]) <= S
+    return reg, S
+
+
+def assert_no_poison(out):
+    """rule 2: no word of any tensor of `out` (made by poisoned() / poisoned_words()) still holds its poison pattern"""
+    left = {k: poison_words(t, POISON_RANK) for k, t in out.items()}
+    assert not any(left.values()), ("outputs that still hold the poison pattern (words)", left)
+
+
+def compare_sample(out, want, sel, reg):
+    """rule 3: the columns of every output that belong to the sampled regions against the restatement"""
+    assert set(out) <= set(want), (sorted(out), sorted(want))
+    for k, t in out.items():
+        got, w = selected(t, sel[k] if isinstance(sel, dict) else sel), want[k]
+        if not bits_equal(got, w):
+            assert got.shape == w.shape and got.dtype == w.dtype, (k, got.shape, w.shape, got.dtype, w.dtype)
+            bad = ~((got == w) | ((got != got) & (w != w)))
+            cols = np.flatnonzero(bad.reshape(-1, bad.shape[-1]).any(axis=0))
+            n = got.shape[-1] // reg.size
+            raise AssertionError((k, "regions", reg[np.unique(cols // n)][:12].tolist(), "words", int(bad.sum())))
+
+
+def timed_device_call(entry, dev, *args):
+    """the device entry `entry` of the library with `args`, the current stream and an error buffer: seconds of the call"""
+    import ctypes as C
+    import time
+    import torch
+    from epidemicmodeling_amd import _lib
+    err = C.create_string_buffer(256)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    rc = getattr(_lib.lib(), entry)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), err)
+    _lib.check(rc, err)
+    torch.cuda.synchronize(dev)
+    return time.perf_counter() - t0
+
+
+def cycled_population(R, dev):
+    """[R] on the device and the 16 values it cycles through (the ens_summary limits case does the same)"""
+    import torch
+    from epidemicmodeling_amd import synth
+    N16 = synth.make_regions(16)["N"].astype(np.float64)
+    return torch.as_tensor(N16, device=dev).index_select(0, torch.arange(R, dtype=torch.int64, device=dev) % 16), N16
+
+
+def scaled_rows(fn, rows_out, scale_row, scale):
+    """fn over an array [n, rows_out, R] flattened to [n * rows_out, R], the rows `scale_row` of every n times `scale` (a power of
+    two: exact) -- the truths and thresholds of the derived row live at N_r v^3"""
+    def on_device(n, R, dev):
+        import torch
+        t = formula_rows(n * rows_out, R, dev, fn, torch.float64).reshape(n, rows_out, R)
+        t[:, scale_row] *= scale
+        return t
+
+    def on_host(n, R, reg):
+        t = formula_sample(n * rows_out, R, reg, fn).reshape(n, rows_out, reg.size)
+        t[:, scale_row] *= scale
+        return t
+    return on_device, on_host
 
 
 # ---------------------------------------------------------------- whole-batch comparisons of the full-size runs

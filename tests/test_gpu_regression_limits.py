@@ -42,8 +42,8 @@ stays inside the arrays):
        the results of later chunks).  Case B has one chunk, k0 = 0, and cannot see it.
 
 What stays uncovered: the product limits themselves (K R, D F R near 2^31: 16 GiB or more per array; asserted through the
-descriptors in tests/test_*_abi.py), and the byte-offset edges of the five newer calls (loglik, npi_plan, smoother_draws,
-ens_score, path_functionals).
+descriptors in tests/test_*_abi.py).  The launch bounds and byte-offset edges of the five newer calls (loglik, npi_plan,
+smoother_draws, ens_score, path_functionals) run in tests/test_gpu_newer_call_limits.py.
 
 Measured on one MI355X (the library call alone / the whole case with input generation, sampling and the restatement /
 torch.cuda.max_memory_allocated):
