@@ -25,12 +25,11 @@
 #include <math.h>
 #include <stdint.h>
 #include <type_traits>
-#include "../../include/epiekf.h"
+#include "launch_plan.hpp"
 
 namespace epi {
 
 constexpr int kNpi = EPI_MAX_NPI;
-constexpr int kWave = 64;
 constexpr double kEps = 2.220446049250313e-16;  // MATLAB eps
 
 #define EPI_DEV __device__ __forceinline__

@@ -28,7 +28,6 @@
 #pragma once
 
 constexpr int kHL = 6;          // lanes per chain
-constexpr int kHG = 10;         // chains per wavefront
 constexpr int kHGp = 11;        // groups incl. the phantom one of lanes 60..63
 constexpr int kHT = 38;         // doubles per chain in a matrix tile: 36 + 2, i.e. 304 B -- 16-byte aligned, and the b128 reads
                                 // of different chains fall into different banks ((76 g + 4 m) mod 64 = 12 g + 4 m: distinct)

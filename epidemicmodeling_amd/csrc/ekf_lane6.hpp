@@ -19,13 +19,11 @@
 //     P+ A', which the gain needs anyway, is (A P+)' bit for bit (P+ is symmetric bit for bit and a product commutes), so
 //     P(k+1|k) = sym((A P+) A' + Q) costs one more 6 x 6 product with A's 21 non-zeros, not two -- the forward kernel's own
 //     sequence of operations, the same bits (eks_bwd_hex does the same across six lanes).
-// Conditions (enqueue_fwd / enqueue_bwd check them): R_v a per-day series (monitor hoisted), fixed diagonal Q_w, fp64
+// Conditions (plan_launch checks them, launch_plan.hpp: lane6_ok): R_v a per-day series (monitor hoisted), fixed diagonal Q_w, fp64
 // storage, lane_block == lanes per workgroup == BLK.  Everything else keeps ekf_sym.hpp.
 #pragma once
 
-// the lane blocks these kernels are instantiated for: the balanced waves (balanced_lanes) of batches beyond one round of 64-lane
-// waves -- 40 is the headline's; not 64 (enqueue_bwd says why)
-constexpr bool lane6_block(int blk) { return blk == 40 || blk == 48 || blk == 56; }
+// (the lane blocks these kernels are instantiated for: lane6_block, launch_plan.hpp)
 constexpr unsigned kLwRecords = 0x7FFFFFF8u;       // just below 2 GiB: the bounds check includes the scalar offset (ekf_hex.hpp)
 
 EPI_DEV rsrc_t lw_rsrc(const void *p) { return mk_rsrc(p, p ? kLwRecords : 0u); }

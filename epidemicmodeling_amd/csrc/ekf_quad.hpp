@@ -19,7 +19,6 @@
 // nearly dense): fma(0, x, acc) == acc for finite operands, the same caveat as in ekf_sym.hpp.
 #pragma once
 
-constexpr int kQC = kWave / 4;   // chains per wavefront
 // One wavefront per workgroup.  (Workgroups of four wavefronts -- one per SIMD of a CU -- were measured: every wave ran
 // 30-45 % slower, 1.65 instead of 1.13 ms for the forward kernel at 300 chains; waves that share a CU get in each other's
 // way, so the fewer per CU the better, and single-wave workgroups spread over all CUs first.)

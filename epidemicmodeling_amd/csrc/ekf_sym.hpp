@@ -124,7 +124,6 @@ __global__ __launch_bounds__(256) void ekf_precheck(const KArgs a, int *__restri
 //   chain-blocked outputs, blk = 8:  recompute 0 / prefetch 1: 8.0 ms (372 VGPRs)   0 / 5: 8.1   0 / 0: 8.4   1 / 0: 9.5
 //   classic [T][rows][B]:            0 / 1: 8.6   0 / 0: 9.1   1 / 0: 9.6
 // eks_bwd_sym<6> therefore prefetches the small group and reads back; eks_bwd_sym<3> does neither (see there).
-constexpr int kPipeLanes = 40;   // lanes per workgroup of the LP = 1 forward variant
 // where the forward kernel keeps the model constants (see ekf_fwd_sym)
 template <int LP> struct PrmSelect { typedef ChainPrm type; };
 template <> struct PrmSelect<1> { typedef LitePrm<VecLdsS> type; };

@@ -857,7 +857,7 @@ __global__ __launch_bounds__(kWave) void eks_bwd_wave_nc(const KArgs a)
 // The 3-state models have no free controls (SIAlphaModelEKF.m:39 returns u as it came), so the NPI lanes only form
 // u_max(k) - u(k) for the fma chain of the alpha map.  Same dense, k-ascending products as above: bit for bit the one-lane
 // kernels' and the oracle's results.
-constexpr int kW3G = 7, kW3E = 9;
+constexpr int kW3E = 9;       // lanes per chain (kW3G chains per wavefront: launch_plan.hpp)
 
 struct Wave3Lane {
     int g, e, i, j, c;         // group, element, row, column, chain

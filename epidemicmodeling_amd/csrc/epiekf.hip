@@ -25,16 +25,6 @@
 
 namespace epi {
 
-struct ModelInfo { int m, flipped, lo_is_zero, phi_ge, obs_clamp, obs_fixed, generic; };
-static const ModelInfo MODEL_TABLE[6] = {
-    /* SIA3             */ {3, 0, 0, 0, 1, 0, 1},
-    /* SIA6             */ {6, 0, 1, 0, 1, 0, 1},
-    /* SIA3_BWD         */ {3, 1, 1, 0, 1, 0, 1},
-    /* SIA6_BWD         */ {6, 1, 1, 0, 1, 0, 1},
-    /* NEWCASE6         */ {6, 0, 1, 1, 1, 0, 0},
-    /* NEWCASE6_CODEGEN */ {6, 0, 1, 1, 0, 1, 0},
-};
-
 struct KArgs {
     int B, T, Sx, Su, n_npi, L, r_mode;
     int q_mode;   // 1: Q is [T][m*m][B], Q(:,:,k) of filter step k (GenericEKF.m:63-73); dense kernels only
@@ -918,7 +908,6 @@ static int copy_counts(int (&dst)[N], const int32_t *src, int k0, int K)
 // [/launch slices]
 
 struct WsLayout { size_t s_minus, s_plus, p_minus, p_plus, x, rank, flag, innov, hand_s, hand_p, hand_i, only, status, total; };
-static int lane_block_of(const epi_batch_desc *d) { return (d->lane_block <= 0 || d->lane_block >= d->B) ? d->B : d->lane_block; }
 static size_t padded_chains(const epi_batch_desc *d)
 {
     const int blk = lane_block_of(d);
@@ -930,7 +919,6 @@ static size_t padded_chains(const epi_batch_desc *d)
 // epi_host_pool_release): the SIMD count of each device, and idle helper streams
 // ---------------------------------------------------------------------------
 constexpr int kMaxDevices = 64;
-constexpr int kHelperEvents = 16;
 // A helper stream of the LOWEST priority (its workgroups are placed after the caller's stream's) with the events one call
 // needs to fork work onto it and join it back.  A call leases one for the time it takes to ENQUEUE its kernels; work of
 // consecutive lessees simply queues up on the stream.
@@ -1014,66 +1002,6 @@ static void helpers_release_all()
     if (have_prev) (void)hipSetDevice(prev);
 }
 
-// The innovation monitor leaves the forward kernels (ekf_monitor, ekf_quad.hpp) when R_v is a per-day series -- then rho
-// feeds nothing back -- and two double-written L-sample windows per lane fit the default dynamic-LDS limit.
-static bool monitor_hoisted(const epi_batch_desc *d)
-{
-    return MODEL_TABLE[d->model].generic && d->r_mode == 1 && d->q_mode == 0 && d->path_hint != 2 &&
-           (size_t)4 * d->L * kWave * sizeof(double) <= 64u * 1024u;
-}
-// Which lane mapping runs the 6-state generic models (epi_batch_desc.shape).  Auto: four lanes per chain while every
-// quad wavefront (16 chains) still gets a SIMD of its own, i.e. up to 16 384 chains on MI355X -- there the chains'
-// per-day latency is what counts and the quad kernels' instruction stream is half as long (9 375 chains: 3.5 instead of
-// 6.1 ms per pass); beyond that the quad waves (one per SIMD at ~290 registers) would run in rounds and one lane per
-// chain, the shape with the least total work, wins (18 750 chains: 6.1 against 8.4 ms).  profiles/r02/batch_size_sweep.txt.
-// Round 4: one WAVEFRONT per chain (ekf_wave.hpp) while every chain can have a SIMD of its own (B <= 1024 on MI355X): a lone
-// wave's day costs ~0.6 us there against 2.1-2.2 us for a quad wave, at ~4 x the quad shape's total VALU work.  It needs the
-// innovation monitor as its own kernel (R_v a per-day series) and a fixed Q_w; otherwise four lanes per chain.
-static int shape_of(const epi_batch_desc *d, int dev)
-{
-    const ModelInfo &mi = MODEL_TABLE[d->model];
-    if (!mi.generic) {
-        // NewCaseEKFEstimatorWithOptimalNPI (round 5): one wavefront per chain (ekf_fwd_wave<0, 1, LC, 0>, eks_bwd_wave_nc) while every
-        // chain can have a SIMD of its own -- the reference's own callers make ONE call per chain
-        // (testScripts/testSIModelOptimalControl04EKS.m:168,302): 2.1 instead of 8.4 ms -- otherwise the dense one-lane kernels
-        const bool ok = mi.m == 6 && !d->storage && d->q_mode == 0 && (size_t)6 * d->L * sizeof(double) <= 48u * 1024u;
-        if (d->shape == EPI_SHAPE_WAVE) return ok ? EPI_SHAPE_WAVE : EPI_SHAPE_LANE;
-        if (d->shape != EPI_SHAPE_AUTO) return EPI_SHAPE_LANE;
-        return (ok && (long)d->B <= (long)simd_count(dev)) ? EPI_SHAPE_WAVE : EPI_SHAPE_LANE;
-    }
-    if (d->storage) return EPI_SHAPE_LANE;
-    if (mi.m == 3) {
-        // 3-state models: seven chains per wavefront, nine lanes each (ekf_fwd_wave3), for small batches; otherwise one lane
-        // per chain.  There is no four-lane shape for them.  Measured (BASELINE config 3's chains x 400 days, ms per pass,
-        // wave / lane): 300 chains 0.91 / 1.04, 2 000 1.09 / 1.20, 7 000 1.47 / 1.26, 20 000 3.08 / 1.80 -- a 3-state step is
-        // bound by its scalar chain (state map, the 12-term NPI sum, two divisions: ~1.4 us per day in EITHER shape), the
-        // 3 x 3 algebra the wave shape spreads over nine lanes is a small part of it.  Chosen up to 2 048 chains.
-        const bool ok = monitor_hoisted(d);
-        if (d->shape == EPI_SHAPE_WAVE) return ok ? EPI_SHAPE_WAVE : EPI_SHAPE_LANE;
-        if (d->shape == EPI_SHAPE_LANE || d->shape == EPI_SHAPE_QUAD || d->shape == EPI_SHAPE_HEX) return EPI_SHAPE_LANE;
-        return (ok && d->B <= 2048) ? EPI_SHAPE_WAVE : EPI_SHAPE_LANE;
-    }
-    // the hex shape needs the monitor as its own kernel (R_v a per-day series) and a fixed Q_w -- and at least a few days of
-    // every array within the 2 GiB its addressing windows span (ekf_hex.hpp, hx_window): 288 B and 8 n_npi B per chain and day
-    const bool hex_ok = monitor_hoisted(d) && (long)d->B <= (1L << 20) && (long)d->n_npi * d->Su <= (1L << 25);
-    // the wave shape also runs the monitor inline (a scalar, possibly adaptive R_v: ekf_fwd_wave<FLIP, 1>, round 5)
-    const bool wave_ok = hex_ok || (mi.generic && d->r_mode == 0 && d->q_mode == 0 && d->path_hint != 2 &&
-                                    (size_t)6 * d->L * sizeof(double) <= 48u * 1024u);
-    if (d->shape == EPI_SHAPE_WAVE) return wave_ok ? EPI_SHAPE_WAVE : EPI_SHAPE_QUAD;
-    if (d->shape == EPI_SHAPE_HEX) return hex_ok ? EPI_SHAPE_HEX : EPI_SHAPE_QUAD;
-    if (d->shape == EPI_SHAPE_QUAD || d->shape == EPI_SHAPE_LANE) return d->shape;
-    // (round 5: with the hex shape there, one wavefront per chain wins only up to ~600 chains: 300 chains 1.59 against 1.81 ms per
-    // call, 1 024 chains 2.15 against 1.84 -- profiles/r05/shape_latency.json; where the hex shape cannot run, up to one chain per SIMD)
-    if (wave_ok && (long)d->B <= (hex_ok ? (long)simd_count(dev) * 5 / 8 : (long)simd_count(dev))) return EPI_SHAPE_WAVE;
-    // round 5: six lanes per chain, ten chains per wavefront (ekf_hex.hpp) up to TWO such wavefronts per SIMD (20 480 chains on
-    // MI355X; beyond one per SIMD its kernels run two waves per SIMD, a third does not fit their registers): 9 375 chains -- the
-    // shard of the headline sweep on one of 8 GPUs -- 2.6 ms against 3.2 (quad) and 4.9 (lane); 18 750 chains (one of 4 GPUs)
-    // 5.1 against 5.6 (lane), 20 480 chains 5.5 against 5.7, 20 500 chains 6.5 against 5.8: profiles/r05/ab_hex_threshold.txt
-    // (with the kernels' day offsets in the scalar offset; before that the shapes were level at 18 750)
-    if (hex_ok && ((long)d->B + kHG - 1) / kHG <= 2 * (long)simd_count(dev)) return EPI_SHAPE_HEX;
-    return ((long)d->B + kQC - 1) / kQC <= (long)simd_count(dev) ? EPI_SHAPE_QUAD : EPI_SHAPE_LANE;
-}
-
 static WsLayout ws_layout(const epi_batch_desc *d)
 {
     const int m = MODEL_TABLE[d->model].m;
@@ -1110,27 +1038,6 @@ static WsLayout ws_layout(const epi_batch_desc *d)
 // ---------------------------------------------------------------------------
 // launch logic
 // ---------------------------------------------------------------------------
-// Lanes per wave for the one-chain-per-lane kernels.  `waves_per_simd` waves of such a kernel fit a SIMD (1 for the
-// 6-state kernels, 2 for the 3-state ones).  6 states: if cn/64 waves exceed what is resident at once, the launch would run
-// in rounds and the last round would leave most SIMDs idle while its few waves are limited by what ONE compute unit
-// can pull from memory; narrower waves, a multiple of 8 lanes (64-byte segments), make every round equally full.
-// 3 states: always full 64-lane waves.  Their arrays have 3 and 9 rows, so a wave writes 1.3 / 4 KB per array and step, and
-// chunks that small only reach the HBM's rate when every row is a whole number of cache lines (64 lanes = 512 B):
-// profiles/layout_probe/run_rows.py measures 4.7 / 5.2 TB/s for 3- / 9-row chunks of 56 lanes against 6.2 / 6.3 TB/s with 64
-// (with 12 rows and more the width stops mattering), and BASELINE config 5 runs 20.6 -> 17.5 ms with full waves although its
-// last round is a third full (profiles/r03/README.md).
-static int balanced_lanes(int cn, int waves_per_simd, int dev)
-{
-    if (waves_per_simd >= 2) return kWave;
-    const long cap = (long)simd_count(dev) * waves_per_simd;
-    const long w64 = (cn + kWave - 1) / kWave;
-    if (w64 <= cap) return kWave;
-    const long rounds = (w64 + cap - 1) / cap;
-    long lw = (cn + rounds * cap - 1) / (rounds * cap);
-    lw = (lw + 7) / 8 * 8;
-    return (int)(lw > kWave ? kWave : lw);
-}
-
 // the scoring tail of the Pareto sweep (epi_sweep_run_device): device pointers, validated by the entry point
 struct Tail {
     int t_hist, R, P;
@@ -1138,251 +1045,106 @@ struct Tail {
     double *J0, *J1;
     int32_t *on_front, *i_opt;
 };
-// what one call enqueues
-struct Launch {
-    int dev, phase, hint, time_pipe;
-    int test_flags;  // epi_batch_desc.test_flags (0 in production)
-    bool smooth;
-    const Tail *tail;
-    bool rerun;      // epi_batch_desc.exact_nonfinite: dense second pass over the chains whose covariance went non-finite
-};
+static_assert(pinv_wg<6>() == pinv_chains(6) && pinv_wg<3>() == pinv_chains(3), "launch_plan.hpp sizes the eks_pinv grid");
+
+// Which kernels run, on which grids, in which order and on which stream is decided by plan_launch (launch_plan.hpp); what
+// follows maps a plan's pick to the kernel it names and walks the plan's list.
+template <class K, class... A>
+static hipError_t launch(K kern, dim3 grid, int wg, size_t lds, hipStream_t st, const A &...args)
+{
+    if (lds > 64u * 1024u) {       // above the default dynamic-LDS limit
+        const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(wg), lds, st, args...);
+    return hipGetLastError();
+}
 
 // the innovation monitor as its own launch (after the forward kernel that wrote the innovations)
 template <int FLIP>
-static hipError_t launch_monitor(const KArgs &ka, int dev, hipStream_t st)
+static hipError_t launch_monitor(const KArgs &ka, const LaunchPlan &p, hipStream_t st)
 {
-    if (!ka.mon_hoist || !(ka.rho || ka.f.rho)) return hipSuccess;
-    const size_t shm = (size_t)4 * ka.L * kWave * sizeof(double);
-    const int mb = (ka.B + kWave - 1) / kWave;
-    // use the scan-free grid (ekf_monitor_par) while the batch has at most TWO 64-chain waves per SIMD (131 072 chains; round 6: the
-    // headline's 75 000 chains included -- forward stage + monitor 5.45-5.6 against 5.8-6.3 ms, the pass 0.3-0.5 ms shorter in each of
-    // four alternating runs, profiles/r06/ab_monitor_par.txt; round 5 had it at one)
-    constexpr int kMonitorParMaxWaves = 2;
-    if (ka.L == 21 && !ka.mon_scan && (long)mb <= (long)kMonitorParMaxWaves * simd_count(dev)) {
-        constexpr int D = 8;
-        hipLaunchKernelGGL((ekf_monitor_par<FLIP, 21, D>), dim3(mb, (ka.T + D - 1) / D), dim3(kWave), 0, st, ka, ka.dense_flag);
-        return hipGetLastError();
-    }
-    // time segments (each pays a 2L-2-step warm-up): enough of them that the grid gives every SIMD about eight of these
-    // light waves (a lane's 100-step scan is latency-bound: 0.70 ms with two segments, 0.25 ms with eight at 75 000 chains),
-    // none shorter than ~64 steps
-    int nseg = (8 * simd_count(dev) + mb - 1) / mb;
-    const int max_seg = ka.T / 64 > 1 ? ka.T / 64 : 1;
-    nseg = nseg < 1 ? 1 : (nseg > max_seg ? max_seg : nseg);
-    if (ka.L == 21) hipLaunchKernelGGL((ekf_monitor<FLIP, 21>), dim3(mb, nseg), dim3(kWave), shm, st, ka, ka.dense_flag);
-    else hipLaunchKernelGGL((ekf_monitor<FLIP, 0>), dim3(mb, nseg), dim3(kWave), shm, st, ka, ka.dense_flag);
-    return hipGetLastError();
+    const dim3 grid(p.mon_gx, p.mon_gy);
+    if (p.mon.kernel == MON_PAR) return launch(ekf_monitor_par<FLIP, 21, kMonitorParDays>, grid, kWave, 0, st, ka, ka.dense_flag);
+    if (p.mon.bits & V_L21) return launch(ekf_monitor<FLIP, 21>, grid, kWave, p.mon.lds, st, ka, ka.dense_flag);
+    return launch(ekf_monitor<FLIP, 0>, grid, kWave, p.mon.lds, st, ka, ka.dense_flag);
 }
 
-// forward kernel(s) over filter steps [ka.k_begin, ka.k_end) of all chains
+// forward kernel(s) over filter steps [o.a, o.b) of the chains [o.c0, o.c0 + o.cn)
 template <int M, int FLIP, int GENERIC>
-static hipError_t enqueue_fwd(KArgs ka, const Launch &L, hipStream_t st, int c0 = 0, int cn = -1)
+static hipError_t enqueue_fwd(KArgs ka, const LaunchPlan &p, const PlanOp &o, hipStream_t st)
 {
-    ka.c0 = 0; ka.cn = ka.B;
-    ka.lw = balanced_lanes(ka.B, M == 6 ? 1 : 2, L.dev);
-    if (cn >= 0) { ka.c0 = c0; ka.cn = cn; }      // a chain range (a multiple of the wave's lanes; the one-lane kernels only)
-    const int blocks = (ka.cn + ka.lw - 1) / ka.lw;
-    const size_t shmem = (size_t)3 * ka.L * kWave * sizeof(double);
-    // hint 0: both variants are enqueued, the one ekf_precheck did not select returns at once
-    const bool run_sym = GENERIC && L.hint != 2, run_dense = !GENERIC || L.hint != 1;
+    ka.k_begin = o.a; ka.k_end = o.b; ka.c0 = o.c0; ka.cn = o.cn;
+    const unsigned v = p.fwd.bits;
+    auto go = [&](auto kern) { return launch(kern, dim3(o.grid), kWave, p.fwd.lds, st, ka, (const int *)ka.dense_flag); };
     hipError_t e = hipSuccess;
     if constexpr (M == 6 && !GENERIC) {
-        if (ka.wave && !ka.only) {  // NewCaseEKFEstimatorWithOptimalNPI, one wavefront per chain (monitor always inline)
-            const size_t wshm = (size_t)6 * ka.L * sizeof(double);
-            if (ka.L == 21) hipLaunchKernelGGL((ekf_fwd_wave<0, 1, 21, 0>), dim3((unsigned)ka.cn), dim3(kWave), wshm, st, ka, (const int *)nullptr);
-            else hipLaunchKernelGGL((ekf_fwd_wave<0, 1, 0, 0>), dim3((unsigned)ka.cn), dim3(kWave), wshm, st, ka, (const int *)nullptr);
-            return hipGetLastError();
+        if (p.fwd.kernel == FWD_WAVE_NC) e = (v & V_L21) ? go(ekf_fwd_wave<0, 1, 21, 0>) : go(ekf_fwd_wave<0, 1, 0, 0>);
+    }
+    if constexpr (M == 6 && GENERIC) {
+        if (p.fwd.kernel == FWD_WAVE)
+            e = !(v & V_INLINE) ? go(ekf_fwd_wave<FLIP, 0>) : (v & V_L21) ? go(ekf_fwd_wave<FLIP, 1, 21>) : go(ekf_fwd_wave<FLIP, 1, 0>);
+        if (p.fwd.kernel == FWD_HEX)
+            e = (v & V_BLK) ? ((v & V_SOLO) ? go(ekf_fwd_hex<FLIP, kHG, 1>) : go(ekf_fwd_hex<FLIP, kHG, 0>))
+                            : ((v & V_SOLO) ? go(ekf_fwd_hex<FLIP, 0, 1>) : go(ekf_fwd_hex<FLIP, 0, 0>));
+        if (p.fwd.kernel == FWD_QUAD) {
+            if (v & V_INLINE) e = (v & V_BLK) ? go(ekf_fwd_quad<FLIP, kQC, 21, 1, 0>) : go(ekf_fwd_quad<FLIP, 0, 0, 1, 0>);
+            else if (v & V_SOLO) e = (v & V_BLK) ? go(ekf_fwd_quad<FLIP, kQC, 21, 0, 1>) : go(ekf_fwd_quad<FLIP, 0, 0, 0, 1>);
+            else e = (v & V_BLK) ? go(ekf_fwd_quad<FLIP, kQC, 21, 0, 0>) : go(ekf_fwd_quad<FLIP, 0, 0, 0, 0>);
         }
     }
-    if (run_sym) {
-        bool done = false;
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.wave) {          // one wavefront per chain (ekf_wave.hpp); with a scalar R_v the monitor runs inline
-                if (ka.mon_hoist) hipLaunchKernelGGL((ekf_fwd_wave<FLIP, 0>), dim3((unsigned)ka.cn), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else if (ka.L == 21) hipLaunchKernelGGL((ekf_fwd_wave<FLIP, 1, 21>), dim3((unsigned)ka.cn), dim3(kWave), (size_t)6 * ka.L * sizeof(double), st, ka, ka.dense_flag);
-                else hipLaunchKernelGGL((ekf_fwd_wave<FLIP, 1, 0>), dim3((unsigned)ka.cn), dim3(kWave), (size_t)6 * ka.L * sizeof(double), st, ka, ka.dense_flag);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                done = true;
-            }
-        }
-        if constexpr (M == 3 && GENERIC) {
-            if (ka.wave) {          // seven chains per wavefront, nine lanes each
-                hipLaunchKernelGGL((ekf_fwd_wave3<FLIP>), dim3((unsigned)((ka.cn + kW3G - 1) / kW3G)), dim3(kWave), 0, st, ka, ka.dense_flag);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                done = true;
-            }
-        }
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.hex && !done) {  // six lanes per chain, ten chains per wavefront (ekf_hex.hpp)
-                const unsigned hblocks = (unsigned)((ka.cn + kHG - 1) / kHG);
-                const bool solo = (long)hblocks <= (long)simd_count(L.dev);   // every wave can have a SIMD of its own: keep it that way
-                if (ka.blk == kHG) {
-                    if (solo) hipLaunchKernelGGL((ekf_fwd_hex<FLIP, kHG, 1>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                    else hipLaunchKernelGGL((ekf_fwd_hex<FLIP, kHG, 0>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                } else {
-                    if (solo) hipLaunchKernelGGL((ekf_fwd_hex<FLIP, 0, 1>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                    else hipLaunchKernelGGL((ekf_fwd_hex<FLIP, 0, 0>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                }
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                done = true;
-            }
-        }
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.quad && !done) {
-                // four lanes per chain, 16 chains per wavefront (ekf_quad.hpp): the specialisation for the layout and the
-                // window length this shape is meant for, or the general one
-                const int qblocks = (ka.cn + kQC - 1) / kQC;
-                const size_t qshm = ((size_t)(ka.mon_hoist ? 0 : 6 * ka.L) + kNpi) * kQC * sizeof(double);
-                const bool fast = ka.blk == kQC && ka.L == 21;
-                const bool solo = qblocks <= simd_count(L.dev);   // every wave can have a SIMD of its own: keep it that way
-                auto go = [&](auto kern) -> hipError_t {
-                    if (qshm > 64u * 1024u) {      // inline monitor with a long window: above the default dynamic-LDS limit
-                        const hipError_t ea = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qshm);
-                        if (ea != hipSuccess) return ea;
-                    }
-                    hipLaunchKernelGGL(kern, dim3(qblocks), dim3(kWave), qshm, st, ka, ka.dense_flag);
-                    return hipGetLastError();
-                };
-                if (ka.mon_hoist) {
-                    if (solo) e = fast ? go(ekf_fwd_quad<FLIP, kQC, 21, 0, 1>) : go(ekf_fwd_quad<FLIP, 0, 0, 0, 1>);
-                    else e = fast ? go(ekf_fwd_quad<FLIP, kQC, 21, 0, 0>) : go(ekf_fwd_quad<FLIP, 0, 0, 0, 0>);
-                } else {
-                    e = fast ? go(ekf_fwd_quad<FLIP, kQC, 21, 1, 0>) : go(ekf_fwd_quad<FLIP, 0, 0, 1, 0>);
-                }
-                if (e != hipSuccess) return e;
-                done = true;
-            }
-        }
-        if (!done) {
-            // narrow (balanced) waves: the variant with LDS-resident model constants and LDS sized by 40 lanes -- 298
-            // instead of 408 VGPRs (a third of the AGPR traffic), still four workgroups per CU
-            const size_t per_lane = ((size_t)3 * ka.L + 4 * kNpi) * sizeof(double);
-            const bool lp = M == 6 && ka.lw <= kPipeLanes && per_lane * kPipeLanes * 4 <= 160u * 1024u;
-            if (ka.mon_hoist) {         // no windows in LDS: only the LP variant's model vectors
-                const size_t lp_shm = (size_t)4 * kNpi * kPipeLanes * sizeof(double);
-                // (Measured and not adopted, round 5: a 3-state forward kernel with a, u_max in LDS and a day's controls consumed on
-                // arrival -- 166 registers, THREE clean waves per SIMD -- took 11.4-11.8 ms on BASELINE config 5 against 8.8-9.5 for the
-                // 224-register kernel at two: the 24 LDS reads a day on the alpha map's dependent chain cost more than the third wave
-                // returns, profiles/r05/ab_cfg5_three_waves.txt.)
-                if (ka.stor) hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 0, 1, 0>), dim3(blocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else if (lp && M == 6 && ka.ws_upper == 3)     // reduced outputs: the variant that fits two waves per SIMD (USD)
-                    hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 1, 0, 0, 1>), dim3(blocks), dim3(kWave), lp_shm, st, ka, ka.dense_flag);
-                else if (lp) hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 1, 0, 0>), dim3(blocks), dim3(kWave), lp_shm, st, ka, ka.dense_flag);
-                else hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 0, 0, 0>), dim3(blocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-            } else if (ka.stor) hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 0, 1>), dim3(blocks), dim3(kWave), shmem, st, ka, ka.dense_flag);
-            else if (lp) {
-                const size_t shm = per_lane * kPipeLanes;
-                if (shm > 64u * 1024u &&
-                    (e = hipFuncSetAttribute((const void *)ekf_fwd_sym<M, FLIP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess)
-                    return e;
-                hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 1>), dim3(blocks), dim3(kWave), shm, st, ka, ka.dense_flag);
-            } else hipLaunchKernelGGL((ekf_fwd_sym<M, FLIP, 0>), dim3(blocks), dim3(kWave), shmem, st, ka, ka.dense_flag);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+    if constexpr (M == 3 && GENERIC) {
+        if (p.fwd.kernel == FWD_WAVE3) e = go(ekf_fwd_wave3<FLIP>);
+    }
+    if constexpr (GENERIC) {
+        if (p.fwd.kernel == FWD_SYM) {
+            if (v & V_INLINE) e = (v & V_STOR) ? go(ekf_fwd_sym<M, FLIP, 0, 1>) : (v & V_LP) ? go(ekf_fwd_sym<M, FLIP, 1>) : go(ekf_fwd_sym<M, FLIP, 0>);
+            else if (v & V_STOR) e = go(ekf_fwd_sym<M, FLIP, 0, 1, 0>);
+            else if (v & V_USD) e = go(ekf_fwd_sym<M, FLIP, 1, 0, 0, 1>);
+            else e = (v & V_LP) ? go(ekf_fwd_sym<M, FLIP, 1, 0, 0>) : go(ekf_fwd_sym<M, FLIP, 0, 0, 0>);
         }
     }
-    if (run_dense) {
-        hipLaunchKernelGGL((ekf_fwd<M, FLIP, GENERIC>), dim3(blocks), dim3(kWave), shmem, st, ka);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess && p.dense) e = launch(ekf_fwd<M, FLIP, GENERIC>, dim3(o.dense_grid), kWave, p.dense_lds, st, ka);
     return e;
 }
 
-// X = pinv(P(j|j-1)) for the `nsteps` array positions from pinv_pos0 + step0 on, all chains
+// X = pinv(P(j|j-1)) for the o.b array positions from pinv_pos0 + o.a on
 template <int M>
-static hipError_t enqueue_pinv(KArgs ka, int step0, int nsteps, hipStream_t st, int c0 = 0, int cn = -1)
+static hipError_t enqueue_pinv(KArgs ka, const PlanOp &o, hipStream_t st)
 {
-    if (nsteps <= 0) return hipSuccess;
-    ka.c0 = 0; ka.cn = ka.B; ka.pinv_step0 = step0;
-    if (cn >= 0) { ka.c0 = c0; ka.cn = cn; }
-    // x extent rounded up to a multiple of 8: the kernel re-orders its tiles so that every XCD gets a contiguous eighth per step
-    unsigned tiles = (unsigned)((ka.cn + pinv_wg<M>() - 1) / pinv_wg<M>());
-    if (ka.only && tiles > 8u) tiles = 8u;      // the second pass of exact_nonfinite walks the list of marked chains (see eks_pinv)
-    if (ka.only) hipLaunchKernelGGL((eks_pinv<M, 1>), dim3(tiles >= 8u ? ((tiles + 7u) & ~7u) : tiles, (unsigned)nsteps), dim3(pinv_wg<M>()), 0, st, ka);
-    else hipLaunchKernelGGL((eks_pinv<M, 0>), dim3(tiles >= 8u ? ((tiles + 7u) & ~7u) : tiles, (unsigned)nsteps), dim3(pinv_wg<M>()), 0, st, ka);
-    return hipGetLastError();
+    ka.c0 = o.c0; ka.cn = o.cn; ka.pinv_step0 = o.a;
+    const dim3 grid(o.grid, (unsigned)o.b);
+    return ka.only ? launch(eks_pinv<M, 1>, grid, pinv_wg<M>(), 0, st, ka) : launch(eks_pinv<M, 0>, grid, pinv_wg<M>(), 0, st, ka);
 }
 
-// backward recursion over smoother steps ka.bk_from ... ka.bk_to (the dense kernels only know the full range)
-// (c0, cn: a chain range -- a multiple of the chains one wave of the shape holds: the layout block of the fixed-descriptor one-lane
-// smoother, ten chains in the hex shape)
+// backward recursion over smoother steps o.a ... o.b (the dense kernels only know the full range) of the chains [o.c0, o.c0 + o.cn)
 template <int M, int FLIP, int GENERIC>
-static hipError_t enqueue_bwd(KArgs ka, const Launch &L, hipStream_t st, int c0 = 0, int cn = -1)
+static hipError_t enqueue_bwd(KArgs ka, const LaunchPlan &p, const PlanOp &o, hipStream_t st)
 {
-    ka.c0 = 0; ka.cn = ka.B;
-    ka.lw = balanced_lanes(ka.B, M == 6 ? 1 : 2, L.dev);
-    if (cn >= 0) { ka.c0 = c0; ka.cn = cn; }      // a chain range: a multiple of the chains a wave of the shape holds
-    const int blocks = (ka.cn + ka.lw - 1) / ka.lw;
-    const bool run_sym = GENERIC && L.hint != 2, run_dense = !GENERIC || L.hint != 1;
+    ka.bk_from = o.a; ka.bk_to = o.b; ka.c0 = o.c0; ka.cn = o.cn;
+    const unsigned v = p.bwd.bits;
+    auto go = [&](auto kern) { return launch(kern, dim3(o.grid), kWave, 0, st, ka, (const int *)ka.dense_flag); };
     hipError_t e = hipSuccess;
     if constexpr (M == 6 && !GENERIC) {
-        if (ka.wave && !ka.only) {
-            hipLaunchKernelGGL(eks_bwd_wave_nc, dim3((unsigned)ka.cn), dim3(kWave), 0, st, ka);
-            return hipGetLastError();
-        }
+        if (p.bwd.kernel == BWD_WAVE_NC) e = launch(eks_bwd_wave_nc, dim3(o.grid), kWave, 0, st, ka);
     }
-    if (run_sym) {
-        bool done = false;
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.wave) {
-                hipLaunchKernelGGL((eks_bwd_wave<FLIP>), dim3((unsigned)ka.cn), dim3(kWave), 0, st, ka, ka.dense_flag);
-                done = true;
-            }
-        }
-        if constexpr (M == 3 && GENERIC) {
-            if (ka.wave) {
-                hipLaunchKernelGGL((eks_bwd_wave3<FLIP>), dim3((unsigned)((ka.cn + kW3G - 1) / kW3G)), dim3(kWave), 0, st, ka, ka.dense_flag);
-                done = true;
-            }
-        }
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.hex && !done) {
-                const unsigned hblocks = (unsigned)((ka.cn + kHG - 1) / kHG);
-                const bool pf = (long)hblocks <= (long)simd_count(L.dev);      // one wave per SIMD: prefetch; beyond: two waves per SIMD
-                if (ka.blk == kHG) {
-                    if (pf) hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 2>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                    else hipLaunchKernelGGL((eks_bwd_hex<FLIP, kHG, 0>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                } else {
-                    if (pf) hipLaunchKernelGGL((eks_bwd_hex<FLIP, 0, 1>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                    else hipLaunchKernelGGL((eks_bwd_hex<FLIP, 0, 0>), dim3(hblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                }
-                done = true;
-            }
-        }
-        if constexpr (M == 6 && GENERIC) {
-            if (ka.quad && !done) {
-                const int qblocks = (ka.cn + kQC - 1) / kQC;
-                if (ka.blk == kQC) hipLaunchKernelGGL((eks_bwd_quad<FLIP, kQC>), dim3(qblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else hipLaunchKernelGGL((eks_bwd_quad<FLIP, 0>), dim3(qblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                done = true;
-            }
-        }
-        if constexpr (M == 6 && GENERIC) {
-            // one lane per chain with fixed descriptors per addressing window (ekf_lane6.hpp): the layout block must be the
-            // lanes a workgroup uses, and a compile-time constant
-            // (not for 64-chain blocks: four workgroups' LDS columns would not fit a CU, and where three suffice -- one round of 64-lane
-            // waves, the N = 2 shard of the headline sweep: 37 500 chains -- the kernel measured 3.84 against eks_bwd_sym's 3.5 ms:
-            // such a batch is not issue-bound, profiles/r06/ab_n2_shard.txt)
-            const bool l6_ok = lane6_block(ka.blk);
-            if (!done && !ka.stor && l6_ok && (long)ka.blk * ka.nblk <= (1L << 20)) {
-                const int lblocks = (ka.cn + ka.blk - 1) / ka.blk;
-                // (X by LDS-DMA where every lane of the launch is alive, see eks_bwd_lane6)
-                if (ka.blk == 40 && ka.cn % 40 == 0) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, 1>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else if (ka.blk == 40) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 40, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else if (ka.blk == 48) hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 48, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                else hipLaunchKernelGGL((eks_bwd_lane6<FLIP, 56, 0>), dim3(lblocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-                done = true;
-            }
-        }
-        if (!done) {
-            if (ka.stor) hipLaunchKernelGGL((eks_bwd_sym<M, FLIP, 1>), dim3(blocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-            else hipLaunchKernelGGL((eks_bwd_sym<M, FLIP>), dim3(blocks), dim3(kWave), 0, st, ka, ka.dense_flag);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+    if constexpr (M == 6 && GENERIC) {
+        if (p.bwd.kernel == BWD_WAVE) e = go(eks_bwd_wave<FLIP>);
+        if (p.bwd.kernel == BWD_HEX)
+            e = (v & V_BLK) ? ((v & V_SOLO) ? go(eks_bwd_hex<FLIP, kHG, 2>) : go(eks_bwd_hex<FLIP, kHG, 0>))
+                            : ((v & V_SOLO) ? go(eks_bwd_hex<FLIP, 0, 1>) : go(eks_bwd_hex<FLIP, 0, 0>));
+        if (p.bwd.kernel == BWD_QUAD) e = (v & V_BLK) ? go(eks_bwd_quad<FLIP, kQC>) : go(eks_bwd_quad<FLIP, 0>);
+        if (p.bwd.kernel == BWD_LANE6)
+            e = p.bwd.wg_chains == 40 ? (o.xd ? go(eks_bwd_lane6<FLIP, 40, 1>) : go(eks_bwd_lane6<FLIP, 40, 0>))
+                                      : (p.bwd.wg_chains == 48 ? go(eks_bwd_lane6<FLIP, 48, 0>) : go(eks_bwd_lane6<FLIP, 56, 0>));
     }
-    if (run_dense) {
-        hipLaunchKernelGGL((eks_bwd<M, FLIP, GENERIC>), dim3(blocks), dim3(kWave), 0, st, ka);
-        e = hipGetLastError();
+    if constexpr (M == 3 && GENERIC) {
+        if (p.bwd.kernel == BWD_WAVE3) e = go(eks_bwd_wave3<FLIP>);
     }
+    if constexpr (GENERIC) {
+        if (p.bwd.kernel == BWD_SYM) e = (v & V_STOR) ? go(eks_bwd_sym<M, FLIP, 1>) : go(eks_bwd_sym<M, FLIP>);
+    }
+    if (e == hipSuccess && p.dense) e = launch(eks_bwd<M, FLIP, GENERIC>, dim3(o.dense_grid), kWave, 0, st, ka);
     return e;
 }
 
@@ -1404,13 +1166,28 @@ static hipError_t enqueue_tail(const KArgs &ka, const Tail &t, hipStream_t st, c
     return hipGetLastError();
 }
 
-// Forward pass in time segments (percent of T where each ends).  pinv(P(k|k-1)) needs nothing but the forward pass's
-// output of day k and the smoother consumes X in REVERSE time order, so only the pinv grid of the last segment stands
-// between the end of the forward pass and the start of the smoother: the last segments are short.
-// (re-measured in round 3 with the cheaper pinv: four segments ending at 50 / 85 / 97 / 100 % give 3.06-3.11 ms against
-// 3.12-3.16 for five ending at 40 / 70 / 90 / 98 / 100 % at 9 375 chains, level at 18 750: profiles/r03/time_cuts.txt)
-constexpr int kTimeCuts[] = {0, 50, 85, 97, 100};
-constexpr int kTimeSeg = (int)(sizeof(kTimeCuts) / sizeof(kTimeCuts[0])) - 1;
+// the plan's operations in the plan's order; `h` is the leased helper stream when the plan asks for one
+template <int M, int FLIP, int GENERIC>
+static hipError_t run_plan(const KArgs &ka, const LaunchPlan &p, const Tail *tail, hipStream_t st, Helper *h)
+{
+    if (p.overflow || (p.helper && !h)) return hipErrorInvalidValue;
+    for (int i = 0; i < p.n_ops; i++) {
+        const PlanOp &o = p.ops[i];
+        hipStream_t s = o.stream == ON_HELPER ? h->stream : st;
+        hipError_t e = hipSuccess;
+        switch (o.kind) {
+        case OP_FWD: e = enqueue_fwd<M, FLIP, GENERIC>(ka, p, o, s); break;
+        case OP_PINV: e = enqueue_pinv<M>(ka, o, s); break;
+        case OP_BWD: e = enqueue_bwd<M, FLIP, GENERIC>(ka, p, o, s); break;
+        case OP_MONITOR: e = launch_monitor<FLIP>(ka, p, s); break;
+        case OP_TAIL: e = enqueue_tail(ka, *tail, s); break;
+        case OP_RECORD: e = hipEventRecord(h->ev[o.a], s); break;
+        case OP_WAIT: e = hipStreamWaitEvent(s, h->ev[o.a], 0); break;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 // epi_batch_desc.exact_nonfinite.  The packed / quad kernels skip products with structural zeros, which is exact for finite
 // operands; once a chain's covariance has overflowed, a skipped `Inf * 0` leaves a finite number where the dense evaluation
@@ -1420,254 +1197,48 @@ constexpr int kTimeSeg = (int)(sizeof(kTimeCuts) / sizeof(kTimeCuts[0])) - 1;
 // the scoring tail is repeated if any chain was re-run.  Costs three launches that return at once when no chain is marked
 // (the pinv grid's ~(B/64)(T-1) empty workgroups: ~0.15 ms at 75 000 x 520).
 template <int M, int FLIP>
-static hipError_t rerun_nonfinite_dense(const KArgs &ka, const Launch &L, hipStream_t st)
+static hipError_t rerun_nonfinite_dense(const KArgs &ka, const PlanIn &in, const Tail *tail, hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(ka.only_buf + ka.B, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mark_nonfinite, dim3((ka.B + 255) / 256), dim3(256), 0, st, (const int32_t *)ka.status, ka.only_buf, ka.B);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    PlanIn ind = in;
+    ind.hint = 2; ind.only = true; ind.smooth = true; ind.rerun = false; ind.has_tail = false;
+    const LaunchPlan pd = plan_launch(ind);
     KArgs kd = ka;
-    kd.only = ka.only_buf; kd.dense_flag = nullptr; kd.quad = 0; kd.hex = 0; kd.mon_hoist = 0;
-    kd.k_begin = 0; kd.k_end = 0; kd.bk_from = ka.T - 2; kd.bk_to = 0;
-    Launch Ld = L;
-    Ld.hint = 2; Ld.tail = nullptr;
-    if ((e = enqueue_fwd<M, FLIP, 1>(kd, Ld, st)) != hipSuccess) return e;
-    if ((e = enqueue_pinv<M>(kd, 0, ka.T - 1, st)) != hipSuccess) return e;
-    if ((e = enqueue_bwd<M, FLIP, 1>(kd, Ld, st)) != hipSuccess) return e;
-    if (L.tail) e = enqueue_tail(ka, *L.tail, st, ka.only_buf + ka.B);
+    kd.only = ka.only_buf; kd.dense_flag = nullptr; kd.quad = pd.quad; kd.hex = pd.hex; kd.mon_hoist = pd.mon_hoist;
+    if ((e = run_plan<M, FLIP, 1>(kd, pd, nullptr, st, nullptr)) != hipSuccess) return e;
+    if (tail) e = enqueue_tail(ka, *tail, st, ka.only_buf + ka.B);
     return e;
 }
 
 template <int M, int FLIP, int GENERIC>
-static hipError_t launch_chain(const KArgs &ka, const Launch &L, hipStream_t st)
+static hipError_t launch_chain(const KArgs &ka, const PlanIn &in, const LaunchPlan &p, const Tail *tail, int dev, hipStream_t st)
 {
-    const size_t shmem = (size_t)3 * ka.L * kWave * sizeof(double);
-    const int T = ka.T, phase = L.phase;
     hipError_t e = hipSuccess;
-    if (phase == 0 || phase == 1) {
-        if (shmem > 64u * 1024u) {   // above the default dynamic-LDS limit
-            e = hipFuncSetAttribute((const void *)ekf_fwd<M, FLIP, GENERIC>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            if (e != hipSuccess) return e;
-            if (GENERIC) {
-                e = hipFuncSetAttribute((const void *)ekf_fwd_sym<M, FLIP, 0>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                if (e != hipSuccess) return e;
-                e = hipFuncSetAttribute((const void *)ekf_fwd_sym<M, FLIP, 0, 1>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                if (e != hipSuccess) return e;
-            }
-        }
-        if (GENERIC) {
-            // hint 0: fast path unless ekf_precheck finds a non-symmetric Ps_init / non-diagonal Q_w in the batch;
-            // hint 1 / 2: the caller decided; the flag the kernels test is set accordingly
-            if ((e = hipMemsetAsync(ka.dense_flag, 0, sizeof(int), st)) != hipSuccess) return e;
-            if (L.hint == 0) {
-                hipLaunchKernelGGL((ekf_precheck<M>), dim3((ka.B + 255) / 256), dim3(256), 0, st, ka, ka.dense_flag, 0);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-            } else if (L.hint == 2) {
-                hipLaunchKernelGGL((ekf_precheck<M>), dim3(1), dim3(64), 0, st, ka, ka.dense_flag, 1);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-            }
-        }
+    if (p.precheck >= 0) {
+        if ((e = hipMemsetAsync(ka.dense_flag, 0, sizeof(int), st)) != hipSuccess) return e;
+        if (p.precheck == 1) hipLaunchKernelGGL((ekf_precheck<M>), dim3((ka.B + 255) / 256), dim3(256), 0, st, ka, ka.dense_flag, 0);
+        if (p.precheck == 2) hipLaunchKernelGGL((ekf_precheck<M>), dim3(1), dim3(64), 0, st, ka, ka.dense_flag, 1);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    // smoother positions of filter steps 2..T (array positions 1..T-1, or 0..T-2 for the time-flipped models)
-    const bool overlap = GENERIC && phase == 0 && L.smooth && L.hint == 1;
-    if (!overlap) {
-        // one stage after the other on the caller's stream (single stages for per-kernel timing, the forward pass alone,
-        // batches that may take the dense kernels, the NewCase models)
-        if (phase == 0 || phase == 1) {
-            if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st)) != hipSuccess) return e;
-            if (GENERIC && L.hint != 2 && (e = launch_monitor<FLIP>(ka, L.dev, st)) != hipSuccess) return e;
-        }
-        if (!L.smooth) return e;
-        if (GENERIC && (phase == 0 || phase == 2 || phase == 3) && (e = enqueue_pinv<M>(ka, 0, T - 1, st)) != hipSuccess) return e;
-        if (phase == 0 || phase == 2 || phase == 4) {
-            if ((e = enqueue_bwd<M, FLIP, GENERIC>(ka, L, st)) != hipSuccess) return e;
-        }
-        if (phase == 0 && L.tail) e = enqueue_tail(ka, *L.tail, st);
-        if constexpr (GENERIC) {
-            if (e == hipSuccess && L.rerun && phase == 0 && L.hint != 2) e = rerun_nonfinite_dense<M, FLIP>(ka, L, st);
-        }
-        return e;
-    }
-
-    // A full call on the packed kernels.  What does not lie on the critical path runs on a helper stream:
-    //   * the innovation monitor (needs the forward pass only) beside the pinv grid and the smoother;
-    //   * pipelined in TIME: a batch that does not fill the chip (the shards of the sweep on 2, 4, 8 GPUs) leaves SIMDs idle
-    //     while its sequential forward waves crawl through the T days.  The forward kernel then runs in kTimeSeg launches (a
-    //     later segment resumes from the S_MINUS / P_MINUS the previous one stored: same bits), and after each of them the
-    //     eks_pinv grid of ITS days starts on the helper stream, beside the next forward segment.  Not for a batch that
-    //     fills the chip (nothing idles: measured level, round 1);
-    //   * the sweep's scoring tail: the horizon's u_opt_smooth is final after the smoother's first T - 1 - t_hist steps,
-    //     so the recursion is cut there and scoring + Pareto filter run beside the rest of it.
-    HelperLease lease(L.dev);
-    {
+    HelperLease lease(dev);
+    if (p.helper) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();    // the legacy default stream cannot be queried while another stream captures
         lease.captured = cs != hipStreamCaptureStatusNone;
+        if ((e = helper_acquire(dev, &lease.h)) != hipSuccess) return e;
     }
-    if ((e = helper_acquire(L.dev, &lease.h)) != hipSuccess) return e;
-    Helper *h = lease.h;
-    int ne = 0;
-    auto fork = [&](hipStream_t from, hipStream_t to) -> hipError_t {     // `to` continues after what `from` holds now
-        hipError_t ee = hipEventRecord(h->ev[ne], from);
-        if (ee == hipSuccess) ee = hipStreamWaitEvent(to, h->ev[ne], 0);
-        ne++;
-        return ee;
-    };
-    const long fwd_waves = ka.hex ? ((long)ka.B + kHG - 1) / kHG : ka.quad ? ((long)ka.B + kQC - 1) / kQC : ((long)ka.B + kWave - 1) / kWave;
-    // (one wavefront per chain: the pinv grid of so few chains takes ~30 us, nothing to pipeline -- unless asked for)
-    const bool force_split = (L.test_flags >> 2) & 1;                                                      // test hook
-    const bool force_rp = (L.test_flags & 1) && ka.hex && ka.mon_hoist && T >= 4 && L.time_pipe >= 0;      // test hook
-    const bool tp = !force_rp && ka.mon_hoist && !ka.stor && T >= 128 && L.time_pipe >= 0 &&
-                    (L.time_pipe == 1 || (!ka.wave && fwd_waves * 4 <= (long)simd_count(L.dev) * 3));
-    bool helper_busy = false;
-    // Pipelined in REVERSE time (round 5, the hex shape): the smoother consumes X = pinv(P(k+1|k)) from the last day backwards, so
-    // only the pinv grid of the LAST days has to stand between the forward kernel and the smoother; the grids of the earlier days
-    // run on the helper stream beside the smoother's first launches, and the smoother is cut where they end (the hand-over rows of
-    // the horizon / observed-days split).  Beside the FORWARD kernel a pinv grid takes exactly what it saves (both want the vector
-    // unit: forward segments 1.07 -> 1.50 ms); the smoother of this shape waits on memory most of the time.
-    const bool rp = force_rp || (!tp && ka.hex && ka.mon_hoist && T >= 128 && L.time_pipe >= 0);
-    // (Round 6, measured and not adopted: the hex shape beyond one wavefront per SIMD -- 10 241 .. 20 480 chains, the shard of the headline
-    // sweep on one of 4 GPUs -- as TWO chain ranges through the one-wave-per-SIMD kernels, pipelined across the ranges (the pinv grid of
-    // the first beside the forward kernel of the second, the grid of the second beside the smoother of the first) instead of the
-    // two-waves-per-SIMD kernels pipelined in reverse time: 5.20-5.28 against 4.58-4.80 ms at 18 750 chains, 3.75-3.80 against 3.06-3.09 at
-    // 10 375 -- profiles/r06/ab_hex_rounds.txt.)
-    if (rp) {
-        if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st)) != hipSuccess) return e;
-        if ((e = fork(st, h->stream)) != hipSuccess) return e;
-        helper_busy = true;
-        // smoother steps k = T-2 ... 0 in segments [hi, lo], descending: the horizon first when there is a scoring tail, the rest in
-        // three parts; segment s needs X of filter steps lo+1 ... hi+1
-        int seg_hi[8], seg_lo[8], ns = 0, tail_seg = -1;
-        int top = T - 2;
-        constexpr int kRpParts = 3;
-        if (L.tail && L.tail->t_hist >= 1 && L.tail->t_hist <= T - 2) {
-            seg_hi[ns] = top; seg_lo[ns] = L.tail->t_hist; tail_seg = ns; ns++;
-            top = L.tail->t_hist - 1;
-        }
-        const int parts = (top + 1 >= 96 || (force_rp && top + 1 >= 6)) ? kRpParts : 1;
-        for (int q = 0; q < parts; q++) {
-            const int lo = (int)((long)(top + 1) * (parts - 1 - q) / parts);
-            seg_hi[ns] = top; seg_lo[ns] = lo; ns++;
-            top = lo - 1;
-        }
-        hipEvent_t ev_pinv[8];
-        for (int sgm = 0; sgm < ns; sgm++) {
-            const int j_lo = seg_lo[sgm] + 1, j_hi = seg_hi[sgm] + 1;
-            hipStream_t ps = sgm == 0 ? st : h->stream;
-            if ((e = enqueue_pinv<M>(ka, FLIP ? (T - 1 - j_hi) : (j_lo - 1), j_hi - j_lo + 1, ps)) != hipSuccess) return e;
-            if (sgm > 0) {
-                ev_pinv[sgm] = h->ev[ne++];
-                if ((e = hipEventRecord(ev_pinv[sgm], h->stream)) != hipSuccess) return e;
-            }
-        }
-        for (int sgm = 0; sgm < ns; sgm++) {
-            if (sgm > 0 && (e = hipStreamWaitEvent(st, ev_pinv[sgm], 0)) != hipSuccess) return e;
-            KArgs kb = ka;
-            kb.bk_from = seg_hi[sgm]; kb.bk_to = seg_lo[sgm];
-            if ((e = enqueue_bwd<M, FLIP, GENERIC>(kb, L, st)) != hipSuccess) return e;
-            if (sgm == tail_seg) {              // the horizon's u_opt_smooth is final: scoring + Pareto filter behind the helper's pinv grids
-                if ((e = fork(st, h->stream)) != hipSuccess) return e;
-                if ((e = enqueue_tail(ka, *L.tail, h->stream)) != hipSuccess) return e;
-            }
-        }
-        if (L.tail && tail_seg < 0 && (e = enqueue_tail(ka, *L.tail, st)) != hipSuccess) return e;
-        if (ka.rho || ka.f.rho) {
-            if ((e = launch_monitor<FLIP>(ka, L.dev, h->stream)) != hipSuccess) return e;
-        }
-    } else {
-    if (tp) {
-        for (int sg = 0; sg < kTimeSeg; sg++) {
-            KArgs kc = ka;
-            kc.k_begin = (int)((long)T * kTimeCuts[sg] / 100);
-            kc.k_end = (sg == kTimeSeg - 1) ? T : (int)((long)T * kTimeCuts[sg + 1] / 100);
-            if (kc.k_end <= kc.k_begin) continue;
-            if ((e = enqueue_fwd<M, FLIP, GENERIC>(kc, L, st)) != hipSuccess) return e;
-            if ((e = fork(st, h->stream)) != hipSuccess) return e;
-            // filter steps whose P(j|j-1) exists now and has not been inverted yet: j_lo .. j_hi (the smoother needs
-            // j = 1 .. T-1); array position of step j: j, or T-1-j for the time-flipped models
-            const int j_lo = kc.k_begin + 1, j_hi = (kc.k_end < T) ? kc.k_end : T - 1;
-            if ((e = enqueue_pinv<M>(ka, FLIP ? (T - 1 - j_hi) : (j_lo - 1), j_hi - j_lo + 1, h->stream)) != hipSuccess) return e;
-        }
-        if ((e = fork(h->stream, st)) != hipSuccess) return e;       // the smoother needs every pinv grid
-        helper_busy = true;
-    } else {
-        // A one-lane batch that runs in ROUNDS of resident waves (more waves than SIMDs: the headline sweep): the chains of the forward
-        // kernel's first round and the rest are two launches, and the pinv grid of the first range runs on the helper stream beside
-        // the forward kernel of the second (whose 851 waves leave SIMDs and registers free at 75 000 chains; the forward kernel is
-        // bound by its stores, the grid by the vector unit): 0.15 ms of the grid's 3.0 hidden (profiles/r06/ab_pinv_beside_fwd.txt).
-        // epi_batch_desc.test_flags bit 2 cuts ANY one-lane batch of two waves or more in the middle the same way (test hook).
-        const int lwf = balanced_lanes(ka.B, M == 6 ? 1 : 2, L.dev);
-        const long wavesf = ((long)ka.B + lwf - 1) / lwf;
-        const int cA = force_split ? (int)(wavesf / 2) * lwf : simd_count(L.dev) * lwf;
-        // (not when neither P(k|k-1) nor P(k|k) is an output: that forward kernel fits TWO waves per SIMD and the headline's 1 875 are
-        // resident at once -- cut in two launches it took 1.1 ms longer, bench_cfg4_reduced 13.6 -> 14.7 ms)
-        if (M == 6 && GENERIC && !ka.hex && !ka.quad && !ka.wave && !ka.only && L.hint != 2 && cA > 0 && cA < ka.B &&
-            (force_split || (lwf < kWave && ka.ws_upper != 3))) {
-            if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st, 0, cA)) != hipSuccess) return e;
-            if ((e = fork(st, h->stream)) != hipSuccess) return e;
-            if ((e = enqueue_pinv<M>(ka, 0, T - 1, h->stream, 0, cA)) != hipSuccess) return e;
-            if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st, cA, ka.B - cA)) != hipSuccess) return e;
-            if (ka.mon_hoist && (ka.rho || ka.f.rho) && (e = fork(st, h->stream)) != hipSuccess) return e;
-            if ((e = enqueue_pinv<M>(ka, 0, T - 1, st, cA, ka.B - cA)) != hipSuccess) return e;     // beside the tail of the first range's grid
-            if ((e = fork(h->stream, st)) != hipSuccess) return e;
-        } else {
-        if ((e = enqueue_fwd<M, FLIP, GENERIC>(ka, L, st)) != hipSuccess) return e;
-        if (ka.mon_hoist && (ka.rho || ka.f.rho) && (e = fork(st, h->stream)) != hipSuccess) return e;
-        if ((e = enqueue_pinv<M>(ka, 0, T - 1, st)) != hipSuccess) return e;
-        }
-    }
-    // A one-lane batch that runs in ROUNDS (more 64-chain waves than SIMDs: the headline sweep) on the fixed-descriptor smoother:
-    // the chains of the smoother's first round of resident waves and the rest are two launches, and the monitor starts between
-    // them -- beside the second launch, whose waves leave SIMDs free (851 waves on 1 024 SIMDs at 75 000 chains), instead of
-    // beside the pinv grid, which is bound by the vector unit and simply takes 0.44 ms longer with the monitor next to it.
-    const bool in_rounds = !ka.hex && !ka.quad && !ka.wave && fwd_waves > (long)simd_count(L.dev);
-    bool mon_late = false;
-    int first_round = 0;
-    if constexpr (M == 6 && GENERIC) {
-        const bool cut = force_split && !ka.hex && !ka.quad && !ka.wave && ka.nblk >= 2;        // test hook: the two launches at any size
-        // (a first launch of 1 004 / 984 / 964 / 944 waves instead of the 1 024 that are resident at once: level, 14.41-14.88 ms per pass
-        // whatever the cut; the monitor ahead of the first launch instead of between the two: +0.15 ms -- profiles/r06/ab_bwd_balance*.txt)
-        first_round = cut ? (ka.nblk / 2) * ka.blk : simd_count(L.dev) * ka.blk;
-        mon_late = !tp && (in_rounds || cut) && !ka.stor && lane6_block(ka.blk) && (long)ka.blk * ka.nblk <= (1L << 20) &&
-                   ka.mon_hoist && (ka.rho || ka.f.rho) && first_round < ka.B;
-    }
-    if (!mon_late && ka.mon_hoist && (ka.rho || ka.f.rho)) {
-        if ((e = launch_monitor<FLIP>(ka, L.dev, h->stream)) != hipSuccess) return e;
-        helper_busy = true;
-    }
-    // (Not for a one-lane batch that runs in ROUNDS of resident waves -- more 64-chain waves than SIMDs, the headline sweep: every
-    // SIMD is taken by a 512-register wave, the tail finds no room beside the smoother and a second launch costs the smoother a
-    // second pair of rounds: 15.1-15.9 against 15.6-16.2 ms per pass over four alternating runs, profiles/r06/ab_monitor_par.txt.)
-    if (!in_rounds && !mon_late && L.tail && L.tail->t_hist >= 1 && L.tail->t_hist <= T - 2 && !ka.wave) {
-        KArgs kb = ka;
-        kb.bk_from = T - 2; kb.bk_to = L.tail->t_hist;              // the horizon days
-        if ((e = enqueue_bwd<M, FLIP, GENERIC>(kb, L, st)) != hipSuccess) return e;
-        if ((e = fork(st, h->stream)) != hipSuccess) return e;
-        if ((e = enqueue_tail(ka, *L.tail, h->stream)) != hipSuccess) return e;
-        helper_busy = true;
-        kb.bk_from = L.tail->t_hist - 1; kb.bk_to = 0;              // the observed days
-        if ((e = enqueue_bwd<M, FLIP, GENERIC>(kb, L, st)) != hipSuccess) return e;
-    } else if (mon_late) {
-        if ((e = enqueue_bwd<M, FLIP, GENERIC>(ka, L, st, 0, first_round)) != hipSuccess) return e;
-        if ((e = fork(st, h->stream)) != hipSuccess) return e;
-        if ((e = launch_monitor<FLIP>(ka, L.dev, h->stream)) != hipSuccess) return e;
-        helper_busy = true;
-        if ((e = enqueue_bwd<M, FLIP, GENERIC>(ka, L, st, first_round, ka.B - first_round)) != hipSuccess) return e;
-        if (L.tail && (e = enqueue_tail(ka, *L.tail, st)) != hipSuccess) return e;
-    } else {
-        if ((e = enqueue_bwd<M, FLIP, GENERIC>(ka, L, st)) != hipSuccess) return e;
-        if (L.tail && (e = enqueue_tail(ka, *L.tail, st)) != hipSuccess) return e;
-    }
-    }
-    if (helper_busy) e = fork(h->stream, st);
+    e = run_plan<M, FLIP, GENERIC>(ka, p, tail, st, lease.h);
     if constexpr (GENERIC) {
-        if (e == hipSuccess && L.rerun) e = rerun_nonfinite_dense<M, FLIP>(ka, L, st);
+        if (e == hipSuccess && p.rerun_after) e = rerun_nonfinite_dense<M, FLIP>(ka, in, tail, st);
     }
     return e;
 }
+
+// the one thing the plan takes from the device: its SIMD count
+static PlanIn plan_input(const epi_batch_desc *d, int dev) { PlanIn in{}; in.d = d; in.n_simds = simd_count(dev); return in; }
 
 }  // namespace epi
 
@@ -1745,10 +1316,7 @@ int epi_ekf_preferred_lane_block(const epi_batch_desc *d)
     if (!d) return 0;
     probe = *d; probe.lane_block = 0;
     if (epi_ekf_validate(&probe, nullptr) != EPI_OK) return 0;
-    const ModelInfo &mi = MODEL_TABLE[d->model];
-    const int dev = current_device();
-    const int sh = shape_of(d, dev);
-    const int lw = sh == EPI_SHAPE_WAVE ? 1 : (sh == EPI_SHAPE_HEX ? kHG : (sh == EPI_SHAPE_QUAD ? kQC : balanced_lanes(d->B, mi.m == 6 ? 1 : 2, dev)));
+    const int lw = plan_launch(plan_input(d, current_device())).chains_per_wave;
     return lw < d->B ? lw : d->B;
 }
 
@@ -1785,10 +1353,6 @@ static int run_device_impl(const epi_batch_desc *d, const epi_inputs *in, const 
     KArgs ka{};
     ka.B = d->B; ka.T = d->T; ka.Sx = d->Sx; ka.Su = d->Su; ka.n_npi = d->n_npi; ka.L = d->L; ka.r_mode = d->r_mode; ka.q_mode = d->q_mode;
     ka.blk = lane_block_of(d); ka.nblk = (d->B + ka.blk - 1) / ka.blk;
-    const int dev = current_device();
-    ka.quad = shape_of(d, dev) == EPI_SHAPE_QUAD ? 1 : 0;
-    ka.wave = shape_of(d, dev) == EPI_SHAPE_WAVE ? 1 : 0;
-    ka.hex = shape_of(d, dev) == EPI_SHAPE_HEX ? 1 : 0;
     ka.mon_scan = (d->test_flags >> 1) & 1;
     ka.hexw = d->test_window;      // test hook (0 in production): days per addressing window, see epi_batch_desc.test_window
     ka.stor = f32 ? 1 : 0;
@@ -1837,7 +1401,14 @@ static int run_device_impl(const epi_batch_desc *d, const epi_inputs *in, const 
         ka.only_buf = (int32_t *)(ws + wl.only);
         if (!ka.status && rerun) ka.status = (int32_t *)(ws + wl.status);
     }
-    ka.mon_hoist = monitor_hoisted(d) ? 1 : 0;
+    const int dev = current_device();
+    PlanIn pin = plan_input(d, dev);
+    // (exact_nonfinite needs the smoother's guard to find the chains: it runs the smoother whatever is selected)
+    pin.smooth = smooth_sel || rerun; pin.rerun = rerun;
+    pin.hint = (mi.generic && d->q_mode == 0) ? d->path_hint : 2;      // a time-varying Q_w is read per step by the dense kernels only
+    pin.ws_upper = ka.ws_upper; pin.want_rho = ka.rho || ka.f.rho; pin.has_tail = tail != nullptr; pin.t_hist = tail ? tail->t_hist : 0;
+    const LaunchPlan plan = plan_launch(pin);
+    ka.quad = plan.quad; ka.wave = plan.wave; ka.hex = plan.hex; ka.mon_hoist = plan.mon_hoist; ka.lw = plan.lw;
     if (ka.mon_hoist && !ka.innovations && (ka.rho || ka.f.rho)) ka.innovations = (double *)(ws + wl.innov);
     ka.X = mi.generic ? (double *)(ws + wl.x) : nullptr;
     ka.rankbuf = mi.generic ? (int32_t *)(ws + wl.rank) : nullptr;
@@ -1858,21 +1429,15 @@ static int run_device_impl(const epi_batch_desc *d, const epi_inputs *in, const 
             if (((om | om32) & q.bit) && !q.p) { char b[128]; snprintf(b, sizeof b, "output %s selected but NULL", q.n); set_err(err, b); return EPI_ERR_BAD_ARG; }
         if (has_uos && ((om | om32) & EPI_OUT_U_OPT_SMOOTH) && !out->u_opt_smooth) { set_err(err, "output u_opt_smooth selected but NULL"); return EPI_ERR_BAD_ARG; }
     }
-    // (exact_nonfinite needs the smoother's guard to find the chains: it runs the smoother whatever is selected)
-    const bool smooth = smooth_sel || rerun;
     hipStream_t st = (hipStream_t)stream;
-    Launch L{};
-    L.dev = dev; L.phase = d->phase; L.time_pipe = d->time_pipe; L.test_flags = d->test_flags; L.smooth = smooth; L.tail = tail; L.rerun = rerun;
-    // a time-varying Q_w is read per step by the dense kernels only
-    L.hint = (mi.generic && d->q_mode == 0) ? d->path_hint : 2;
     if (tail && (!ka.u_opt_smooth || d->phase != 0)) { set_err(err, "the sweep's scoring tail needs a full call (phase 0) with fp64 u_opt_smooth selected"); return EPI_ERR_BAD_ARG; }
     hipError_t e;
     switch (d->model) {
-    case EPI_MODEL_SIA3: e = launch_chain<3, 0, 1>(ka, L, st); break;
-    case EPI_MODEL_SIA6: e = launch_chain<6, 0, 1>(ka, L, st); break;
-    case EPI_MODEL_SIA3_BWD: e = launch_chain<3, 1, 1>(ka, L, st); break;
-    case EPI_MODEL_SIA6_BWD: e = launch_chain<6, 1, 1>(ka, L, st); break;
-    default: e = launch_chain<6, 0, 0>(ka, L, st); break;
+    case EPI_MODEL_SIA3: e = launch_chain<3, 0, 1>(ka, pin, plan, tail, dev, st); break;
+    case EPI_MODEL_SIA6: e = launch_chain<6, 0, 1>(ka, pin, plan, tail, dev, st); break;
+    case EPI_MODEL_SIA3_BWD: e = launch_chain<3, 1, 1>(ka, pin, plan, tail, dev, st); break;
+    case EPI_MODEL_SIA6_BWD: e = launch_chain<6, 1, 1>(ka, pin, plan, tail, dev, st); break;
+    default: e = launch_chain<6, 0, 0>(ka, pin, plan, tail, dev, st); break;
     }
     if (e != hipSuccess) return hip_fail(err, e, "kernel launch");
     return EPI_OK;

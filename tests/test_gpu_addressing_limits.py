@@ -2,7 +2,7 @@
 rejections beyond them.
 
 The filter / smoother kernels address memory through buffer descriptors and 32-bit byte offsets.  The limits that keep
-this safe are written into epi_ekf_validate, shape_of and enqueue_bwd (epiekf.hip) and into lw_window / hx_window
+this safe are written into epi_ekf_validate (epiekf.hip), shape_of and plan_launch (launch_plan.hpp) and into lw_window / hx_window
 (ekf_lane6.hpp, ekf_hex.hpp); here each is run AT its value.  An offset that wraps, or a store the descriptor's bounds
 check drops, gives plausible numbers for the wrong chain or leaves the output untouched, so every case follows three rules:
 

@@ -64,7 +64,7 @@ def _check(w, got, ref, tag, f32=False):
 
 
 # The 6-state generic model (SIAlphaModelEKFOptControlled and its time-flipped wrapper): (id, workload, EkfRunner arguments)
-# with the launches each reaches, following enqueue_fwd / enqueue_bwd / launch_chain in epiekf.hip.  Workloads: "b80" = 4
+# with the launches each reaches, following plan_launch in csrc/launch_plan.hpp (tests/launch_plan_test.cpp asserts them).  Workloads: "b80" = 4
 # regions x 20 cost weights (80 chains, two 40-chain blocks) x 40 days, "b70" = its first 70 chains, "dense" = b80 with a
 # non-diagonal Q_w, "long" = 40 chains x 130 days (forward model only).
 SIA6_LAUNCHES = [
@@ -98,9 +98,11 @@ SIA6_LAUNCHES = [
     ("hex-reverse-pipe", "b80", dict(shape="hex", lane_block=10, test_window=4, test_flags=1)),
     # non-diagonal Q_w: the precheck sends the batch to the dense kernels ekf_fwd<6, FLIP, 1> + eks_bwd<6, FLIP, 1>
     ("dense", "dense", dict(shape="lane")),
-    # T >= 128 with time_pipe = 1: the forward kernel in time segments, the pinv grid of each beside the next
+    # T >= 128 with time_pipe = 1: the forward kernel in time segments, the pinv grid of each beside the next (40 chains in the
+    # classic layout are one 40-chain block: the XD smoother)
     ("time-pipe", "long", dict(shape="lane", time_pipe=1)),
-    # reduced outputs: u_opt_smooth alone (forward quantities in the workspace, the two-waves-per-SIMD forward variant), XD smoother
+    # reduced outputs: u_opt_smooth alone (forward quantities in the workspace, upper triangles only; 80 chains run 64-lane waves, so
+    # ekf_fwd_sym<6, FLIP, 0, 0, 0> -- the two-waves-per-SIMD variant needs waves of <= 40 lanes, tests/launch_plan_test.cpp), XD smoother
     ("reduced-u-blk40", "b80", dict(shape="lane", lane_block=40, outputs=["u_opt_smooth"])),
     # reduced outputs S_SMOOTH, u_opt_smooth, rho, classic layout
     ("reduced-3-classic", "b80", dict(shape="lane", outputs=["S_SMOOTH", "u_opt_smooth", "rho"])),
