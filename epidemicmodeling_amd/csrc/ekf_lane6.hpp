@@ -19,8 +19,10 @@
 //     P+ A', which the gain needs anyway, is (A P+)' bit for bit (P+ is symmetric bit for bit and a product commutes), so
 //     P(k+1|k) = sym((A P+) A' + Q) costs one more 6 x 6 product with A's 21 non-zeros, not two -- the forward kernel's own
 //     sequence of operations, the same bits (eks_bwd_hex does the same across six lanes).
-// Conditions (plan_launch checks them, launch_plan.hpp: lane6_ok): R_v a per-day series (monitor hoisted), fixed diagonal Q_w, fp64
-// storage, lane_block == lanes per workgroup == BLK.  Everything else keeps ekf_sym.hpp.
+// Conditions (plan_launch checks them, launch_plan.hpp: lane6_ok): the packed path (fixed diagonal Q_w), fp64 storage, lane_block ==
+// lanes per workgroup == BLK.  R_v may be a per-day series (monitor hoisted) or a scalar, adaptive or not (the forward kernel then
+// keeps its inline monitor): the smoother reads neither R nor rho -- tests/kernel_ledger.py, rows "row3/*-blk40 / 48 / 56" and
+// "lp/blk40-inline-monitor", run that combination against the oracle.  Everything else keeps ekf_sym.hpp.
 #pragma once
 
 // (the lane blocks these kernels are instantiated for: lane6_block, launch_plan.hpp)

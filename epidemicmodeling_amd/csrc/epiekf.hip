@@ -1372,7 +1372,11 @@ static int run_device_impl(const epi_batch_desc *d, const epi_inputs *in, const 
     ka.S_PLUS = (om & EPI_OUT_S_PLUS) ? out->S_PLUS : (double *)(ws + wl.s_plus);
     ka.P_MINUS = (om & EPI_OUT_P_MINUS) ? out->P_MINUS : (double *)(ws + wl.p_minus);
     ka.P_PLUS = (om & EPI_OUT_P_PLUS) ? out->P_PLUS : (double *)(ws + wl.p_plus);
-    ka.ws_upper = ((om & EPI_OUT_P_MINUS) ? 0 : 1) | ((om & EPI_OUT_P_PLUS) ? 0 : 2);
+    // what the plan is asked for this call (plan_call_input, launch_plan.hpp): smoother or not, the dense second pass, ws_upper
+    const int dev = current_device();
+    const PlanIn pin = plan_call_input(d, plan_input(d, dev).n_simds, out->pinv_rank != nullptr, out->status != nullptr, tail != nullptr,
+                                       tail ? tail->t_hist : 0);
+    ka.ws_upper = pin.ws_upper;
     // fp32 storage, 3 states: the packed smoother recomputes s(k+1|k) from s(k|k) (ekf_sym.hpp, RC), nothing reads an
     // fp64 S_MINUS back -- the forward kernel then stores the caller's fp32 copy only
     if (f32 && mi.m == 3) ka.S_MINUS = nullptr;
@@ -1392,21 +1396,10 @@ static int run_device_impl(const epi_batch_desc *d, const epi_inputs *in, const 
     ka.f.K_GAIN = sel32(EPI_OUT_K_GAIN, out->K_GAIN); ka.f.innovations = sel32(EPI_OUT_INNOVATIONS, out->innovations);
     ka.f.rho = sel32(EPI_OUT_RHO, out->rho);
     ka.pinv_rank = out->pinv_rank; ka.status = out->status;
-    // exact_nonfinite: 1 = always (runs the smoother to find the chains, whatever is selected); 0, the default = whenever the call
-    // runs the smoother anyway; -1 = never
-    const bool smooth_sel = ((om | om32) & (EPI_OUT_S_SMOOTH | EPI_OUT_P_SMOOTH)) || (has_uos && ((om | om32) & EPI_OUT_U_OPT_SMOOTH)) ||
-                            out->pinv_rank || out->status;
-    const bool rerun = mi.generic && (d->exact_nonfinite > 0 || (d->exact_nonfinite == 0 && smooth_sel)) && d->q_mode == 0 && d->phase == 0 && !f32;
     if (mi.generic && d->exact_nonfinite >= 0) {
         ka.only_buf = (int32_t *)(ws + wl.only);
-        if (!ka.status && rerun) ka.status = (int32_t *)(ws + wl.status);
+        if (!ka.status && pin.rerun) ka.status = (int32_t *)(ws + wl.status);
     }
-    const int dev = current_device();
-    PlanIn pin = plan_input(d, dev);
-    // (exact_nonfinite needs the smoother's guard to find the chains: it runs the smoother whatever is selected)
-    pin.smooth = smooth_sel || rerun; pin.rerun = rerun;
-    pin.hint = (mi.generic && d->q_mode == 0) ? d->path_hint : 2;      // a time-varying Q_w is read per step by the dense kernels only
-    pin.ws_upper = ka.ws_upper; pin.want_rho = ka.rho || ka.f.rho; pin.has_tail = tail != nullptr; pin.t_hist = tail ? tail->t_hist : 0;
     const LaunchPlan plan = plan_launch(pin);
     ka.quad = plan.quad; ka.wave = plan.wave; ka.hex = plan.hex; ka.mon_hoist = plan.mon_hoist; ka.lw = plan.lw;
     if (ka.mon_hoist && !ka.innovations && (ka.rho || ka.f.rho)) ka.innovations = (double *)(ws + wl.innov);

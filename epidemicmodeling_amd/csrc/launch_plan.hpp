@@ -170,8 +170,31 @@ struct PlanIn {
     bool want_rho, only;         // rho is an output (fp64 or fp32); this IS the dense second pass (KArgs.only is set)
     bool has_tail; int t_hist;   // the sweep's scoring tail
 };
+// The plan's input of ONE call, from the descriptor, the SIMD count and what the call's pointers say: are pinv_rank / status
+// outputs, and the sweep's scoring tail with its t_hist.  run_device_impl (epiekf.hip) and the plan query of the tests
+// (tests/plan_query.cpp) both come through here, so a test that asks which kernels a call launches asks the call's own question.
+static inline PlanIn plan_call_input(const epi_batch_desc *d, int n_simds, bool has_pinv_rank, bool has_status, bool has_tail, int t_hist)
+{
+    const ModelInfo &mi = MODEL_TABLE[d->model];
+    const bool f32 = d->storage == 1;
+    const uint32_t sel = d->out_mask, om = f32 ? 0u : d->out_mask;   // selected in either storage; the fp64 outputs among them
+    PlanIn in{}; in.d = d; in.n_simds = n_simds;
+    // exact_nonfinite: 1 = always (runs the smoother to find the chains, whatever is selected); 0, the default = whenever the call
+    // runs the smoother anyway; -1 = never
+    const bool smooth_sel = (sel & (EPI_OUT_S_SMOOTH | EPI_OUT_P_SMOOTH)) || (mi.generic && (sel & EPI_OUT_U_OPT_SMOOTH)) ||
+                            has_pinv_rank || has_status;
+    in.rerun = mi.generic && (d->exact_nonfinite > 0 || (d->exact_nonfinite == 0 && smooth_sel)) && d->q_mode == 0 && d->phase == 0 && !f32;
+    // (exact_nonfinite needs the smoother's guard to find the chains: it runs the smoother whatever is selected)
+    in.smooth = smooth_sel || in.rerun;
+    in.hint = (mi.generic && d->q_mode == 0) ? d->path_hint : 2;      // a time-varying Q_w is read per step by the dense kernels only
+    // fp32 storage: every fp64 forward quantity the kernels see is workspace, upper triangles only
+    in.ws_upper = ((om & EPI_OUT_P_MINUS) ? 0 : 1) | ((om & EPI_OUT_P_PLUS) ? 0 : 2);
+    in.want_rho = (sel & EPI_OUT_RHO) != 0;
+    in.has_tail = has_tail; in.t_hist = has_tail ? t_hist : 0;
+    return in;
+}
 struct LaunchPlan {
-    bool overflow;               // the lists below did not fit (never for a validated descriptor; launch_plan_test)
+    bool overflow;              // the lists below did not fit (never for a validated descriptor; launch_plan_test)
     int shape, chains_per_wave;  // EPI_SHAPE_*; chains a wave of that shape holds (what epi_ekf_preferred_lane_block answers)
     int lw, quad, wave, hex, mon_hoist;   // KArgs fields of the same names
     unsigned schedule;           // ScheduleBits
