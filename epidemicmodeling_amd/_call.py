@@ -354,8 +354,10 @@ def smoother_draws(be, S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_te
                               _lib.sdraw_shapes(B, T, D, k0), names, out_f32=("X",) if out_f32 else ())
 
 
-def ensemble_score(be, src, truth, R, D, alpha, n_bins, population, truth_series, first_day, k0, k1, outputs, test_launch_items=0):
-    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+def _scored_inputs(be, src, truth, R, D, population, truth_series, first_day):
+    """The checks ensemble_score and ensemble_joint_score share on src [T, rows, R * D] or [T, R * D], truth [T, rows', Rt],
+    population, truth_series and first_day; returns (R, D, T, rows, Rt, population, truth, truth_series, first_day) as the
+    backend's arrays"""
     if src.ndim not in (2, 3):
         raise ValueError("src must be [T, rows, B] or [T, B]")
     R, D = int(R), int(D)
@@ -384,6 +386,12 @@ def ensemble_score(be, src, truth, R, D, alpha, n_bins, population, truth_series
                 raise ValueError("truth_series must hold entries in 0 .. Rt-1")
     if fd is not None and tuple(fd.shape) != (R,):
         raise ValueError("first_day must be [R]")
+    return R, D, T, rows, Rt, pop, truth, ts, fd
+
+
+def ensemble_score(be, src, truth, R, D, alpha, n_bins, population, truth_series, first_day, k0, k1, outputs, test_launch_items=0):
+    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+    R, D, T, rows, Rt, pop, truth, ts, fd = _scored_inputs(be, src, truth, R, D, population, truth_series, first_day)
     d = _lib.make_escore_desc(T, rows, R, D, Rt, alpha, n_bins, storage=int(_is_f32(src)), derive_newcases=int(pop is not None),
                               k0=k0, k1=k1, test_launch_items=test_launch_items)
     names = _lib.escore_out_names(outputs, n_bins)
@@ -440,6 +448,29 @@ def path_functionals(be, src, R, D, thresholds, population, first_day, k0, k1, o
     _lib.check(_lib.lib().epi_pathfn_validate(C.byref(d), C.byref(ins), C.byref(probe), err), err)   # before anything is allocated
     out = run_with_workspace("pathfn", be, d, ins, _lib.PathfnOutputs(), _lib.PATHFN_OUT_NAMES, _lib.PATHFN_OUT_I32,
                              _lib.pathfn_shapes(rows, R, D, n_thr, d.k1 - d.k0, d.derive_newcases), names)
+    if src.ndim == 2:
+        out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
+    return out
+
+
+def ensemble_joint_score(be, src, truth, R, D, vs_p, max_lag, population, truth_series, first_day, k0, k1, outputs, test_launch_tiles=0):
+    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+    R, D, T, rows, Rt, pop, truth, ts, fd = _scored_inputs(be, src, truth, R, D, population, truth_series, first_day)
+    if vs_p not in _lib.EJOINT_VS_ORDERS:
+        raise ValueError("vs_p must be None, 0.5 or 1: the variogram score is pinned for these two exponents only")
+    d = _lib.make_ejoint_desc(T, rows, R, D, Rt, _lib.EJOINT_VS_ORDERS[vs_p], max_lag, storage=int(_is_f32(src)),
+                              derive_newcases=int(pop is not None), k0=k0, k1=k1, test_launch_tiles=test_launch_tiles)
+    names = _lib.ejoint_out_names(outputs, d.vs_order)
+    ins = _lib.EjointInputs()
+    for k, v in zip(_lib.EJOINT_IN_NAMES, (src, pop, truth, ts, fd)):
+        setattr(ins, k, be.ptr(v))
+    probe = _lib.EjointOutputs()
+    for k in names:
+        setattr(probe, k, 1)                            # validate looks only at which outputs are asked for
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_ejoint_validate(C.byref(d), C.byref(ins), C.byref(probe), err), err)   # before anything is allocated
+    out = run_with_workspace("ejoint", be, d, ins, _lib.EjointOutputs(), _lib.EJOINT_OUT_NAMES, _lib.EJOINT_OUT_I32,
+                             _lib.ejoint_shapes(rows, R, D, d.derive_newcases), names)
     if src.ndim == 2:
         out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
     return out

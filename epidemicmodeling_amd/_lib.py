@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
     "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
     "epi_pathfn_validate", "epi_pathfn_workspace_bytes", "epi_pathfn_run_device", "epi_pathfn_run_host",
+    "epi_ejoint_validate", "epi_ejoint_workspace_bytes", "epi_ejoint_run_device", "epi_ejoint_run_host",
 ]
 
 
@@ -758,6 +759,52 @@ def make_pathfn_desc(T, rows, R, D, n_thr=0, storage=0, derive_newcases=0, k0=0,
     return d
 
 
+class EjointDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "Rt", "storage", "derive_newcases", "k0", "k1", "vs_order",
+                                         "max_lag", "test_launch_tiles", "reserved")]
+
+
+EJOINT_IN_NAMES = ESCORE_IN_NAMES
+EJOINT_OUT_NAMES = ("es", "truth_term", "spread_term", "vs", "n_members", "n_days", "member_dist")
+EJOINT_OUT_I32 = ("n_members", "n_days")
+EJOINT_VS_ORDERS = {0: 0, None: 0, 0.5: 1, 1: 2, 1.0: 2}        # the exponent p of the variogram score -> vs_order
+
+
+class EjointInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in EJOINT_IN_NAMES]
+
+
+class EjointOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in EJOINT_OUT_NAMES]
+
+
+def ejoint_shapes(rows, R, D, derive_newcases=0):
+    """shape of every output of epi_ejoint_run_* (rows' = rows + derive_newcases)"""
+    ro = int(rows) + int(derive_newcases)
+    sh = {k: (ro, R) for k in EJOINT_OUT_NAMES}
+    sh["member_dist"] = (ro, R * D)
+    return sh
+
+
+def ejoint_out_names(outputs, vs_order):
+    """None -> every output (vs only with vs_order > 0); else the names asked for, in the ABI's order"""
+    default = [k for k in EJOINT_OUT_NAMES if k != "vs" or int(vs_order) > 0]
+    names = out_names(EJOINT_OUT_NAMES, outputs, default)
+    return [k for k in EJOINT_OUT_NAMES if k in names]
+
+
+def make_ejoint_desc(T, rows, R, D, Rt, vs_order=0, max_lag=0, storage=0, derive_newcases=0, k0=0, k1=None, test_launch_tiles=0) -> EjointDesc:
+    """storage: 0 / "f64" = double source, 1 / "f32" = float source.  vs_order: 0 (off), 1 (p = 0.5), 2 (p = 1).  k1 = None: T."""
+    d = EjointDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.rows, d.R, d.D, d.Rt = int(T), int(rows), int(R), int(D), int(Rt)
+    d.storage = {"f64": 0, "f32": 1}.get(storage, storage)
+    d.derive_newcases = int(derive_newcases)
+    d.k0, d.k1 = int(k0), int(T) if k1 is None else int(k1)
+    d.vs_order, d.max_lag, d.test_launch_tiles = int(vs_order), int(max_lag), int(test_launch_tiles)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -885,6 +932,11 @@ def lib():
         h.epi_pathfn_run_device.argtypes = [C.POINTER(PathfnDesc), C.POINTER(PathfnInputs), C.POINTER(PathfnOutputs),
                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_pathfn_run_host.argtypes = [C.POINTER(PathfnDesc), C.POINTER(PathfnInputs), C.POINTER(PathfnOutputs), C.c_int, C.c_char_p]
+        h.epi_ejoint_validate.argtypes = [C.POINTER(EjointDesc), C.POINTER(EjointInputs), C.POINTER(EjointOutputs), C.c_char_p]
+        h.epi_ejoint_workspace_bytes.argtypes = [C.POINTER(EjointDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_ejoint_run_device.argtypes = [C.POINTER(EjointDesc), C.POINTER(EjointInputs), C.POINTER(EjointOutputs),
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_ejoint_run_host.argtypes = [C.POINTER(EjointDesc), C.POINTER(EjointInputs), C.POINTER(EjointOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

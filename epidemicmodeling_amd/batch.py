@@ -1183,3 +1183,32 @@ def path_functionals(src, R, D, thresholds=None, population=None, first_day=None
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.path_functionals(DeviceBackend(dev, st), src.contiguous(), R, D, thresholds, population, first_day, k0, k1,
                                       outputs, test_segments, test_launch_groups)
+
+
+def ensemble_joint_score(src, truth, R, D, vs_p=None, max_lag=0, population=None, truth_series=None, first_day=None, k0=0, k1=None,
+                         outputs=None, stream=None, test_launch_tiles=0):
+    """Joint (multivariate) scores of a Monte-Carlo ensemble's paths against a truth in one device call (epi_ejoint_run_device,
+    DESIGN.md §4.20): what tells joint draws from draws with the same marginals and no dependence between days, which
+    ensemble_score cannot.  src, truth, population, truth_series and first_day are ensemble_score's: src [T, rows, B] or [T, B]
+    (float32 or float64, on the device), B = R * D chains, region-major; truth [T, rows', Rt].  An item is one (row, region); its
+    days are the t in [max(k0, first_day[r]), k1) (k1 = None: T) whose truth is not NaN, its members the draws without a NaN on
+    any of those days.  Per item [rows', R]: es, the energy score (1/n) sum ||x_i - y|| - (1/(2 n^2)) sum sum ||x_i - x_j|| over the
+    days (with one day: the CRPS), its two terms truth_term and spread_term, n_members, n_days (int32) and, with vs_p = 0.5 or 1,
+    vs: the variogram score of order p over the pairs of days at most max_lag calendar days apart (0: every pair).  member_dist
+    [rows', R * D]: every member's distance to the truth (NaN for absent members), itself an ensemble_summary source.  An item
+    without members or days gives NaN (its counts are still written).
+    outputs: any of these names (default: all, vs only with vs_p).  Returns a dict of device tensors.  Enqueued on `stream`
+    (default: the current stream) without a host synchronisation.  A chain-blocked output (EkfRunner(lane_block=...)) is not
+    accepted.  test_launch_tiles: the tests' launch cut (0 in production)."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a torch tensor (NumPy arrays: hostapi.ensemble_joint_score)")
+    if src.dim() == 4:
+        raise ValueError("src is a chain-blocked tensor [T, nblk, rows, blk]; ensemble_score takes the classic layout "
+                         "[T, rows, B]: pass EkfRunner.unblocked(name).contiguous(), or run with lane_block=0")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError("src must be float32 or float64")
+    dev = src.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.ensemble_joint_score(DeviceBackend(dev, st), src.contiguous(), truth, R, D, vs_p, max_lag, population, truth_series,
+                                          first_day, k0, k1, outputs, test_launch_tiles)

@@ -779,6 +779,7 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "ens_summary.hpp"
 #include "ens_score.hpp"
 #include "path_functionals.hpp"
+#include "ens_joint.hpp"
 #include "ar_forecast.hpp"
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
@@ -4157,6 +4158,135 @@ int epi_pathfn_run_host(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, c
         HostIO::bind_opt(dout, i32p, o_p, base);
         HostIO::bind_opt(dout, i32r, o_r, base);
         return epi_pathfn_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+// ---- joint scores of the ensembles: ejoint_members, ejoint_pairs, ejoint_vario, ejoint_final (ens_joint.hpp) ----
+static int ejoint_check_desc(const epi_ejoint_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->rows < 1) { set_err(err, "rows must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->Rt < 1) { set_err(err, "Rt must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1 || d->D > kEnsMaxD) { set_err(err, "D must lie in 1 .. 4096 (a wavefront holds the draws of an item in registers)"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k1 < d->k0 || d->k1 > d->T) { set_err(err, "k0, k1 must satisfy 0 <= k0 <= k1 <= T"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases != 0 && d->derive_newcases != 1) { set_err(err, "derive_newcases must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && d->rows < 3) { set_err(err, "derive_newcases needs at least 3 rows"); return EPI_ERR_BAD_ARG; }
+    if (d->vs_order < 0 || d->vs_order > 2) { set_err(err, "vs_order must be 0 (no variogram score), 1 (p = 0.5) or 2 (p = 1)"); return EPI_ERR_BAD_ARG; }
+    if (d->max_lag < 0) { set_err(err, "max_lag must be >= 0 (0: every lag)"); return EPI_ERR_BAD_ARG; }
+    if (d->test_launch_tiles < 0) { set_err(err, "test_launch_tiles must be >= 0"); return EPI_ERR_BAD_ARG; }
+    const int64_t items = (int64_t)(d->rows + d->derive_newcases) * d->R, nb = (d->D + 63) / 64, tiles = nb * (nb + 1) / 2, wcap = d->k1 - d->k0;
+    if (items > (int64_t)0x7fffffff) { set_err(err, "(rows + derive_newcases) * R is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (items * (tiles > wcap ? tiles : wcap) > ((int64_t)1 << 40)) {
+        set_err(err, "(rows + derive_newcases) * R * max(tiles, k1 - k0) is limited to 2^40 (the workspace holds a double for each)");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+int epi_ejoint_validate(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, char *err)
+{
+    int rc = ejoint_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->src) { set_err(err, "NULL src"); return EPI_ERR_BAD_ARG; }
+    if (!in->truth) { set_err(err, "NULL truth"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && !in->population) { set_err(err, "NULL population (derive_newcases)"); return EPI_ERR_BAD_ARG; }
+    if (!in->truth_series && d->Rt != d->R) { set_err(err, "without truth_series, truth must hold R columns (Rt = R)"); return EPI_ERR_BAD_ARG; }
+    if (out->vs && d->vs_order == 0) { set_err(err, "vs needs vs_order 1 (p = 0.5) or 2 (p = 1)"); return EPI_ERR_BAD_ARG; }
+    if (!(out->es || out->truth_term || out->spread_term || out->vs || out->n_members || out->n_days || out->member_dist)) {
+        set_err(err, "no output requested");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+static size_t ejoint_ws_bytes(const epi_ejoint_desc *d)
+{
+    const size_t nb = (size_t)(d->D + 63) / 64;
+    return ejoint_ws_size((size_t)(d->rows + d->derive_newcases) * (size_t)d->R, nb, nb * (nb + 1) / 2, (size_t)(d->k1 - d->k0));
+}
+
+int epi_ejoint_workspace_bytes(const epi_ejoint_desc *d, size_t *bytes, char *err)
+{
+    int rc = ejoint_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = ejoint_ws_bytes(d);
+    return EPI_OK;
+}
+
+int epi_ejoint_run_device(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_ejoint_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    if (!ws || ws_bytes < ejoint_ws_bytes(d)) { set_err(err, "workspace too small (epi_ejoint_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    EjArgs g{};
+    g.T = d->T; g.rows = d->rows; g.rows_out = d->rows + d->derive_newcases; g.R = d->R; g.D = d->D; g.Rt = d->Rt;
+    g.f32 = d->storage; g.derive = d->derive_newcases; g.k0 = d->k0; g.k1 = d->k1; g.vs_order = d->vs_order; g.max_lag = d->max_lag;
+    g.nb = (d->D + 63) / 64; g.tiles = g.nb * (g.nb + 1) / 2; g.wcap = d->k1 - d->k0;
+    g.src = in->src; g.population = in->population; g.truth = in->truth; g.truth_series = in->truth_series; g.first_day = in->first_day;
+    const size_t items = (size_t)g.rows_out * (size_t)d->R;
+    const bool pairs = out->es || out->spread_term, vario = out->vs != nullptr;
+    ejoint_carve(g, ws, items, pairs, vario);
+    g.es = out->es; g.truth_term = out->truth_term; g.spread_term = out->spread_term; g.vs = out->vs;
+    g.n_members = out->n_members; g.n_days = out->n_days; g.member_dist = out->member_dist;
+    const hipStream_t st = (hipStream_t)stream;
+    const long long cap = d->test_launch_tiles > 0 ? (long long)d->test_launch_tiles : (long long)kEnsLaunchItems;
+    auto run = [&](int which, long long units) {                      // one 64-lane workgroup per unit, in launches below 2^31 threads
+        return ejoint_for_units(units, cap, [&](long long u0, long long nu) {
+            g.unit0 = u0; g.units = nu;
+            return (int)ejoint_launch(which, g, (unsigned)nu, st);
+        });
+    };
+    int e = run(0, (long long)items);
+    if (e) return hip_fail(err, (hipError_t)e, "ejoint_members launch");
+    if (pairs && (e = run(2, (long long)items * g.tiles))) return hip_fail(err, (hipError_t)e, "ejoint_pairs launch");
+    if (vario && g.wcap > 0 && (e = run(1, (long long)items * g.wcap))) return hip_fail(err, (hipError_t)e, "ejoint_vario launch");
+    if (out->es || out->truth_term || out->spread_term || out->vs || out->n_members || out->n_days) {
+        hipLaunchKernelGGL(ejoint_final, dim3((unsigned)((items + kEjFinalWg - 1) / kEjFinalWg)), dim3(kEjFinalWg), 0, st, g);
+        const hipError_t f = hipGetLastError();
+        if (f != hipSuccess) return hip_fail(err, f, "ejoint_final launch");
+    }
+    return EPI_OK;
+}
+
+int epi_ejoint_run_host(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, int device, char *err)
+{
+    int rc = epi_ejoint_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, B = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases), Rt = (size_t)d->Rt;
+    const size_t none = HostIO::kAbsent;
+    HostIO io;
+    const size_t o_src = io.add_in(in->src, T * (size_t)d->rows, d->storage ? 4 : 8, B, 0, B);
+    const size_t o_pop = d->derive_newcases ? io.add_in(in->population, 1, 8, R, 0, R) : none;
+    const size_t o_tr = io.add_in(in->truth, T * ro, 8, Rt, 0, Rt);
+    const size_t o_ts = in->truth_series ? io.add_in(in->truth_series, 1, 4, R, 0, R) : none;
+    const size_t o_fd = in->first_day ? io.add_in(in->first_day, 1, 4, R, 0, R) : none;
+    using EO = epi_ejoint_outputs;
+    const HostIO::Opt<EO, double> f64[4] = {{&EO::es, ro}, {&EO::truth_term, ro}, {&EO::spread_term, ro}, {&EO::vs, ro}};
+    const HostIO::Opt<EO, int32_t> i32[2] = {{&EO::n_members, ro}, {&EO::n_days, ro}};
+    size_t o_d[4], o_i[2];
+    io.add_opt(*out, f64, o_d, R);
+    io.add_opt(*out, i32, o_i, R);
+    const size_t o_md = out->member_dist ? io.add_out(out->member_dist, ro, 8, B, 0, B) : none;
+    const size_t wsb = ejoint_ws_bytes(d);
+    const size_t o_ws = io.reserve(wsb);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_ejoint_inputs din{};
+        din.src = base + o_src; din.population = HostIO::at<const double>(base, o_pop); din.truth = (const double *)(base + o_tr);
+        din.truth_series = HostIO::at<const int32_t>(base, o_ts); din.first_day = HostIO::at<const int32_t>(base, o_fd);
+        epi_ejoint_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        dout.member_dist = HostIO::at<double>(base, o_md);
+        return epi_ejoint_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -718,7 +718,7 @@ def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None,
 
 def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draws=256, alpha=(0.5, 0.05), n_bins=10, seed=0,
                 storage="f64", clamp=True, num_regression_days=60, W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0,
-                z=None):
+                z=None, joint=False, vs_p=0.5, max_lag=0):
     """The look-ahead study of forecast_quality done with fans: instead of one point estimate per day, every forecast is the
     smoother's joint posterior law, scored against the truth by the ensemble CRPS, the weighted interval score, interval coverage
     and the rank histogram (batch.ensemble_score).
@@ -734,7 +734,11 @@ def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draw
     k0, `scores` (the dict of batch.ensemble_score over the days k0 .. LL-1: rows s, i, alpha carry no truth and are NaN / -1,
     row 3 is the new cases; its per-region outputs are the per-chain aggregates), and by lead time l = day - origin, averaged over
     the starts that reach it, crps_by_lead, wis_by_lead [max(starts), S] and cover_by_lead [n_a, max(starts), S] (torch
-    reductions over the per-item scores)."""
+    reductions over the per-item scores).
+    joint=True adds, from the same paths and origins, `joint_scores`: the dict of batch.ensemble_joint_score
+    over the same days, whose row 3 scores every chain's new-case paths as paths from its origin on -- es (the energy score), vs
+    (the variogram score of order vs_p over pairs of days at most max_lag apart) and n_days, each [4, B] -- and es, vs, n_days
+    [B], that row.  The default returns exactly the keys above."""
     LL, S = cases.shape
     F = int(num_forecast_days)
     T = LL - F
@@ -784,6 +788,11 @@ def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draw
                starts=st, scores=scores, crps_by_lead=by_lead(scores["crps"][:, 3]), wis_by_lead=by_lead(scores["wis"][:, 3]),
                cover_by_lead=torch.stack([by_lead((cover >> k) & 1) for k in range(n_a)]) if n_a else
                torch.empty((0, H, S), dtype=torch.float64, device=dev))
+    if joint:
+        js = batch.ensemble_joint_score(X, torch.as_tensor(tw, device=dev), S * J, D, vs_p=vs_p, max_lag=max_lag, population=N[rr],
+                                        truth_series=torch.as_tensor(rr.astype(np.int32), device=dev), first_day=fd,
+                                        outputs=("es", "vs", "n_days") if vs_p else ("es", "n_days"))
+        out.update(joint_scores=js, es=js["es"][3], n_days=js["n_days"][3], **({"vs": js["vs"][3]} if vs_p else {}))
     return out
 
 

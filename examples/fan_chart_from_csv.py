@@ -2,7 +2,7 @@
 joint posterior draws of the smoother's paths (epidemicmodeling_amd/pipeline.py: forecast_fan), for all regions of
 the file at once.
 
-    python examples/fan_chart_from_csv.py [--score-last N] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
+    python examples/fan_chart_from_csv.py [--score-last N [--joint]] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
 
 The front half of Tools/TrainPredictPrescribeNPI.m (preprocessing, two EKF rounds, two regressions), then its forecast filter
 (:356-377: NaN observations over the horizon, the last day's NPIs held), then 256 backward-simulated paths per region and their
@@ -13,7 +13,9 @@ no data set in this repository).
 --score-last N holds the last N days of the window out, forecasts them from the days before, and prints how good the fans were
 (pipeline.fan_quality): per region the mean CRPS and weighted interval score of the daily new cases, the share of
 days the 50 % and the 95 % band held the truth, and the rank histogram in ten bins, with forecast starts N and N / 2 days before
-the end of the window.
+the end of the window.  With --joint the same fans are also scored as paths (pipeline.fan_quality(joint=True)):
+the energy score and the variogram score (p = 0.5, pairs of days up to a week apart) of every region's forecast, which tell
+joint draws from draws with the same bands and no dependence between days.
 
 --threshold C (or --outlook for the peak alone) prints the outlook over the horizon from the same joint draws (pipeline.path_outlook;
 DESIGN.md 4.18): per region the median and the 95 % band of the day of the peak of the daily new cases and of its height, the median
@@ -35,10 +37,11 @@ from prescribe_from_csv import synthetic_files  # noqa: E402
 Q = (0.025, 0.25, 0.5, 0.75, 0.975)
 
 
-def score_table(d, N, keep, n_last, draws):
+def score_table(d, N, keep, n_last, draws, joint=False):
     """the forecast of the last n_last days of the window, scored against them: one row per region and start"""
     starts = sorted({n_last, max(1, n_last // 2)}, reverse=True)
-    fq = pipeline.fan_quality(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], n_last, starts, n_draws=draws)
+    fq = pipeline.fan_quality(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], n_last, starts, n_draws=draws,
+                              joint=joint, vs_p=0.5, max_lag=7)
     sc = {k: v.cpu().numpy() for k, v in fq["scores"].items()}
     rows = []
     for j, r in enumerate(keep):
@@ -46,7 +49,11 @@ def score_table(d, N, keep, n_last, draws):
             c = j * len(starts) + i                       # chain = region * len(starts) + start; row 3 is the new cases
             rows.append([d["geo_ids"][r], s, int(sc["n_scored"][3, c]), sc["crps_mean"][3, c], sc["wis_mean"][3, c], sc["ae_mean"][3, c],
                          sc["cover_frac"][0, 3, c], sc["cover_frac"][1, 3, c], " ".join(str(v) for v in sc["pit_hist"][:, 3, c])])
-    return pd.DataFrame(rows, columns=["region", "start", "days", "crps", "wis", "abs_err", "cover50", "cover95", "pit_hist"])
+    table = pd.DataFrame(rows, columns=["region", "start", "days", "crps", "wis", "abs_err", "cover50", "cover95", "pit_hist"])
+    if joint:                                             # per chain, in the rows' order
+        table.insert(5, "energy", fq["es"].cpu().numpy())
+        table.insert(6, "variogram", fq["vs"].cpu().numpy())
+    return table
 
 
 def outlook_table(out, d, N, keep, draws, per_100k):
@@ -81,6 +88,9 @@ def main():
         i = sys.argv.index("--threshold")
         outlook, per_100k = True, float(sys.argv[i + 1])
         del sys.argv[i:i + 2]
+    joint = "--joint" in sys.argv
+    if joint:
+        sys.argv.remove("--joint")
     if "--score-last" in sys.argv:
         i = sys.argv.index("--score-last")
         n_last = int(sys.argv[i + 1])
@@ -113,7 +123,7 @@ def main():
         print(outlook_table(out, d, N, keep, draws, per_100k).to_string(index=False))
     if n_last > 0:
         print(f"the last {n_last} days held out and forecast from the days before them:")
-        print(score_table(d, N, keep, n_last, draws).to_string(index=False))
+        print(score_table(d, N, keep, n_last, draws, joint).to_string(index=False))
 
 
 if __name__ == "__main__":

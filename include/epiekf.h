@@ -1444,6 +1444,73 @@ int epi_pathfn_run_device(const epi_pathfn_desc *d, const epi_pathfn_inputs *in,
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_pathfn_run_host(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, const epi_pathfn_outputs *out, int device, char *err);
 
+/* ---- Joint scores of the Monte-Carlo ensembles: energy score and variogram score (not a script of the reference) ----
+ * src [T][rows][B], B = R * D, region-major, double or float, the derived row, truth [T][rows'][Rt], truth_series and first_day
+ * exactly as epi_escore_run_* take them.  An item is one (row, region r), item = row * R + r.  Definition (pinned; restated in
+ * tests/ejoint_ref.py and tests/ejoint_ref.c; one IEEE double operation per written operation, sqrt correctly rounded):
+ *   days of the item: the t in [max(k0, first_day[r]), k1) whose truth y_t = truth[(t * rows' + row) * Rt + ts] is not NaN
+ *     (ts = truth_series ? truth_series[r] : r), ascending; W their number
+ *   members of the item: member i is absent when x_it is NaN on any day of the item (with W = 0 nobody is); n the number present
+ *   n = 0 or W = 0: every floating output of the item is NaN; n_members = n and n_days = W are still written
+ *   d2(i, y) = sum over the item's days, ascending from 0.0, of (x_it - y_t) * (x_it - y_t);  e_i = sqrt(d2(i, y))
+ *   d2(i, j) the same sum with x_jt in place of y_t;  dist_ij = sqrt(d2(i, j))
+ *   truth_term = tree(e) / n: tree() the pairwise sum of epi_ens_run_* over P positions, P the power of two >= max(D, 64);
+ *     absent members and the positions >= D count as +0.0, selected by position
+ *   pair sum: members in blocks of 64, block I = members 64 I .. 64 I + 63; tile (I, J), I <= J.  Lane i of the tile (member
+ *     64 I + i) forms s_i = (..((0.0 + c_i0) + c_i1) + .. + c_i63), c_ij = dist between members 64 I + i and 64 J + j when both are
+ *     present (and below D) and, for I = J, j > i; else +0.0 (selected: the sum still adds it).  The tile sum is tree(s) over
+ *     the 64 lanes.  pairsum = the tile sums added from 0.0 in the order I ascending, then J ascending from I.
+ *   spread_term = pairsum / (n * n);  es = truth_term - spread_term: the ensemble energy score
+ *     (1/n) sum ||x_i - y|| - (1/(2 n n)) sum sum ||x_i - x_j||; with W = 1 the ensemble CRPS
+ *   variogram score, vs_order 1 (p = 0.5: g(a) = sqrt(fabs(a))) or 2 (p = 1: g(a) = fabs(a)); for days s < t of the item with
+ *     t - s <= max_lag in calendar days (max_lag = 0: every pair): m_st = tree(g(x_is - x_it)) / n with absent members and
+ *     positions >= D as +0.0;  term = g(y_s - y_t) - m_st;  v_s = sum over t ascending from 0.0 of term * term (0.0 for a day
+ *     without a later one);  vs = sum over every day s of the item ascending from 0.0 of v_s
+ *   non-finite members give what IEEE arithmetic gives in this order
+ * Outputs (each may be NULL; at least one must not be): es, truth_term, spread_term, vs [rows'][R]; n_members, n_days [rows'][R]
+ *   int32; member_dist [rows'][R * D], the e_i, NaN for absent members (region-major: itself a source of epi_ens_run_*);
+ *   rows' = rows + derive_newcases */
+typedef struct epi_ejoint_desc {
+    int32_t abi_version;
+    int32_t T, rows, R;          /* days, rows of src, regions: each >= 1; rows' * R <= INT32_MAX */
+    int32_t D;                   /* draws per region, 1 .. 4096; R * D <= INT32_MAX */
+    int32_t Rt;                  /* columns of truth, >= 1 (= R without truth_series) */
+    int32_t storage;             /* element type of src: 0 = double, 1 = float */
+    int32_t derive_newcases;     /* 0, or 1: append the row ((N * row0) * row1) * row2 */
+    int32_t k0, k1;              /* the window, 0 <= k0 <= k1 <= T */
+    int32_t vs_order;            /* 0: no variogram score; 1: p = 0.5; 2: p = 1 */
+    int32_t max_lag;             /* >= 0: the largest t - s of a pair of days in the variogram score (0: every pair) */
+    int32_t test_launch_tiles;   /* 0; > 0: units (items, tiles, days) per launch (the tests cut small calls into several launches) */
+    int32_t reserved;            /* 0 */
+} epi_ejoint_desc;
+typedef struct epi_ejoint_inputs {
+    const void *src;                     /* [T][rows][R * D] */
+    const double *population;            /* [R] (derive_newcases) or NULL */
+    const double *truth;                 /* [T][rows'][Rt] */
+    const int32_t *truth_series;         /* [R] or NULL */
+    const int32_t *first_day;            /* [R] or NULL */
+} epi_ejoint_inputs;
+typedef struct epi_ejoint_outputs {
+    double *es, *truth_term, *spread_term, *vs; /* [rows'][R] */
+    int32_t *n_members, *n_days;         /* [rows'][R] */
+    double *member_dist;                 /* [rows'][R * D] */
+} epi_ejoint_outputs;
+/* no GPU needed: EPI_ERR_BAD_ARG for T, rows, R, Rt < 1, D outside 1 .. 4096, R * D or rows' * R > INT32_MAX, rows' * R *
+ * max(tiles, k1 - k0) > 2^40 (tiles = nb (nb + 1) / 2, nb = ceil(D / 64): refused, not cut), k0 / k1 outside 0 <= k0 <= k1 <= T,
+ * storage or derive_newcases outside {0, 1}, derive_newcases with rows < 3 or without population, vs_order outside 0 .. 2, a
+ * negative max_lag or test_launch_tiles, a NULL src / truth, Rt != R without truth_series, vs with vs_order = 0, no output at all */
+int epi_ejoint_validate(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, char *err);
+/* bytes of device workspace epi_ejoint_run_device needs: per item a double, the tile sums, the v_s, the masks of present members
+ * (a 64-bit word per block), n, W and the day list */
+int epi_ejoint_workspace_bytes(const epi_ejoint_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; a wavefront per item, then per (item, tile) when es or spread_term is asked for, then per (item, day) when vs
+ * is, then a lane per (row, region), each cut into launches below 2^31 threads, enqueued on `stream`: no host synchronisation, no
+ * allocation, no atomics.  EPI_ERR_WORKSPACE for a workspace below epi_ejoint_workspace_bytes */
+int epi_ejoint_run_device(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_ejoint_run_host(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

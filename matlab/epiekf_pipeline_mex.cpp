@@ -108,6 +108,12 @@
 //       from;  k_first, k_last ([] = 1, T)  the days the per-region outputs run over, ONE-based and inclusive.  crps, wis, ae,
 //       rank, ties, cover, count  R x rows' x T (rank, ties -1 and NaN scores: not scored);  width  R x rows' x n_a x T;
 //       crps_mean, wis_mean, ae_mean, n_scored  R x rows';  cover_frac  R x rows' x n_a;  pit_hist  R x rows' x n_bins.
+//   [es, vs, truth_term, spread_term, n_members, n_days, member_dist] = epiekf_pipeline_mex('jscore', src, truth, D, vs_p, max_lag, population, truth_series, first_day, k_first, k_last)
+//       Joint scores of a Monte-Carlo ensemble's paths against a truth: the energy score and the variogram score of every (row,
+//       region) over a window of days.  src, truth, D, population, truth_series, first_day, k_first, k_last  as
+//       'escore' takes them;  vs_p ([] or 0 = no variogram score)  0.5 or 1;  max_lag ([] = 0: every pair of days)  the largest
+//       distance in days of a pair in the variogram score.  es, vs (NaN without vs_p), truth_term, spread_term, n_members,
+//       n_days  R x rows';  member_dist  B x rows' (NaN: an absent member).
 //   [peak_value, peak_day, min_value, min_day, total, first_cross, days_above, longest_run, n_valid, n_paths, peak_day_hist, n_cross, cross_day_hist] = epiekf_pipeline_mex('pathfn', src, D, thr, population, first_day, k_first, k_last)
 //       Functionals of every joint path of a Monte-Carlo ensemble.  src, D, population  as 'ens_summary' takes
 //       them;  thr ([] = none)  R x rows' x n_thr (R x n_thr for a B x T src), at most 8 thresholds, NaN = not asked;  first_day
@@ -608,6 +614,86 @@ static void escore(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void jscore(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 11) mexErrMsgTxt("epiekf_pipeline_mex('jscore', src, truth, D, vs_p, max_lag, population, truth_series, first_day, k_first, k_last): 11 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1])) mexErrMsgTxt("src must be a double array B x rows x T (or B x T)");
+    const mwSize *ds = mxGetDimensions(prhs[1]);
+    const mwSize B = ds[0], rows = nd == 3 ? ds[1] : 1, T = nd == 3 ? ds[2] : ds[1];
+    const double Dd = mxGetScalar(prhs[3]);
+    if (!(Dd >= 1.0 && Dd <= 4096.0) || (double)(mwSize)Dd != Dd || B % (mwSize)Dd != 0) mexErrMsgTxt("D must be an integer in 1 .. 4096 that divides the number of chains");
+    const mwSize D = (mwSize)Dd, R = B / D;
+    const double p = mxIsEmpty(prhs[4]) ? 0.0 : mxGetScalar(prhs[4]);
+    if (p != 0.0 && p != 0.5 && p != 1.0) mexErrMsgTxt("vs_p must be [] or 0 (no variogram score), 0.5 or 1");
+    const double lag = mxIsEmpty(prhs[5]) ? 0.0 : mxGetScalar(prhs[5]);
+    if (!(lag >= 0.0 && lag <= 2147483647.0) || (double)(mwSize)lag != lag) mexErrMsgTxt("max_lag must be an integer >= 0");
+    const bool derive = !mxIsEmpty(prhs[6]);
+    if (derive && mxGetNumberOfElements(prhs[6]) != R) mexErrMsgTxt("population must have one entry per region");
+    const mwSize ro = rows + (derive ? 1 : 0);
+    const mwSize ndt = mxGetNumberOfDimensions(prhs[2]);
+    if (ndt > 3 || mxIsEmpty(prhs[2]) || !mxGetPr(prhs[2])) mexErrMsgTxt("truth must be a double array Rt x rows' x T (or Rt x T)");
+    const mwSize *dt = mxGetDimensions(prhs[2]);
+    const mwSize Rt = dt[0];
+    if (nd == 3 ? !((ndt == 3 && dt[1] == ro && dt[2] == T) || (ndt == 2 && T == 1 && dt[1] == ro)) : !(ndt == 2 && dt[1] == T && ro == 1))
+        mexErrMsgTxt("truth must be Rt x rows' x T (Rt x T for a B x T src), rows' = rows + 1 with a population");
+    std::vector<int32_t> ser, fd;
+    if (!mxIsEmpty(prhs[7])) {
+        if (mxGetNumberOfElements(prhs[7]) != R) mexErrMsgTxt("truth_series must have one entry per region");
+        ser.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[7])[r];
+            if (!(v >= 1.0 && v <= (double)Rt) || (double)(mwSize)v != v) mexErrMsgTxt("truth_series must hold ONE-based columns of truth");
+            ser[(size_t)r] = (int32_t)v - 1;
+        }
+    } else if (Rt != R) {
+        mexErrMsgTxt("truth must hold one column per region (or pass truth_series)");
+    }
+    if (!mxIsEmpty(prhs[8])) {
+        if (mxGetNumberOfElements(prhs[8]) != R) mexErrMsgTxt("first_day must have one entry per region");
+        fd.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[8])[r];
+            if (!(v >= 1.0 && v <= 2147483647.0) || (double)(mwSize)v != v) mexErrMsgTxt("first_day must hold ONE-based days");
+            fd[(size_t)r] = (int32_t)v - 1;
+        }
+    }
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[9])) kf = mxGetScalar(prhs[9]);
+    if (!mxIsEmpty(prhs[10])) kl = mxGetScalar(prhs[10]);
+    if (!(kf >= 1.0 && kf <= (double)T && kl >= kf - 1.0 && kl <= (double)T) || (double)(mwSize)kf != kf || (double)(mwSize)kl != kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= T and k_first - 1 <= k_last <= T");
+    epi_ejoint_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.rows = (int32_t)rows; d.R = (int32_t)R; d.D = (int32_t)D; d.Rt = (int32_t)Rt;
+    d.storage = 0; d.derive_newcases = derive ? 1 : 0; d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    d.vs_order = p == 0.5 ? 1 : (p == 1.0 ? 2 : 0); d.max_lag = (int32_t)lag;
+    epi_ejoint_inputs in;
+    memset(&in, 0, sizeof in);
+    in.src = mxGetPr(prhs[1]); in.population = derive ? mxGetPr(prhs[6]) : NULL; in.truth = mxGetPr(prhs[2]);
+    in.truth_series = ser.empty() ? NULL : ser.data(); in.first_day = fd.empty() ? NULL : fd.data();
+    // the ABI's [rows'][R] and [rows'][R * D] are MATLAB's R x rows' and B x rows': no transposition
+    mxArray *o[7];
+    for (int k = 0; k < 6; k++) o[k] = mxCreateDoubleMatrix(R, ro, mxREAL);
+    o[6] = mxCreateDoubleMatrix(B, ro, mxREAL);
+    const size_t cols = (size_t)(R * ro);
+    std::vector<int32_t> ibuf(2 * cols + 1);
+    epi_ejoint_outputs out;
+    memset(&out, 0, sizeof out);
+    out.es = mxGetPr(o[0]); out.vs = d.vs_order ? mxGetPr(o[1]) : NULL; out.truth_term = mxGetPr(o[2]); out.spread_term = mxGetPr(o[3]);
+    out.n_members = ibuf.data(); out.n_days = ibuf.data() + cols; out.member_dist = mxGetPr(o[6]);
+    char err[256] = {0};
+    const int rc = epi_ejoint_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < cols; k++) {
+        if (!d.vs_order) mxGetPr(o[1])[k] = std::numeric_limits<double>::quiet_NaN();
+        mxGetPr(o[4])[k] = (double)ibuf[k];
+        mxGetPr(o[5])[k] = (double)ibuf[cols + k];
+    }
+    for (int k = 0; k < 7; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void pathfn(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 8) mexErrMsgTxt("epiekf_pipeline_mex('pathfn', src, D, thr, population, first_day, k_first, k_last): 8 inputs expected");
@@ -985,6 +1071,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "escore") == 0) escore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "pathfn") == 0) pathfn(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "jscore") == 0) jscore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }

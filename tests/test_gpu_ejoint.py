@@ -1,0 +1,172 @@
+"""The joint scores on the device (epi_ejoint_run_device / _host, batch.ensemble_joint_score, hostapi.ensemble_joint_score,
+pipeline.fan_quality(joint=True)): every output word equal bit for bit (every NaN one value) to the sequential C restatement
+tests/ejoint_ref.c of DESIGN.md §4.20.  Outputs and workspace start as a finite sentinel and carry guard elements behind them."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import ejoint_ref as J
+
+pytestmark = pytest.mark.gpu
+
+FILL, I32_FILL, GUARD = -98765.4321, -12345, 8
+
+
+@pytest.fixture(scope="module")
+def cref(tmp_path_factory):
+    return J.EjointC(tmp_path_factory.mktemp("ejoint_ref_gpu"))
+
+
+def _run_device(src, truth, R, D, vs_order=0, max_lag=0, population=None, truth_series=None, first_day=None, k0=0, k1=None, names=None,
+                device="cuda:0", test_launch_tiles=0):
+    """epi_ejoint_run_device on sentinel-filled outputs and workspace with GUARD elements behind each; returns the dict of every
+    output (NumPy), those not named (never handed to the library) included"""
+    import torch
+    from epidemicmodeling_amd import _lib
+    dev = torch.device(device)
+    put = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+    sd = torch.as_tensor(np.ascontiguousarray(src), device=dev)
+    ins_t = (sd, put(population, np.float64), put(truth, np.float64), put(truth_series, np.int32), put(first_day, np.int32))
+    T, rows, _ = src.shape
+    d = _lib.make_ejoint_desc(T, rows, R, D, np.shape(truth)[2], vs_order, max_lag, storage=1 if src.dtype == np.float32 else 0,
+                              derive_newcases=int(population is not None), k0=k0, k1=k1, test_launch_tiles=test_launch_tiles)
+    shapes = _lib.ejoint_shapes(rows, R, D, d.derive_newcases)
+    names = _lib.ejoint_out_names(None, vs_order) if names is None else names
+    ins = _lib.EjointInputs()
+    for k, v in zip(_lib.EJOINT_IN_NAMES, ins_t):
+        setattr(ins, k, None if v is None else C.c_void_p(v.data_ptr()))
+    st = torch.cuda.current_stream(dev)
+    err = C.create_string_buffer(256)
+    n = C.c_size_t(0)
+    _lib.check(_lib.lib().epi_ejoint_workspace_bytes(C.byref(d), C.byref(n), err), err)
+    assert n.value % 4 == 0
+    ws = torch.full(((n.value + 7) // 8 + GUARD,), FILL, dtype=torch.float64, device=dev)
+    flat = {k: torch.full((int(np.prod(sh)) + GUARD,), I32_FILL if k in _lib.EJOINT_OUT_I32 else FILL,
+                          dtype=torch.int32 if k in _lib.EJOINT_OUT_I32 else torch.float64, device=dev) for k, sh in shapes.items()}
+    outs = _lib.EjointOutputs()
+    for k in _lib.EJOINT_OUT_NAMES:
+        setattr(outs, k, C.c_void_p(flat[k].data_ptr()) if k in names else None)
+    rc = _lib.lib().epi_ejoint_run_device(C.byref(d), C.byref(ins), C.byref(outs), C.c_void_p(ws.data_ptr()), n.value,
+                                          C.c_void_p(st.cuda_stream), err)
+    _lib.check(rc, err)
+    torch.cuda.synchronize(dev)
+    assert (ws[-GUARD:].cpu().numpy() == FILL).all(), "workspace guard elements overwritten"
+    out = {}
+    for k, sh in shapes.items():
+        a = flat[k].cpu().numpy()
+        fill = I32_FILL if k in _lib.EJOINT_OUT_I32 else FILL
+        assert (a[len(a) - GUARD:] == fill).all(), f"{k}: guard elements overwritten"
+        out[k] = a[:len(a) - GUARD].reshape(sh)
+        if k in names:
+            assert not (out[k] == fill).any(), f"{k}: a word left unwritten"
+        else:
+            assert (out[k] == fill).all(), f"{k}: written without being asked for"
+    return out
+
+
+def _same(got, want, names):
+    for k in names:
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, (k, g.shape, w.shape, g.dtype, w.dtype)
+        if not J.same_bits(g, w):
+            bad = ~((g == w) | (np.isnan(g) & np.isnan(w))) if g.dtype == np.float64 else g != w
+            raise AssertionError((k, np.argwhere(bad)[:4].tolist(), g[bad][:4], w[bad][:4]))
+
+
+@pytest.mark.parametrize("W", J.CASE_W)
+@pytest.mark.parametrize("D", J.CASE_D)
+def test_cases_equal_the_c_restatement(gpu_device, cref, D, W):
+    """D = 65: a tile with one member; 130: 6 tiles, a partial last block; 1: no pair; W = 33: past any 32-day chunk; float32
+    storage and the derived row in every case"""
+    for dtype in (np.float64, np.float32):
+        for variant in (0, 1):
+            c = J.case(D, W, dtype, variant)
+            for k, (vs_order, max_lag) in enumerate(((1, 0), (1, 1), (1, 5), (2, 0), (2, 1), (2, 5))):
+                names = J.NAMES if k == 0 else ("vs",)
+                got = _run_device(vs_order=vs_order, max_lag=max_lag, names=names, device=gpu_device, **c)
+                _same(got, cref.joint(vs_order=vs_order, max_lag=max_lag, **c), names)
+            und = (got["vs"] != got["vs"])
+            assert und[:, 1].all() and und[:, 2].all() == (variant == 0)       # undefined items come back NaN
+
+
+def test_every_output_alone_and_all_together(gpu_device, cref):
+    c = J.case(130, 33, np.float64, 1)
+    want = cref.joint(vs_order=2, max_lag=3, **c)
+    _same(_run_device(vs_order=2, max_lag=3, device=gpu_device, **c), want, J.NAMES)
+    for name in J.NAMES:                                                # _run_device checks that the others are left alone
+        _same(_run_device(vs_order=2, max_lag=3, names=(name,), device=gpu_device, **c), want, (name,))
+    got = _run_device(vs_order=0, device=gpu_device, **c)              # the default without a variogram score: vs is not written
+    _same(got, want, [k for k in J.NAMES if k != "vs"])
+    assert np.isnan(want["es"][:, 1]).all() and (got["n_days"][:, 1] == 0).all() and (got["n_members"][:, 1] == 130).all()
+    assert np.isnan(got["member_dist"][:, 130:260]).all()
+
+
+def test_launch_cut_equals_the_uncut_call(gpu_device, cref):
+    """3 items of 6 tiles in launches of 4 units (the pre-pass, the tiles and the days alike): the same bits as one launch each"""
+    rng = np.random.default_rng(4)
+    D, R, T = 130, 3, 9
+    src, truth = rng.standard_normal((T, 1, R * D)).astype(np.float32), rng.standard_normal((T, 1, R))
+    src[4, 0, 2 * D + 129] = np.nan                                     # region 2, the last block's last member
+    kw = dict(vs_order=1, max_lag=2, first_day=np.array([0, 3, 1], dtype=np.int32))
+    whole = _run_device(src, truth, R, D, device=gpu_device, **kw)
+    assert (D + 63) // 64 == 3 and 18 > 4 * 4
+    _same(_run_device(src, truth, R, D, device=gpu_device, test_launch_tiles=4, **kw), whole, J.NAMES)
+    _same(whole, cref.joint(src, truth, R, D, **kw), J.NAMES)
+    assert whole["n_members"].tolist() == [[130, 130, 129]] and whole["n_days"].tolist() == [[9, 6, 8]]
+
+
+def test_non_finite_members(gpu_device, cref):
+    rng = np.random.default_rng(6)
+    D, R, T = 65, 2, 5
+    src, truth = rng.standard_normal((T, 1, R * D)), rng.standard_normal((T, 1, R))
+    src[1, 0, [3, 64]] = [np.inf, -np.inf]                              # Inf - (-Inf) and Inf - Inf among the pairs
+    src[2, 0, D + 7] = np.inf
+    truth[2, 0, 1] = np.inf                                             # Inf - Inf against the truth: a present member with a NaN e_i
+    got = _run_device(src, truth, R, D, vs_order=2, device=gpu_device)
+    _same(got, cref.joint(src, truth, R, D, vs_order=2), J.NAMES)
+    assert (got["n_members"] == D).all() and got["es"][0, 0] != got["es"][0, 0] and np.isnan(got["member_dist"][0, D + 7])
+
+
+def test_hostapi_equals_batch_on_a_side_stream(gpu_device, cref):
+    import torch
+    from epidemicmodeling_amd import batch, hostapi
+    side = torch.cuda.Stream(device=gpu_device)
+    for dtype in (np.float64, np.float32):
+        c = J.case(130, 33, dtype, 0)
+        kw = {k: c[k] for k in ("population", "truth_series", "first_day", "k0", "k1")}
+        host = hostapi.ensemble_joint_score(c["src"], c["truth"], 3, 130, vs_p=0.5, max_lag=4, **kw)
+        src = torch.as_tensor(c["src"], device=gpu_device)
+        torch.cuda.synchronize(gpu_device)                              # the upload is on the default stream
+        dev = batch.ensemble_joint_score(src, c["truth"], 3, 130, vs_p=0.5, max_lag=4, stream=side, **kw)
+        side.synchronize()
+        assert list(host) == list(dev) == list(J.NAMES)
+        dev = {k: v.cpu().numpy() for k, v in dev.items()}
+        _same(host, dev, J.NAMES)
+        _same(host, cref.joint(vs_order=1, max_lag=4, **c), J.NAMES)
+    res = batch.ensemble_joint_score(src[:, 1], c["truth"][:, 1], 3, 130, truth_series=c["truth_series"], outputs=("n_days", "es"))
+    assert list(res) == ["es", "n_days"] and tuple(res["es"].shape) == (3,)
+    with pytest.raises(ValueError, match="EkfRunner.unblocked"):
+        batch.ensemble_joint_score(torch.zeros((4, 25, 2, 8), device=gpu_device), c["truth"], 3, 130)
+
+
+def test_fan_quality_joint(gpu_device):
+    import torch
+    from epidemicmodeling_amd import batch, pipeline, synth
+    Sg, LL, F, D, starts = 3, 40, 10, 65, (10, 4)
+    raw = synth.make_raw_counts(n_regions=Sg, T=LL, seed=3)
+    raw["cases"][:, -1] = np.cumsum(np.full(LL, 40.0))               # the all-NaN region of the generator: give it data
+    args = (raw["cases"], raw["deaths"], raw["population"], raw["ip"], F, starts)
+    plain = pipeline.fan_quality(*args, n_draws=D, seed=5, device=gpu_device)
+    out = pipeline.fan_quality(*args, n_draws=D, seed=5, device=gpu_device, joint=True, vs_p=0.5, max_lag=3)
+    joint_keys = {"joint_scores", "es", "vs", "n_days"}                 # joint=False returns exactly what it returned before
+    assert set(out) - set(plain) == joint_keys and set(plain) < set(out) and not joint_keys & set(plain)
+    B, k0, N = Sg * 2, out["k0"], np.asarray(raw["population"], dtype=np.float64)
+    rr = np.repeat(np.arange(Sg), 2)
+    tw = np.full((LL - k0, 4, Sg), np.nan)
+    tw[:, 3] = out["truth"][k0:]
+    direct = batch.ensemble_joint_score(out["X"], tw, B, D, vs_p=0.5, max_lag=3, population=N[rr], truth_series=rr.astype(np.int32),
+                                        first_day=out["origin"] - k0)
+    assert torch.equal(out["es"], direct["es"][3]) and torch.equal(out["vs"], direct["vs"][3])
+    assert out["n_days"].tolist() == [10, 4] * Sg and torch.isfinite(out["es"]).all() and (out["vs"] >= 0).all()
+    assert torch.isnan(direct["es"][:3]).all() and (direct["n_days"][:3] == 0).all()      # rows s, i, alpha carry no truth
