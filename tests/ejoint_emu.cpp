@@ -267,6 +267,13 @@ int main()
                     bad += run_case(c, 0, 0, 5, true);
                     cases += 4;
                 }
+    // D = 4 096: 64 blocks, 2 080 tiles an item, 24 960 tile units in launches of 1 003 (1 003 = 8 x 125 + 3: unequal groups of the
+    // block -> unit map, a boundary inside every item, a ragged last launch of 888); float storage, W = 2
+    {
+        const Case c = make_case(4096, 2, 1, 1);
+        bad += run_case(c, 1, 0, 1003, true);
+        cases += 1;
+    }
     if (bad) return 1;
     std::printf("ejoint emu ok: %d cases\n", cases);
     return 0;

@@ -168,3 +168,35 @@ def case(D, W, dtype, variant, seed=None):
     first_day = np.array([0, 0, k1] if variant == 0 else [k0 + 1, k1 + 2, 0], dtype=np.int32)
     return dict(src=src, truth=truth, R=R, D=D, population=pop, truth_series=np.array([0, 1, 0], dtype=np.int32), first_day=first_day,
                 k0=k0, k1=k1)
+
+
+# ---- the member-count grid: every register count NV of ejoint_launch's dispatch, every block count of ejoint_pairs ----
+nv_of = lambda D: max(64, 1 << (D - 1).bit_length()) // 64            # D <= 64: 1, <= 128: 2, .. <= 2048: 32, else 64
+nb_of = lambda D: (D + 63) // 64
+# the member counts of the CPU comparison of the two restatements beyond CASE_D: one of each of NV = 16, 32, 64
+BIG_D = (1000, 2000, 4096)
+
+
+def grid_absent(D):
+    """the members grid_case makes absent on one day beyond case()'s (region, row, member): for D > 64 the last member (the
+    last block) and, for D > 128, one of block 1 and one of the middle block -- blocks I, J > 0 whose mask words decide a bit"""
+    if D <= 64:
+        return []
+    nb = nb_of(D)
+    out = [(0, 1, D - 1), (2, 0, D - 1)]
+    if nb > 2:
+        out += [(0, 1, 64 + 5), (2, 0, (nb // 2) * 64 + 7)]
+    return out
+
+
+def grid_case(D, W, dtype, variant):
+    """case(D, W, dtype, variant) with the members of grid_absent(D) absent on one day of their items (W >= 2)"""
+    c = case(D, W, dtype, variant)
+    assert W >= 2
+    k0, k1 = c["k0"], c["k1"]
+    t_gap = k0 + (W + 1) // 2
+    t_abs = k1 - 1                                                      # a day of every defined item: W >= 2 keeps it off t_gap
+    assert t_abs != t_gap and t_abs >= k0 + 1
+    for r, row, e in grid_absent(D):
+        c["src"][t_abs, row, r * D + e] = np.nan
+    return c

@@ -2,7 +2,8 @@
 with tests/ejoint_ref.c into a stand-alone program with -fsanitize=address,undefined and run.  It runs the header's workspace
 layout, launch loop, block -> unit map, tile numbering and final pass on the restatement cases (D in 1, 2, 63, 64, 65, 130, 300; W
 in 1, 2, 33; both storages; both first_day variants), uncut and in launches of 4, 5 and 7 units, and compares every output with the
-C restatement bit for bit; a slot outside the workspace is a sanitizer report."""
+C restatement bit for bit, and one case of D = 4 096 (64 blocks, 2 080 tiles an item) in launches of 1 003 units, a size that is no
+multiple of 8; a slot outside the workspace is a sanitizer report."""
 import os
 import shutil
 import subprocess
@@ -26,4 +27,4 @@ def test_final_pass_and_unit_arithmetic_equal_the_c_restatement(tmp_path):
                     os.path.join(H.ROOT, "tests", "ejoint_emu.cpp"), ref_o, "-o", exe, "-lm"], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, stdin=subprocess.DEVNULL)
     print(r.stdout)
-    assert r.returncode == 0 and "ejoint emu ok: 336 cases" in r.stdout and not r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "ejoint emu ok: 337 cases" in r.stdout and not r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -39,6 +39,42 @@ def test_restatements_agree(cref, D, W):
                 assert want["n_members"][1, 0] == D - 1 and want["n_members"][0, 0] == D and want["n_members"][3, 0] == D - 1
 
 
+@pytest.mark.parametrize("D", J.BIG_D)
+def test_restatements_agree_at_16_32_and_64_registers(cref, D):
+    """one D of each of NV = 16, 32, 64 (1 000: the workload's instantiation; 4 096: 64 blocks, 2 080 tiles), W = 2, both storages,
+    the grid's case with its absent members in the last and in middle blocks.  NumPy takes about a second an item at 4 096."""
+    assert {J.nv_of(d) for d in J.BIG_D} == {16, 32, 64}
+    for dtype in (np.float64, np.float32):
+        c = J.grid_case(D, 2, dtype, 1)
+        for k, (vs_order, max_lag) in enumerate(((1, 0), (2, 5))):
+            want = J.joint(vs_order=vs_order, max_lag=max_lag, parts=("es", "vs") if k == 0 else ("vs",), **c)
+            got = cref.joint(vs_order=vs_order, max_lag=max_lag, **c)
+            for name in J.NAMES if k == 0 else ("vs", "n_members", "n_days", "truth_term", "member_dist"):
+                assert J.same_bits(got[name], want[name]), (name, dtype, vs_order, max_lag)
+        assert want["n_members"][1, 0] == D - 3 and want["n_members"][0, 2] == D - 2 and (want["n_days"][:, 2] == 2).all()
+
+
+def test_the_gpu_grid_reaches_every_instantiation():
+    """What tests/test_gpu_ejoint.py's member-count grid (GRID_D of tests/test_gpu_ens_summary.py x both storages, every case
+    asking for member_dist, es and vs) covers of ejoint_launch's dispatch (D <= 64: ejoint_members<1, S> and ejoint_vario<1, S>,
+    <= 128: <2, S>, .. <= 2048: <32, S>, else <64, S>): all seven NV, each on its edge and one past the edge below it, so 7 x 2
+    storages x 2 kernels = 28 instantiations; and ejoint_pairs at every block count its tile walk and mask reads differ at.  Thinning
+    the grid fails here, without a device."""
+    from tests.test_gpu_ens_summary import GRID_D
+    assert {J.nv_of(D) for D in GRID_D} == {1, 2, 4, 8, 16, 32, 64}
+    for edge in (64, 128, 256, 512, 1024, 2048):
+        assert edge in GRID_D and edge + 1 in GRID_D and J.nv_of(edge + 1) == 2 * J.nv_of(edge), edge
+    assert 1 in GRID_D and 4096 in GRID_D                                # validate's ends: 1 .. kEnsMaxD
+    assert {1, 2, 3, 5, 16, 17, 33, 64} <= {J.nb_of(D) for D in GRID_D}  # 1, 3, 6, 15, 136, 153, 561, 2 080 tiles
+    for n in (2, 8, 16, 32, 64):
+        assert any(J.nv_of(D) == n and D % 64 for D in GRID_D), n        # with a partly filled last block
+    for D in GRID_D:                                                     # the absent members: inside the item, the last block and,
+        blocks = {e // 64 for _, _, e in J.grid_absent(D)}               # from three blocks on, one strictly between
+        assert all(0 <= e < D for _, _, e in J.grid_absent(D)) and (D <= 64 or J.nb_of(D) - 1 in blocks and 0 not in blocks)
+        assert J.nb_of(D) < 3 or len(blocks) == 3 or J.nb_of(D) == 3 and len(blocks) == 2
+        assert D // 2 not in {e for _, _, e in J.grid_absent(D)}         # case()'s own absent member is another one
+
+
 def brute(x, y, days, vs_order, max_lag):
     """x [W, n] the present members, y [W]: es, truth_term and vs by broadcast double sums added with math.fsum"""
     n = x.shape[1]

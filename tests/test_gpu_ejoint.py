@@ -1,12 +1,19 @@
 """The joint scores on the device (epi_ejoint_run_device / _host, batch.ensemble_joint_score, hostapi.ensemble_joint_score,
 pipeline.fan_quality(joint=True)): every output word equal bit for bit (every NaN one value) to the sequential C restatement
-tests/ejoint_ref.c of DESIGN.md §4.20.  Outputs and workspace start as a finite sentinel and carry guard elements behind them."""
+tests/ejoint_ref.c of DESIGN.md §4.20.  Outputs and workspace start as a finite sentinel and carry guard elements behind them.
+
+The member-count grid runs every instantiation of ejoint_launch's dispatch (tests/test_ejoint_ref.py asserts, without a device,
+what it covers).  That it bites: with D <= 2048 dispatched to NV = 16 in a scratch build, the grid fails at 1 025, 2 000 and
+2 048 in both storages on "member_dist: a word left unwritten" and passes at every other D, and the launch cut at D = 1 025 fails;
+with ej = I * 64 + lane in ejoint_pairs, the grid fails at every D from 65 on and passes at 1 .. 64 (es and spread_term of every
+defined item differ).  tests/test_gpu_ejoint_limits.py lists all five such mutations."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from tests import ejoint_ref as J
+from tests.test_gpu_ens_summary import GRID_D
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +95,89 @@ def test_cases_equal_the_c_restatement(gpu_device, cref, D, W):
                 _same(got, cref.joint(vs_order=vs_order, max_lag=max_lag, **c), names)
             und = (got["vs"] != got["vs"])
             assert und[:, 1].all() and und[:, 2].all() == (variant == 0)       # undefined items come back NaN
+
+
+def _grid_runs(D):
+    """(W, variant, the (vs_order, max_lag) pairs) of one grid case.  Below D = 2 048: W in {2, 33}, both first_day variants, both
+    pairs.  From D = 2 048 on the C restatement takes 0.4 - 3.1 s a call at W = 33 (8.4 M pairs of 33 days per item at 4 096), so
+    both variants and both pairs run at W in {2, 5} and W = 33 keeps one call (variant 0, the first pair): 3 s a case at 4 096."""
+    pairs = ((1, 0), (2, 5))
+    if D < 2048:
+        return [(W, variant, pairs) for W in (2, 33) for variant in (0, 1)]
+    return [(W, variant, pairs) for W in (2, 5) for variant in (0, 1)] + [(33, 0, pairs[:1])]
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32"])
+@pytest.mark.parametrize("D", GRID_D)
+def test_member_count_grid_equals_the_c_restatement(gpu_device, cref, D, storage):
+    """Every NV = 1 .. 64 of ejoint_members / ejoint_vario in both storages, on and one past every edge of the dispatch, and
+    ejoint_pairs at 1 .. 64 blocks (tests/test_ejoint_ref.py asserts what the grid covers): J.grid_case, whose absent members lie
+    in the last block and in blocks between (J.grid_absent), so that mask words with I, J > 0 decide bits of spread_term; vs_order
+    1 with every lag (every output) and vs_order 2 with max_lag 5 (vs alone).  W as _grid_runs gives it."""
+    dtype = np.float64 if storage == "f64" else np.float32
+    for W, variant, pairs in _grid_runs(D):
+        c = J.grid_case(D, W, dtype, variant)
+        for k, (vs_order, max_lag) in enumerate(pairs):
+            names = J.NAMES if k == 0 else ("vs",)
+            got = _run_device(vs_order=vs_order, max_lag=max_lag, names=names, device=gpu_device, **c)
+            want = cref.joint(vs_order=vs_order, max_lag=max_lag, **c)
+            _same(got, want, names)
+            if k == 0:
+                absent = sum(1 for r, row, _ in J.grid_absent(D) if (r, row) == (0, 1))
+                assert got["n_members"][1, 0] == D - absent - (D > 1) and got["n_members"][0, 0] == D
+                assert np.isfinite(got["es"][:, 0]).all() and (got["n_members"][:, 1] * got["n_days"][:, 1] == 0).all()
+                if variant == 1 and D > 64:
+                    assert got["n_members"][0, 2] == D - len(J.grid_absent(D)) // 2 and np.isfinite(got["spread_term"][0, 2])
+
+
+def test_launch_cut_at_seventeen_blocks(gpu_device, cref):
+    """D = 1 025: 17 blocks, 153 tiles an item, the last block holding one member.  Launches of 100 units: the cap divides neither
+    the 153 tiles of an item nor the 459 tile units nor the 27 day units, and 100 = 8 x 12 + 4 gives ejoint_swizzle unequal groups
+    (so does the last launch of 59).  The same bits as the uncut call and as the restatement."""
+    rng = np.random.default_rng(1025)
+    D, R, T = 1025, 3, 9
+    src, truth = rng.standard_normal((T, 1, R * D)).astype(np.float32), rng.standard_normal((T, 1, R))
+    src[4, 0, 2 * D + 1024] = np.nan                                    # region 2: the last block's only member is absent
+    src[6, 0, 0 * D + 700] = np.nan                                     # region 0: a member of block 10
+    kw = dict(vs_order=1, max_lag=2, first_day=np.array([0, 3, 1], dtype=np.int32))
+    assert (D + 63) // 64 == 17 and 153 % 100 and (3 * 153) % 100 and (3 * T) % 100 and 100 % 8 and (3 * 153 % 100) % 8
+    whole = _run_device(src, truth, R, D, device=gpu_device, **kw)
+    _same(_run_device(src, truth, R, D, device=gpu_device, test_launch_tiles=100, **kw), whole, J.NAMES)
+    _same(whole, cref.joint(src, truth, R, D, **kw), J.NAMES)
+    assert whole["n_members"].tolist() == [[1024, 1025, 1024]] and whole["n_days"].tolist() == [[9, 6, 8]]
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32"])
+def test_non_finite_members_at_64_registers(gpu_device, cref, storage):
+    """D = 4 096 (NV = 64, 64 blocks): Inf and -Inf in blocks 3 and 40 of one item (Inf - (-Inf) and Inf - Inf among the pairs of
+    the tiles (3, 3), (3, 40), (40, 40) and of every tile that holds one of the two blocks), and an Inf member against an Inf
+    truth in block 63 of the other: a present member with a NaN e_i."""
+    rng = np.random.default_rng(4096)
+    D, R, T = 4096, 2, 4
+    src = rng.standard_normal((T, 1, R * D)).astype(np.float64 if storage == "f64" else np.float32)
+    truth = rng.standard_normal((T, 1, R))
+    src[1, 0, [3 * 64 + 9, 40 * 64 + 63]] = [np.inf, -np.inf]
+    src[2, 0, [3 * 64 + 10, 40 * 64]] = np.inf                          # two +Inf on one day: Inf - Inf, a NaN pair
+    src[2, 0, D + 63 * 64 + 5] = np.inf
+    truth[2, 0, 1] = np.inf
+    got = _run_device(src, truth, R, D, vs_order=2, device=gpu_device)
+    _same(got, cref.joint(src, truth, R, D, vs_order=2), J.NAMES)
+    assert (got["n_members"] == D).all() and np.isnan(got["es"]).all() and np.isnan(got["member_dist"][0, D + 63 * 64 + 5])
+    assert np.isinf(got["member_dist"][0, 3 * 64 + 9]) and np.isfinite(got["member_dist"][0, :64]).all()
+
+
+@pytest.mark.parametrize("D", (130, 4096))
+def test_an_empty_window(gpu_device, cref, D):
+    """k0 == k1: wcap = 0, the day list and the v_s are empty arrays of the workspace, the variogram launch is skipped.  Every
+    floating output is NaN, n_days 0, n_members D (no day on which a member could be absent); _run_device holds the guards."""
+    for dtype in (np.float64, np.float32):
+        c = J.case(D, 2, dtype, 0)
+        c.update(k0=2, k1=2)
+        got = _run_device(vs_order=1, max_lag=3, device=gpu_device, **c)
+        _same(got, cref.joint(vs_order=1, max_lag=3, **c), J.NAMES)
+        for k in J.F64 + ("member_dist",):
+            assert np.isnan(got[k]).all(), k
+        assert (got["n_days"] == 0).all() and (got["n_members"] == D).all()
 
 
 def test_every_output_alone_and_all_together(gpu_device, cref):
