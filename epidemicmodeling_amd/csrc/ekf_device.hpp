@@ -384,6 +384,42 @@ EPI_DEV double slope_term(const PRM &p, const double (&u)[kNpi], const double (&
     }
     return a36;
 }
+// slope_term() and resolve_control() of a column in which EVERY one of the twelve controls is free (a horizon day of the sweep), as
+// one pass without a NaN test: phi(k) is formed once and serves the slope test and the substitution, the four 12-vectors are read
+// once.  Every value comes from the operations those two perform, in their order -- a36 takes its terms k ascending, the control
+// applied is folded into dot = (gamma a') (u_max - u) as nlin_state_update() folds it -- so the results are theirs bit for bit.
+template <int M, int FLIP, class PRM>
+EPI_DEV void all_free_slope_and_dot(const PRM &p, const ModelFlags &mf, const double (&s)[M], double &a36, double &dot)
+{
+    const double dt = p.dt;
+    const double gs6 = p.gamma * s[M == 6 ? 5 : 0];
+    const double inv_sigma = 1.0 / p.sigma;
+    a36 = 0.0;
+    dot = 0.0;
+#pragma unroll
+    for (int k = 0; k < kNpi; k++) {
+        const double ak = p.A(k), wk = p.W(k), lo_k = p.Umin(k), hi_k = p.Umax(k);
+        const double phi = p.epsilon * wk - gs6 * ak;
+        const double term = p.gamma * dt * (p.sigma / 2.0) * ak * (hi_k - lo_k);
+        const double with_term = FLIP ? (a36 + term) : (a36 - term);
+        a36 = (phi > -inv_sigma && phi < inv_sigma) ? with_term : a36;
+        const bool lo = mf.phi_ge ? (phi >= 0.0) : (phi > 0.0);
+        const double uk = lo ? lo_k : hi_k;
+        dot = k == 0 ? (p.gamma * ak) * (hi_k - uk) : fma(p.gamma * ak, hi_k - uk, dot);
+    }
+}
+// resolve_control() of such a column: put(k, u(k)) receives every control, k ascending
+template <int M, class PRM, class PUT>
+EPI_DEV void all_free_resolve(const PRM &p, const ModelFlags &mf, const double (&s)[M], PUT put)
+{
+    const double gs6 = p.gamma * s[M == 6 ? 5 : 0];
+#pragma unroll
+    for (int k = 0; k < kNpi; k++) {
+        const double phi = p.epsilon * p.W(k) - gs6 * p.A(k);
+        const bool lo = mf.phi_ge ? (phi >= 0.0) : (phi > 0.0);
+        put(k, lo ? p.Umin(k) : p.Umax(k));
+    }
+}
 template <int M, int FLIP, class PRM>
 EPI_DEV void jacobian_entries(const PRM &p, const double (&s)[M], double a36, double (&A)[M * M]);
 template <int M, int FLIP, class PRM>

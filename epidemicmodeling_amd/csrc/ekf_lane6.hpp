@@ -14,7 +14,9 @@
 //     check, no store sits behind a branch;
 //   * the bang-bang substitution and the slope term of A(3,6) (OptControlled.m:49-58,107-114) test every control for NaN in
 //     EVERY lane: 36 exec-mask branches a day.  A wave now asks once a day whether ANY of its lanes has a free control (the sum
-//     of the twelve is NaN iff one of them is) and skips all of them on historic days with one scalar branch;
+//     of the twelve is NaN iff one of them is) and skips all of them on historic days with one scalar branch; where the answer is
+//     yes it asks whether EVERY control of every lane is free -- the sweep's horizon days -- and then runs the substitutions and the
+//     slope term as one pass without tests (all_free_slope_and_dot, all_free_resolve: ekf_device.hpp), phi(k) formed once for both;
 //   * the smoother does NOT read s(k+1|k), P(k+1|k) back (27 of its 75 loads a step, 8.4 GB of the headline pass):
 //     P+ A', which the gain needs anyway, is (A P+)' bit for bit (P+ is symmetric bit for bit and a product commutes), so
 //     P(k+1|k) = sym((A P+) A' + Q) costs one more 6 x 6 product with A's 21 non-zeros, not two -- the forward kernel's own
@@ -125,6 +127,16 @@ EPI_DEV bool lw_wave_has_free_control(const double (&u)[kNpi])
 {
     const double s = ((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7])) + ((u[8] + u[9]) + (u[10] + u[11]));
     return __builtin_amdgcn_ballot_w64(is_nan(s)) != 0ull;
+}
+// "is every one of the twelve controls free in every live lane?" -- a horizon day of the sweep (synth.make_cfg4, the prescriber's own
+// call: u(:, T_hist + 1 : T) = NaN).  Asked only where the question above was answered yes, so a historic day does not pay for it.
+// Rows k >= n_npi are padded with 0.0 (load_u), so the answer can be yes at n_npi == 12 only.
+EPI_DEV bool lw_wave_all_controls_free(const double (&u)[kNpi])
+{
+    bool all = is_nan(u[0]);
+#pragma unroll
+    for (int k = 1; k < kNpi; k++) all = all & is_nan(u[k]);
+    return __builtin_amdgcn_ballot_w64(!all) == 0ull;
 }
 
 // P(k+1|k) = sym(A P+ A' + Q) from PA = P+ A' (row-major: PA[6 q + i] = (P+ A')(q, i) == (A P+)(i, q)): predict_cov_sym's second
@@ -339,17 +351,26 @@ __global__ __launch_bounds__(kWave) void eks_bwd_lane6(const KArgs a, const int 
         for (int q = 0; q < kNpi; q++) l_upend[q * BLK] = cur.u[q];
 
         // A = StateJacobians(u, s+) :206; the slope term and the bang-bang substitution only where some lane has a free control
+        // and, where EVERY control of every lane is free (the horizon days of the sweep), both as one pass without tests
         const bool wave_free = lw_wave_has_free_control(cur.u);
+        const bool wave_all = wave_free && lw_wave_all_controls_free(cur.u);
         double A[M * M];
-        jacobian_entries<M, FLIP>(p, cur.Sp, wave_free ? slope_term<M, FLIP>(p, cur.u, cur.Sp) : 0.0, A);
-        {                      // s(k+1|k) = StateHardMargins(NlinStateUpdate(u, s+)) :155,164
-            double u_app[kNpi];
+        {
+            double a36 = 0.0, dot;                             // the slope term of A(3,6); (gamma a') (u_max - u) of the control applied
+            if (wave_all) {
+                all_free_slope_and_dot<M, FLIP>(p, a.mf, cur.Sp, a36, dot);
+            } else {
+                if (wave_free) a36 = slope_term<M, FLIP>(p, cur.u, cur.Sp);
+                double u_app[kNpi];
 #pragma unroll
-            for (int q = 0; q < kNpi; q++) u_app[q] = cur.u[q];
-            if (wave_free) resolve_control<M>(p, a.mf, cur.Sp, u_app);
-            double dot = (p.gamma * p.A(0)) * (p.Umax(0) - u_app[0]);
+                for (int q = 0; q < kNpi; q++) u_app[q] = cur.u[q];
+                if (wave_free) resolve_control<M>(p, a.mf, cur.Sp, u_app);
+                dot = (p.gamma * p.A(0)) * (p.Umax(0) - u_app[0]);
 #pragma unroll
-            for (int q = 1; q < kNpi; q++) dot = fma(p.gamma * p.A(q), p.Umax(q) - u_app[q], dot);
+                for (int q = 1; q < kNpi; q++) dot = fma(p.gamma * p.A(q), p.Umax(q) - u_app[q], dot);
+            }
+            jacobian_entries<M, FLIP>(p, cur.Sp, a36, A);
+            // s(k+1|k) = StateHardMargins(NlinStateUpdate(u, s+)) :155,164
             state_map<M, FLIP>(p, dot, cur.Sp, Sm1);
             state_hard_margins<M>(p, Sm1);
         }
@@ -463,7 +484,9 @@ __global__ __launch_bounds__(kWave) void eks_bwd_lane6(const KArgs a, const int 
             }
         }
         pin_u();
-        if (wave_free) {       // :229 -- only the control NlinStateUpdate returns is kept: the free ones, resolved with the smoothed costate
+        if (wave_all) {        // :229 where every control is free: each goes to its park as it is resolved, nothing is read back
+            all_free_resolve<M>(p, a.mf, Ss, [&](int q, double v) __attribute__((always_inline)) { l_upend[q * BLK] = v; });
+        } else if (wave_free) {       // :229 -- only the control NlinStateUpdate returns is kept: the free ones, resolved with the smoothed costate
             double u_pend[kNpi];
             const double *lu = vlds + 4 * kNpi * BLK + lw_opaque(lane);
 #pragma unroll
