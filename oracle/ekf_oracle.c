@@ -153,9 +153,11 @@ static double eps_of(double x) /* MATLAB eps(x) for finite x >= 0 */
 
 #define ORC_JACOBI_MAX_SWEEPS 50
 
-static void jacobi_eig(int m, double *a /* in: sym matrix (destroyed) */, double *d, double *v, int skip_dead)
+/* returns 1 if the iteration ended at the sweep cap, not on a sweep whose off-diagonal sum was zero */
+static int jacobi_eig(int m, double *a /* in: sym matrix (destroyed) */, double *d, double *v, int skip_dead)
 {
     double b[MM], z[MM];
+    int capped = 1;
     for (int j = 0; j < m; j++)
         for (int i = 0; i < m; i++) v[IX(i, j, m)] = (i == j) ? 1.0 : 0.0;
     for (int i = 0; i < m; i++) {
@@ -184,7 +186,7 @@ static void jacobi_eig(int m, double *a /* in: sym matrix (destroyed) */, double
                 la[IX(p, q, m)] = (dead[p] && dead[q]) || (dead[p] != dead[q] && (dl + 100.0 * fabs(apq)) == dl);
                 if (!la[IX(p, q, m)]) sm = sm + fabs(apq);
             }
-        if (sm == 0.0) break;
+        if (sm == 0.0) { capped = 0; break; }
         double tresh = (sweep < 4) ? 0.2 * sm / (double)(m * m) : 0.0;
         for (int p = 0; p < m - 1; p++)
             for (int q = p + 1; q < m; q++) {
@@ -236,12 +238,14 @@ static void jacobi_eig(int m, double *a /* in: sym matrix (destroyed) */, double
             z[i] = 0.0;
         }
     }
+    return capped;
 }
 
 /* MATLAB pinv of a symmetric matrix through the eigen-decomposition by two-sided cyclic Jacobi (jacobi_eig above): valid
  * for ANY symmetric matrix.  orc_sym_pinv uses it for the matrices its faster route declines (indefinite ones). */
-static int sym_pinv_two_sided(int m, const double *A, double *X)
+static int sym_pinv_two_sided(int m, const double *A, double *X, int *capped)
 {
+    if (capped) *capped = 0;
     double a[MM * MM], d[MM], v[MM * MM];
     double amax = 0.0;
     for (int i = 0; i < m * m; i++) amax = fmax(amax, fabs(A[i]));
@@ -251,7 +255,8 @@ static int sym_pinv_two_sided(int m, const double *A, double *X)
     /* only the upper triangle (i<=j) is referenced, as the iteration does */
     for (int j = 0; j < m; j++)
         for (int i = 0; i < m; i++) a[IX(i, j, m)] = ldexp(A[IX(i <= j ? i : j, i <= j ? j : i, m)], -e);
-    jacobi_eig(m, a, d, v, m > 3); /* the eigenpairs below tol are discarded right below; 3 x 3: plain iteration */
+    const int cap = jacobi_eig(m, a, d, v, m > 3); /* the eigenpairs below tol are discarded right below; 3 x 3: plain iteration */
+    if (capped) *capped = cap;
     double smax = 0.0;
     for (int i = 0; i < m; i++) smax = fmax(smax, fabs(d[i]));
     double tol = (double)m * eps_of(smax);
@@ -297,11 +302,13 @@ static int sym_pinv_two_sided(int m, const double *A, double *X)
  * and both stand at the same distance from a LAPACK SVD evaluation (tests/test_oracle.py). */
 #define ORC_PINV_MAX_SWEEPS 30
 /* route (may be NULL): 0 = factorisation + one-sided Jacobi, 1 = handed to the two-sided Jacobi, 2 = full rank certified: the
- * inverse from the factor; sweeps (may be NULL): one-sided sweeps run (the last one finds nothing to rotate) */
-int orc_sym_pinv_ex(int m, const double *A, double *X, int *route, int *sweeps)
+ * inverse from the factor; sweeps (may be NULL): one-sided sweeps run (the last one finds nothing to rotate); capped (may be
+ * NULL): 1 if a Jacobi iteration, one-sided or two-sided, ended at its sweep cap and not because it had converged */
+int orc_sym_pinv_cap(int m, const double *A, double *X, int *route, int *sweeps, int *capped)
 {
     if (route) *route = 0;
     if (sweeps) *sweeps = 0;
+    if (capped) *capped = 0;
     double a[MM * MM], G[MM * MM];
     double amax = 0.0;
     for (int i = 0; i < m * m; i++) amax = fmax(amax, fabs(A[i]));
@@ -358,7 +365,7 @@ int orc_sym_pinv_ex(int m, const double *A, double *X, int *route, int *sweeps)
     }
     if (indefinite) {
         if (route) *route = 1;
-        return sym_pinv_two_sided(m, A, X);
+        return sym_pinv_two_sided(m, A, X, capped);
     }
     if (r == m) {
         /* Every index has been a pivot: A is positive definite as far as the factorisation can tell, and if ALL its
@@ -426,6 +433,7 @@ int orc_sym_pinv_ex(int m, const double *A, double *X, int *route, int *sweeps)
                 }
             }
         if (!rotated) break;
+        if (sweep == ORC_PINV_MAX_SWEEPS && capped) *capped = 1;
     }
     double lam[MM], lmax = 0.0;
     for (int k = 0; k < r; k++) {
@@ -451,6 +459,8 @@ int orc_sym_pinv_ex(int m, const double *A, double *X, int *route, int *sweeps)
         }
     return rank;
 }
+
+int orc_sym_pinv_ex(int m, const double *A, double *X, int *route, int *sweeps) { return orc_sym_pinv_cap(m, A, X, route, sweeps, NULL); }
 
 int orc_sym_pinv(int m, const double *A, double *X) { return orc_sym_pinv_ex(m, A, X, NULL, NULL); }
 

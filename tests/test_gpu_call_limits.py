@@ -477,7 +477,7 @@ def test_two_filter_past_one_launch(gpu_device, m, B, lane_block, storage, form,
     # status is OR-ed over all T days of a chain, so the sample cannot predict it: no item is non-finite (bit 0 stays clear in
     # every chain), but the one-sided Jacobi iteration of the pseudo-inverse runs into its 30-sweep cap on ~1.3e-4 of these
     # integer matrices (diag(0, [13 6; 6 8]) is one: the oracle's orc_sym_pinv_ex reports 30 sweeps for it too, with the same
-    # bits), which the call reports in bit 1 and the restatement cannot see
+    # bits), which the call reports in bit 1; the restatement reports it too, but only for the sampled days it is run on
     st = out["status"].cpu().numpy()
     assert st.shape == (B,) and not (st & ~_lib.FUSE_SWEEP_CAP).any(), st
     _report(f"two_filter m={m} B={B} lane_block={lane_block} {storage} form={form} p_solver={p_solver} T={T} (2 launches), "

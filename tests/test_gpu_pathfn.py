@@ -53,7 +53,7 @@ def _run_device(src, R, D, thr=None, population=None, first_day=None, k0=0, k1=N
     _lib.check(_lib.lib().epi_pathfn_workspace_bytes(C.byref(d), C.byref(n), err), err)
     runs = []
     for _ in range(calls):
-        ws = torch.full((n.value // 8 + GUARD,), FILL, dtype=torch.float64, device=dev)
+        ws = torch.full(((n.value + 7) // 8 + GUARD,), FILL, dtype=torch.float64, device=dev)   # n is a multiple of 4, not always of 8
         flat = {k: torch.full((int(np.prod(sh)) + GUARD,), I32_FILL if k in _lib.PATHFN_OUT_I32 else FILL,
                               dtype=torch.int32 if k in _lib.PATHFN_OUT_I32 else torch.float64, device=dev) for k, sh in shapes.items()}
         outs = _lib.PathfnOutputs()
@@ -249,3 +249,23 @@ def test_counts_alone_over_a_window_longer_than_the_bins(gpu_device, cref):
     assert list(want["n_paths"][0]) == [3, 2] and list(want["n_cross"][0, 0]) == [3, 0]
     with pytest.raises(_lib.EpiError, match="at most 4096 days"):
         _run_device(src, 2, 3, thr, device=gpu_device)
+
+
+def test_a_workspace_that_ends_on_half_a_double(gpu_device, cref):
+    """The shape a random hunt met (tests/test_gpu_fuzz_calls.py, seed 18 of its first run): 68 days in the library's own
+    three segments, 5 rows' x 63 paths, two thresholds.  The workspace's int32 tail then holds an odd number of words, so its
+    size is a multiple of 4 and not of 8, and a helper that sized the guarded workspace with bytes // 8 took the call's last
+    word for a write behind its end.  Every output against the C restatement; the guards hold."""
+    import ctypes as C
+    from epidemicmodeling_amd import _lib
+    rng = np.random.default_rng(18)
+    T, rows, R, D = 68, 4, 1, 63
+    src = rng.standard_normal((T, rows, R * D)) * 10.0 ** rng.uniform(-2, 2, size=(T, rows, 1))
+    pop = np.array([2.0e4])
+    thr = rng.standard_normal((2, rows + 1, R))
+    kw = dict(src=src, R=R, D=D, thr=thr, population=pop, first_day=np.array([18], dtype=np.int32), k0=0, k1=T)
+    d = _lib.make_pathfn_desc(T, rows, R, D, 2, storage=0, derive_newcases=1, k0=0, k1=T)
+    n, err = C.c_size_t(0), C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_pathfn_workspace_bytes(C.byref(d), C.byref(n), err), err)
+    assert n.value % 8 == 4
+    _same(_run_device(device=gpu_device, **kw), cref.functionals(**kw))

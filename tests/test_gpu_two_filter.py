@@ -1,8 +1,8 @@
 """The forward-backward filter fusion on the device (epi_fuse_run_device / _host, batch.two_filter, hostapi.two_filter,
 pipeline.two_filter_smooth): s, P, d2, rank and status equal bit for bit -- any NaN equal to any NaN -- to the restatement
 tests/two_filter_ref.py of DESIGN.md §4.9.  Every output starts as a poison value and carries guard elements; the
-restatement's results are computed once per case and shared.  (The restatement cannot see a Jacobi sweep cap, so equality
-of status also asserts that no item of these cases hit one.)"""
+restatement's results are computed once per case and shared.  Bit 1 of status (a Jacobi sweep cap) is the restatement's too:
+the oracle's iteration has the kernel's caps and reports them (test_an_item_at_the_sweep_cap)."""
 import ctypes as C
 import functools
 
@@ -68,7 +68,7 @@ def _run_device(arrs, m, B, T, form, p_solver, storage="f64", blk=0, outputs=Non
         poison = I32_FILL if h.dtype == np.int32 else h.dtype.type(FILL)
         ok = bool((h[n:] == poison).all())
         a = h[:n].reshape(shapes[k])
-        if blk and k in ("s_out", "P_out"):
+        if blk and k in ("s_out", "P_out") and a.ndim == 4:   # lane_block = B is the classic layout: one block, no padding
             Tn, nblk, rows, bl = a.shape
             pad = a.transpose(0, 2, 1, 3).reshape(Tn, rows, nblk * bl)[:, :, B:]
             ok = ok and bool((pad == poison).all())
@@ -231,3 +231,18 @@ def test_host_entry_point(gpu_device):
         got = hostapi.two_filter(*(a.astype(dt) for a in arrs), form=0, p_solver=0)
         for k in ("s", "P", "d2", "rank", "status"):
             assert TF.same_bits(got[k], want[k]), (storage, k)
+
+
+@pytest.mark.parametrize("form, p_solver", FORMS)
+def test_an_item_at_the_sweep_cap(gpu_device, form, p_solver):
+    """TF.CAPPED, the example a random hunt met: item (day 12, chain 5) runs the one-sided Jacobi iteration to its 30th sweep.
+    Every output bit for bit, status exactly [0 0 0 1 0 2 0 ...] in double storage (bit 0: the planted non-finite item of
+    chain 3) and without bit 1 in float storage, classic and chain-blocked."""
+    m, T, B, seed = TF.CAPPED
+    arrs = TF.planted(m, T, B, seed)
+    for storage, st5 in (("f64", 2), ("f32", 0)):
+        want = TF.fuse(*arrs, form, p_solver, storage=storage)
+        assert list(want["status"]) == [0, 0, 0, 1, 0, st5] + [0] * 8
+        for blk in (0, 8):
+            got, clean = _run_device(arrs, m, B, T, form, p_solver, storage=storage, blk=blk, device=gpu_device)
+            _assert_equal(got, clean, want, f"form={form} p_solver={p_solver} {storage} blk={blk}")

@@ -207,3 +207,17 @@ def test_blocked_layout_round_trip():
     # element (t, row, c) at ((t * nblk + c / blk) * rows + row) * blk + c % blk
     t, row, c = 1, 2, 5
     assert b.ravel()[((t * 2 + c // 4) * 3 + row) * 4 + c % 4] == a[t, row, c]
+
+
+def test_a_sweep_cap_sets_bit_1_of_its_chain_only():
+    """TF.CAPPED: the one-sided Jacobi iteration of item (12, 5) ends at its 30th sweep still rotating; bit 1 of chain 5 and of no
+    other chain, in every form, and the item's values are finite all the same.  Rounded to float the item converges: no bit."""
+    sf, Pf, sb, Pb = TF.planted(*TF.CAPPED)
+    for form, p_solver in FORMS:
+        r = TF.fuse(sf, Pf, sb, Pb, form, p_solver)
+        assert list(np.flatnonzero(r["status"] & 2)) == [5] and list(np.flatnonzero(r["status"] & 1)) == [3]
+        assert r["rank"][12, 5] == 5 and r["route"][12, 5] == 0 and np.isfinite(r["s"][12, :, 5]).all() and np.isfinite(r["P"][12, :, 5]).all()
+        assert not (TF.fuse(sf, Pf, sb, Pb, form, p_solver, storage="f32")["status"] & 2).any()
+    m = TF.CAPPED[0]
+    S = [[float(Pf[12, min(i, j) + m * max(i, j), 5] + Pb[12, min(i, j) + m * max(i, j), 5]) for j in range(m)] for i in range(m)]
+    assert TF.sym_pinv(m, S)[3] and not TF.sym_pinv(m, [[float(i == j) for j in range(m)] for i in range(m)])[3]

@@ -1,9 +1,11 @@
 """The forward-backward filter fusion of DESIGN.md §4.9 (include/epiekf.h, epi_fuse_*) restated in plain Python loops: what
 the kernel csrc/two_filter.hpp is held to bit for bit.  Scalar Python floats are IEEE doubles and every written operation
 rounds once, so `acc = acc + a * b` below is the kernel's `acc = acc + a * b`.  The pseudo-inverse and the LU solve are the
-oracle's orc_sym_pinv_ex / orc_mrdivide (oracle/libekf_oracle.so), reached through ctypes.
+oracle's orc_sym_pinv_cap / orc_mrdivide (oracle/libekf_oracle.so), reached through ctypes.
 
-The restatement cannot see a Jacobi sweep cap (the oracle does not report one), so its status never holds bit 1."""
+Bit 1 of status (a Jacobi iteration of the pseudo-inverse ended at its sweep cap) comes from the oracle's own iteration, which
+has the kernel's caps (30 one-sided sweeps, 50 two-sided) and reports whether it stopped there.  CAPPED names an input that
+reaches the cap."""
 import ctypes as C
 import math
 import os
@@ -12,6 +14,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
+# planted(*CAPPED): item (day 12, chain 5), of planted rank 5, keeps the one-sided Jacobi iteration rotating through all 30 sweeps in
+# double storage (met by a random hunt: tests/test_gpu_fuzz_calls.py, seed 734000005); rounded to float the same item converges
+CAPPED = (6, 14, 14, 999652951)
 
 _lib = None
 
@@ -22,19 +27,20 @@ def _oracle():
         from oracle import oracle_lib as olib
         olib.build()
         _lib = C.CDLL(os.path.join(ROOT, "oracle", "libekf_oracle.so"))
-        _lib.orc_sym_pinv_ex.restype = C.c_int
+        _lib.orc_sym_pinv_cap.restype = C.c_int
         _lib.orc_mrdivide.restype = None
     return _lib
 
 
 def sym_pinv(m, S):
-    """(X [m][m] as nested lists, rank, route) of orc_sym_pinv_ex for the symmetric S (nested lists)"""
+    """(X [m][m] as nested lists, rank, route, capped) of orc_sym_pinv_cap for the symmetric S (nested lists); capped: a Jacobi
+    iteration of the route ended at its sweep cap"""
     A = np.array([[S[i][j] for i in range(m)] for j in range(m)], dtype=np.float64).ravel()   # column-major: e = i + m j
     X = np.zeros(m * m)
-    route, sweeps = C.c_int(0), C.c_int(0)
-    rank = _oracle().orc_sym_pinv_ex(C.c_int(m), A.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p), C.byref(route),
-                                     C.byref(sweeps))
-    return [[float(X[i + m * j]) for j in range(m)] for i in range(m)], int(rank), int(route.value)
+    route, sweeps, capped = C.c_int(0), C.c_int(0), C.c_int(0)
+    rank = _oracle().orc_sym_pinv_cap(C.c_int(m), A.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p), C.byref(route),
+                                      C.byref(sweeps), C.byref(capped))
+    return [[float(X[i + m * j]) for j in range(m)] for i in range(m)], int(rank), int(route.value), bool(capped.value)
 
 
 def mrdivide(m, Bm, A):
@@ -73,8 +79,8 @@ def fuse_item(m, sf, Pf, sb, Pb, form, p_solver=0):
     bad = any(not math.isfinite(S[i][j]) for i in range(m) for j in range(m)) or any(not math.isfinite(v) for v in sf) or \
         any(not math.isfinite(v) for v in sb)
     if bad:
-        return dict(s=[NAN] * m, P=[[NAN] * m for _ in range(m)], d2=NAN, rank=-1, bad=True, route=-1)
-    X, rank, route = sym_pinv(m, S)
+        return dict(s=[NAN] * m, P=[[NAN] * m for _ in range(m)], d2=NAN, rank=-1, bad=True, route=-1, capped=False)
+    X, rank, route, capped = sym_pinv(m, S)
     e = [sf[i] - sb[i] for i in range(m)]
     Xe = _matvec(X, e)
     d2 = e[0] * Xe[0]
@@ -101,7 +107,7 @@ def fuse_item(m, sf, Pf, sb, Pb, form, p_solver=0):
         P = _matmul(Pf, Y)
         Q = [[(P[i][j] + P[j][i]) / 2.0 for j in range(m)] for i in range(m)]
         P = Q
-    return dict(s=s, P=P, d2=d2, rank=rank, bad=False, route=route)
+    return dict(s=s, P=P, d2=d2, rank=rank, bad=False, route=route, capped=capped)
 
 
 def fuse(sf, Pf, sb, Pb, form, p_solver=0, storage="f64"):
@@ -126,6 +132,8 @@ def fuse(sf, Pf, sb, Pb, form, p_solver=0, storage="f64"):
             out["d2"][t, c], out["rank"][t, c], out["route"][t, c] = r["d2"], r["rank"], r["route"]
             if r["bad"]:
                 out["status"][c] |= 1
+            if r["capped"]:
+                out["status"][c] |= 2                        # a Jacobi iteration of pinv(S) ended at its sweep cap
     if storage == "f32":
         with np.errstate(over="ignore"):
             out["s"], out["P"] = out["s"].astype(np.float32), out["P"].astype(np.float32)
