@@ -23,10 +23,11 @@ from . import _lib
 from . import layout as L
 
 
-def run_family(fam, be, desc, args, shapes, names, f32=()):
+def run_family(fam, be, desc, args, shapes, names, f32=(), noise=None):
     """Allocate the outputs `names` of family `fam` (a key of _lib.FAMILIES) from `shapes` -- int32 where the family says so,
     float32 for those in `f32`, else float64 --, bind them (the others stay NULL), call epi_<fam>_<be.kind>(desc, *args,
-    outputs, be.tail(), err) and check its status.  Returns the dict of outputs in the order of the family's names."""
+    outputs, be.tail(), err) and check its status.  Returns the dict of outputs in the order of the family's names.  noise: a
+    _lib.NoiseDesc, for the seeded sibling epi_<fam>_<be.kind>_seeded(desc, noise, ...)."""
     f = _lib.FAMILIES[fam]
     out = {k: be.empty(shapes[k], np.int32 if k in f.out_i32 else (np.float32 if k in f32 else np.float64))
            for k in f.out_names if k in names}
@@ -34,7 +35,31 @@ def run_family(fam, be, desc, args, shapes, names, f32=()):
     for k, v in out.items():
         setattr(outs, k, be.ptr(v))
     err = C.create_string_buffer(256)
-    rc = getattr(_lib.lib(), f"epi_{fam}_{be.kind}")(C.byref(desc), *args, C.byref(outs), be.tail(), err)
+    if noise is None:
+        rc = getattr(_lib.lib(), f"epi_{fam}_{be.kind}")(C.byref(desc), *args, C.byref(outs), be.tail(), err)
+    else:
+        rc = getattr(_lib.lib(), f"epi_{fam}_{be.kind}_seeded")(C.byref(desc), C.byref(noise), *args, C.byref(outs), be.tail(), err)
+    _lib.check(rc, err)
+    return out
+
+
+def normal_draws(be, nt, rows, lanes, seed, stream=0, t0=0, lane0=0, f32=False, test_launch_groups=0):
+    """The window [t0, t0 + nt) x rows x [lane0, lane0 + lanes) of the seeded standard-normal array (epi_noise_fill_*, DESIGN.md
+    §4.21) as the backend's array [nt, rows, lanes], float64 or float32"""
+    nt, rows, lanes = int(nt), int(rows), int(lanes)
+    if rows not in (1, 3):
+        raise ValueError("rows must be 1 or 3")
+    if nt < 1 or lanes < 1:
+        raise ValueError("nt and lanes must be >= 1")
+    d = _lib.make_noise_desc(seed, stream)
+    args = (C.byref(d), int(t0), nt, rows, int(lane0), lanes, int(bool(f32)))
+    err = C.create_string_buffer(256)
+    h = _lib.lib()
+    out = be.empty((nt, rows, lanes), np.float32 if f32 else np.float64)
+    if be.kind == "run_device":
+        rc = h.epi_noise_fill_device(*args, be.ptr(out), int(test_launch_groups), be.tail(), err)
+    else:
+        rc = h.epi_noise_fill_host(*args, be.ptr(out), be.tail(), err)
     _lib.check(rc, err)
     return out
 
@@ -177,11 +202,12 @@ def svr(be, X, y, n_rows, kernel, box, epsilon, kernel_scale, tol, max_iter, out
     return run_family("svr", be, d, [C.byref(ins)], _lib.svr_shapes(D, F, R, K), names)
 
 
-def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, names, out_f32=()):
+def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, names, out_f32=(), noise=None):
     """The call helper of the calls whose device entry takes a workspace (epi_<prefix>_workspace_bytes / _run_device /
     _run_host), which are no families: allocate the outputs `names`, and for the device entry the workspace, through the
     backend; bind them into the outputs structure `outs`, call and check the status.  Returns the dict of outputs in the ABI's
-    order.  out_f32: the outputs the descriptor asks for as float32."""
+    order.  out_f32: the outputs the descriptor asks for as float32.  noise: a _lib.NoiseDesc, for the seeded siblings
+    epi_<prefix>_run_device_seeded / _run_host_seeded(desc, noise, ...)."""
     h = _lib.lib()
     out = {k: be.empty(shapes[k], np.int32 if k in out_i32 else (np.float32 if k in out_f32 else np.float64))
            for k in out_names if k in names}
@@ -192,9 +218,13 @@ def run_with_workspace(prefix, be, desc, ins, outs, out_names, out_i32, shapes, 
         n = C.c_size_t(0)
         _lib.check(getattr(h, f"epi_{prefix}_workspace_bytes")(C.byref(desc), C.byref(n), err), err)
         ws = be.empty(((max(n.value, 8) + 7) // 8,), np.float64)
-        rc = getattr(h, f"epi_{prefix}_run_device")(C.byref(desc), C.byref(ins), C.byref(outs), be.ptr(ws), n.value, be.tail(), err)
+        tail = (C.byref(ins), C.byref(outs), be.ptr(ws), n.value, be.tail(), err)
     else:
-        rc = getattr(h, f"epi_{prefix}_run_host")(C.byref(desc), C.byref(ins), C.byref(outs), be.tail(), err)
+        tail = (C.byref(ins), C.byref(outs), be.tail(), err)
+    if noise is None:
+        rc = getattr(h, f"epi_{prefix}_{be.kind}")(C.byref(desc), *tail)
+    else:
+        rc = getattr(h, f"epi_{prefix}_{be.kind}_seeded")(C.byref(desc), C.byref(noise), *tail)
     _lib.check(rc, err)
     return out
 
@@ -296,7 +326,8 @@ def _is_f32(v):
 
 
 def smoother_draws(be, S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k0, clamp, lane_block, B, out_dtype, outputs,
-                   test_launch_groups=0):
+                   test_launch_groups=0, seed=None, stream=0):
+    noise = _lib.noise_of(seed, stream, z)
     big = (S_PLUS, P_PLUS, S_MINUS, P_MINUS)
     f32 = all(_is_f32(v) for v in big)
     put = be.f32 if f32 else be.f64
@@ -351,7 +382,7 @@ def smoother_draws(be, S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_te
     for k, v in zip(_lib.SDRAW_IN_NAMES, (sp, pp, sm, pm, prm, z, s_term, P_term)):
         setattr(ins, k, be.ptr(v))
     return run_with_workspace("sdraw", be, d, ins, _lib.SdrawOutputs(), _lib.SDRAW_OUT_NAMES, _lib.SDRAW_OUT_I32,
-                              _lib.sdraw_shapes(B, T, D, k0), names, out_f32=("X",) if out_f32 else ())
+                              _lib.sdraw_shapes(B, T, D, k0), names, out_f32=("X",) if out_f32 else (), noise=noise)
 
 
 def _scored_inputs(be, src, truth, R, D, population, truth_series, first_day):

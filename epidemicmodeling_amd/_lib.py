@@ -41,6 +41,10 @@ ABI_SYMBOLS = [
     "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
     "epi_pathfn_validate", "epi_pathfn_workspace_bytes", "epi_pathfn_run_device", "epi_pathfn_run_host",
     "epi_ejoint_validate", "epi_ejoint_workspace_bytes", "epi_ejoint_run_device", "epi_ejoint_run_host",
+    "epi_noise_validate", "epi_noise_fill_device", "epi_noise_fill_host",
+    "epi_sdraw_run_device_seeded", "epi_sdraw_run_host_seeded", "epi_arfc_run_device_seeded", "epi_arfc_run_host_seeded",
+    "epi_sialpha_sim_device_seeded", "epi_sialpha_score_device_seeded", "epi_sialpha_sim_host_seeded",
+    "epi_random_npi_mc_device_seeded", "epi_random_npi_mc_host_seeded",
 ]
 
 
@@ -103,6 +107,33 @@ class SimDesc(C.Structure):
 class McDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "R", "n_scen", "K", "n_npi", "noise", "prefix_days")] + [
         ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
+class NoiseDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("stream", C.c_uint32)]
+
+
+def make_noise_desc(seed, stream=0) -> NoiseDesc:
+    """The descriptor of the seeded draws (include/epiekf.h): seed a 64-bit integer (the Philox key), stream below 2^30"""
+    seed, stream = int(seed), int(stream)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must lie in 0 .. 2^64 - 1")
+    if not 0 <= stream < 1 << 32:
+        raise ValueError("stream must lie in 0 .. 2^30 - 1")       # 2^30 .. 2^32 - 1 reach the library's own check
+    d = NoiseDesc()
+    d.abi_version, d.seed_lo, d.seed_hi, d.stream = ABI_VERSION, seed & 0xFFFFFFFF, seed >> 32, stream
+    return d
+
+
+def noise_of(seed, stream, z):
+    """The seed= / stream= keywords of the Monte-Carlo calls -> a NoiseDesc, or None without a seed; seed and z together raise"""
+    if seed is None:
+        if stream:
+            raise ValueError("stream without seed")
+        return None
+    if z is not None:
+        raise ValueError("seed and z together: the draws have one source")
+    return make_noise_desc(seed, stream)
 
 
 class RtDesc(C.Structure):
@@ -940,6 +971,15 @@ def lib():
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail
+        nd = C.POINTER(NoiseDesc)                   # the seeded siblings: the noise descriptor behind the call's own
+        h.epi_noise_validate.argtypes = [nd, C.c_char_p]
+        fill = [nd, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+        h.epi_noise_fill_device.argtypes = fill + [C.c_int32, C.c_void_p, C.c_char_p]
+        h.epi_noise_fill_host.argtypes = fill + [C.c_int, C.c_char_p]
+        for name in ("epi_sdraw_run_device", "epi_sdraw_run_host", "epi_arfc_run_device", "epi_arfc_run_host", "epi_sialpha_sim_device",
+                     "epi_sialpha_score_device", "epi_sialpha_sim_host", "epi_random_npi_mc_device", "epi_random_npi_mc_host"):
+            at = getattr(h, name).argtypes
+            getattr(h, name + "_seeded").argtypes = [at[0], nd] + list(at[1:])
         own = ("epi_status_string", "epi_host_pool_release", "epi_ekf_workspace_bytes", "epi_preprocess_workspace_bytes",
                "epi_lookahead_workspace_bytes")
         h.epi_status_string.restype = C.c_char_p

@@ -421,9 +421,27 @@ SIM_FIELDS = {"s0": 0, "i0": 1, "alpha0": 2, "alpha_min": 3, "alpha_max": 4, "ga
 SIM_A, SIM_U_MAX, SIM_W, SIM_PRM_COUNT = 12, 24, 36, 48
 
 
-def sialpha_sim(u, sp, z=None, u_series=None, with_cost=False, store=True, device="cuda:0"):
+def normal_draws(nt, rows, lanes, seed, stream=0, t0=0, lane0=0, dtype=torch.float64, device="cuda:0", cuda_stream=None):
+    """Standard-normal draws from a seed, generated on the device (epi_noise_fill_device): the window
+    [t0, t0 + nt) x rows x [lane0, lane0 + lanes) of the logical array of (seed, stream) as a device tensor [nt, rows, lanes],
+    float64 or float32 (the float64 draw rounded once).  rows is 1 or 3, seed a 64-bit integer, stream < 2^30.  The value of
+    draw (t, row, lane) is a pure function of (seed, stream, t, row, lane): Philox4x32-10, then the inverse normal CDF (AS241),
+    |z| <= 8.2096.  A call with seed= / noise_stream= equals, bit for bit, the same call given z = normal_draws(...) of its z's
+    shape (`stream` here is the noise stream, as in the descriptor; the HIP stream is `cuda_stream`).
+    Enqueued on `cuda_stream` (default: the current stream) without a host synchronisation."""
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("dtype must be torch.float64 or torch.float32")
+    dev = torch.device(device)
+    st = torch.cuda.current_stream(dev) if cuda_stream is None else cuda_stream
+    with torch.cuda.stream(st):
+        return _call.normal_draws(DeviceBackend(dev, st), nt, rows, lanes, seed, stream, t0, lane0, dtype == torch.float32)
+
+
+def sialpha_sim(u, sp, z=None, u_series=None, with_cost=False, store=True, device="cuda:0", seed=None, noise_stream=0):
     """Batched SIalpha_Controlled (+ fused NPICost).  u [K, n_npi, Su], sp [48, B] (SIM_* rows), z [K, 3, B]
-    standard-normal draws or None.  Returns dict of torch tensors s,i,alpha [K,B] (+ J0,J1 [B])."""
+    standard-normal draws or None; or seed= (and noise_stream=): the draws normal_draws(K, 3, B, seed, noise_stream) generated inside the
+    kernel (seed and z together raise).  Returns dict of torch tensors s,i,alpha [K,B] (+ J0,J1 [B])."""
+    noise = _lib.noise_of(seed, noise_stream, z)
     dev = torch.device(device)
     t = lambda a, dt=torch.float64: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev) \
         if not isinstance(a, torch.Tensor) else a
@@ -443,20 +461,27 @@ def sialpha_sim(u, sp, z=None, u_series=None, with_cost=False, store=True, devic
         out["J1"] = torch.empty((B,), dtype=torch.float64, device=dev)
     err = C.create_string_buffer(256)
     st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_sialpha_sim_device(C.byref(d), _ptr(us), _ptr(u), _ptr(sp), _ptr(z), _ptr(out.get("s")),
-                                           _ptr(out.get("i")), _ptr(out.get("alpha")), _ptr(out.get("J0")),
-                                           _ptr(out.get("J1")), C.c_void_p(st.cuda_stream), err)
+    tail = (_ptr(us), _ptr(u), _ptr(sp), _ptr(z), _ptr(out.get("s")), _ptr(out.get("i")), _ptr(out.get("alpha")), _ptr(out.get("J0")),
+            _ptr(out.get("J1")), C.c_void_p(st.cuda_stream), err)
+    if noise is None:
+        rc = _lib.lib().epi_sialpha_sim_device(C.byref(d), *tail)
+    else:
+        rc = _lib.lib().epi_sialpha_sim_device_seeded(C.byref(d), C.byref(noise), *tail)
     _lib.check(rc, err)
     return out
 
 
 def random_npi_mc(sp, u_min, n_scen, K, seed=0, z=None, J0_prefix=None, J1_prefix=None, prefix_days=0,
-                  store_u=False, device="cuda:0"):
+                  store_u=False, device="cuda:0", noise_seed=None, noise_stream=0):
     """Random-NPI Monte-Carlo scenarios (Tools/TrainPredictPrescribeNPI.m:496-521) on the device.
 
     sp [48, R] per-region SIM_* rows (end-of-history state, model constants, SIM_U_MAX = NPI_MAXES, SIM_W = NPICost
     weights), u_min [n_npi, R] = NPI_MINS, z [K, 3, n_scen*R] standard-normal draws or None; J0_prefix/J1_prefix [R]
-    sequential historic sums over prefix_days.  Returns dict J0, J1 [n_scen, R] (+ u [K, n_npi, n_scen*R])."""
+    sequential historic sums over prefix_days.  `seed` keys the integer draws of the plans, as ever; noise_seed= (and noise_stream=)
+    asks for the state noise normal_draws(K, 3, n_scen*R, noise_seed, noise_stream) generated inside the kernel (noise_seed and z
+    together raise).  The two may be the same number: their Philox counters never meet.  Returns dict J0, J1 [n_scen, R]
+    (+ u [K, n_npi, n_scen*R])."""
+    noise = _lib.noise_of(noise_seed, noise_stream, z)
     dev = torch.device(device)
     t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else
                                           torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev))
@@ -472,9 +497,12 @@ def random_npi_mc(sp, u_min, n_scen, K, seed=0, z=None, J0_prefix=None, J1_prefi
         out["u"] = torch.empty((K, n_npi, n_scen * R), dtype=torch.float64, device=dev)
     err = C.create_string_buffer(256)
     st = torch.cuda.current_stream(dev)
-    rc = _lib.lib().epi_random_npi_mc_device(C.byref(d), _ptr(sp), _ptr(u_min), _ptr(z), _ptr(J0p), _ptr(J1p),
-                                             _ptr(out.get("u")), _ptr(out["J0"]), _ptr(out["J1"]),
-                                             C.c_void_p(st.cuda_stream), err)
+    tail = (_ptr(sp), _ptr(u_min), _ptr(z), _ptr(J0p), _ptr(J1p), _ptr(out.get("u")), _ptr(out["J0"]), _ptr(out["J1"]),
+            C.c_void_p(st.cuda_stream), err)
+    if noise is None:
+        rc = _lib.lib().epi_random_npi_mc_device(C.byref(d), *tail)
+    else:
+        rc = _lib.lib().epi_random_npi_mc_device_seeded(C.byref(d), C.byref(noise), *tail)
     _lib.check(rc, err)
     return out
 
@@ -908,7 +936,7 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
 
 
 def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series=None, A=None, noise_var=None, nv_mode=0,
-                stream=None, device="cuda:0"):
+                stream=None, device="cuda:0", seed=None, noise_stream=0):
     """The autoregressive alpha forecaster of Tools/PrescribeNPI.m:204-215 for R regions x D draws in one device call
     (epi_arfc_run_device): ar(seg, p) -> filtic -> filter(sqrt(nv), A, z, zi) (+ drive) -> negatives to 0 ->
     SI_Controlled over [segment, forecast].  seg [L, R] (the last L days of each region's alpha), beta / s0 / i0 [R], dt a
@@ -922,7 +950,9 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     to `device`).  Returns a dict of device tensors: S [L + H, 3, B] with rows (s, i, alpha_hat) -- what
     ensemble_summary(S, R, D, population=N) takes -- A [p, R], noise_var [R], status [R] int32 (_lib.ARFC_OK,
     ARFC_RANK_DEFICIENT: NaN from day L on, ARFC_BAD_INPUT: NaN everywhere).  Enqueued on `stream` (default: the current
-    stream) without a host synchronisation."""
+    stream) without a host synchronisation.  seed= (and noise_stream=, since `stream` is the HIP stream here): the draws
+    normal_draws(H, 1, B, seed, noise_stream)[:, 0] generated inside the kernel; seed and z together raise."""
+    noise = _lib.noise_of(seed, noise_stream, z)
     if (A is None) != (noise_var is None):
         raise ValueError("A and noise_var are given together (the given-model mode) or not at all")
     tensors = [v for v in (seg, beta, s0, i0, z, drive, drive_series, A, noise_var) if isinstance(v, torch.Tensor)]
@@ -967,7 +997,8 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     ins = _lib.ArfcInputs()
     for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, ser, A, noise_var)):
         setattr(ins, k, _ptr(v))
-    out = _call.run_family("arfc", DeviceBackend(dev, stream), d, [C.byref(ins)], _lib.arfc_shapes(R, D, L, p, H), _lib.ARFC_OUT_NAMES)
+    out = _call.run_family("arfc", DeviceBackend(dev, stream), d, [C.byref(ins)], _lib.arfc_shapes(R, D, L, p, H), _lib.ARFC_OUT_NAMES,
+                           noise=noise)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
 
 
@@ -1092,7 +1123,7 @@ def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None,
 
 
 def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None, P_term=None, k0=0, clamp=True, lane_block=0, B=None,
-                   out_dtype=None, outputs=("X", "rank", "status"), stream=None):
+                   out_dtype=None, outputs=("X", "rank", "status"), stream=None, seed=None, noise_stream=0):
     """Joint posterior draws of the smoothed paths by backward simulation, from what a 3-state filter run left on the device
     (epi_sdraw_run_device): D paths per chain of the law whose mean and covariance recursions are the
     smoother's own (GenericExtendedKalmanFilter.m:218, :223),
@@ -1110,7 +1141,8 @@ def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None
     _lib.SDRAW_NONFINITE: a non-finite input entry met -- J = 0 by the guard :211, or a NaN record; bit 1,
     _lib.SDRAW_RANK_DEFICIENT: a rank below 3 on some day), "J", "L" [T, 9, B] float64 (entry i + 3 j; L = F, a row-permuted lower
     triangle).  Returns a dict of device tensors.  Enqueued on `stream` (default: the current stream) without a host
-    synchronisation."""
+    synchronisation.  seed= (and noise_stream=, since `stream` is the HIP stream here): the draws normal_draws(T - k0, 3, B * D,
+    seed, noise_stream) generated inside the kernel -- no z array exists; seed and z together raise."""
     for name, v in (("S_PLUS", S_PLUS), ("P_PLUS", P_PLUS), ("S_MINUS", S_MINUS), ("P_MINUS", P_MINUS)):
         if not isinstance(v, torch.Tensor) or not v.is_cuda:
             raise ValueError(f"{name} must be a device tensor")
@@ -1122,7 +1154,7 @@ def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.smoother_draws(DeviceBackend(dev, st), S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k0, clamp,
-                                    lane_block, B, out_dtype, outputs)
+                                    lane_block, B, out_dtype, outputs, 0, seed, noise_stream)
 
 
 def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, population=None, truth_series=None, first_day=None,

@@ -769,6 +769,48 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
     }
 }
 
+#include "noise.hpp"
+// sialpha_sim with the three draws of (step t, chain c) generated: draws (t, 0 .. 2, c) of noise.hpp.  A body of its
+// own, so that sialpha_sim keeps its text and its code
+__global__ __launch_bounds__(256) void sialpha_sim_seeded(const epi_sim_desc d, const NoiseKey nk, const int32_t *__restrict__ u_series,
+                                                          const double *__restrict__ u, const double *__restrict__ sp,
+                                                          double *__restrict__ so, double *__restrict__ io, double *__restrict__ ao,
+                                                          double *__restrict__ J0, double *__restrict__ J1,
+                                                          const double *__restrict__ J0_prefix, const double *__restrict__ J1_prefix)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= d.B) return;
+    const int B = d.B;
+    const int su = u_series ? u_series[c] : c;
+    SimPrm p;
+    double s, i, al;
+    load_sim_prm(p, sp, B, c, s, i, al);
+    // NPICost over [historic days, simulated days] (TrainPredictPrescribeNPI.m:481-493): the historic part of
+    // the two sequential sums arrives as a per-chain prefix and the simulated days are added in order
+    const bool pre = (d.prefix_days > 0) && J0_prefix && J1_prefix;
+    double acc0 = pre ? J0_prefix[c] : 0.0, acc1 = pre ? J1_prefix[c] : 0.0;
+    // u: [K][n_npi][Su], or chain-blocked ((t*nblk + su/blk)*n_npi + k)*blk + su%blk
+    const int ublk = (d.u_block <= 0 || d.u_block >= d.Su) ? d.Su : d.u_block;
+    const size_t unb = (size_t)(d.Su + ublk - 1) / ublk, ucb = (size_t)su / ublk, ucr = (size_t)su % ublk;
+    for (int t = 0; t < d.K; t++) {
+        double uk[kNpi];
+#pragma unroll
+        for (int k = 0; k < kNpi; k++) uk[k] = (k < d.n_npi) ? u[(((size_t)t * unb + ucb) * d.n_npi + k) * ublk + ucr] : 0.0;
+        double z1, z2, z3;
+        epi_normal_three(nk, (uint32_t)t, (uint64_t)c, z1, z2, z3);
+        sialpha_step(p, uk, z1, z2, z3, s, i, al);
+        if (so) so[(size_t)t * B + c] = s;
+        if (io) io[(size_t)t * B + c] = i;
+        if (ao) ao[(size_t)t * B + c] = al;
+        if (d.with_cost) npicost_accumulate(p, uk, d.n_npi, t == 0 && !pre, s, i, al, acc0, acc1);
+    }
+    if (d.with_cost) {
+        const size_t days = (size_t)d.K + (size_t)(pre ? d.prefix_days : 0);
+        if (J0) J0[c] = acc0 / (double)days;
+        if (J1) J1[c] = acc1 / (double)((size_t)d.n_npi * days);
+    }
+}
+
 #include "scenario_kernels.hpp"
 #include "rt_expfit.hpp"
 #include "preprocess.hpp"
@@ -781,6 +823,82 @@ __global__ __launch_bounds__(256) void sialpha_sim(const epi_sim_desc d, const i
 #include "path_functionals.hpp"
 #include "ens_joint.hpp"
 #include "ar_forecast.hpp"
+// ar_simulate with the draw of (forecast day t, chain c) generated: draw (t, 0, c) of noise.hpp.  A body of its own: ar_forecast.hpp
+// stays free of ekf_device.hpp (tests/ar_forecast_emu.cpp compiles it alone) and ar_simulate keeps its text and its code
+__global__ __launch_bounds__(64) void ar_simulate_seeded(const ArSimArgs a, const NoiseKey nk)
+{
+    extern __shared__ double ar_lds[];
+    const int lane = threadIdx.x, L = a.L, p = a.p, H = a.H;
+    const long long blk = a.blk0 + (long long)blockIdx.x;
+    const size_t R = (size_t)a.R, r = (size_t)(blk / a.bpr), B = R * (size_t)a.D;
+    const int d = (int)(blk % a.bpr) * 64 + lane;
+    const bool active = d < a.D;
+    const size_t c = r * (size_t)a.D + (size_t)(active ? d : 0);
+    double *y = ar_lds;                      // [L] the segment
+    double *coef = y + ar_lds_seg(L);        // [32]
+    double *ring = coef + 32;                // [p][64] past values of the recursion, one column per lane
+    const double qnan = __builtin_nan("");
+    int bad = 0;
+    for (int t = lane; t < L; t += 64) {
+        const double v = a.seg[(size_t)t * R + r];
+        y[t] = v;
+        bad |= !ar_finite(v);
+    }
+    int dead = 0;
+    if (lane < p) {
+        const double v = a.A[(size_t)lane * R + r];
+        coef[lane] = v;
+        dead = !ar_finite(v);
+    }
+    const double b0 = sqrt(a.nv[r]);
+    dead |= !ar_finite(b0);
+    bad = __ballot(bad) != 0;                // BAD_INPUT: every day is NaN
+    dead = bad || __ballot(dead) != 0;       // no usable model: NaN from day L on
+    __syncthreads();
+    const double beta = a.beta[r], dt = a.dt;
+    double s = a.s0[r], i = a.i0[r];
+    size_t ser = 0;
+    if (a.drive && active) ser = a.drive_series ? (size_t)a.drive_series[c] : c;
+    double *o = a.S + c;
+    // ---- the segment: alpha_hat = seg clamped, SI_Controlled.m:19-22 ----
+    for (int t = 0; t < L; t++) {
+        const double v = y[t];
+        const double al = v < 0.0 ? 0.0 : v;
+        if (active) {
+            o[0] = bad ? qnan : s; o[B] = bad ? qnan : i; o[2 * B] = bad ? qnan : al;
+        }
+        o += 3 * B;
+        const double sn = fmax(0.0, fmin(1.0, s - dt * al * s * i));
+        const double in = fmax(0.0, fmin(1.0, i + dt * (al * s * i - beta * i)));
+        s = sn; i = in;
+    }
+    // ---- the forecast: y(t) = b0 z(t) - sum a_k y(t-k), k ascending, the past from the segment first ----
+    for (int j = 0; j < p; j++) ring[j * 64 + lane] = y[L - p + j];
+    int head = 0;
+    for (int t = 0; t < H; t++) {
+        const double zt = epi_normal_draw(nk, (uint32_t)t, 0u, (uint64_t)c);
+        double acc = b0 * zt;
+        int idx = head;
+        for (int k = 0; k < p; k++) {
+            idx = idx == 0 ? p - 1 : idx - 1;
+            acc = fma(-coef[k], ring[idx * 64 + lane], acc);
+        }
+        ring[head * 64 + lane] = acc;
+        head = head + 1 == p ? 0 : head + 1;
+        double v = acc;
+        if (a.drive && active) v = acc + a.drive[(size_t)t * (size_t)a.Sd + ser];
+        const double al = v < 0.0 ? 0.0 : v;
+        if (active) {
+            o[0] = dead ? qnan : s; o[B] = dead ? qnan : i; o[2 * B] = dead ? qnan : al;
+        }
+        o += 3 * B;
+        if (t + 1 < H) {
+            const double sn = fmax(0.0, fmin(1.0, s - dt * al * s * i));
+            const double in = fmax(0.0, fmin(1.0, i + dt * (al * s * i - beta * i)));
+            s = sn; i = in;
+        }
+    }
+}
 #include "two_filter.hpp"
 #include "robust_fit.hpp"
 #include "rate_map.hpp"
@@ -1976,18 +2094,33 @@ int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *st
     return EPI_OK;
 }
 
+// the seeded calls' common checks: a valid noise descriptor and no z beside it
+static int noise_key(const epi_noise_desc *noise, const void *z, NoiseKey *nk, char *err)
+{
+    int rc = epi_noise_validate(noise, err);
+    if (rc != EPI_OK) return rc;
+    if (z) { set_err(err, "a seeded call takes no z: the draws have one source"); return EPI_ERR_BAD_ARG; }
+    nk->seed_lo = noise->seed_lo; nk->seed_hi = noise->seed_hi; nk->stream = noise->stream;
+    return EPI_OK;
+}
+
+// nk: NULL (the draws are read from z) or the seeded call's key
 static int sialpha_launch(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
-                          const double *z, double *s, double *i, double *alpha, double *J0, double *J1,
+                          const double *z, const NoiseKey *nk, double *s, double *i, double *alpha, double *J0, double *J1,
                           const double *J0_prefix, const double *J1_prefix, void *stream, char *err)
 {
     if (!d || d->abi_version != EPIEKF_ABI_VERSION || d->B < 1 || d->K < 1 || d->Su < 1 || d->n_npi < 1 ||
-        d->n_npi > EPI_MAX_NPI || !u || !sp || (d->noise && !z) || (!u_series && d->Su != d->B) || d->prefix_days < 0 ||
+        d->n_npi > EPI_MAX_NPI || !u || !sp || (!nk && d->noise && !z) || (!u_series && d->Su != d->B) || d->prefix_days < 0 ||
         (d->prefix_days > 0 && (!J0_prefix || !J1_prefix))) {
         set_err(err, "bad simulator descriptor"); return EPI_ERR_BAD_ARG;
     }
     const int blocks = (d->B + 255) / 256;
-    hipLaunchKernelGGL(sialpha_sim, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *d, u_series, u, sp, z, s, i, alpha,
-                       J0, J1, J0_prefix, J1_prefix, (const int32_t *)nullptr);
+    if (nk)
+        hipLaunchKernelGGL(sialpha_sim_seeded, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *d, *nk, u_series, u, sp, s, i, alpha,
+                           J0, J1, J0_prefix, J1_prefix);
+    else
+        hipLaunchKernelGGL(sialpha_sim, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *d, u_series, u, sp, z, s, i, alpha,
+                           J0, J1, J0_prefix, J1_prefix, (const int32_t *)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(err, e, "sialpha_sim launch");
     return EPI_OK;
@@ -1998,31 +2131,73 @@ int epi_sialpha_sim_device(const epi_sim_desc *d, const int32_t *u_series, const
                            void *stream, char *err)
 {
     if (d && d->prefix_days != 0) { set_err(err, "prefix_days needs epi_sialpha_score_device"); return EPI_ERR_BAD_ARG; }
-    return sialpha_launch(d, u_series, u, sp, z, s, i, alpha, J0, J1, nullptr, nullptr, stream, err);
+    return sialpha_launch(d, u_series, u, sp, z, nullptr, s, i, alpha, J0, J1, nullptr, nullptr, stream, err);
+}
+
+int epi_sialpha_sim_device_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                  const double *sp, const double *z, double *s, double *i, double *alpha, double *J0, double *J1,
+                                  void *stream, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, z, &nk, err);
+    if (rc != EPI_OK) return rc;
+    if (d && d->prefix_days != 0) { set_err(err, "prefix_days needs epi_sialpha_score_device_seeded"); return EPI_ERR_BAD_ARG; }
+    return sialpha_launch(d, u_series, u, sp, nullptr, &nk, s, i, alpha, J0, J1, nullptr, nullptr, stream, err);
 }
 
 int epi_sialpha_score_device(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
                              const double *z, const double *J0_prefix, const double *J1_prefix, double *s, double *i,
                              double *alpha, double *J0, double *J1, void *stream, char *err)
 {
-    return sialpha_launch(d, u_series, u, sp, z, s, i, alpha, J0, J1, J0_prefix, J1_prefix, stream, err);
+    return sialpha_launch(d, u_series, u, sp, z, nullptr, s, i, alpha, J0, J1, J0_prefix, J1_prefix, stream, err);
+}
+
+int epi_sialpha_score_device_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                    const double *sp, const double *z, const double *J0_prefix, const double *J1_prefix, double *s,
+                                    double *i, double *alpha, double *J0, double *J1, void *stream, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, z, &nk, err);
+    if (rc != EPI_OK) return rc;
+    return sialpha_launch(d, u_series, u, sp, nullptr, &nk, s, i, alpha, J0, J1, J0_prefix, J1_prefix, stream, err);
+}
+
+static int random_npi_mc_launch(const epi_mc_desc *d, const double *sp, const double *u_min, const double *z, const NoiseKey *nk,
+                                const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0, double *J1,
+                                void *stream, char *err)
+{
+    if (!d || d->abi_version != EPIEKF_ABI_VERSION || d->R < 1 || d->n_scen < 1 || d->K < 1 || d->n_npi < 1 ||
+        d->n_npi > EPI_MAX_NPI || !sp || !u_min || !J0 || !J1 || (!nk && d->noise && !z) || d->prefix_days < 0 ||
+        (d->prefix_days > 0 && (!J0_prefix || !J1_prefix)) || (int64_t)d->R * d->n_scen > (int64_t)1 << 30) {
+        set_err(err, "bad Monte-Carlo scenario descriptor"); return EPI_ERR_BAD_ARG;
+    }
+    const int B = d->R * d->n_scen;
+    if (nk)
+        hipLaunchKernelGGL(random_npi_mc_seeded, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, *d, *nk, sp, u_min,
+                           J0_prefix, J1_prefix, u_out, J0, J1);
+    else
+        hipLaunchKernelGGL(random_npi_mc, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, *d, sp, u_min, z,
+                           J0_prefix, J1_prefix, u_out, J0, J1);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(err, e, "random_npi_mc launch");
+    return EPI_OK;
 }
 
 int epi_random_npi_mc_device(const epi_mc_desc *d, const double *sp, const double *u_min, const double *z,
                              const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0, double *J1,
                              void *stream, char *err)
 {
-    if (!d || d->abi_version != EPIEKF_ABI_VERSION || d->R < 1 || d->n_scen < 1 || d->K < 1 || d->n_npi < 1 ||
-        d->n_npi > EPI_MAX_NPI || !sp || !u_min || !J0 || !J1 || (d->noise && !z) || d->prefix_days < 0 ||
-        (d->prefix_days > 0 && (!J0_prefix || !J1_prefix)) || (int64_t)d->R * d->n_scen > (int64_t)1 << 30) {
-        set_err(err, "bad Monte-Carlo scenario descriptor"); return EPI_ERR_BAD_ARG;
-    }
-    const int B = d->R * d->n_scen;
-    hipLaunchKernelGGL(random_npi_mc, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, *d, sp, u_min, z,
-                       J0_prefix, J1_prefix, u_out, J0, J1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(err, e, "random_npi_mc launch");
-    return EPI_OK;
+    return random_npi_mc_launch(d, sp, u_min, z, nullptr, J0_prefix, J1_prefix, u_out, J0, J1, stream, err);
+}
+
+int epi_random_npi_mc_device_seeded(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min,
+                                    const double *z, const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0,
+                                    double *J1, void *stream, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, z, &nk, err);
+    if (rc != EPI_OK) return rc;
+    return random_npi_mc_launch(d, sp, u_min, nullptr, &nk, J0_prefix, J1_prefix, u_out, J0, J1, stream, err);
 }
 
 int epi_pareto_front_device(int32_t R, int32_t P, const double *J0, const double *J1, int32_t *on_front,
@@ -2086,9 +2261,9 @@ int epi_sir_sim_device(int32_t B, int32_t K, double dt, const double *prm, doubl
 
 // ---- host-pointer variants of the simulators and the cost (what a MEX gateway binds: matlab/epiekf_sim_mex.cpp) ----
 
-int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
-                         const double *z, double *s, double *i, double *alpha, double *J0, double *J1, int device,
-                         char *err)
+static int sialpha_sim_host(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u, const double *sp,
+                            const double *z, double *s, double *i, double *alpha, double *J0, double *J1, int device,
+                            char *err)
 {
     if (!d || d->B < 1 || d->K < 1 || d->Su < 1 || d->n_npi < 1 || !u || !sp) { set_err(err, "bad simulator descriptor"); return EPI_ERR_BAD_ARG; }
     if (d->u_block != 0) { set_err(err, "u_block is a device-side layout"); return EPI_ERR_BAD_ARG; }
@@ -2099,8 +2274,28 @@ int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const d
     void *ds = h.out(s, K * B * 8), *di = h.out(i, K * B * 8), *da = h.out(alpha, K * B * 8);
     void *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
     if (h.failed()) return h.fail(err);
+    if (noise)
+        return h.finish(epi_sialpha_sim_device_seeded(d, noise, (const int32_t *)dus, (const double *)du, (const double *)dsp, nullptr,
+                                                      (double *)ds, (double *)di, (double *)da, (double *)d0, (double *)d1, nullptr, err), err);
     return h.finish(epi_sialpha_sim_device(d, (const int32_t *)dus, (const double *)du, (const double *)dsp, (const double *)dz,
                                            (double *)ds, (double *)di, (double *)da, (double *)d0, (double *)d1, nullptr, err), err);
+}
+
+int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
+                         const double *z, double *s, double *i, double *alpha, double *J0, double *J1, int device,
+                         char *err)
+{
+    return sialpha_sim_host(d, nullptr, u_series, u, sp, z, s, i, alpha, J0, J1, device, err);
+}
+
+int epi_sialpha_sim_host_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                const double *sp, const double *z, double *s, double *i, double *alpha, double *J0, double *J1,
+                                int device, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, z, &nk, err);                // before anything is staged
+    if (rc != EPI_OK) return rc;
+    return sialpha_sim_host(d, noise, u_series, u, sp, nullptr, s, i, alpha, J0, J1, device, err);
 }
 
 int epi_seirp_sim_host(int32_t B, int32_t K, int32_t par_steps, double dt, int32_t saturated, int32_t integrator,
@@ -2188,9 +2383,9 @@ int epi_nnls_affine_fit_host(const epi_nnls_desc *d, const double *X, const doub
                                                (int32_t *)di, (int32_t *)df, nullptr, err), err);
 }
 
-int epi_random_npi_mc_host(const epi_mc_desc *d, const double *sp, const double *u_min, const double *z,
-                           const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0, double *J1,
-                           int device, char *err)
+static int random_npi_mc_host(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min, const double *z,
+                              const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0, double *J1,
+                              int device, char *err)
 {
     if (!d || d->R < 1 || d->n_scen < 1 || d->K < 1 || d->n_npi < 1 || d->n_npi > EPI_MAX_NPI ||
         (int64_t)d->R * d->n_scen > (int64_t)1 << 30) { set_err(err, "bad Monte-Carlo scenario descriptor"); return EPI_ERR_BAD_ARG; }
@@ -2200,8 +2395,28 @@ int epi_random_npi_mc_host(const epi_mc_desc *d, const double *sp, const double 
     const void *dz = h.in(z, K * 3 * B * 8), *dj0 = h.in(J0_prefix, R * 8), *dj1 = h.in(J1_prefix, R * 8);
     void *du = h.out(u_out, K * (size_t)d->n_npi * B * 8), *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
     if (h.failed()) return h.fail(err);
+    if (noise)
+        return h.finish(epi_random_npi_mc_device_seeded(d, noise, (const double *)dsp, (const double *)dum, nullptr, (const double *)dj0,
+                                                        (const double *)dj1, (double *)du, (double *)d0, (double *)d1, nullptr, err), err);
     return h.finish(epi_random_npi_mc_device(d, (const double *)dsp, (const double *)dum, (const double *)dz, (const double *)dj0,
                                              (const double *)dj1, (double *)du, (double *)d0, (double *)d1, nullptr, err), err);
+}
+
+int epi_random_npi_mc_host(const epi_mc_desc *d, const double *sp, const double *u_min, const double *z,
+                           const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0, double *J1,
+                           int device, char *err)
+{
+    return random_npi_mc_host(d, nullptr, sp, u_min, z, J0_prefix, J1_prefix, u_out, J0, J1, device, err);
+}
+
+int epi_random_npi_mc_host_seeded(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min,
+                                  const double *z, const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0,
+                                  double *J1, int device, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, z, &nk, err);                // before anything is staged
+    if (rc != EPI_OK) return rc;
+    return random_npi_mc_host(d, noise, sp, u_min, nullptr, J0_prefix, J1_prefix, u_out, J0, J1, device, err);
 }
 
 int epi_rt_expfit_validate(const epi_rt_desc *d, char *err)
@@ -3222,7 +3437,9 @@ int epi_arfc_validate(const epi_arfc_desc *d, const epi_arfc_inputs *in, const e
     return EPI_OK;
 }
 
-int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, void *stream, char *err)
+// nk: NULL (the draws are read from in->z) or the seeded call's key
+static int arfc_run_device(const epi_arfc_desc *d, const NoiseKey *nk, const epi_arfc_inputs *in, const epi_arfc_outputs *out, void *stream,
+                           char *err)
 {
     int rc = epi_arfc_validate(d, in, out, err);
     if (rc != EPI_OK) return rc;
@@ -3266,13 +3483,29 @@ int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const
     for (int64_t b0 = 0; b0 < blocks; b0 += kArLaunchBlocks) {
         g.blk0 = (long long)b0;
         const unsigned nb = (unsigned)(blocks - b0 < kArLaunchBlocks ? blocks - b0 : kArLaunchBlocks);
-        hipLaunchKernelGGL(ar_simulate, dim3(nb), dim3(64), shm, st, g);
+        if (nk) hipLaunchKernelGGL(ar_simulate_seeded, dim3(nb), dim3(64), shm, st, g, *nk);
+        else hipLaunchKernelGGL(ar_simulate, dim3(nb), dim3(64), shm, st, g);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "ar_simulate launch");
     }
     return EPI_OK;
 }
 
-int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err)
+int epi_arfc_run_device(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, void *stream, char *err)
+{
+    return arfc_run_device(d, nullptr, in, out, stream, err);
+}
+
+int epi_arfc_run_device_seeded(const epi_arfc_desc *d, const epi_noise_desc *noise, const epi_arfc_inputs *in, const epi_arfc_outputs *out,
+                               void *stream, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, in ? in->z : nullptr, &nk, err);
+    if (rc != EPI_OK) return rc;
+    return arfc_run_device(d, &nk, in, out, stream, err);
+}
+
+static int arfc_run_host(const epi_arfc_desc *d, const epi_noise_desc *noise, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device,
+                         char *err)
 {
     int rc = epi_arfc_validate(d, in, out, err);
     if (rc != EPI_OK) return rc;
@@ -3298,9 +3531,23 @@ int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const e
         epi_arfc_outputs dout{};
         dout.S = (double *)(base + o_S); dout.A_out = (double *)(base + o_Ao); dout.noise_var_out = (double *)(base + o_nvo);
         dout.status = (int32_t *)(base + o_st);
-        return epi_arfc_run_device(d, &din, &dout, st, err);
+        return noise ? epi_arfc_run_device_seeded(d, noise, &din, &dout, st, err) : epi_arfc_run_device(d, &din, &dout, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err)
+{
+    return arfc_run_host(d, nullptr, in, out, device, err);
+}
+
+int epi_arfc_run_host_seeded(const epi_arfc_desc *d, const epi_noise_desc *noise, const epi_arfc_inputs *in, const epi_arfc_outputs *out,
+                             int device, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, in ? in->z : nullptr, &nk, err);   // before anything is staged: no z is copied
+    if (rc != EPI_OK) return rc;
+    return arfc_run_host(d, noise, in, out, device, err);
 }
 
 // ---- the forward-backward filter fusion, one item per (chain, day) (Tools/TrainPredictPrescribeNPI.m:464-478) ----
@@ -3725,8 +3972,9 @@ static int sdraw_check_arrays(const epi_sdraw_inputs *in, const epi_sdraw_output
     return EPI_OK;
 }
 
-int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, void *ws, size_t ws_bytes,
-                         void *stream, char *err)
+// nk: NULL (the draws are read from in->z, if any) or the seeded call's key
+static int sdraw_run_device(const epi_sdraw_desc *d, const NoiseKey *nk, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, void *ws,
+                            size_t ws_bytes, void *stream, char *err)
 {
     int rc = epi_sdraw_validate(d, err);
     if (rc != EPI_OK) return rc;
@@ -3761,13 +4009,31 @@ int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, co
     for (long long w0 = 0; w0 < pg; w0 += cap) {
         g.wg0 = w0;
         const unsigned nb = (unsigned)(pg - w0 < cap ? pg - w0 : cap);
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(kSdPathWg), 0, st, g);
+        if (nk && d->out_f32) hipLaunchKernelGGL(sdraw_paths_seeded<1>, dim3(nb), dim3(kSdPathWg), 0, st, g, *nk);
+        else if (nk) hipLaunchKernelGGL(sdraw_paths_seeded<0>, dim3(nb), dim3(kSdPathWg), 0, st, g, *nk);
+        else hipLaunchKernelGGL(kern, dim3(nb), dim3(kSdPathWg), 0, st, g);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "sdraw_paths launch");
     }
     return EPI_OK;
 }
 
-int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err)
+int epi_sdraw_run_device(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, void *ws, size_t ws_bytes,
+                         void *stream, char *err)
+{
+    return sdraw_run_device(d, nullptr, in, out, ws, ws_bytes, stream, err);
+}
+
+int epi_sdraw_run_device_seeded(const epi_sdraw_desc *d, const epi_noise_desc *noise, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out,
+                                void *ws, size_t ws_bytes, void *stream, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, in ? in->z : nullptr, &nk, err);
+    if (rc != EPI_OK) return rc;
+    return sdraw_run_device(d, &nk, in, out, ws, ws_bytes, stream, err);
+}
+
+static int sdraw_run_host(const epi_sdraw_desc *d, const epi_noise_desc *noise, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out,
+                          int device, char *err)
 {
     int rc = epi_sdraw_validate(d, err);
     if (rc != EPI_OK) return rc;
@@ -3795,7 +4061,82 @@ int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, cons
         epi_sdraw_outputs dout{};
         dout.X = HostIO::at<char>(base, o_X); dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_ss);
         dout.J = HostIO::at<double>(base, o_J); dout.L = HostIO::at<double>(base, o_L);
-        return epi_sdraw_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+        return noise ? epi_sdraw_run_device_seeded(d, noise, &din, &dout, base + o_ws, wsb, st, err)
+                     : epi_sdraw_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+    };
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
+
+int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err)
+{
+    return sdraw_run_host(d, nullptr, in, out, device, err);
+}
+
+int epi_sdraw_run_host_seeded(const epi_sdraw_desc *d, const epi_noise_desc *noise, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out,
+                              int device, char *err)
+{
+    NoiseKey nk;
+    int rc = noise_key(noise, in ? in->z : nullptr, &nk, err);   // before anything is staged: no z is copied
+    if (rc != EPI_OK) return rc;
+    return sdraw_run_host(d, noise, in, out, device, err);
+}
+
+// ---- standard-normal draws from a seed: noise_fill (noise.hpp) ----
+int epi_noise_validate(const epi_noise_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL noise descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->stream >= (1u << 30)) { set_err(err, "stream must be below 2^30"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+static int noise_fill_check(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t rows, int64_t lane0, int64_t n_lanes, int32_t out_f32,
+                            const void *out, int32_t test_launch_groups, char *err)
+{
+    int rc = epi_noise_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (rows != 1 && rows != 3) { set_err(err, "rows must be 1 or 3"); return EPI_ERR_BAD_ARG; }
+    if (nt < 1 || n_lanes < 1) { set_err(err, "nt and n_lanes must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (t0 < 0 || t0 > ((int64_t)1 << 32) || nt > ((int64_t)1 << 32) - t0) { set_err(err, "t0 .. t0 + nt must lie in 0 .. 2^32 (t is one counter word)"); return EPI_ERR_BAD_ARG; }
+    if (lane0 < 0 || n_lanes - 1 > INT64_MAX - lane0) { set_err(err, "lane0 .. lane0 + n_lanes must lie in 0 .. 2^63"); return EPI_ERR_BAD_ARG; }
+    if (n_lanes > ((int64_t)1 << 62) / (3 * nt)) { set_err(err, "more than 2^62 elements"); return EPI_ERR_BAD_ARG; }
+    if (out_f32 != 0 && out_f32 != 1) { set_err(err, "out_f32 must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (test_launch_groups < 0) { set_err(err, "test_launch_groups must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (!out) { set_err(err, "NULL out"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_noise_fill_device(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t rows, int64_t lane0, int64_t n_lanes, int32_t out_f32,
+                          void *out, int32_t test_launch_groups, void *stream, char *err)
+{
+    int rc = noise_fill_check(d, t0, nt, rows, lane0, n_lanes, out_f32, out, test_launch_groups, err);
+    if (rc != EPI_OK) return rc;
+    NoiseFillArgs a{};
+    a.nk.seed_lo = d->seed_lo; a.nk.seed_hi = d->seed_hi; a.nk.stream = d->stream;
+    a.rows = rows; a.f32 = out_f32; a.t0 = (uint32_t)t0; a.lane0 = (uint64_t)lane0; a.n_lanes = (uint64_t)n_lanes;
+    a.items = (uint64_t)nt * (uint64_t)((rows + 1) / 2) * (uint64_t)n_lanes;
+    a.out = out;
+    const long long cap = test_launch_groups > 0 ? (long long)test_launch_groups : kNoiseLaunchGroups;
+    const long long groups = (long long)((a.items + kNoiseWg - 1) / kNoiseWg);
+    for (long long w0 = 0; w0 < groups; w0 += cap) {                  // in slices, as sdraw's
+        a.wg0 = w0;
+        const unsigned nb = (unsigned)(groups - w0 < cap ? groups - w0 : cap);
+        hipLaunchKernelGGL(noise_fill, dim3(nb), dim3(kNoiseWg), 0, (hipStream_t)stream, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(err, e, "noise_fill launch");
+    }
+    return EPI_OK;
+}
+
+int epi_noise_fill_host(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t rows, int64_t lane0, int64_t n_lanes, int32_t out_f32,
+                        void *out, int device, char *err)
+{
+    int rc = noise_fill_check(d, t0, nt, rows, lane0, n_lanes, out_f32, out, 0, err);
+    if (rc != EPI_OK) return rc;
+    HostIO io;
+    const size_t o_out = io.add_out(out, (size_t)nt * (size_t)rows, out_f32 ? 4 : 8, (size_t)n_lanes, 0, (size_t)n_lanes);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        return epi_noise_fill_device(d, t0, nt, rows, lane0, n_lanes, out_f32, base + o_out, 0, st, err);
     };
     return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
 }

@@ -21,6 +21,7 @@
 // Host-compilation contract: the body of each kernel is an EPI_DEV function of its own indices (sdraw_gain_lane, sdraw_path_lane);
 // tests/sdraw_emu.cpp compiles them with the host compiler and calls them one lane at a time.
 #pragma once
+#include "noise.hpp"
 
 constexpr int kSdRec = 24;                                // doubles per (day, chain) record: J 9, F 9, S+ 3, S-(k+1) 3
 constexpr int kSdPrefetch = 4;                            // days the z loads run ahead of their use (measured)
@@ -247,11 +248,14 @@ EPI_DEV void sdraw_gain_lane(const SdArgs &a, size_t t, size_t cl, double *lds)
     if (a.status && bits) atomicOr(a.status + c, bits);
 }
 
-// ---- one path: ZM 0 no noise (the deterministic path), 1 double z, 2 float z; OF 1 float X ----
+// ---- one path: ZM 0 no noise (the deterministic path), 1 double z, 2 float z, 3 z generated from nk (draw (k - k0, row, p)
+// of noise.hpp, at the point of use: there is no load latency to run ahead of, and the queue's registers stay free); OF 1 float X.
+// nk is an argument of its own (read with ZM 3 only), so that SdArgs and the kernels that take nothing else stay as they were ----
 template <int ZM>
-EPI_DEV void sd_ldz(const SdArgs &a, size_t N, size_t p, int k, double (&z)[3])
+EPI_DEV void sd_ldz(const SdArgs &a, size_t N, size_t p, int k, double (&z)[3], const NoiseKey &nk)
 {
     if (ZM == 0) return;
+    if (ZM == 3) { epi_normal_three(nk, (uint32_t)(k - a.k0), (uint64_t)p, z[0], z[1], z[2]); return; }
     const size_t o = (size_t)(k - a.k0) * 3 * N + p;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -261,7 +265,7 @@ EPI_DEV void sd_ldz(const SdArgs &a, size_t N, size_t p, int k, double (&z)[3])
 }
 
 template <int ZM, int OF>
-EPI_DEV void sdraw_path_lane(const SdArgs &a, size_t p)
+EPI_DEV void sdraw_path_lane(const SdArgs &a, size_t p, const NoiseKey &nk = NoiseKey{})
 {
     constexpr int M = 3, PF = kSdPrefetch;
     const size_t B = (size_t)a.B, N = B * (size_t)a.D, c = p / (size_t)a.D;
@@ -274,7 +278,7 @@ EPI_DEV void sdraw_path_lane(const SdArgs &a, size_t p)
     for (int q = 0; q < PF; q++) {
 #pragma unroll
         for (int i = 0; i < 3; i++) zq[q][i] = 0.0;
-        if (T - 1 - q >= k0) sd_ldz<ZM>(a, N, p, T - 1 - q, zq[q]);
+        if (ZM != 3 && T - 1 - q >= k0) sd_ldz<ZM>(a, N, p, T - 1 - q, zq[q], nk);
     }
     double x[M] = {0.0, 0.0, 0.0};
     for (int kb = T - 1; kb >= k0; kb -= PF) {
@@ -300,6 +304,7 @@ EPI_DEV void sdraw_path_lane(const SdArgs &a, size_t p)
                 }
             }
             if (ZM != 0) {
+                if (ZM == 3) sd_ldz<ZM>(a, N, p, k, zq[q], nk);
 #pragma unroll
                 for (int i = 0; i < M; i++) {
                     double nz = w[9 + IXM(i, 0)] * zq[q][0];
@@ -307,7 +312,7 @@ EPI_DEV void sdraw_path_lane(const SdArgs &a, size_t p)
                     for (int j = 1; j < M; j++) nz = nz + w[9 + IXM(i, j)] * zq[q][j];
                     v[i] = v[i] + nz;
                 }
-                if (k - PF >= k0) sd_ldz<ZM>(a, N, p, k - PF, zq[q]);
+                if (ZM != 3 && k - PF >= k0) sd_ldz<ZM>(a, N, p, k - PF, zq[q], nk);
             }
             if (a.clamp) {                                 // :221 on every draw; a NaN draw stays NaN
                 double cl[M];
@@ -345,5 +350,12 @@ __global__ __launch_bounds__(kSdPathWg) void sdraw_paths(const SdArgs a)
     const size_t p = (size_t)(a.wg0 + (long long)blockIdx.x) * (size_t)kSdPathWg + threadIdx.x;
     if (p >= (size_t)a.B * (size_t)a.D) return;
     sdraw_path_lane<ZM, OF>(a, p);
+}
+template <int OF>
+__global__ __launch_bounds__(kSdPathWg) void sdraw_paths_seeded(const SdArgs a, const NoiseKey nk)
+{
+    const size_t p = (size_t)(a.wg0 + (long long)blockIdx.x) * (size_t)kSdPathWg + threadIdx.x;
+    if (p >= (size_t)a.B * (size_t)a.D) return;
+    sdraw_path_lane<3, OF>(a, p, nk);
 }
 #endif

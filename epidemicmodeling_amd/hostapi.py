@@ -143,9 +143,18 @@ def nnls_affine_fit(X, y, max_iters=100, device=0):
     return out
 
 
-def random_npi_mc(sp, u_min, n_scen, K, seed=0, z=None, J0_prefix=None, J1_prefix=None, prefix_days=0, store_u=False, device=0):
+def normal_draws(nt, rows, lanes, seed, stream=0, t0=0, lane0=0, dtype=np.float64, device=0):
+    """epi_noise_fill_host: batch.normal_draws as a NumPy array [nt, rows, lanes] (synchronous), the same bits"""
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype must be float64 or float32")
+    return _call.normal_draws(HostBackend(device), nt, rows, lanes, seed, stream, t0, lane0, np.dtype(dtype) == np.dtype(np.float32))
+
+
+def random_npi_mc(sp, u_min, n_scen, K, seed=0, z=None, J0_prefix=None, J1_prefix=None, prefix_days=0, store_u=False, device=0,
+                  noise_seed=None, noise_stream=0):
     """epi_random_npi_mc_host (TrainPredictPrescribeNPI.m:496-521): sp [48, R], u_min [n, R] -> dict J0, J1 [n_scen, R]
-    (+ u [K, n, n_scen * R])."""
+    (+ u [K, n, n_scen * R]).  noise_seed= / noise_stream=: as batch.random_npi_mc (no z is copied)."""
+    noise = _lib.noise_of(noise_seed, noise_stream, z)
     keep = []
     n, R = np.shape(u_min)
     d = _lib.McDesc()
@@ -156,9 +165,12 @@ def random_npi_mc(sp, u_min, n_scen, K, seed=0, z=None, J0_prefix=None, J1_prefi
     if store_u:
         out["u"] = np.empty((K, n, n_scen * R))
     err = C.create_string_buffer(256)
-    rc = _lib.lib().epi_random_npi_mc_host(C.byref(d), _f(sp, keep), _f(u_min, keep), _f(z, keep), _f(J0_prefix, keep), _f(J1_prefix, keep),
-                                           out["u"].ctypes.data if store_u else None, out["J0"].ctypes.data, out["J1"].ctypes.data,
-                                           int(device), err)
+    tail = (_f(sp, keep), _f(u_min, keep), _f(z, keep), _f(J0_prefix, keep), _f(J1_prefix, keep),
+            out["u"].ctypes.data if store_u else None, out["J0"].ctypes.data, out["J1"].ctypes.data, int(device), err)
+    if noise is None:
+        rc = _lib.lib().epi_random_npi_mc_host(C.byref(d), *tail)
+    else:
+        rc = _lib.lib().epi_random_npi_mc_host_seeded(C.byref(d), C.byref(noise), *tail)
     _lib.check(rc, err)
     return out
 
@@ -248,10 +260,12 @@ def ensemble_summary(src, R, D, q=_lib.ENS_DEFAULT_Q, population=None, outputs=N
 
 
 def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series=None, A=None, noise_var=None, nv_mode=0,
-                device=0):
+                device=0, seed=None, noise_stream=0):
     """epi_arfc_run_host: the autoregressive alpha forecaster of batch.ar_forecast on NumPy arrays (synchronous).
     seg [L, R], beta / s0 / i0 [R], z [H, R * D] or None, drive [H, Sd] or None with drive_series [R * D] or None, A [p, R]
-    and noise_var [R] (both or neither).  Returns the dict of batch.ar_forecast as NumPy arrays."""
+    and noise_var [R] (both or neither).  seed= / noise_stream=: as batch.ar_forecast (no z is copied).  Returns the dict of
+    batch.ar_forecast as NumPy arrays."""
+    noise = _lib.noise_of(seed, noise_stream, z)
     if (A is None) != (noise_var is None):
         raise ValueError("A and noise_var are given together (the given-model mode) or not at all")
     be = HostBackend(device)
@@ -283,7 +297,7 @@ def ar_forecast(seg, beta, s0, i0, dt, p, H, D, z=None, drive=None, drive_series
     for k, v in zip(_lib.ARFC_IN_NAMES, (seg, beta, s0, i0, z, drive, None, A, noise_var)):
         setattr(ins, k, be.ptr(be.f64(v)))
     ins.drive_series = be.ptr(ser)
-    out = _call.run_family("arfc", be, d, [C.byref(ins)], _lib.arfc_shapes(R, D, Ls, p, H), _lib.ARFC_OUT_NAMES)
+    out = _call.run_family("arfc", be, d, [C.byref(ins)], _lib.arfc_shapes(R, D, Ls, p, H), _lib.ARFC_OUT_NAMES, noise=noise)
     return {"S": out["S"], "A": out["A_out"], "noise_var": out["noise_var_out"], "status": out["status"]}
 
 
@@ -337,13 +351,14 @@ def npi_plan(sp, u_min, eps, horizon, u_fixed=None, u_init=None, J0_prefix=None,
 
 
 def smoother_draws(S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z=None, s_term=None, P_term=None, k0=0, clamp=True, lane_block=0, B=None,
-                   out_dtype=None, outputs=("X", "rank", "status"), device=0):
+                   out_dtype=None, outputs=("X", "rank", "status"), device=0, seed=None, noise_stream=0):
     """epi_sdraw_run_host: batch.smoother_draws on NumPy arrays (synchronous): the same arguments, and the same keys, order,
     dtypes and bits.  The four filter arrays all float32 = float storage, anything else is taken as float64; z float32 or
-    float64; out_dtype np.float64 (default) or np.float32."""
+    float64; out_dtype np.float64 (default) or np.float32.  seed= / noise_stream=: no z is made or copied."""
     z = None if z is None else np.asarray(z)
     return _call.smoother_draws(HostBackend(device), *(np.asarray(v) for v in (S_PLUS, P_PLUS, S_MINUS, P_MINUS)), prm, D, z, s_term,
-                                P_term, k0, clamp, lane_block, B, None if out_dtype is None else np.dtype(out_dtype), outputs)
+                                P_term, k0, clamp, lane_block, B, None if out_dtype is None else np.dtype(out_dtype), outputs, 0, seed,
+                                noise_stream)
 
 
 def ensemble_score(src, truth, R, D, alpha=_lib.ESCORE_DEFAULT_ALPHA, n_bins=0, population=None, truth_series=None, first_day=None,

@@ -500,13 +500,14 @@ def monte_carlo_eks(w, n_regions, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=
 
 def ar_forecast(cases, deaths, population, ip, horizon=90, ar_order=24, history=120, n_draws=256, plan=None,
                 q=(0.025, 0.25, 0.5, 0.75, 0.975), seed=0, regression="nonnegls", nv_mode=0, num_regression_days=60, W=7,
-                cv_folds=50, cv_seed=0, device="cuda:0"):
+                cv_folds=50, cv_seed=0, device="cuda:0", rng="torch"):
     """The autoregressive alpha forecast of Tools/PrescribeNPI.m:204-241 as a Monte-Carlo fan chart for ALL regions: the front
     half (preprocessing, EKF round 1, regression, round 2, regression), then ar(alpha(end-history+1:end), ar_order) ->
     filtic -> filter over n_draws noise realisations per region -> negatives to 0 -> SI_Controlled from ((N - I0) / N, I0 / N)
     over [segment, forecast] (batch.ar_forecast, one device call), then the distribution over the draws of s, i, alpha_hat and
     the new cases ((N s) i) alpha per day and region (batch.ensemble_summary, one more; nothing is copied back in between).
-    The noise is torch.randn on the device from `seed`.  plan [horizon, n, S] (None = no exogenous term) adds
+    The noise is torch.randn on the device from `seed`; with rng="device" it is generated inside the simulation kernel from
+    `seed`, no z array exists and the returned z is None.  plan [horizon, n, S] (None = no exogenous term) adds
     gamma * ((u_max - u)' a + b) of the second regression to the continuation before the clamp: the regressor is the one the
     regression was trained on (X = u_max - u), where PrescribeNPI.m:237 multiplies the raw plan.
     Returns the front half's intermediates, seg [history, S], `forecast` (the dict of batch.ar_forecast: S [history + horizon,
@@ -522,9 +523,11 @@ def ar_forecast(cases, deaths, population, ip, horizon=90, ar_order=24, history=
     I0, fit2 = out["pre"]["I0"], out["fit2"]
     seg = np.ascontiguousarray(out["alpha_round2"][T - history:])
     dev = torch.device(device)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(int(seed))
-    z = torch.randn((horizon, S * n_draws), dtype=torch.float64, device=dev, generator=gen)
+    z = None
+    if not _check_rng(rng):
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        z = torch.randn((horizon, S * n_draws), dtype=torch.float64, device=dev, generator=gen)
     drive = ser = None
     if plan is not None:
         plan = np.asarray(plan, dtype=np.float64)
@@ -534,7 +537,7 @@ def ar_forecast(cases, deaths, population, ip, horizon=90, ar_order=24, history=
         drive = synth.MODEL_GAMMA * ((x * fit2["a"][None]).sum(axis=1) + fit2["b"][None])          # [horizon, S]
         ser = np.repeat(np.arange(S, dtype=np.int32), n_draws)
     fc = batch.ar_forecast(seg, np.full(S, synth.MODEL_BETA), (N - I0) / N, I0 / N, 1.0, ar_order, horizon, n_draws, z=z,
-                           drive=drive, drive_series=ser, nv_mode=nv_mode, device=device)
+                           drive=drive, drive_series=ser, nv_mode=nv_mode, device=device, seed=int(seed) if z is None else None)
     summary = batch.ensemble_summary(fc["S"], S, n_draws, q=q, population=N)
     out.update(seg=seg, forecast=fc, summary=summary, z=z, drive=drive)
     return out
@@ -651,23 +654,35 @@ def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None
             "best": res["best"], "best_loglik": res["best_loglik"], "chosen": chosen, "table": tab, "runner": r, "workload": gw}
 
 
+def _check_rng(rng, z=None):
+    if rng not in ("torch", "device"):
+        raise ValueError('rng must be "torch" or "device"')
+    if rng == "device" and z is not None:
+        raise ValueError('rng="device" and z together: the draws have one source')
+    return rng == "device"
+
+
 def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, seed=0, k0=0, storage="f64", clamp=True,
-                 device="cuda:0", lane_block="auto", z=None):
+                 device="cuda:0", lane_block="auto", z=None, rng="torch", noise_stream=0):
     """The fan chart of the EKF/EKS itself: run the smoother of `w` (a synth.Workload of SIAlphaModelEKF), draw n_draws joint
     posterior paths per chain by backward simulation (batch.smoother_draws on the runner's arrays as they lie; the terminal law is
     the smoothed last day, so s_final / Ps_final of the workload are honoured) and summarise them over the draws of each chain
     (batch.ensemble_summary: mean, std, min, max, quantiles at `q`; population [B] appends the new-case row ((N s) i) alpha).
     The noise is torch.randn on the device from `seed` (or `z` [T - k0, 3, B * n_draws], to repeat a call on given draws); k0 is
     the first day returned.  Nothing is copied back in between.
+    rng="device": the noise is generated inside the draw kernel from (`seed`, noise_stream) and no z array
+    exists -- the fan's memory halves; the returned z is None, and batch.normal_draws(T - k0, 3, B * n_draws, seed, noise_stream)
+    is the array that, passed as z, gives the same bits.  Another generator than torch's: other draws of the same law.
     Returns (runner, X [T - k0, 3, B * n_draws], the summary dict, z).  No host synchronisation."""
     if w.model != "SIAlphaModelEKF":
         raise ValueError("smoothed_fan needs a workload of the 3-state SIAlphaModelEKF")
+    seeded = _check_rng(rng, z)
     n_draws, k0 = int(n_draws), int(k0)
     dev = torch.device(device)
     dw = batch.DeviceWorkload(w, device)
     r = batch.EkfRunner(dw, ["S_PLUS", "P_PLUS", "S_MINUS", "P_MINUS", "S_SMOOTH", "P_SMOOTH"], lane_block=lane_block, storage=storage)
     r.run()
-    if z is None:
+    if z is None and not seeded:
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
         z = torch.randn((w.T - k0, 3, w.B * n_draws), dtype=torch.float64, device=dev, generator=gen)
@@ -677,19 +692,21 @@ def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None,
         ss = ss.permute(1, 0, 2).reshape(3, -1)[:, :w.B]
         ps = ps.permute(1, 0, 2).reshape(9, -1)[:, :w.B]
     res = batch.smoother_draws(r.out["S_PLUS"], r.out["P_PLUS"], r.out["S_MINUS"], r.out["P_MINUS"], dw.prm, n_draws, z=z,
-                               s_term=ss.to(torch.float64), P_term=ps.to(torch.float64), k0=k0, clamp=clamp, lane_block=blk, B=w.B)
+                               s_term=ss.to(torch.float64), P_term=ps.to(torch.float64), k0=k0, clamp=clamp, lane_block=blk, B=w.B,
+                               seed=int(seed) if seeded else None, noise_stream=noise_stream if seeded else 0)
     summary = batch.ensemble_summary(res["X"], w.B, n_draws, q=q, population=population)
     summary["rank"], summary["status"] = res["rank"], res["status"]
     return r, res["X"], summary, z
 
 
 def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975), seed=0, k0=None,
-                 storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0, device="cuda:0"):
+                 storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0, device="cuda:0",
+                 rng="torch"):
     """The forecast of Tools/TrainPredictPrescribeNPI.m:356-377 as a fan chart of the smoother's own joint law: the front half
     (preprocessing, EKF round 1, regression, round 2, regression), then the forecast filter -- the observations padded with NaN
     over `horizon` days, R_v padded with its mean (:360), the NPIs of `plan` [horizon, n, S] or, with plan = None, the last day's
     held (the reference's "fixed" forecast, :373-375) -- and smoothed_fan on it.  k0: the first day returned (default: the start
-    of the horizon).  Returns the front half's intermediates, `workload` (the forecast filter's), `runner`, X [T + horizon - k0,
+    of the horizon).  rng: smoothed_fan's ("device": no z array, z is None).  Returns the front half's intermediates, `workload` (the forecast filter's), `runner`, X [T + horizon - k0,
     3, S * n_draws], `summary` (rows s, i, alpha, new cases) and z."""
     T, S = cases.shape
     n = ip.shape[1]
@@ -711,14 +728,14 @@ def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None,
     uf = np.concatenate([u, tail])
     wf = workload3(xf, Rf, uf, N, pre["I0"], fit2["a"], fit2["b"])
     r, X, summary, z = smoothed_fan(wf, n_draws, q=q, population=N, seed=seed, k0=T if k0 is None else int(k0), storage=storage,
-                                    clamp=clamp, device=device)
+                                    clamp=clamp, device=device, rng=rng)
     out.update(workload=wf, runner=r, X=X, summary=summary, z=z)
     return out
 
 
 def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draws=256, alpha=(0.5, 0.05), n_bins=10, seed=0,
                 storage="f64", clamp=True, num_regression_days=60, W=7, device="cuda:0", regression="nonnegls", cv_folds=50, cv_seed=0,
-                z=None, joint=False, vs_p=0.5, max_lag=0):
+                z=None, joint=False, vs_p=0.5, max_lag=0, rng="torch"):
     """The look-ahead study of forecast_quality done with fans: instead of one point estimate per day, every forecast is the
     smoother's joint posterior law, scored against the truth by the ensemble CRPS, the weighted interval score, interval coverage
     and the rank histogram (batch.ensemble_score).
@@ -738,7 +755,7 @@ def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draw
     joint=True adds, from the same paths and origins, `joint_scores`: the dict of batch.ensemble_joint_score
     over the same days, whose row 3 scores every chain's new-case paths as paths from its origin on -- es (the energy score), vs
     (the variogram score of order vs_p over pairs of days at most max_lag apart) and n_days, each [4, B] -- and es, vs, n_days
-    [B], that row.  The default returns exactly the keys above."""
+    [B], that row.  The default returns exactly the keys above.  rng: smoothed_fan's ("device": no z array, z is None)."""
     LL, S = cases.shape
     F = int(num_forecast_days)
     T = LL - F
@@ -763,7 +780,8 @@ def fan_quality(cases, deaths, population, ip, num_forecast_days, starts, n_draw
     w = workload3(x, R_full[:, rr], ent["ip_filled"][:, :, rr], N[rr], I0[rr], fit2["a"][:, rr], fit2["b"][rr])
     k0 = int(origin.min())
     dev = torch.device(device)
-    r, X, _, z = smoothed_fan(w, D, q=(0.5,), population=None, seed=seed, k0=k0, storage=storage, clamp=clamp, device=device, z=z)
+    r, X, _, z = smoothed_fan(w, D, q=(0.5,), population=None, seed=seed, k0=k0, storage=storage, clamp=clamp, device=device, z=z,
+                              rng=rng)
     truth = ent["new_smoothed"]
     tw = np.full((LL - k0, 4, S), np.nan)
     tw[:, 3] = truth[k0:]
@@ -825,13 +843,14 @@ def path_outlook(X, R, D, thresholds=None, population=None, q=(0.025, 0.25, 0.5,
 
 def forecast_outlook(cases, deaths, population, ip, horizon, thresholds=None, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975),
                      seed=0, storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0,
-                     device="cuda:0"):
+                     device="cuda:0", rng="torch"):
     """forecast_fan, then path_outlook over the horizon: per region the law of the peak day and height of the forecast, of the
     cases over the horizon, and of the days above `thresholds` [n_thr, 4, S] (rows s, i, alpha, new cases; NaN: not asked).
-    Returns forecast_fan's dict with `outlook` (path_outlook's; day 0 of its histograms is the first day of the horizon)."""
+    rng: smoothed_fan's.  Returns forecast_fan's dict with `outlook` (path_outlook's; day 0 of its histograms is the first day of the
+    horizon)."""
     out = forecast_fan(cases, deaths, population, ip, horizon, n_draws=n_draws, plan=plan, q=q, seed=seed, storage=storage, clamp=clamp,
                        regression=regression, num_regression_days=num_regression_days, W=W, cv_folds=cv_folds, cv_seed=cv_seed,
-                       device=device)
+                       device=device, rng=rng)
     S = cases.shape[1]
     out["outlook"] = path_outlook(out["X"], S, int(n_draws), thresholds, population=np.asarray(population, dtype=np.float64), q=q)
     return out

@@ -2,7 +2,7 @@
 joint posterior draws of the smoother's paths (epidemicmodeling_amd/pipeline.py: forecast_fan), for all regions of
 the file at once.
 
-    python examples/fan_chart_from_csv.py [--score-last N [--joint]] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
+    python examples/fan_chart_from_csv.py [--rng device] [--score-last N [--joint]] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
 
 The front half of Tools/TrainPredictPrescribeNPI.m (preprocessing, two EKF rounds, two regressions), then its forecast filter
 (:356-377: NaN observations over the horizon, the last day's NPIs held), then 256 backward-simulated paths per region and their
@@ -20,7 +20,10 @@ joint draws from draws with the same bands and no dependence between days.
 --threshold C (or --outlook for the peak alone) prints the outlook over the horizon from the same joint draws (pipeline.path_outlook;
 DESIGN.md 4.18): per region the median and the 95 % band of the day of the peak of the daily new cases and of its height, the median
 of the cases summed over the horizon, and with a threshold the probability that the daily new cases reach C per 100 000 inhabitants
-within the horizon, the median first day they do, and the median longest run of days at or above it."""
+within the horizon, the median first day they do, and the median longest run of days at or above it.
+
+--rng device draws the noise inside the kernel from the seed instead of filling an array with torch.randn first:
+other draws of the same law, and half the memory."""
 import os
 import sys
 import tempfile
@@ -37,11 +40,11 @@ from prescribe_from_csv import synthetic_files  # noqa: E402
 Q = (0.025, 0.25, 0.5, 0.75, 0.975)
 
 
-def score_table(d, N, keep, n_last, draws, joint=False):
+def score_table(d, N, keep, n_last, draws, joint=False, rng="torch"):
     """the forecast of the last n_last days of the window, scored against them: one row per region and start"""
     starts = sorted({n_last, max(1, n_last // 2)}, reverse=True)
     fq = pipeline.fan_quality(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], n_last, starts, n_draws=draws,
-                              joint=joint, vs_p=0.5, max_lag=7)
+                              joint=joint, vs_p=0.5, max_lag=7, rng=rng)
     sc = {k: v.cpu().numpy() for k, v in fq["scores"].items()}
     rows = []
     for j, r in enumerate(keep):
@@ -80,7 +83,11 @@ def outlook_table(out, d, N, keep, draws, per_100k):
 
 def main():
     horizon, draws = 30, 256
-    n_last, outlook, per_100k = 0, False, None
+    n_last, outlook, per_100k, rng = 0, False, None, "torch"
+    if "--rng" in sys.argv:
+        i = sys.argv.index("--rng")
+        rng = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
     if "--outlook" in sys.argv:
         sys.argv.remove("--outlook")
         outlook = True
@@ -106,7 +113,7 @@ def main():
     d = dataio.read_oxcgrt(data, start, end)
     N = dataio.read_populations(pops, d["geo_ids"])
     keep = np.flatnonzero(np.isfinite(N) & np.isfinite(d["cases"]).any(axis=0))
-    out = pipeline.forecast_fan(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon, n_draws=draws, q=Q)
+    out = pipeline.forecast_fan(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon, n_draws=draws, q=Q, rng=rng)
     qs = out["summary"]["quantiles"].cpu().numpy()[:, :, 3]       # [horizon, n_q, S]: row 3 is the new cases
     mean = out["summary"]["mean"].cpu().numpy()[:, 3]
     status = out["summary"]["status"].cpu().numpy()
@@ -123,7 +130,7 @@ def main():
         print(outlook_table(out, d, N, keep, draws, per_100k).to_string(index=False))
     if n_last > 0:
         print(f"the last {n_last} days held out and forecast from the days before them:")
-        print(score_table(d, N, keep, n_last, draws, joint).to_string(index=False))
+        print(score_table(d, N, keep, n_last, draws, joint, rng).to_string(index=False))
 
 
 if __name__ == "__main__":

@@ -1511,6 +1511,70 @@ int epi_ejoint_run_device(const epi_ejoint_desc *d, const epi_ejoint_inputs *in,
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_ejoint_run_host(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, const epi_ejoint_outputs *out, int device, char *err);
 
+/* ---- Standard-normal draws from a seed, generated on the device (not a script of the reference) ----
+ * The Monte-Carlo calls above take their draws as an input array z.  The *_seeded calls below generate the same draws in registers
+ * where they are used: a seeded call gives, bit for bit, what its unseeded sibling gives when it is handed the array that
+ * epi_noise_fill_* writes for the same descriptor.  Definition (pinned; restated in tests/noise_ref.c and tests/noise_ref.py).
+ * Draw (t, row, lane) of a logical array [nt][rows][lanes], rows in {1, 3}, lane a 64-bit index, t a 32-bit index:
+ *   block    one Philox4x32-10 block (Salmon et al., SC'11), key (seed_lo, seed_hi), counter
+ *              (lane & 0xffffffff, lane >> 32, t, 0x80000000 | (stream << 1) | (row >> 1)),   stream < 2^30.
+ *            The set top bit keeps these blocks apart from the integer draws of epi_random_npi_mc_*, whose fourth counter word is a
+ *            day: the same seed may drive both
+ *   uniform  j = row & 1 takes the output words w[2j], w[2j+1]:  n = (w[2j] >> 6) * 2^26 + (w[2j+1] >> 6),  u = (n + 0.5) * 2^-52,
+ *            exact in double and strictly inside (0, 1)
+ *   normal   z = the inverse normal CDF of u by Wichura's algorithm AS241 (PPND16) with the published coefficients: q = u - 0.5;
+ *            |q| <= 0.425: r = 0.180625 - q q, z = (A(r) q) / B(r);  else r = sqrt(-epi_log(q < 0 ? u : 1 - u)), r <= 5: r - 1.6 and
+ *            C / D, else r - 5 and E / F, negated for q < 0.  Every polynomial is Horner in written operations (acc = acc * r + c,
+ *            no contraction), the logarithm is the library's own (fixed operation order), sqrt is correctly rounded, the quotient
+ *            is one division.  |z| <= 8.2096 (u = 2^-53): a seeded call never draws beyond that, where an input array may
+ *   t        the index in the array's own first dimension: the day k - k0 of epi_sdraw_*, the step of the simulators, the
+ *            forecast day of epi_arfc_*;  lane: the path p of epi_sdraw_*, the chain c of the others
+ *   rows 0 and 1 of a (t, lane) cost one block; row 2, and the single row of epi_arfc_*, use one block and discard half of it.
+ *   Nothing depends on launch geometry, lane_block, launch cuts or k0 beyond the t above. */
+typedef struct epi_noise_desc {
+    int32_t abi_version;
+    uint32_t seed_lo, seed_hi;   /* the Philox key */
+    uint32_t stream;             /* < 2^30: independent arrays under one seed */
+} epi_noise_desc;
+/* no GPU needed: EPI_ERR_BAD_ARG for a NULL descriptor, another ABI version, stream >= 2^30 */
+int epi_noise_validate(const epi_noise_desc *d, char *err);
+/* The window [t0, t0 + nt) x rows x [lane0, lane0 + n_lanes) of the logical array into out [nt][rows][n_lanes], double (out_f32 = 0)
+ * or float (1: the double draw rounded once).  DEVICE pointer; one kernel, cut into launches below 2^31 threads, enqueued on
+ * `stream`.  EPI_ERR_BAD_ARG for rows outside {1, 3}, nt or n_lanes < 1, t0 < 0 or t0 + nt > 2^32 (t is one counter word), lane0 < 0 or
+ * lane0 + n_lanes > 2^63, out_f32 outside {0, 1}, a NULL out, more than 2^62 elements.  test_launch_groups: 0; > 0: workgroups per
+ * launch (the tests cut small calls into several launches with it) */
+int epi_noise_fill_device(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t rows, int64_t lane0, int64_t n_lanes, int32_t out_f32,
+                          void *out, int32_t test_launch_groups, void *stream, char *err);
+/* HOST pointer, on a pooled context of `device` */
+int epi_noise_fill_host(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t rows, int64_t lane0, int64_t n_lanes, int32_t out_f32,
+                        void *out, int device, char *err);
+/* The seeded siblings: the arguments of the unseeded call with `noise` behind the descriptor.  z must be NULL (EPI_ERR_BAD_ARG: the
+ * draws have one source) and the descriptor's own noise / z_f32 field is not read: the noise term is always formed.  The host forms
+ * copy no z. */
+int epi_sdraw_run_device_seeded(const epi_sdraw_desc *d, const epi_noise_desc *noise, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out,
+                                void *ws, size_t ws_bytes, void *stream, char *err);
+int epi_sdraw_run_host_seeded(const epi_sdraw_desc *d, const epi_noise_desc *noise, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out,
+                              int device, char *err);
+int epi_arfc_run_device_seeded(const epi_arfc_desc *d, const epi_noise_desc *noise, const epi_arfc_inputs *in, const epi_arfc_outputs *out,
+                               void *stream, char *err);
+int epi_arfc_run_host_seeded(const epi_arfc_desc *d, const epi_noise_desc *noise, const epi_arfc_inputs *in, const epi_arfc_outputs *out,
+                             int device, char *err);
+int epi_sialpha_sim_device_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                  const double *sp, const double *z, double *s, double *i, double *alpha, double *J0, double *J1,
+                                  void *stream, char *err);
+int epi_sialpha_score_device_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                    const double *sp, const double *z, const double *J0_prefix, const double *J1_prefix, double *s,
+                                    double *i, double *alpha, double *J0, double *J1, void *stream, char *err);
+int epi_sialpha_sim_host_seeded(const epi_sim_desc *d, const epi_noise_desc *noise, const int32_t *u_series, const double *u,
+                                const double *sp, const double *z, double *s, double *i, double *alpha, double *J0, double *J1,
+                                int device, char *err);
+int epi_random_npi_mc_device_seeded(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min,
+                                    const double *z, const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0,
+                                    double *J1, void *stream, char *err);
+int epi_random_npi_mc_host_seeded(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min,
+                                  const double *z, const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0,
+                                  double *J1, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -71,7 +71,8 @@
 //       model)  R x p and R x 1: get(ar_sys, 'A')(2:end) and get(ar_sys, 'NoiseVariance') -- which normalisation MATLAB's
 //       NoiseVariance uses is not pinned by the reference, nv_mode (0 or 1) chooses ours when the model is fitted.
 //       S  B x 3 x (L + H), rows (s, i, alpha_hat): what 'ens_summary' takes;  A  R x p (a_1 .. a_p);  noise_var, status
-//       R x 1 (0 ok, 1 rank-deficient: NaN from day L + 1 on, 2 non-finite seg: NaN).
+//       R x 1 (0 ok, 1 rank-deficient: NaN from day L + 1 on, 2 non-finite seg: NaN).  An optional 14th input `seed` (see 'noise')
+//       with z = []: the draws 'noise'(H, 1, B, seed) are generated inside the kernel.
 //   [S_FRW_BCK, P_FRW_BCK, d2, rank] = epiekf_pipeline_mex('fuse', S_f, P_f, S_b, P_b, form, p_solver)
 //       The "Backward filtering (under test)" fusion of :464-478 for one chain.  S_f, S_b  m x T and P_f, P_b
 //       m x m x T (m = 3 or 6): the outputs of a forward filter and of its reverse-time twin as they come back (un-flipped);
@@ -99,7 +100,8 @@
 //       noise: with the clamp the path is S_SMOOTH)  D x 3 x (T - k_first + 1) standard-normal inputs;  s_term, P_term ([] = S_PLUS,
 //       P_PLUS of day T)  3 x 1, 3 x 3;  k_first ([] = 1)  the first day returned, ONE-based;  clamp ([] = 1).  X  D x 3 x
 //       (T - k_first + 1);  rank  1 x T (-1: a NaN record);  status  scalar (bit 0: a non-finite input entry met, bit 1: a rank
-//       below 3);  J, L  3 x 3 x T, only when requested.
+//       below 3);  J, L  3 x 3 x T, only when requested.  An optional 13th input `seed` (see 'noise') with z = []: "D draws,
+//       seed 7" -- the draws 'noise'(T - k_first + 1, 3, D, seed) are generated inside the kernel and no z is made or copied.
 //   [crps, wis, ae, width, rank, ties, cover, count, crps_mean, wis_mean, ae_mean, n_scored, cover_frac, pit_hist] = epiekf_pipeline_mex('escore', src, truth, D, alpha, n_bins, population, truth_series, first_day, k_first, k_last)
 //       Probabilistic forecast scores of a Monte-Carlo ensemble against a truth.  src, D, population  as
 //       'ens_summary' takes them;  truth  Rt x rows' x T (or Rt x T for a B x T src);  alpha ([] = none)  up to 8 levels of
@@ -123,7 +125,13 @@
 //       k_first + 1, at most 4096);  n_cross  R x rows' x n_thr;  cross_day_hist  R x rows' x n_thr x W.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
-//       u  (n_scen*R) x n_npi x K (only when requested).
+//       u  (n_scen*R) x n_npi x K (only when requested).  An optional 11th input `noise_seed` (see 'noise'; it may equal seed)
+//       with z = []: the state noise 'noise'(K, 3, n_scen*R, noise_seed) is generated inside the kernel.
+//   z = epiekf_pipeline_mex('noise', nt, rows, lanes, seed, t0, lane0)
+//       Standard-normal draws from a seed: the window [t0, t0 + nt) x rows x [lane0, lane0 + lanes) of the
+//       array the seed stands for (t0, lane0 ZERO-based offsets, [] or absent = 0), z  lanes x rows x nt.  rows 1 or 3.  seed  a
+//       double scalar (an integer in 0 .. 2^53) or [seed, stream] with stream < 2^30.  A command given `seed` equals the same
+//       command given z = 'noise'(...) of its z's shape, bit for bit.  |z| <= 8.21.
 // Build on a MATLAB host:  mex -I../include epiekf_pipeline_mex.cpp -L../epidemicmodeling_amd -lepiekf
 #include <stdio.h>
 #include <string.h>
@@ -137,6 +145,20 @@ static void fail_if(int rc, const char *err)
     if (rc != EPI_OK) mexErrMsgIdAndTxt("epiekf:error", "%s (%s)", err, epi_status_string(rc));
 }
 static const double *opt(const mxArray *a) { return mxIsEmpty(a) ? NULL : mxGetPr(a); }
+// the optional seed argument at position k: absent or [] = none (false); a double scalar or [seed, stream]
+static bool seed_arg(int nrhs, const mxArray *prhs[], int k, epi_noise_desc *nd)
+{
+    if (nrhs <= k || mxIsEmpty(prhs[k])) return false;
+    const mwSize n = mxGetNumberOfElements(prhs[k]);
+    if (!mxGetPr(prhs[k]) || n > 2) mexErrMsgTxt("seed must be a double scalar or [seed, stream]");
+    const double sd = mxGetPr(prhs[k])[0], st = n == 2 ? mxGetPr(prhs[k])[1] : 0.0;
+    if (!(sd >= 0.0 && sd <= 9007199254740992.0) || (double)(uint64_t)sd != sd) mexErrMsgTxt("seed must be an integer in 0 .. 2^53");
+    if (!(st >= 0.0 && st < 4294967296.0) || (double)(uint64_t)st != st) mexErrMsgTxt("stream must be a non-negative integer");
+    memset(nd, 0, sizeof *nd);
+    nd->abi_version = EPIEKF_ABI_VERSION; nd->seed_lo = (uint32_t)((uint64_t)sd & 0xFFFFFFFFu); nd->seed_hi = (uint32_t)((uint64_t)sd >> 32);
+    nd->stream = (uint32_t)st;                             // 2^30 and above reach the library's own check
+    return true;
+}
 static void want(const mxArray *a, mwSize rows, mwSize cols, const char *what)
 {
     if (mxGetM(a) != rows || mxGetN(a) != cols) mexErrMsgIdAndTxt("epiekf:arg", "%s must be %d x %d", what, (int)rows, (int)cols);
@@ -775,7 +797,10 @@ static void pathfn(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 
 static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
-    if (nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected");
+    if (nrhs != 13 && nrhs != 14) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected (a 14th: seed)");
+    epi_noise_desc nd;
+    const bool seeded = seed_arg(nrhs, prhs, 13, &nd);
+    if (seeded && !mxIsEmpty(prhs[7])) mexErrMsgTxt("seed and z together: the draws have one source");
     if (mxIsEmpty(prhs[1]) || mxGetNumberOfDimensions(prhs[1]) != 2) mexErrMsgTxt("seg must be R x L");
     const mwSize R = mxGetM(prhs[1]), L = mxGetN(prhs[1]);
     want(prhs[2], R, 3, "prm");
@@ -829,7 +854,7 @@ static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs
     memset(&out, 0, sizeof out);
     out.S = mxGetPr(o[0]); out.A_out = mxGetPr(o[1]); out.noise_var_out = mxGetPr(o[2]); out.status = st.data();
     char err[256] = {0};
-    const int rc = epi_arfc_run_host(&d, &in, &out, /*device=*/0, err);
+    const int rc = seeded ? epi_arfc_run_host_seeded(&d, &nd, &in, &out, /*device=*/0, err) : epi_arfc_run_host(&d, &in, &out, /*device=*/0, err);
     if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
     for (size_t k = 0; k < st.size(); k++) mxGetPr(o[3])[k] = (double)st[k];
     for (int k = 0; k < 4; k++)
@@ -973,7 +998,10 @@ static void plan(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 
 static void sdraw(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
-    if (nrhs != 12) mexErrMsgTxt("epiekf_pipeline_mex('sdraw', S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k_first, clamp): 12 inputs expected");
+    if (nrhs != 12 && nrhs != 13) mexErrMsgTxt("epiekf_pipeline_mex('sdraw', S_PLUS, P_PLUS, S_MINUS, P_MINUS, prm, D, z, s_term, P_term, k_first, clamp): 12 inputs expected (a 13th: seed)");
+    epi_noise_desc nd;
+    const bool seeded = seed_arg(nrhs, prhs, 12, &nd);
+    if (seeded && !mxIsEmpty(prhs[7])) mexErrMsgTxt("seed and z together: the draws have one source");
     for (int k = 1; k <= 6; k++)
         if (mxIsEmpty(prhs[k]) || !mxGetPr(prhs[k])) mexErrMsgTxt("S_PLUS ... D must be non-empty double arrays");
     if (mxGetNumberOfDimensions(prhs[1]) != 2 || mxGetM(prhs[1]) != 3) mexErrMsgTxt("S_PLUS must be 3 x T");
@@ -1015,7 +1043,7 @@ static void sdraw(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     memset(&out, 0, sizeof out);
     out.X = mxGetPr(o[0]); out.rank = rk.data(); out.status = &st;
     out.J = o[3] ? mxGetPr(o[3]) : NULL; out.L = o[4] ? mxGetPr(o[4]) : NULL;
-    const int rc = epi_sdraw_run_host(&d, &in, &out, /*device=*/0, err);
+    const int rc = seeded ? epi_sdraw_run_host_seeded(&d, &nd, &in, &out, /*device=*/0, err) : epi_sdraw_run_host(&d, &in, &out, /*device=*/0, err);
     if (rc != EPI_OK) { for (mxArray *a : o) if (a) mxDestroyArray(a); fail_if(rc, err); }
     for (size_t k = 0; k < (size_t)T; k++) mxGetPr(o[1])[k] = (double)rk[k];
     mxGetPr(o[2])[0] = (double)st;
@@ -1025,7 +1053,10 @@ static void sdraw(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
-    if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected");
+    if (nrhs != 10 && nrhs != 11) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected (an 11th: noise_seed)");
+    epi_noise_desc nd;
+    const bool seeded = seed_arg(nrhs, prhs, 10, &nd);
+    if (seeded && !mxIsEmpty(prhs[6])) mexErrMsgTxt("noise_seed and z together: the draws have one source");
     const mwSize R = mxGetM(prhs[1]), n = mxGetN(prhs[2]);
     want(prhs[1], R, EPI_SIM_PRM_COUNT, "sp");
     if (mxGetM(prhs[2]) != R) mexErrMsgTxt("u_min must be R x n_npi");
@@ -1042,12 +1073,39 @@ static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     mxArray *j0 = mxCreateDoubleMatrix(R, (mwSize)d.n_scen, mxREAL), *j1 = mxCreateDoubleMatrix(R, (mwSize)d.n_scen, mxREAL);
     mxArray *uo = nlhs > 2 ? dbl3(B, n, (mwSize)d.K) : NULL;
     char err[256] = {0};
-    const int rc = epi_random_npi_mc_host(&d, mxGetPr(prhs[1]), mxGetPr(prhs[2]), opt(prhs[6]), d.prefix_days > 0 ? mxGetPr(prhs[7]) : NULL,
-                                          d.prefix_days > 0 ? mxGetPr(prhs[8]) : NULL, uo ? mxGetPr(uo) : NULL, mxGetPr(j0), mxGetPr(j1), /*device=*/0, err);
+    const double *j0p = d.prefix_days > 0 ? mxGetPr(prhs[7]) : NULL, *j1p = d.prefix_days > 0 ? mxGetPr(prhs[8]) : NULL;
+    const int rc = seeded ? epi_random_npi_mc_host_seeded(&d, &nd, mxGetPr(prhs[1]), mxGetPr(prhs[2]), NULL, j0p, j1p, uo ? mxGetPr(uo) : NULL,
+                                                          mxGetPr(j0), mxGetPr(j1), /*device=*/0, err)
+                          : epi_random_npi_mc_host(&d, mxGetPr(prhs[1]), mxGetPr(prhs[2]), opt(prhs[6]), j0p, j1p, uo ? mxGetPr(uo) : NULL,
+                                                   mxGetPr(j0), mxGetPr(j1), /*device=*/0, err);
     if (rc != EPI_OK) { mxDestroyArray(j0); mxDestroyArray(j1); mxDestroyArray(uo); fail_if(rc, err); }
     plhs[0] = j0;
     if (nlhs > 1) plhs[1] = j1; else mxDestroyArray(j1);
     if (nlhs > 2) plhs[2] = uo;
+}
+
+static void noise(int, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 5 || nrhs > 7) mexErrMsgTxt("epiekf_pipeline_mex('noise', nt, rows, lanes, seed, t0, lane0): 5 to 7 inputs expected");
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};              // nt, rows, lanes, t0, lane0
+    const int at[5] = {1, 2, 3, 5, 6};
+    for (int k = 0; k < 5; k++) {
+        if (at[k] >= nrhs || (k >= 3 && mxIsEmpty(prhs[at[k]]))) continue;
+        if (!mxGetPr(prhs[at[k]]) || mxGetNumberOfElements(prhs[at[k]]) != 1) mexErrMsgTxt("nt, rows, lanes, t0 and lane0 must be double scalars");
+        v[k] = mxGetScalar(prhs[at[k]]);
+        if (!(v[k] >= 0.0 && v[k] <= 9007199254740992.0) || (double)(int64_t)v[k] != v[k]) mexErrMsgTxt("nt, rows, lanes, t0 and lane0 must be non-negative integers");
+    }
+    epi_noise_desc nd;
+    if (!seed_arg(nrhs, prhs, 4, &nd)) mexErrMsgTxt("seed must be a double scalar or [seed, stream]");
+    char err[256] = {0};
+    if (v[0] < 1.0 || v[2] < 1.0) mexErrMsgTxt("nt and lanes must be >= 1");
+    if (v[1] != 1.0 && v[1] != 3.0) mexErrMsgTxt("rows must be 1 or 3");
+    if (v[0] * v[1] * v[2] > 2147483647.0) mexErrMsgTxt("nt * rows * lanes is limited to 2^31 - 1: ask for a window");
+    // the ABI's [nt][rows][lanes] is MATLAB's lanes x rows x nt
+    mxArray *z = dbl3((mwSize)v[2], (mwSize)v[1], (mwSize)v[0]);
+    const int rc = epi_noise_fill_host(&nd, (int64_t)v[3], (int64_t)v[0], (int32_t)v[1], (int64_t)v[4], (int64_t)v[2], 0, mxGetPr(z), /*device=*/0, err);
+    if (rc != EPI_OK) { mxDestroyArray(z); fail_if(rc, err); }
+    plhs[0] = z;
 }
 
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
@@ -1073,5 +1131,6 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "pathfn") == 0) pathfn(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "jscore") == 0) jscore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "noise") == 0) noise(nlhs, plhs, nrhs, prhs);
     else mexErrMsgTxt("epiekf_pipeline_mex: unknown command");
 }
