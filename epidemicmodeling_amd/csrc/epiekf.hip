@@ -19,7 +19,6 @@
 #include <functional>
 #include <mutex>
 #include <thread>
-#include <tuple>
 #include <vector>
 #include "ekf_device.hpp"
 
@@ -2268,17 +2267,20 @@ static int sialpha_sim_host(const epi_sim_desc *d, const epi_noise_desc *noise, 
     if (!d || d->B < 1 || d->K < 1 || d->Su < 1 || d->n_npi < 1 || !u || !sp) { set_err(err, "bad simulator descriptor"); return EPI_ERR_BAD_ARG; }
     if (d->u_block != 0) { set_err(err, "u_block is a device-side layout"); return EPI_ERR_BAD_ARG; }
     const size_t B = d->B, K = d->K;
-    HostStage h(device);
-    const void *dus = h.in(u_series, B * 4), *du = h.in(u, K * d->n_npi * (size_t)d->Su * 8);
-    const void *dsp = h.in(sp, (size_t)EPI_SIM_PRM_COUNT * B * 8), *dz = h.in(z, K * 3 * B * 8);
-    void *ds = h.out(s, K * B * 8), *di = h.out(i, K * B * 8), *da = h.out(alpha, K * B * 8);
-    void *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
-    if (h.failed()) return h.fail(err);
-    if (noise)
-        return h.finish(epi_sialpha_sim_device_seeded(d, noise, (const int32_t *)dus, (const double *)du, (const double *)dsp, nullptr,
-                                                      (double *)ds, (double *)di, (double *)da, (double *)d0, (double *)d1, nullptr, err), err);
-    return h.finish(epi_sialpha_sim_device(d, (const int32_t *)dus, (const double *)du, (const double *)dsp, (const double *)dz,
-                                           (double *)ds, (double *)di, (double *)da, (double *)d0, (double *)d1, nullptr, err), err);
+    HostIO io;
+    const size_t o_us = io.in(u_series, B * 4), o_u = io.in(u, K * d->n_npi * (size_t)d->Su * 8);
+    const size_t o_sp = io.in(sp, (size_t)EPI_SIM_PRM_COUNT * B * 8), o_z = io.in(z, K * 3 * B * 8);
+    const size_t o_s = io.out(s, K * B * 8), o_i = io.out(i, K * B * 8), o_a = io.out(alpha, K * B * 8);
+    const size_t o_0 = io.out(J0, B * 8), o_1 = io.out(J1, B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        const int32_t *dus = HostIO::at<const int32_t>(base, o_us);
+        if (noise)
+            return epi_sialpha_sim_device_seeded(d, noise, dus, f64(o_u), f64(o_sp), nullptr, f64(o_s), f64(o_i), f64(o_a), f64(o_0),
+                                                 f64(o_1), st, err);
+        return epi_sialpha_sim_device(d, dus, f64(o_u), f64(o_sp), f64(o_z), f64(o_s), f64(o_i), f64(o_a), f64(o_0), f64(o_1), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_sialpha_sim_host(const epi_sim_desc *d, const int32_t *u_series, const double *u, const double *sp,
@@ -2302,25 +2304,29 @@ int epi_seirp_sim_host(int32_t B, int32_t K, int32_t par_steps, double dt, int32
                        const double *par, const double *init, const double *sat, double *out, int device, char *err)
 {
     if (B < 1 || K < 1 || par_steps < 1 || !par || !init || !out) { set_err(err, "bad SEIRP arguments"); return EPI_ERR_BAD_ARG; }
-    HostStage h(device);
-    const void *dp = h.in(par, (size_t)par_steps * 7 * B * 8), *di = h.in(init, (size_t)5 * B * 8), *ds = h.in(sat, (size_t)6 * B * 8);
-    void *dout = h.out(out, (size_t)K * 5 * B * 8);
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_seirp_sim_device(B, K, par_steps, dt, saturated, integrator, (const double *)dp, (const double *)di,
-                                         (const double *)ds, (double *)dout, nullptr, err), err);
+    HostIO io;
+    const size_t o_p = io.in(par, (size_t)par_steps * 7 * B * 8), o_i = io.in(init, (size_t)5 * B * 8), o_s = io.in(sat, (size_t)6 * B * 8);
+    const size_t o_out = io.out(out, (size_t)K * 5 * B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        return epi_seirp_sim_device(B, K, par_steps, dt, saturated, integrator, f64(o_p), f64(o_i), f64(o_s), f64(o_out), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_si_controlled_host(int32_t B, int32_t K, int32_t Sa, double dt, const int32_t *alpha_series, const double *alpha,
                            const double *prm, double *s, double *i, int device, char *err)
 {
     if (B < 1 || K < 1 || Sa < 1) { set_err(err, "bad SI_Controlled arguments"); return EPI_ERR_BAD_ARG; }
-    HostStage h(device);
-    const void *das = h.in(alpha_series, (size_t)B * 4), *da = h.in(alpha, (size_t)(K > 1 ? K - 1 : 1) * Sa * 8);
-    const void *dp = h.in(prm, (size_t)3 * B * 8);
-    void *ds = h.out(s, (size_t)K * B * 8), *di = h.out(i, (size_t)K * B * 8);
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_si_controlled_device(B, K, Sa, dt, (const int32_t *)das, (const double *)da, (const double *)dp,
-                                             (double *)ds, (double *)di, nullptr, err), err);
+    HostIO io;
+    const size_t o_as = io.in(alpha_series, (size_t)B * 4), o_a = io.in(alpha, (size_t)(K > 1 ? K - 1 : 1) * Sa * 8);
+    const size_t o_p = io.in(prm, (size_t)3 * B * 8);
+    const size_t o_s = io.out(s, (size_t)K * B * 8), o_i = io.out(i, (size_t)K * B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        return epi_si_controlled_device(B, K, Sa, dt, HostIO::at<const int32_t>(base, o_as), f64(o_a), f64(o_p), f64(o_s), f64(o_i), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_npi_cost_host(int32_t B, int32_t T, int32_t n_npi, int32_t Su, int32_t weights_per_day, const int32_t *u_series,
@@ -2328,24 +2334,28 @@ int epi_npi_cost_host(int32_t B, int32_t T, int32_t n_npi, int32_t Su, int32_t w
                       int device, char *err)
 {
     if (B < 1 || T < 1 || n_npi < 1 || Su < 1) { set_err(err, "bad NPICost arguments"); return EPI_ERR_BAD_ARG; }
-    HostStage h(device);
-    const void *dus = h.in(u_series, (size_t)B * 4), *dn = h.in(newcases, (size_t)T * B * 8);
-    const void *du = h.in(inputs, (size_t)T * n_npi * Su * 8);
-    const void *dw = h.in(weights, (size_t)(weights_per_day ? T : 1) * n_npi * B * 8);
-    void *d0 = h.out(J0, (size_t)B * 8), *d1 = h.out(J1, (size_t)B * 8);
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_npi_cost_device(B, T, n_npi, Su, weights_per_day, (const int32_t *)dus, (const double *)dn,
-                                        (const double *)du, (const double *)dw, (double *)d0, (double *)d1, nullptr, err), err);
+    HostIO io;
+    const size_t o_us = io.in(u_series, (size_t)B * 4), o_n = io.in(newcases, (size_t)T * B * 8);
+    const size_t o_u = io.in(inputs, (size_t)T * n_npi * Su * 8);
+    const size_t o_w = io.in(weights, (size_t)(weights_per_day ? T : 1) * n_npi * B * 8);
+    const size_t o_0 = io.out(J0, (size_t)B * 8), o_1 = io.out(J1, (size_t)B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        return epi_npi_cost_device(B, T, n_npi, Su, weights_per_day, HostIO::at<const int32_t>(base, o_us), f64(o_n), f64(o_u), f64(o_w),
+                                   f64(o_0), f64(o_1), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_sir_sim_host(int32_t B, int32_t K, double dt, const double *prm, double *out, int device, char *err)
 {
     if (B < 1 || K < 1) { set_err(err, "bad SIR arguments"); return EPI_ERR_BAD_ARG; }
-    HostStage h(device);
-    const void *dp = h.in(prm, (size_t)6 * B * 8);
-    void *dout = h.out(out, (size_t)K * 3 * B * 8);
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_sir_sim_device(B, K, dt, (const double *)dp, (double *)dout, nullptr, err), err);
+    HostIO io;
+    const size_t o_p = io.in(prm, (size_t)6 * B * 8), o_out = io.out(out, (size_t)K * 3 * B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        return epi_sir_sim_device(B, K, dt, HostIO::at<const double>(base, o_p), HostIO::at<double>(base, o_out), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_preprocess_host(const epi_pre_desc *d, const double *cases, const double *deaths, const double *population,
@@ -2353,20 +2363,24 @@ int epi_preprocess_host(const epi_pre_desc *d, const double *cases, const double
 {
     if (!d || !out || d->S < 1 || d->T < 1 || d->n_npi < 0 || d->n_npi > EPI_MAX_NPI) { set_err(err, "bad preprocessing descriptor"); return EPI_ERR_BAD_ARG; }
     const size_t TS = (size_t)d->T * d->S * 8;
-    HostStage h(device);
-    const void *dc = h.in(cases, TS), *dd = h.in(deaths, TS), *dp = h.in(population, (size_t)d->S * 8);
-    const void *dip = h.in(ip, TS * (size_t)d->n_npi);
-    epi_pre_outputs dout{};
-    dout.new_refined = (double *)h.out(out->new_refined, TS); dout.new_smoothed = (double *)h.out(out->new_smoothed, TS);
-    dout.zero_lag = (double *)h.out(out->zero_lag, TS); dout.x_new = (double *)h.out(out->x_new, TS);
-    dout.x_total = (double *)h.out(out->x_total, TS); dout.R_v = (double *)h.out(out->R_v, TS);
-    dout.fatality = (double *)h.out(out->fatality, TS); dout.I0 = (double *)h.out(out->I0, (size_t)d->S * 8);
-    dout.ip_filled = (double *)h.out(out->ip_filled, TS * (size_t)d->n_npi);
+    HostIO io;
+    const size_t o_c = io.in(cases, TS), o_d = io.in(deaths, TS), o_p = io.in(population, (size_t)d->S * 8);
+    const size_t o_ip = io.in(ip, TS * (size_t)d->n_npi);
+    using PO = epi_pre_outputs;
+    struct O { double *PO::*arr; size_t bytes; };
+    const O outs[9] = {{&PO::new_refined, TS}, {&PO::new_smoothed, TS}, {&PO::zero_lag, TS}, {&PO::x_new, TS}, {&PO::x_total, TS},
+                       {&PO::R_v, TS}, {&PO::fatality, TS}, {&PO::I0, (size_t)d->S * 8}, {&PO::ip_filled, TS * (size_t)d->n_npi}};
+    size_t o_out[9];
+    for (int k = 0; k < 9; k++) o_out[k] = io.out(out->*outs[k].arr, outs[k].bytes);
     const size_t wsb = epi_preprocess_workspace_bytes(d);
-    void *ws = wsb ? h.scratch(wsb) : nullptr;
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_preprocess_device(d, (const double *)dc, (const double *)dd, (const double *)dp, (const double *)dip, &dout,
-                                          ws, wsb, nullptr, err), err);
+    const size_t o_ws = wsb ? io.reserve(wsb) : HostIO::kAbsent;
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        epi_pre_outputs dout{};
+        for (int k = 0; k < 9; k++) dout.*outs[k].arr = f64(o_out[k]);
+        return epi_preprocess_device(d, f64(o_c), f64(o_d), f64(o_p), f64(o_ip), &dout, HostIO::at<void>(base, o_ws), wsb, st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_nnls_affine_fit_host(const epi_nnls_desc *d, const double *X, const double *y, double *a, double *b,
@@ -2374,13 +2388,16 @@ int epi_nnls_affine_fit_host(const epi_nnls_desc *d, const double *X, const doub
 {
     if (!d || d->S < 1 || d->D < 1 || d->n < 1 || d->n > EPI_MAX_NPI) { set_err(err, "bad NNLS descriptor"); return EPI_ERR_BAD_ARG; }
     const size_t S = d->S;
-    HostStage h(device);
-    const void *dX = h.in(X, (size_t)d->D * d->n * S * 8), *dy = h.in(y, (size_t)d->D * S * 8);
-    void *da = h.out(a, (size_t)d->n * S * 8), *db = h.out(b, S * 8), *dm = h.out(min_err, S * 8);
-    void *di = h.out(iters, S * 4), *df = h.out(flag, S * 4);
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_nnls_affine_fit_device(d, (const double *)dX, (const double *)dy, (double *)da, (double *)db, (double *)dm,
-                                               (int32_t *)di, (int32_t *)df, nullptr, err), err);
+    HostIO io;
+    const size_t o_X = io.in(X, (size_t)d->D * d->n * S * 8), o_y = io.in(y, (size_t)d->D * S * 8);
+    const size_t o_a = io.out(a, (size_t)d->n * S * 8), o_b = io.out(b, S * 8), o_m = io.out(min_err, S * 8);
+    const size_t o_i = io.out(iters, S * 4), o_f = io.out(flag, S * 4);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        return epi_nnls_affine_fit_device(d, f64(o_X), f64(o_y), f64(o_a), f64(o_b), f64(o_m), HostIO::at<int32_t>(base, o_i),
+                                          HostIO::at<int32_t>(base, o_f), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 static int random_npi_mc_host(const epi_mc_desc *d, const epi_noise_desc *noise, const double *sp, const double *u_min, const double *z,
@@ -2390,16 +2407,18 @@ static int random_npi_mc_host(const epi_mc_desc *d, const epi_noise_desc *noise,
     if (!d || d->R < 1 || d->n_scen < 1 || d->K < 1 || d->n_npi < 1 || d->n_npi > EPI_MAX_NPI ||
         (int64_t)d->R * d->n_scen > (int64_t)1 << 30) { set_err(err, "bad Monte-Carlo scenario descriptor"); return EPI_ERR_BAD_ARG; }
     const size_t R = d->R, B = R * (size_t)d->n_scen, K = d->K;
-    HostStage h(device);
-    const void *dsp = h.in(sp, (size_t)EPI_SIM_PRM_COUNT * R * 8), *dum = h.in(u_min, (size_t)d->n_npi * R * 8);
-    const void *dz = h.in(z, K * 3 * B * 8), *dj0 = h.in(J0_prefix, R * 8), *dj1 = h.in(J1_prefix, R * 8);
-    void *du = h.out(u_out, K * (size_t)d->n_npi * B * 8), *d0 = h.out(J0, B * 8), *d1 = h.out(J1, B * 8);
-    if (h.failed()) return h.fail(err);
-    if (noise)
-        return h.finish(epi_random_npi_mc_device_seeded(d, noise, (const double *)dsp, (const double *)dum, nullptr, (const double *)dj0,
-                                                        (const double *)dj1, (double *)du, (double *)d0, (double *)d1, nullptr, err), err);
-    return h.finish(epi_random_npi_mc_device(d, (const double *)dsp, (const double *)dum, (const double *)dz, (const double *)dj0,
-                                             (const double *)dj1, (double *)du, (double *)d0, (double *)d1, nullptr, err), err);
+    HostIO io;
+    const size_t o_sp = io.in(sp, (size_t)EPI_SIM_PRM_COUNT * R * 8), o_um = io.in(u_min, (size_t)d->n_npi * R * 8);
+    const size_t o_z = io.in(z, K * 3 * B * 8), o_p0 = io.in(J0_prefix, R * 8), o_p1 = io.in(J1_prefix, R * 8);
+    const size_t o_u = io.out(u_out, K * (size_t)d->n_npi * B * 8), o_0 = io.out(J0, B * 8), o_1 = io.out(J1, B * 8);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        auto f64 = [&](size_t o) { return HostIO::at<double>(base, o); };
+        if (noise)
+            return epi_random_npi_mc_device_seeded(d, noise, f64(o_sp), f64(o_um), nullptr, f64(o_p0), f64(o_p1), f64(o_u), f64(o_0),
+                                                   f64(o_1), st, err);
+        return epi_random_npi_mc_device(d, f64(o_sp), f64(o_um), f64(o_z), f64(o_p0), f64(o_p1), f64(o_u), f64(o_0), f64(o_1), st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_random_npi_mc_host(const epi_mc_desc *d, const double *sp, const double *u_min, const double *z,
@@ -2468,18 +2487,23 @@ int epi_rt_expfit_run_host(const epi_rt_desc *d, const int32_t *x_series, const 
     if (rc != EPI_OK) return rc;
     if (!x || !rp || !out) { set_err(err, "NULL input array"); return EPI_ERR_BAD_ARG; }
     const size_t B = d->B, T = d->T;
-    HostStage h(device);
-    const void *dxs = h.in(x_series, B * 4), *dx = h.in(x, T * d->Sx * 8), *drp = h.in(rp, (size_t)EPI_RT_PRM_COUNT * B * 8);
+    HostIO io;
+    const size_t o_xs = io.in(x_series, B * 4), o_x = io.in(x, T * d->Sx * 8), o_rp = io.in(rp, (size_t)EPI_RT_PRM_COUNT * B * 8);
     struct O { double *epi_rt_outputs::*arr; size_t bytes; bool required; };
     const size_t n2 = T * 2 * B * 8, n4 = T * 4 * B * 8, n1 = T * B * 8;
     const O outs[] = {{&epi_rt_outputs::S_MINUS, n2, true}, {&epi_rt_outputs::S_PLUS, n2, true}, {&epi_rt_outputs::P_MINUS, n4, true},
                       {&epi_rt_outputs::P_PLUS, n4, true}, {&epi_rt_outputs::K_GAIN, n2, false}, {&epi_rt_outputs::S_SMOOTH, n2, false},
                       {&epi_rt_outputs::P_SMOOTH, n4, false}, {&epi_rt_outputs::innovations, n1, false}, {&epi_rt_outputs::rho, n1, false}};
-    epi_rt_outputs dout{};
-    for (auto &o : outs)   // forward quantities the caller does not want still feed the smoother: a device buffer, no download
-        dout.*o.arr = (double *)(out->*o.arr ? h.out(out->*o.arr, o.bytes) : (o.required ? h.scratch(o.bytes) : nullptr));
-    if (h.failed()) return h.fail(err);
-    return h.finish(epi_rt_expfit_run_device(d, (const int32_t *)dxs, (const double *)dx, (const double *)drp, &dout, nullptr, err), err);
+    size_t o_out[9];
+    for (int k = 0; k < 9; k++)   // forward quantities the caller does not want still feed the smoother: a device copy, no download
+        o_out[k] = outs[k].required ? io.add_out(out->*outs[k].arr, 1, 1, outs[k].bytes, 0, outs[k].bytes) : io.out(out->*outs[k].arr, outs[k].bytes);
+    auto enqueue = [&](char *base, hipStream_t st) {
+        epi_rt_outputs dout{};
+        for (int k = 0; k < 9; k++) dout.*outs[k].arr = HostIO::at<double>(base, o_out[k]);
+        return epi_rt_expfit_run_device(d, HostIO::at<const int32_t>(base, o_xs), HostIO::at<const double>(base, o_x),
+                                        HostIO::at<const double>(base, o_rp), &dout, st, err);
+    };
+    return run_host(device, io, err, enqueue);
 }
 
 static int pre_validate(const epi_pre_desc *d, int *W2, int *nfact, char *err)
@@ -2858,7 +2882,7 @@ int epi_rtwin_run_host(const epi_rtwin_desc *d, const double *new_cases, const e
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_rtwin_run_device(d, (const double *)(base + o_x), &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- REGRESSION_TYPE = 'LASSO': lasso(X, y, 'CV', K) per region (TrainPredictPrescribeNPI.m:254-290) ----
@@ -2947,7 +2971,7 @@ int epi_lasso_run_host(const epi_lasso_desc *d, const double *X, const double *y
         return epi_lasso_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), HostIO::at<const int32_t>(base, o_f),
                                     &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- REGRESSION_TYPE = 'NONNEGATIVELS-ELEMENT-WISE': a robust bounded affine fit per (NPI, region) (TrainPredictPrescribeNPI.m:279-292) ----
@@ -3029,7 +3053,7 @@ int epi_robfit_run_host(const epi_robfit_desc *d, const double *X, const double 
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_robfit_run_device(d, (const double *)(base + o_X), (const double *)(base + o_y), &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- the NPI-to-growth-rate predictor per (train end, region) (test04FullFeatureExtMLpipeline.m:292-404, :418-431, :576-642) ----
@@ -3152,7 +3176,7 @@ int epi_ratemap_run_host(const epi_ratemap_desc *d, const epi_ratemap_inputs *in
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_ratemap_run_device(d, &din, &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- MATLAB's rectangular backslash per (row count, region) (test01FitExponential.m:159, test03 :169, test05 :185) ----
@@ -3239,7 +3263,7 @@ int epi_mldiv_run_host(const epi_mldiv_desc *d, const epi_mldiv_inputs *in, cons
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_mldiv_run_device(d, &din, &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- support-vector regression per (row count, region) (test05DirectNewCasesLearning.m:198-268, test04 :435-445, test03 :242-262) ----
@@ -3335,7 +3359,7 @@ int epi_svr_run_host(const epi_svr_desc *d, const epi_svr_inputs *in, const epi_
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_svr_run_device(d, &din, &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- Monte-Carlo ensemble statistics over the draws of every region (BASELINE config 5) ----
@@ -3408,7 +3432,7 @@ int epi_ens_run_host(const epi_ens_desc *d, const void *src, const double *popul
         dout.count = (int32_t *)(base + o_cnt);
         return epi_ens_run_device(d, base + o_src, HostIO::at<const double>(base, o_pop), &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- the autoregressive alpha forecaster, R regions x D draws (Tools/PrescribeNPI.m:204-215) ----
@@ -3533,7 +3557,7 @@ static int arfc_run_host(const epi_arfc_desc *d, const epi_noise_desc *noise, co
         dout.status = (int32_t *)(base + o_st);
         return noise ? epi_arfc_run_device_seeded(d, noise, &din, &dout, st, err) : epi_arfc_run_device(d, &din, &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_arfc_run_host(const epi_arfc_desc *d, const epi_arfc_inputs *in, const epi_arfc_outputs *out, int device, char *err)
@@ -3628,7 +3652,7 @@ int epi_fuse_run_host(const epi_fuse_desc *d, const epi_fuse_inputs *in, const e
         dout.rank = HostIO::at<int32_t>(base, o_rk); dout.status = HostIO::at<int32_t>(base, o_st);
         return epi_fuse_run_device(d, &din, &dout, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- the Gaussian innovation log-likelihood of every chain, from the arrays a filter run left (loglik.hpp) ----
@@ -3799,7 +3823,7 @@ int epi_loglik_run_host(const epi_loglik_desc *d, const epi_loglik_inputs *in, c
         dout.best = HostIO::at<int32_t>(base, o_b); dout.best_loglik = HostIO::at<double>(base, o_bl);
         return epi_loglik_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- the direct optimal-NPI planner: one lane per (region, cost weight) chain (npi_plan.hpp) ----
@@ -3926,7 +3950,7 @@ int epi_plan_run_host(const epi_plan_desc *d, const epi_plan_inputs *in, const e
         dout.states = HostIO::at<double>(base, o_x); dout.mu = HostIO::at<double>(base, o_mu); dout.F_trace = HostIO::at<double>(base, o_ft);
         return epi_plan_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- joint posterior draws of the smoothed paths: sdraw_gain, then sdraw_paths (smoother_draws.hpp) ----
@@ -4064,7 +4088,7 @@ static int sdraw_run_host(const epi_sdraw_desc *d, const epi_noise_desc *noise, 
         return noise ? epi_sdraw_run_device_seeded(d, noise, &din, &dout, base + o_ws, wsb, st, err)
                      : epi_sdraw_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 int epi_sdraw_run_host(const epi_sdraw_desc *d, const epi_sdraw_inputs *in, const epi_sdraw_outputs *out, int device, char *err)
@@ -4138,7 +4162,7 @@ int epi_noise_fill_host(const epi_noise_desc *d, int64_t t0, int64_t nt, int32_t
     auto enqueue = [&](char *base, hipStream_t st) -> int {
         return epi_noise_fill_device(d, t0, nt, rows, lane0, n_lanes, out_f32, base + o_out, 0, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- probabilistic forecast scores of the ensembles: escore_items, then escore_regions (ens_score.hpp) ----
@@ -4288,7 +4312,7 @@ int epi_escore_run_host(const epi_escore_desc *d, const epi_escore_inputs *in, c
         HostIO::bind_opt(dout, i32, o_i, base);
         return epi_escore_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- path functionals of the ensembles: pathfn_paths, pathfn_combine over time segments, pathfn_regions (path_functionals.hpp) ----
@@ -4500,7 +4524,7 @@ int epi_pathfn_run_host(const epi_pathfn_desc *d, const epi_pathfn_inputs *in, c
         HostIO::bind_opt(dout, i32r, o_r, base);
         return epi_pathfn_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 // ---- joint scores of the ensembles: ejoint_members, ejoint_pairs, ejoint_vario, ejoint_final (ens_joint.hpp) ----
@@ -4629,7 +4653,7 @@ int epi_ejoint_run_host(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, c
         dout.member_dist = HostIO::at<double>(base, o_md);
         return epi_ejoint_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
-    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+    return run_host(device, io, err, enqueue);
 }
 
 }  // extern "C"

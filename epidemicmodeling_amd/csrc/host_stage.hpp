@@ -1,6 +1,6 @@
 // The host-pointer staging layer of epiekf.hip, which includes this file once (one translation unit: set_err, hip_fail and
-// kMaxDevices are the ones defined there).  Pooled contexts for the batched calls -- HostCtx and its pool, with_ctx,
-// place_and_run, HostIO, run_call -- and HostStage, the synchronous stager of the simulators and small fits.
+// kMaxDevices are the ones defined there).  EVERY *_host entry point runs on it: HostCtx and its pool, with_ctx,
+// place_and_run, HostIO, run_call and, for the calls without a placement search, run_host.
 #pragma once
 namespace epi {
 constexpr size_t kStageBytes = (size_t)64 << 20;
@@ -190,6 +190,9 @@ struct HostIO {
         off += (rows * cols * elem + align - 1) / align * align;
         return o;
     }
+    // a whole dense array of `bytes` bytes, or kAbsent (NULL to the kernels) when the caller does not have it or it is empty
+    size_t in(const void *host, size_t bytes) { return host && bytes ? add_in(host, 1, 1, bytes, 0, bytes) : kAbsent; }
+    size_t out(void *host, size_t bytes) { return host && bytes ? add_out(host, 1, 1, bytes, 0, bytes) : kAbsent; }
     size_t reserve(size_t bytes)       // device-only scratch inside the same arena
     {
         off = (off + 255) & ~(size_t)255;
@@ -371,44 +374,10 @@ static int run_call(HostCtx *cx, const HostIO &io, int tries, epi_placement_repo
     return EPI_OK;
 }
 
-// Synchronous device copies of host arrays for one call of a simulator or fit on `device`, which is left current; everything
-// is freed on destruction.  After the first HIP error the staging calls do nothing and return NULL: the caller asks failed()
-// once, before it enqueues.
-struct HostStage {
-    std::vector<void *> allocs;
-    std::vector<std::tuple<void *, void *, size_t>> downloads;
-    hipError_t e;
-    const char *what = "hipSetDevice";
-    explicit HostStage(int device) : e(hipSetDevice(device)) { if (e == hipSuccess) what = "host staging"; }
-    ~HostStage() { for (void *p : allocs) (void)hipFree(p); }
-    bool failed() const { return e != hipSuccess; }
-    int fail(char *err) const { return hip_fail(err, e, what); }
-    void *scratch(size_t bytes)        // device-only memory
-    {
-        void *p = nullptr;
-        if (e != hipSuccess || (e = hipMalloc(&p, bytes)) != hipSuccess) return nullptr;
-        allocs.push_back(p);
-        return p;
-    }
-    void *in(const void *host, size_t bytes)
-    {
-        void *p = host ? scratch(bytes) : nullptr;
-        if (p) e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
-        return p;
-    }
-    void *out(void *host, size_t bytes)
-    {
-        void *p = host ? scratch(bytes) : nullptr;
-        if (p) downloads.emplace_back(host, p, bytes);
-        return p;
-    }
-    int finish(int rc, char *err)
-    {
-        if (rc != EPI_OK) return rc;
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        for (auto &d : downloads)
-            if (e == hipSuccess) e = hipMemcpy(std::get<0>(d), std::get<1>(d), std::get<2>(d), hipMemcpyDeviceToHost);
-        return e == hipSuccess ? EPI_OK : fail(err);
-    }
-};
+// Every host call without a placement search: a pooled context of `device`, and the call on it.
+template <class F>
+static int run_host(int device, const HostIO &io, char *err, F &&enqueue)
+{
+    return with_ctx(device, err, [&](HostCtx *cx) { return run_call(cx, io, 0, nullptr, err, enqueue); });
+}
 }   // namespace epi

@@ -46,7 +46,11 @@
  * helper streams (one per concurrent call and device, with their events), and
  * for the *_host entry points a pool of contexts per device (stream, device
  * arena, pinned staging buffer) and one worker thread per device used by the
- * *_multi calls.  Return value 0 or a negative epi_status; `err` (256 bytes,
+ * *_multi calls.  EVERY *_host entry point, the simulators and small fits
+ * included, runs on such a context: its kernels on the context's stream, which
+ * alone it waits for, one copy each way, no allocation once the arena is large
+ * enough, and the calling thread's current device as it found it.
+ * Return value 0 or a negative epi_status; `err` (256 bytes,
  * may be NULL) receives the reference's own error() text for the four
  * reference errors.
  */

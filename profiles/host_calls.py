@@ -3,7 +3,11 @@
     arrays to (J0, J1), front, I_opt and the optimum's plan -- the whole of TrainPredictPrescribeNPI.m:421-493, 624-633;
   * epi_ekf_run_host_multi: one 9 375-chain block (the shard of the sweep one of 8 GPUs runs), reduced outputs;
   * epi_ekf_run_host: ONE reference-shaped call (B = 1) and the 250 cost weights of one region (B = 250), all outputs.
-python profiles/host_calls.py"""
+  * the simulators and small fits a MATLAB host calls for one region at a time: SIalpha_Controlled (B = 1, K = 120),
+    epi_sialpha_sim_host at 250 chains, epi_preprocess_host at the size of examples/prescribe_from_csv.py (8 regions x 200 days)
+    and epi_random_npi_mc_host at 300 regions x 100 scenarios; the first call of the process is reported apart from the
+    steady state (it creates the pooled context).
+python profiles/host_calls.py [--small]          (--small: the last group only)"""
 import json
 import os
 import sys
@@ -13,94 +17,123 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from epidemicmodeling_amd import hostapi, pipeline, synth  # noqa: E402
+from epidemicmodeling_amd import _lib, hostapi, pipeline, synth, tools  # noqa: E402
 from tests import helpers as H  # noqa: E402
 
 rep = {}
-S, P, T_hist, hor = 300, 250, 400, 120
-w0 = synth.make_cfg4(S, 1, T_hist, hor)
-rng = np.random.default_rng(0)
-reg_tab = synth.make_regions(S)
-N = np.asarray(reg_tab["N"], dtype=np.float64)
-I0 = np.full(S, 100.0)
-a, b = np.ascontiguousarray(reg_tab["a"].T), reg_tab["b"]
-eps = synth.epsilon_grid(P)
-reg = pipeline.sweep_region_inputs(N, I0, a, b, 12)
-sp = pipeline.scoring_region_inputs(np.stack([1.0 - 100.0 / N, 100.0 / N, np.full(S, synth.ALPHA0)]), a, b, synth.IP_MAXES[:12], np.ones((12, S)))
-J0p, J1p = rng.random(S) * 1e-2, rng.random(S) * 40.0
-args = (w0.x, w0.u, w0.R_series, reg, eps, sp, J0p, J1p, T_hist)
-hostapi.sweep_prescribe(*args)                                   # first call: contexts, arena
-ts = []
-for _ in range(5):
-    t0 = time.perf_counter(); got = hostapi.sweep_prescribe(*args); ts.append(time.perf_counter() - t0)
-in_mb = sum(np.asarray(v).nbytes for v in (w0.x, w0.u, w0.R_series, sp, *reg.values())) / 1e6
-out_mb = sum(v.nbytes for v in got.values() if hasattr(v, "nbytes")) / 1e6
-rep["sweep_prescribe_host_300x250x520"] = {
-    "ms_median": 1e3 * float(np.median(ts)), "ms_min": 1e3 * min(ts), "host_to_device_MB": in_mb, "device_to_host_MB": out_mb,
-    "region_day_steps": S * P * (T_hist + hor), "steps_per_s": S * P * (T_hist + hor) / float(np.median(ts)),
-    "front_points_mean": float(got["on_front"].sum(axis=1).mean()),
-    "note": "per-region inputs expanded on the device; filter + scoring + Pareto filter + gather of the optimum's plan; python packing of the ctypes call included"}
-print(json.dumps(rep["sweep_prescribe_host_300x250x520"]), flush=True)
-
-def timed(w, n, **kw):
-    """median / min ms of the C call alone (output arrays of the first call written again) and of the python call that
-    allocates and NaN-fills fresh output arrays every time (what a MEX gateway's mxCreateDoubleMatrix costs as well)"""
-    out = H.host_call(w, **kw)
-    tc, tw = [], []
-    for _ in range(n):
-        H.host_call(w, out=out, timing=tc, **kw)
-    for _ in range(max(3, n // 2)):
-        t0 = time.perf_counter(); H.host_call(w, **kw); tw.append(time.perf_counter() - t0)
-    mb = sum(v.nbytes for v in out.values()) / 1e6
-    return {"c_call_ms_median": 1e3 * float(np.median(tc)), "c_call_ms_min": 1e3 * min(tc),
-            "with_fresh_output_arrays_ms_median": 1e3 * float(np.median(tw)), "device_to_host_MB": mb,
-            "c_call_GB_per_s_of_outputs": mb / 1e3 / float(np.median(tc))}
 
 
-full = synth.make_cfg4(75, 125, 400, 120)                         # 9 375 chains
-for tag, devs in (("one_block", [0]), ("two_blocks_strided", [0, 0])):
-    r = timed(full, 5, devices=devs, outputs=["u_opt_smooth", "S_SMOOTH"], extras=False)
-    r["note"] = ("epi_ekf_run_host_multi, 9 375 chains (the shard of the sweep one of 8 GPUs runs), reduced outputs into pageable memory; "
-                 + ("one block on device 0" if len(devs) == 1 else "two chain blocks, both on device 0, one after the other: every array is moved as a strided piece"))
-    rep["run_host_multi_9375_chains_reduced_outputs_" + tag] = r
-    print(json.dumps(r), flush=True)
+def timed_py(f, n):
+    """ms of the first call, then median / min of n calls after one more warm call (the Python wrapper included)"""
+    ts = []
+    for _ in range(n + 2):
+        t0 = time.perf_counter(); f(); ts.append(1e3 * (time.perf_counter() - t0))
+    return {"first_call_ms": ts[0], "ms_median": float(np.median(ts[2:])), "ms_min": min(ts[2:]), "calls": n}
 
-# all 11 outputs of the 9 375-chain shard (6.2 GB back over PCIe): into arrays the previous call already wrote (resident pages) and into
-# fresh, never-touched ones (np.empty: the pages are faulted in under the copy -- what a MEX gateway's freshly created outputs cost)
-def timed_cold(w, n, **kw):
-    names = [k for k in H.OUT_NAMES]
-    m, n_npi, B, T = w.m, w.n_npi, w.B, w.T
-    rows = {"u_opt": n_npi, "u_opt_smooth": n_npi, "S_MINUS": m, "S_PLUS": m, "S_SMOOTH": m, "P_MINUS": m * m, "P_PLUS": m * m, "P_SMOOTH": m * m, "K_GAIN": m}
-    tc = []
-    for _ in range(n):
-        out = {k: np.empty((T, rows[k], B) if k in rows else (T, B)) for k in names}
-        H.host_call(w, out=out, timing=tc, extras=False, **kw)
+
+rng = np.random.default_rng(1)
+K, n_npi = 120, 12
+sim = (rng.random((n_npi, K)) * 2, 0.99, 0.01, 0.3, synth.IP_MAXES, 0.0, 100.0, 1 / 7, np.full(n_npi, 0.01), 0.0, synth.MODEL_BETA,
+       1e-3, 1e-3, 1e-3, K, 1.0)
+z1 = rng.standard_normal((3, K))
+spB = np.zeros((48, 300)); spB[0] = 0.99; spB[1] = 0.01; spB[2] = 0.3; spB[4] = 100.0; spB[5] = 1 / 7; spB[7] = synth.MODEL_BETA; spB[8:11] = 1e-3; spB[11] = 1.0
+spB[12:24] = 0.01; spB[24:36] = synth.IP_MAXES[:, None]; spB[36:48] = 1.0
+sd = _lib.SimDesc()
+sd.abi_version, sd.B, sd.K, sd.Su, sd.n_npi, sd.noise, sd.with_cost = _lib.ABI_VERSION, 250, K, 1, n_npi, 1, 1
+sim250 = [sd, np.zeros(250, dtype=np.int32), rng.random((K, n_npi, 1)) * 2, np.ascontiguousarray(spB[:, :250]), rng.standard_normal((K, 3, 250)),
+          ("s", (K, 250)), ("i", (K, 250)), ("alpha", (K, 250)), ("J0", (250,)), ("J1", (250,))]
+raw = synth.make_raw_counts(8, 200, seed=1)
+for tag, f, n in (("SIalpha_Controlled_B1_K120", lambda: tools.SIalpha_Controlled(*sim, noise=z1), 200),
+                  ("sialpha_sim_host_B250_K120", lambda: H.flat_call("sialpha_sim", sim250), 200),
+                  ("preprocess_host_S8_T200", lambda: hostapi.preprocess(raw["cases"], raw["population"], raw["deaths"], raw["ip"]), 200),
+                  ("random_npi_mc_host_R300_x100_K120", lambda: hostapi.random_npi_mc(spB, np.zeros((n_npi, 300)), 100, K, seed=1), 50)):
+    rep[tag] = timed_py(f, n)
+    print(tag, json.dumps(rep[tag]), flush=True)
+if "--small" not in sys.argv:          # the large calls
+    S, P, T_hist, hor = 300, 250, 400, 120
+    w0 = synth.make_cfg4(S, 1, T_hist, hor)
+    rng = np.random.default_rng(0)
+    reg_tab = synth.make_regions(S)
+    N = np.asarray(reg_tab["N"], dtype=np.float64)
+    I0 = np.full(S, 100.0)
+    a, b = np.ascontiguousarray(reg_tab["a"].T), reg_tab["b"]
+    eps = synth.epsilon_grid(P)
+    reg = pipeline.sweep_region_inputs(N, I0, a, b, 12)
+    sp = pipeline.scoring_region_inputs(np.stack([1.0 - 100.0 / N, 100.0 / N, np.full(S, synth.ALPHA0)]), a, b, synth.IP_MAXES[:12], np.ones((12, S)))
+    J0p, J1p = rng.random(S) * 1e-2, rng.random(S) * 40.0
+    args = (w0.x, w0.u, w0.R_series, reg, eps, sp, J0p, J1p, T_hist)
+    hostapi.sweep_prescribe(*args)                                   # first call: contexts, arena
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter(); got = hostapi.sweep_prescribe(*args); ts.append(time.perf_counter() - t0)
+    in_mb = sum(np.asarray(v).nbytes for v in (w0.x, w0.u, w0.R_series, sp, *reg.values())) / 1e6
+    out_mb = sum(v.nbytes for v in got.values() if hasattr(v, "nbytes")) / 1e6
+    rep["sweep_prescribe_host_300x250x520"] = {
+        "ms_median": 1e3 * float(np.median(ts)), "ms_min": 1e3 * min(ts), "host_to_device_MB": in_mb, "device_to_host_MB": out_mb,
+        "region_day_steps": S * P * (T_hist + hor), "steps_per_s": S * P * (T_hist + hor) / float(np.median(ts)),
+        "front_points_mean": float(got["on_front"].sum(axis=1).mean()),
+        "note": "per-region inputs expanded on the device; filter + scoring + Pareto filter + gather of the optimum's plan; python packing of the ctypes call included"}
+    print(json.dumps(rep["sweep_prescribe_host_300x250x520"]), flush=True)
+
+    def timed(w, n, **kw):
+        """median / min ms of the C call alone (output arrays of the first call written again) and of the python call that
+        allocates and NaN-fills fresh output arrays every time (what a MEX gateway's mxCreateDoubleMatrix costs as well)"""
+        out = H.host_call(w, **kw)
+        tc, tw = [], []
+        for _ in range(n):
+            H.host_call(w, out=out, timing=tc, **kw)
+        for _ in range(max(3, n // 2)):
+            t0 = time.perf_counter(); H.host_call(w, **kw); tw.append(time.perf_counter() - t0)
         mb = sum(v.nbytes for v in out.values()) / 1e6
-        del out
-    return {"c_call_ms_median": 1e3 * float(np.median(tc)), "c_call_ms_min": 1e3 * min(tc), "device_to_host_MB": mb,
-            "c_call_GB_per_s_of_outputs": mb / 1e3 / float(np.median(tc))}
+        return {"c_call_ms_median": 1e3 * float(np.median(tc)), "c_call_ms_min": 1e3 * min(tc),
+                "with_fresh_output_arrays_ms_median": 1e3 * float(np.median(tw)), "device_to_host_MB": mb,
+                "c_call_GB_per_s_of_outputs": mb / 1e3 / float(np.median(tc))}
 
 
-r = timed(full, 4, extras=False)
-r["note"] = "epi_ekf_run_host, 9 375 chains, ALL 11 outputs, output arrays of the previous call written again (resident pages)"
-rep["run_host_9375_chains_all_outputs_reused_arrays"] = r
-print(json.dumps(r), flush=True)
-r = timed_cold(full, 3)
-r["note"] = "the same into fresh never-touched arrays (np.empty): page faults under the copy"
-rep["run_host_9375_chains_all_outputs_fresh_arrays"] = r
-print(json.dumps(r), flush=True)
-
-two = synth.make_cfg4(2, 250, 400, 120)
-for tag, w in (("B1", two.select(np.array([137]))), ("B250", two.select(np.arange(250)))):
-    r = timed(w, 9, extras=False)
-    t0 = time.perf_counter(); H.oracle_batch(w, n_threads=1); t_cpu = time.perf_counter() - t0
-    r.update({"chains": w.B, "days": w.T, "cpu_oracle_one_thread_ms": 1e3 * t_cpu, "note": "epi_ekf_run_host, all 11 outputs"})
-    rep["run_host_" + tag] = r
-    print(json.dumps(r), flush=True)
-    if tag == "B250":
-        r = timed_cold(w, 7)
-        r["note"] = "B = 250, all 11 outputs into fresh never-touched arrays"
-        rep["run_host_B250_fresh_arrays"] = r
+    full = synth.make_cfg4(75, 125, 400, 120)                         # 9 375 chains
+    for tag, devs in (("one_block", [0]), ("two_blocks_strided", [0, 0])):
+        r = timed(full, 5, devices=devs, outputs=["u_opt_smooth", "S_SMOOTH"], extras=False)
+        r["note"] = ("epi_ekf_run_host_multi, 9 375 chains (the shard of the sweep one of 8 GPUs runs), reduced outputs into pageable memory; "
+                     + ("one block on device 0" if len(devs) == 1 else "two chain blocks, both on device 0, one after the other: every array is moved as a strided piece"))
+        rep["run_host_multi_9375_chains_reduced_outputs_" + tag] = r
         print(json.dumps(r), flush=True)
+
+    # all 11 outputs of the 9 375-chain shard (6.2 GB back over PCIe): into arrays the previous call already wrote (resident pages) and into
+    # fresh, never-touched ones (np.empty: the pages are faulted in under the copy -- what a MEX gateway's freshly created outputs cost)
+    def timed_cold(w, n, **kw):
+        names = [k for k in H.OUT_NAMES]
+        m, n_npi, B, T = w.m, w.n_npi, w.B, w.T
+        rows = {"u_opt": n_npi, "u_opt_smooth": n_npi, "S_MINUS": m, "S_PLUS": m, "S_SMOOTH": m, "P_MINUS": m * m, "P_PLUS": m * m, "P_SMOOTH": m * m, "K_GAIN": m}
+        tc = []
+        for _ in range(n):
+            out = {k: np.empty((T, rows[k], B) if k in rows else (T, B)) for k in names}
+            H.host_call(w, out=out, timing=tc, extras=False, **kw)
+            mb = sum(v.nbytes for v in out.values()) / 1e6
+            del out
+        return {"c_call_ms_median": 1e3 * float(np.median(tc)), "c_call_ms_min": 1e3 * min(tc), "device_to_host_MB": mb,
+                "c_call_GB_per_s_of_outputs": mb / 1e3 / float(np.median(tc))}
+
+
+    r = timed(full, 4, extras=False)
+    r["note"] = "epi_ekf_run_host, 9 375 chains, ALL 11 outputs, output arrays of the previous call written again (resident pages)"
+    rep["run_host_9375_chains_all_outputs_reused_arrays"] = r
+    print(json.dumps(r), flush=True)
+    r = timed_cold(full, 3)
+    r["note"] = "the same into fresh never-touched arrays (np.empty): page faults under the copy"
+    rep["run_host_9375_chains_all_outputs_fresh_arrays"] = r
+    print(json.dumps(r), flush=True)
+
+    two = synth.make_cfg4(2, 250, 400, 120)
+    for tag, w in (("B1", two.select(np.array([137]))), ("B250", two.select(np.arange(250)))):
+        r = timed(w, 9, extras=False)
+        t0 = time.perf_counter(); H.oracle_batch(w, n_threads=1); t_cpu = time.perf_counter() - t0
+        r.update({"chains": w.B, "days": w.T, "cpu_oracle_one_thread_ms": 1e3 * t_cpu, "note": "epi_ekf_run_host, all 11 outputs"})
+        rep["run_host_" + tag] = r
+        print(json.dumps(r), flush=True)
+        if tag == "B250":
+            r = timed_cold(w, 7)
+            r["note"] = "B = 250, all 11 outputs into fresh never-touched arrays"
+            rep["run_host_B250_fresh_arrays"] = r
+            print(json.dumps(r), flush=True)
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
 json.dump(rep, open(os.path.join(ROOT, "gpurun_out", "host_calls.json"), "w"), indent=1)

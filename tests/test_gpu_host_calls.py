@@ -1,4 +1,4 @@
-"""What the shared frame of the pooled host-pointer entry points owns (csrc/host_stage.hpp: with_ctx, run_call): the calling
+"""What the shared frame of the host-pointer entry points owns (csrc/host_stage.hpp: with_ctx, run_call): the calling
 thread keeps its current device, a failed context acquisition is an ordinary error that leaves nothing behind, and a context
 one entry point returns to the pool serves the next one.  Every call is made at a tiny shape (the frame does not depend on
 size) and compared bit for bit with the same call made before; that the calls compute the right thing is the business of
@@ -11,6 +11,8 @@ from tests import helpers as H
 pytestmark = pytest.mark.gpu
 
 R, D, T = 3, 16, 24
+MOVED = ("sialpha_sim", "sialpha_sim_seeded", "random_npi_mc", "random_npi_mc_seeded", "seirp_sim", "si_controlled", "npi_cost", "sir_sim",
+         "preprocess", "nnls_affine_fit", "rt_expfit_run")
 
 
 def _same(got, want, tag):
@@ -21,7 +23,7 @@ def _same(got, want, tag):
 
 @pytest.fixture(scope="module")
 def calls(gpu_device):
-    """name -> f(device): every pooled entry point on fixed inputs, returning a dict of NumPy arrays."""
+    """name -> f(device): every kind of host entry point on fixed inputs, returning a dict of NumPy arrays."""
     from epidemicmodeling_amd import batch, hostapi, synth
     rng = np.random.default_rng(5)
     w4 = synth.make_cfg4(n_regions=R, n_eps=2, T_hist=16, horizon=8)            # one block of 6 chains x 24 days
@@ -37,7 +39,11 @@ def calls(gpu_device):
     sf, sb = rng.standard_normal((5, 3, R)), rng.standard_normal((5, 3, R))
     G = rng.standard_normal((2, 5, 3, 3, R))
     Pf, Pb = (np.ascontiguousarray((np.einsum("tikb,tjkb->tijb", g, g) + np.eye(3)[None, :, :, None]).reshape(5, 9, R)) for g in G)
+    flat = H.flat_call_cases()        # the simulators and small fits, straight on the library: the Tools/ wrappers take one chain
+    moved = {k: flat[k + "/full"] for k in MOVED if not k.endswith("_seeded")}
+    moved.update({k: flat[k[:-len("_seeded")] + "/seeded"] for k in MOVED if k.endswith("_seeded")})
     return {
+        **{k: (lambda dev, c=c: H.flat_call(c[0], c[1], device=dev)) for k, c in moved.items()},
         "ekf_run_host": lambda dev: H.host_call(w4, device=dev),
         "lookahead": lambda dev: batch.lookahead_host(w3, truth, N, 6, 4, device=dev, chains=True),
         "rtwin": lambda dev: hostapi.rt_window(cases, 7, 1.0, 1, 3, device=dev),
@@ -89,6 +95,8 @@ def test_a_context_left_by_one_entry_point_serves_another(calls, first, hip_lib)
     import torch
     torch.cuda.set_device(0)
     hip_lib.epi_host_pool_release()
-    order = ("ekf_run_host", "lasso", "ekf_run_host", "fuse", "arfc", "lookahead", "ens", "rtwin", "robfit", "ekf_run_host")
+    order = ("ekf_run_host", "lasso", "sir_sim", "ekf_run_host", "fuse", "preprocess", "arfc", "sialpha_sim", "lookahead",
+             "random_npi_mc_seeded", "ens", "rt_expfit_run", "rtwin", "nnls_affine_fit", "robfit", "seirp_sim", "sialpha_sim_seeded",
+             "si_controlled", "random_npi_mc", "npi_cost", "ekf_run_host")
     for k in order:                               # the first call creates the device's one context, the others reuse it
         _same(calls[k](0), first[k], k)

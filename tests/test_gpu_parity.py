@@ -1089,6 +1089,35 @@ def test_host_forms_of_the_stages_around_the_filter(gpu_device):
         assert np.array_equal(ma[k], mb[k].cpu().numpy()), k
 
 
+def test_host_forms_of_the_simulators_and_small_fits_equal_their_device_forms(gpu_device):
+    """Each of the nine host functions of the simulators and small fits = its *_device sibling on the same inputs, word for
+    word, once with every optional array present and once with every optional array absent (H.flat_call_cases: u_series /
+    alpha_series NULL against a shared series, no z, no J0 / J1, no u_out, prefix_days 0 and 7, no sat, no deaths / ip with
+    n_npi = 0, single outputs of the fits, Rt_ExpFitEKF asked for S_SMOOTH alone -- its four forward arrays then live on the
+    device only -- and for everything).  The seeded forms = the unseeded ones fed normal_draws of the same seed and stream."""
+    from epidemicmodeling_amd import _lib, hostapi
+    cases = H.flat_call_cases()
+    host = {}
+    for name, (sym, args, dev_args) in cases.items():
+        host[name] = H.flat_call(sym, args)
+        dev = H.flat_call(sym, dev_args, gpu=gpu_device)
+        assert host[name] and set(host[name]) <= set(dev), name
+        for k, v in host[name].items():
+            assert v.dtype == dev[k].dtype and np.array_equal(v, dev[k], equal_nan=True), (name, k)
+            assert not (np.isnan(v).all() if v.dtype == np.float64 else (v == -1).all()), (name, k)     # (written at all)
+    for fn in ("sialpha_sim", "random_npi_mc"):
+        sym, args, _ = cases[fn + "/seeded"]
+        args = [a for a in args if not isinstance(a, _lib.NoiseDesc)]
+        zi = next(i for i, a in enumerate(args) if a is None)               # the first NULL of a seeded call is its z
+        K, lanes = (args[0].K, args[0].B) if fn == "sialpha_sim" else (args[0].K, args[0].R * args[0].n_scen)
+        args[zi] = hostapi.normal_draws(K, 3, lanes, H.FLAT_SEED, stream=H.FLAT_STREAM)
+        args[0].noise = 1
+        fed = H.flat_call(sym, args)
+        args[0].noise = 0
+        for k, v in host[fn + "/seeded"].items():
+            assert np.array_equal(v, fed[k], equal_nan=True), (fn, k)
+
+
 @pytest.mark.parametrize("adaptive", [False, True])
 def test_quad_shape_with_the_longest_monitor_window(gpu_device, adaptive):
     """inv_monitor_len = 106 (the largest the library accepts) with four lanes per chain: with an adaptive scalar R_v the
@@ -2241,10 +2270,22 @@ def test_host_call_copy_routes(gpu_device):
             assert not (got["status"] == -7).any()
 
 
+def test_simulator_host_call_takes_both_copy_routes(gpu_device):
+    """epi_sir_sim_host at B = 4096, K = 128 writes one dense 12.6 MB array, above the 8 MiB below which a call is packed
+    through the pinned buffer: it goes straight into the caller's array and equals the device call; a small call on the same
+    context then goes through the pinned buffer again."""
+    rng = np.random.default_rng(3)
+    for B, K in ((4096, 128), (5, 6)):
+        prm = np.stack([0.3 + 0.1 * rng.random(B), np.full(B, 0.1), np.full(B, 0.01), np.full(B, 0.99), np.full(B, 0.01), np.zeros(B)])
+        args = [B, K, 0.5, prm, ("out", (K, 3, B))]
+        got, want = H.flat_call("sir_sim", args)["out"], H.flat_call("sir_sim", args, gpu=gpu_device)["out"]
+        assert np.isfinite(got).all() and np.array_equal(got, want), (B, K)
+
+
 def test_host_entry_points_from_concurrent_threads_and_pool_release(gpu_device):
     """The host entry points are thread-safe and keep their state in pools that epi_host_pool_release frees: six threads
-    call epi_ekf_run_host / epi_ekf_run_host_multi (three blocks on the one device: the per-device worker) / the sweep entry at
-    the same time, several rounds (contexts and helper streams are leased concurrently, workers are shared); every result
+    call epi_ekf_run_host / epi_ekf_run_host_multi (three blocks on the one device: the per-device worker) / the sweep entry /
+    SIalpha_Controlled / nnls_affine_fit at the same time, several rounds (contexts and helper streams are leased concurrently, workers are shared); every result
     equals the oracle's.  Then the pools are released and everything runs again (pools, helper streams and worker threads are
     created anew)."""
     import threading
@@ -2254,6 +2295,14 @@ def test_host_entry_points_from_concurrent_threads_and_pool_release(gpu_device):
     refs = [H.oracle_batch(w) for w in ws]
     pr = _region_sweep_problem(4, 7, 50, 12, seed=3)
     sweep_ref = hostapi.sweep_prescribe(pr["x"], pr["u"], pr["R"], pr["reg"], pr["eps"], pr["sp"], pr["J0p"], pr["J1p"], 50)
+    # two workers also make one call of a simulator / a small fit per round (the same pooled contexts)
+    from epidemicmodeling_amd import tools
+    rng = np.random.default_rng(8)
+    sim_args = (rng.random((2, 30)), 0.99, 0.01, 0.3, [3.0, 2.0], 0.0, 100.0, 1 / 7, [0.01, 0.02], 0.0, synth.MODEL_BETA, 1e-3, 1e-3, 1e-3, 30, 1.0)
+    sim_noise = rng.standard_normal((3, 30))
+    sim_ref = tools.SIalpha_Controlled(*sim_args, noise=sim_noise)
+    X, y = rng.integers(0, 4, size=(16, 3, 3)).astype(np.float64), rng.random((16, 3))
+    fit_ref = hostapi.nnls_affine_fit(X, y)
     errors = []
 
     def worker(i):
@@ -2269,6 +2318,12 @@ def test_host_entry_points_from_concurrent_threads_and_pool_release(gpu_device):
                                                 devices=(0, 0))
                     if not (np.array_equal(g["J0"], sweep_ref["J0"]) and np.array_equal(g["u_opt"], sweep_ref["u_opt"])):
                         errors.append((i, rnd, "sweep"))
+                if i == 1 and not all(np.array_equal(a, b) for a, b in zip(tools.SIalpha_Controlled(*sim_args, noise=sim_noise), sim_ref)):
+                    errors.append((i, rnd, "SIalpha_Controlled"))
+                if i == 2:
+                    fit = hostapi.nnls_affine_fit(X, y)
+                    if not all(np.array_equal(fit[k], fit_ref[k]) for k in fit_ref):
+                        errors.append((i, rnd, "nnls_affine_fit"))
         except Exception as e:                       # noqa: BLE001 -- reported below
             errors.append((i, repr(e)))
 
