@@ -505,3 +505,34 @@ def ensemble_joint_score(be, src, truth, R, D, vs_p, max_lag, population, truth_
     if src.ndim == 2:
         out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
     return out
+
+
+def innovation_diagnostics(be, innovations, S, n_lags, k0, k1, flip, lane_block, B, outputs):
+    f32 = str(innovations.dtype).endswith("float32")
+    e = (be.f32 if f32 else be.f64)(innovations)
+    if e.ndim != 2:
+        raise ValueError("innovations must be [T, B] ([T, nblk * blk] for chain-blocked arrays)")
+    T, Bp = (int(v) for v in e.shape)
+    blk = int(lane_block)
+    if blk < 0:
+        raise ValueError("lane_block must be >= 0")
+    if B is None:
+        if blk > 0 and S is None:
+            raise ValueError("chain-blocked innovations without S need B")
+        B = Bp if blk == 0 else int(S.shape[-1])
+    B = int(B)
+    if blk <= 0 or blk >= B:
+        blk = 0
+    if Bp != (B if blk == 0 else (B + blk - 1) // blk * blk):
+        raise ValueError("innovations must be [T, B] ([T, nblk * blk] for chain-blocked arrays)")
+    S = be.f64(S)
+    if S is not None and tuple(S.shape) != (T, B):
+        raise ValueError("S must be [T, B]")
+    names = _lib.idiag_out_names(outputs)
+    d = _lib.make_idiag_desc(B, T, n_lags, k0, k1, int(bool(flip)), blk, int(f32))
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_idiag_validate(C.byref(d), err), err)      # before anything is allocated from n_lags
+    ins = _lib.IdiagInputs()
+    ins.e, ins.S = be.ptr(e), be.ptr(S)
+    return run_with_workspace("idiag", be, d, ins, _lib.IdiagOutputs(), _lib.IDIAG_OUT_NAMES, _lib.IDIAG_OUT_I32,
+                              _lib.idiag_shapes(B, d.n_lags), names)

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "epi_mldiv_validate", "epi_mldiv_run_device", "epi_mldiv_run_host",
     "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
     "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
+    "epi_idiag_validate", "epi_idiag_workspace_bytes", "epi_idiag_run_device", "epi_idiag_run_host",
     "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
     "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
     "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
@@ -836,6 +837,49 @@ def make_ejoint_desc(T, rows, R, D, Rt, vs_order=0, max_lag=0, storage=0, derive
     return d
 
 
+class IdiagDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "B", "T", "lane_block", "storage", "flip", "k0", "k1", "n_lags", "reserved")]
+
+
+IDIAG_IN_NAMES = ("e", "S")
+IDIAG_OUT_F64 = ("mean", "var", "skew", "kurt", "jb", "nis_sum", "nis_mean", "lb_q", "het", "cusumsq_max", "max_abs")
+IDIAG_OUT_I32 = ("n", "lb_lags", "het_n1", "het_n2", "cusumsq_step", "max_abs_step", "status")
+IDIAG_OUT_NAMES = IDIAG_OUT_F64 + IDIAG_OUT_I32 + ("acf",)
+IDIAG_BAD_DAY, IDIAG_EMPTY, IDIAG_DEGENERATE, IDIAG_FEW_LAGS = 1, 2, 4, 8          # bits of status
+
+
+class IdiagInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in IDIAG_IN_NAMES]
+
+
+class IdiagOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in IDIAG_OUT_NAMES]
+
+
+def idiag_shapes(B, H):
+    sh = {k: (int(B),) for k in IDIAG_OUT_F64 + IDIAG_OUT_I32}
+    sh["acf"] = (int(H), int(B))
+    return sh
+
+
+def idiag_out_names(outputs):
+    """None -> every output; else the names given, in the ABI's order"""
+    if outputs is None:
+        return list(IDIAG_OUT_NAMES)
+    for k in outputs:
+        if k not in IDIAG_OUT_NAMES:
+            raise ValueError(f"unknown output {k!r}")
+    return [k for k in IDIAG_OUT_NAMES if k in outputs]
+
+
+def make_idiag_desc(B, T, n_lags=10, k0=0, k1=None, flip=0, lane_block=0, storage=0) -> IdiagDesc:
+    d = IdiagDesc()
+    d.abi_version = ABI_VERSION
+    d.B, d.T, d.lane_block, d.storage, d.flip = int(B), int(T), int(lane_block), int(storage), int(flip)
+    d.k0, d.k1, d.n_lags, d.reserved = int(k0), int(T) if k1 is None else int(k1), int(n_lags), 0
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -968,6 +1012,12 @@ def lib():
         h.epi_ejoint_run_device.argtypes = [C.POINTER(EjointDesc), C.POINTER(EjointInputs), C.POINTER(EjointOutputs),
                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_ejoint_run_host.argtypes = [C.POINTER(EjointDesc), C.POINTER(EjointInputs), C.POINTER(EjointOutputs), C.c_int, C.c_char_p]
+        h.epi_idiag_validate.argtypes = [C.POINTER(IdiagDesc), C.c_char_p]
+        h.epi_idiag_workspace_bytes.argtypes = [C.POINTER(IdiagDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_idiag_run_device.argtypes = [C.POINTER(IdiagDesc), C.POINTER(IdiagInputs), C.POINTER(IdiagOutputs),
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_idiag_run_host.argtypes = [C.POINTER(IdiagDesc), C.POINTER(IdiagInputs), C.POINTER(IdiagOutputs),
+                                         C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

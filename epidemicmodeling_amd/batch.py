@@ -1244,3 +1244,38 @@ def ensemble_joint_score(src, truth, R, D, vs_p=None, max_lag=0, population=None
     with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
         return _call.ensemble_joint_score(DeviceBackend(dev, st), src.contiguous(), truth, R, D, vs_p, max_lag, population, truth_series,
                                           first_day, k0, k1, outputs, test_launch_tiles)
+
+
+def innovation_diagnostics(innovations, S=None, n_lags=10, k0=0, k1=None, flip=False, lane_block=0, B=None, outputs=None, stream=None):
+    """Whiteness diagnostics of the innovations of every chain in one device call (epi_idiag_run_device): is
+    the filter run statistically consistent -- serially uncorrelated, homoskedastic, Gaussian, of unit variance -- over the
+    window k0 <= k < k1 of filter steps (k1 = None: T)?
+    innovations [T, B] device tensor, float64 or float32 -- or, with lane_block = an EkfRunner's `blk` and B = the number of
+    chains, its chain-blocked [T, nblk * blk] as it lies.  S [T, B] float64 by day, exactly innovation_likelihood's output "S"
+    (NaN: the day does not count), or None: the innovations are taken as already standardised (e = NaN: the day does not
+    count), which makes the call usable on any residual series.  flip: filter step k is row T-1-k (the backward models).
+    nu = e / sqrt(S).  A day inside the window whose S is not a normal positive number or whose innovation is not finite is
+    left out and sets bit 0 of status (_lib.IDIAG_BAD_DAY).
+    outputs: any of, [B] float64, "mean", "var", "skew", "kurt" (of nu; Gaussian: 0, 1, 0, 3), "jb" (Jarque-Bera, chi2 with 2
+    degrees of freedom), "nis_sum" (sum of nu^2: chi2 with n degrees of freedom), "nis_mean", "lb_q" (Ljung-Box over lb_lags
+    lags, chi2 with lb_lags degrees of freedom), "het" (mean nu^2 of the last third of the window over that of the first: F with
+    (het_n2, het_n1) degrees of freedom), "cusumsq_max" (largest |CUSUM of squares| and "cusumsq_step", the step where the
+    variance breaks most), "max_abs" (the largest |nu|, at "max_abs_step"); [B] int32 "n" (days that count), "lb_lags" =
+    min(n_lags, n - 1), "het_n1", "het_n2", "cusumsq_step", "max_abs_step", "status" (bit 1 IDIAG_EMPTY: n = 0, everything NaN
+    / 0 / -1; bit 2 IDIAG_DEGENERATE: no variance, "acf", "skew", "kurt", "jb", "lb_q" NaN; bit 3 IDIAG_FEW_LAGS: lb_lags <
+    n_lags); and "acf" [n_lags, B] float64, the autocorrelations of lags 1 .. n_lags.  n_lags 0 .. 64.  Default: all of them.
+    Every sum runs in a pinned order, so the bits are reproducible.  Returns a dict of device tensors.  Enqueued on `stream`
+    (default: the current stream) without a host synchronisation."""
+    for name, v in (("innovations", innovations),) + ((("S", S),) if S is not None else ()):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be a device tensor")
+        if not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if innovations.dtype not in (torch.float64, torch.float32):
+        raise ValueError("innovations must be float64 or float32")
+    if S is not None and S.dtype != torch.float64:
+        raise ValueError("S must be float64")
+    dev = innovations.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.innovation_diagnostics(DeviceBackend(dev, st), innovations, S, n_lags, k0, k1, flip, lane_block, B, outputs)

@@ -904,6 +904,7 @@ __global__ __launch_bounds__(64) void ar_simulate_seeded(const ArSimArgs a, cons
 #include "mldivide.hpp"
 #include "svr.hpp"
 #include "loglik.hpp"
+#include "innov_diag.hpp"
 #include "npi_plan.hpp"
 #include "smoother_draws.hpp"
 
@@ -4652,6 +4653,147 @@ int epi_ejoint_run_host(const epi_ejoint_desc *d, const epi_ejoint_inputs *in, c
         HostIO::bind_opt(dout, i32, o_i, base);
         dout.member_dist = HostIO::at<double>(base, o_md);
         return epi_ejoint_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
+    };
+    return run_host(device, io, err, enqueue);
+}
+
+// ---- whiteness diagnostics of the innovations of every chain (innov_diag.hpp) ----
+// the workspace: the per-block records of the two passes [nb32][B], the lagged products [nb32][H][B] and the per-chain words of
+// pass 1; every piece starts at a multiple of 256 bytes
+struct IdWs { size_t d8[10], i4[7], c8[2], c4[2], rc, bytes; };
+static IdWs id_workspace(const epi_idiag_desc *d)
+{
+    const size_t B = (size_t)d->B, nb = ((size_t)d->T + kIdBlock - 1) / kIdBlock;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    IdWs w{};
+    size_t o = 0;
+    for (size_t &p : w.d8) { p = o; o += up(nb * B * 8); }     // p_sum p_q pre_q r_m2 r_m3 r_m4 r_f r_l r_max r_cs
+    for (size_t &p : w.i4) { p = o; o += up(nb * B * 4); }     // p_n p_bad pre_n r_nf r_nl r_maxk r_csk
+    for (size_t &p : w.c8) { p = o; o += up(B * 8); }          // c_mean c_q
+    for (size_t &p : w.c4) { p = o; o += up(B * 4); }          // c_n c_bad
+    w.rc = o; o += up(nb * (size_t)d->n_lags * B * 8);
+    w.bytes = o;
+    return w;
+}
+
+int epi_idiag_validate(const epi_idiag_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->B < 1) { set_err(err, "B must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->lane_block < 0 || d->lane_block > d->B) { set_err(err, "lane_block must lie in 0 .. B (0 or B: the classic [T][B])"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->flip != 0 && d->flip != 1) { set_err(err, "flip must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k1 > d->T || d->k0 > d->k1) { set_err(err, "the window must satisfy 0 <= k0 <= k1 <= T"); return EPI_ERR_BAD_ARG; }
+    if (d->n_lags < 0) { set_err(err, "n_lags must be >= 0"); return EPI_ERR_BAD_ARG; }
+    if (d->reserved != 0) { set_err(err, "reserved must be 0"); return EPI_ERR_BAD_ARG; }
+    if (d->n_lags > kIdMaxLags) { set_err(err, "n_lags is limited to 64 (the rows a block's lags reach ahead are held in LDS)"); return EPI_ERR_UNSUPPORTED; }
+    if (d->T >= (1 << 21)) { set_err(err, "T is limited to 2^21 - 1"); return EPI_ERR_UNSUPPORTED; }
+    if (((int64_t)d->B + 255) / 256 * 256 * (((int64_t)d->T + kIdBlock - 1) / kIdBlock) >= ((int64_t)1 << 31)) {
+        set_err(err, "B * ceil(T / 32) is limited to 2^31 - 1 (one launch covers every block of every chain)");
+        return EPI_ERR_UNSUPPORTED;
+    }
+    return EPI_OK;
+}
+
+int epi_idiag_workspace_bytes(const epi_idiag_desc *d, size_t *bytes, char *err)
+{
+    int rc = epi_idiag_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = id_workspace(d).bytes;
+    return EPI_OK;
+}
+
+static int id_check_arrays(const epi_idiag_inputs *in, const epi_idiag_outputs *out, char *err)
+{
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->e) { set_err(err, "NULL e"); return EPI_ERR_BAD_ARG; }
+    bool any = out->acf != nullptr;
+    for (double *const p : {out->mean, out->var, out->skew, out->kurt, out->jb, out->nis_sum, out->nis_mean, out->lb_q, out->het,
+                            out->cusumsq_max, out->max_abs}) any = any || p;
+    for (int32_t *const p : {out->n, out->lb_lags, out->het_n1, out->het_n2, out->cusumsq_step, out->max_abs_step, out->status}) any = any || p;
+    if (!any) { set_err(err, "no output requested"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+int epi_idiag_run_device(const epi_idiag_desc *d, const epi_idiag_inputs *in, const epi_idiag_outputs *out, void *ws,
+                         size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_idiag_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = id_check_arrays(in, out, err)) != EPI_OK) return rc;
+    const IdWs w = id_workspace(d);
+    if (!ws || ws_bytes < w.bytes) { set_err(err, "workspace too small (epi_idiag_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    char *base = (char *)ws;
+    IdArgs a{};
+    a.B = d->B; a.T = d->T; a.H = d->n_lags; a.lags = (out->acf || out->lb_q) ? d->n_lags : 0; a.f32 = d->storage; a.flip = d->flip;
+    a.k0 = d->k0; a.k1 = d->k1; a.nb32 = (d->T + kIdBlock - 1) / kIdBlock; a.h3 = (int)((2 * (int64_t)(d->k1 - d->k0) + 3) / 6);
+    int blk, nblk;
+    ll_geometry(d->B, d->lane_block, &blk, &nblk);
+    a.bp = (size_t)blk * (size_t)nblk;
+    a.e = in->e; a.S = in->S;
+    auto D = [&](int k) { return (double *)(base + w.d8[k]); };
+    auto I = [&](int k) { return (int32_t *)(base + w.i4[k]); };
+    a.p_sum = D(0); a.p_q = D(1); a.pre_q = D(2); a.r_m2 = D(3); a.r_m3 = D(4); a.r_m4 = D(5); a.r_f = D(6); a.r_l = D(7);
+    a.r_max = D(8); a.r_cs = D(9);
+    a.p_n = I(0); a.p_bad = I(1); a.pre_n = I(2); a.r_nf = I(3); a.r_nl = I(4); a.r_maxk = I(5); a.r_csk = I(6);
+    a.c_mean = (double *)(base + w.c8[0]); a.c_q = (double *)(base + w.c8[1]);
+    a.c_n = (int32_t *)(base + w.c4[0]); a.c_bad = (int32_t *)(base + w.c4[1]);
+    a.r_c = (double *)(base + w.rc);
+    a.mean = out->mean; a.var = out->var; a.skew = out->skew; a.kurt = out->kurt; a.jb = out->jb; a.nis_sum = out->nis_sum;
+    a.nis_mean = out->nis_mean; a.lb_q = out->lb_q; a.het = out->het; a.cusumsq_max = out->cusumsq_max; a.max_abs = out->max_abs;
+    a.n = out->n; a.lb_lags = out->lb_lags; a.het_n1 = out->het_n1; a.het_n2 = out->het_n2; a.cusumsq_step = out->cusumsq_step;
+    a.max_abs_step = out->max_abs_step; a.status = out->status; a.acf = out->acf;
+    const unsigned t256 = (unsigned)(((int64_t)d->B + 255) / 256), t64 = (unsigned)(((int64_t)d->B + kWave - 1) / kWave);
+    hipLaunchKernelGGL(id_blocks1, dim3(t256 * (unsigned)a.nb32), dim3(256), 0, st, a, t256);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "id_blocks1 launch");
+    hipLaunchKernelGGL(id_chains1, dim3(t256), dim3(256), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "id_chains1 launch");
+    hipLaunchKernelGGL(id_blocks2, dim3(t64 * (unsigned)a.nb32), dim3(kWave), (size_t)(kIdBlock + a.lags) * kWave * sizeof(double), st, a, t64);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "id_blocks2 launch");
+    hipLaunchKernelGGL(id_chains2, dim3(t256), dim3(256), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(err, e, "id_chains2 launch");
+    return EPI_OK;
+}
+
+int epi_idiag_run_host(const epi_idiag_desc *d, const epi_idiag_inputs *in, const epi_idiag_outputs *out, int device, char *err)
+{
+    int rc = epi_idiag_validate(d, err);
+    if (rc != EPI_OK) return rc;
+    if ((rc = id_check_arrays(in, out, err)) != EPI_OK) return rc;
+    const size_t B = (size_t)d->B, T = (size_t)d->T, none = HostIO::kAbsent;
+    int gblk, gnblk;
+    ll_geometry(d->B, d->lane_block, &gblk, &gnblk);
+    const size_t Bp = (size_t)gnblk * (size_t)gblk;
+    static const HostIO::Opt<epi_idiag_outputs, double> f64[] = {
+        {&epi_idiag_outputs::mean, 1}, {&epi_idiag_outputs::var, 1}, {&epi_idiag_outputs::skew, 1}, {&epi_idiag_outputs::kurt, 1},
+        {&epi_idiag_outputs::jb, 1}, {&epi_idiag_outputs::nis_sum, 1}, {&epi_idiag_outputs::nis_mean, 1}, {&epi_idiag_outputs::lb_q, 1},
+        {&epi_idiag_outputs::het, 1}, {&epi_idiag_outputs::cusumsq_max, 1}, {&epi_idiag_outputs::max_abs, 1}};
+    static const HostIO::Opt<epi_idiag_outputs, int32_t> i32[] = {
+        {&epi_idiag_outputs::n, 1}, {&epi_idiag_outputs::lb_lags, 1}, {&epi_idiag_outputs::het_n1, 1}, {&epi_idiag_outputs::het_n2, 1},
+        {&epi_idiag_outputs::cusumsq_step, 1}, {&epi_idiag_outputs::max_abs_step, 1}, {&epi_idiag_outputs::status, 1}};
+    HostIO io;
+    const size_t o_e = io.add_in(in->e, T, d->storage ? 4 : 8, Bp, 0, Bp);
+    const size_t o_S = in->S ? io.add_in(in->S, T, 8, B, 0, B) : none;
+    size_t o_d[11], o_i[7];
+    io.add_opt(*out, f64, o_d, B);
+    io.add_opt(*out, i32, o_i, B);
+    const size_t o_acf = (out->acf && d->n_lags > 0) ? io.add_out(out->acf, (size_t)d->n_lags, 8, B, 0, B) : none;
+    const size_t wsb = id_workspace(d).bytes;
+    const size_t o_ws = io.reserve(wsb);
+    const bool only_empty_acf = out->acf && d->n_lags == 0;
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_idiag_inputs din{};
+        din.e = base + o_e; din.S = HostIO::at<const double>(base, o_S);
+        epi_idiag_outputs dout{};
+        HostIO::bind_opt(dout, f64, o_d, base);
+        HostIO::bind_opt(dout, i32, o_i, base);
+        dout.acf = only_empty_acf ? (double *)(base + o_ws) : HostIO::at<double>(base, o_acf);   // H = 0: nothing is written
+        return epi_idiag_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
     };
     return run_host(device, io, err, enqueue);
 }

@@ -395,3 +395,10 @@ def ensemble_joint_score(src, truth, R, D, vs_p=None, max_lag=0, population=None
     src = np.ascontiguousarray(src, dtype=np.float32 if src.dtype == np.float32 else np.float64)
     return _call.ensemble_joint_score(HostBackend(device), src, truth, R, D, vs_p, max_lag, population, truth_series, first_day, k0, k1,
                                       outputs, test_launch_tiles)
+
+
+def innovation_diagnostics(innovations, S=None, n_lags=10, k0=0, k1=None, flip=False, lane_block=0, B=None, outputs=None, device=0):
+    """epi_idiag_run_host: batch.innovation_diagnostics on NumPy arrays (synchronous): the same arguments, and the same keys,
+    order, dtypes and bits.  float32 innovations = float storage, anything else is taken as float64."""
+    return _call.innovation_diagnostics(HostBackend(device), np.asarray(innovations), None if S is None else np.asarray(S), n_lags,
+                                        k0, k1, flip, lane_block, B, outputs)

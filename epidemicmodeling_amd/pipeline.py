@@ -631,7 +631,7 @@ def likelihood_grid(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=
 
 
 def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None, burn_in=0, storage="f64", lane_block="auto",
-                shape=0, device="cuda:0"):
+                shape=0, device="cuda:0", min_lb_p=None, n_lags=10):
     """Choose the filter's noise settings per region by likelihood: likelihood_grid(w, ...) run as one batch of R x G chains by
     filter_likelihood with k0 = burn_in (the first burn_in filter steps, where Ps_init still dominates, do not count), and per
     region the candidate with the largest log-likelihood.
@@ -642,9 +642,15 @@ def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None
     comparable between regions or windows.
     Returns {"loglik" [R, G], "n_valid" [R, G], "status" [R, G], "best" [R] int32 (-1: no usable candidate), "best_loglik" [R],
     "chosen" [R, 4] (q_scale, r_scale, gamma_ekf, beta_ekf of the best candidate; NaN for best = -1 and for an axis left at
-    None), "table" [G, 4], "runner", "workload"}, tensors on the device.  No host synchronisation."""
+    None), "table" [G, 4], "runner", "workload"}, tensors on the device.  No host synchronisation.
+    min_lb_p (None: the above, unchanged): a largest likelihood says nothing about whether the candidate's innovations are
+    white.  With a value, every candidate's innovations also go through batch.innovation_diagnostics (n_lags lags, the same
+    window) and "best" / "best_loglik" / "chosen" are taken among the usable candidates whose Ljung-Box p-value lb_p >=
+    min_lb_p (-1 / NaN where none qualifies); "best_any" [R] keeps the choice by likelihood alone and "lb_p" [R, G] is returned."""
     gw, table = likelihood_grid(w, q_scale, r_scale, gamma_ekf, beta_ekf)
     G, R = table.shape[0], w.B
+    if min_lb_p is not None:
+        return _tune_filter_white(gw, table, R, burn_in, storage, lane_block, shape, device, float(min_lb_p), n_lags)
     r, res = filter_likelihood(gw, k0=burn_in, storage=storage, lane_block=lane_block, shape=shape, device=device, G=G)
     tab = torch.as_tensor(table, dtype=torch.float64).to(res["best"].device)
     best = res["best"].to(torch.int64)
@@ -652,6 +658,67 @@ def tune_filter(w, q_scale=(1.0,), r_scale=(1.0,), gamma_ekf=None, beta_ekf=None
     chosen = torch.where((best < 0)[:, None], torch.full_like(chosen, float("nan")), chosen)
     return {"loglik": res["loglik"].view(R, G), "n_valid": res["n_valid"].view(R, G), "status": res["status"].view(R, G),
             "best": res["best"], "best_loglik": res["best_loglik"], "chosen": chosen, "table": tab, "runner": r, "workload": gw}
+
+
+def diagnostic_pvalues(stats):
+    """The p-values of batch.innovation_diagnostics' statistics under the hypothesis of white Gaussian innovations of unit
+    variance, with torch on the tensors' own device (plumbing: not part of the pinned arithmetic of DESIGN.md §4.22):
+        lb_p  = P(chi2(lb_lags) >= lb_q) = gammaincc(lb_lags / 2, lb_q / 2)       serial correlation (Ljung-Box)
+        jb_p  = P(chi2(2) >= jb) = exp(-jb / 2)                                   normality (Jarque-Bera)
+        nis_p = 2 min(P(chi2(n) <= nis_sum), P(chi2(n) >= nis_sum))               the NIS consistency test, two-sided
+    NaN where the statistic is NaN or has no degrees of freedom.  het gets none: under the hypothesis it is F(het_n2, het_n1)
+    distributed, and torch has no F distribution.  `stats` needs the keys of the p-values wanted; returns a dict of those."""
+    out = {}
+    nan = float("nan")
+    if "lb_q" in stats and "lb_lags" in stats:
+        dof = stats["lb_lags"].to(torch.float64)
+        p = torch.special.gammaincc(0.5 * dof.clamp(min=1.0), 0.5 * stats["lb_q"])
+        out["lb_p"] = torch.where(dof > 0, p, torch.full_like(p, nan))
+    if "jb" in stats:
+        out["jb_p"] = torch.exp(-0.5 * stats["jb"])
+    if "nis_sum" in stats and "n" in stats:
+        dof = stats["n"].to(torch.float64)
+        a, x = 0.5 * dof.clamp(min=1.0), 0.5 * stats["nis_sum"]
+        p = 2.0 * torch.minimum(torch.special.gammainc(a, x), torch.special.gammaincc(a, x))
+        out["nis_p"] = torch.where(dof > 0, p, torch.full_like(p, nan))
+    return out
+
+
+def filter_diagnostics(w, n_lags=10, burn_in=0, k1=None, storage="f64", lane_block="auto", shape=0, device="cuda:0", outputs=None):
+    """Is the filter run of `w` statistically consistent?  An EkfRunner with the outputs S_MINUS, P_MINUS, innovations, then
+    batch.innovation_likelihood for the per-day innovation variance S, then batch.innovation_diagnostics on the innovations and S
+    as they lie (chain-blocked or classic, float64 or float32; nothing is unblocked or copied back), over the filter steps
+    burn_in <= k < k1 (k1 = None: T).  outputs: as batch.innovation_diagnostics (None: all).  Returns (runner, dict of device
+    tensors): the statistics, diagnostic_pvalues' "lb_p", "jb_p", "nis_p" where their statistics were asked for, and the
+    likelihood's "loglik".  No host synchronisation."""
+    r, lik = filter_likelihood(w, k0=burn_in, k1=k1, storage=storage, lane_block=lane_block, shape=shape, device=device,
+                               outputs=("loglik", "S"))
+    res = batch.innovation_diagnostics(r.out["innovations"], lik["S"], n_lags=n_lags, k0=burn_in, k1=k1, flip="Backward" in w.model,
+                                       lane_block=0 if r.blk == w.B else r.blk, B=w.B, outputs=outputs)
+    res.update(diagnostic_pvalues(res))
+    res["loglik"] = lik["loglik"]
+    return r, res
+
+
+def _tune_filter_white(gw, table, R, burn_in, storage, lane_block, shape, device, min_lb_p, n_lags):
+    """tune_filter with min_lb_p: the grid run once, the likelihood with S, the diagnostics, and the choice among the candidates
+    that pass the Ljung-Box test"""
+    G = table.shape[0]
+    r, res = filter_likelihood(gw, k0=burn_in, storage=storage, lane_block=lane_block, shape=shape, device=device, G=G,
+                               outputs=("loglik", "n_valid", "status", "S", "best", "best_loglik"))
+    dg = batch.innovation_diagnostics(r.out["innovations"], res["S"], n_lags=n_lags, k0=burn_in, flip="Backward" in gw.model,
+                                      lane_block=0 if r.blk == gw.B else r.blk, B=gw.B, outputs=("lb_q", "lb_lags"))
+    lb_p = diagnostic_pvalues(dg)["lb_p"].view(R, G)
+    ll, nv, st = res["loglik"].view(R, G), res["n_valid"].view(R, G), res["status"].view(R, G)
+    ok = ((st & 1) == 0) & (nv > 0) & (lb_p >= min_lb_p) & ~torch.isnan(ll)
+    score = torch.where(ok, ll, torch.full_like(ll, float("-inf")))
+    best = torch.where(ok.any(dim=1), torch.argmax(score, dim=1), torch.full((R,), -1, dtype=torch.int64, device=ll.device))
+    best_ll = torch.where(best >= 0, ll.gather(1, best.clamp(min=0)[:, None])[:, 0], torch.full((R,), float("nan"), dtype=ll.dtype, device=ll.device))
+    tab = torch.as_tensor(table, dtype=torch.float64).to(ll.device)
+    chosen = tab[best.clamp(min=0)]
+    chosen = torch.where((best < 0)[:, None], torch.full_like(chosen, float("nan")), chosen)
+    return {"loglik": ll, "n_valid": nv, "status": st, "best": best.to(torch.int32), "best_loglik": best_ll, "chosen": chosen,
+            "table": tab, "runner": r, "workload": gw, "best_any": res["best"], "lb_p": lb_p}
 
 
 def _check_rng(rng, z=None):

@@ -1579,6 +1579,28 @@ int epi_random_npi_mc_host_seeded(const epi_mc_desc *d, const epi_noise_desc *no
                                   const double *z, const double *J0_prefix, const double *J1_prefix, double *u_out, double *J0,
                                   double *J1, int device, char *err);
 
+/* ---- Whiteness diagnostics of the innovations of every chain ----
+ * The definition and the structures epi_idiag_desc / _inputs / _outputs are in epiekf_idiag.h (tests/test_noise_abi.py pins the
+ * set of structures this file itself defines, so a new call's structures get a header of their own). */
+#ifdef __cplusplus
+}
+#endif
+#include "epiekf_idiag.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* no GPU needed: EPI_ERR_BAD_ARG with a message for anything outside the limits, EPI_ERR_UNSUPPORTED for n_lags above 64, T of
+ * 2^21 or more, or B * ceil(T / 32) of 2^31 or more */
+int epi_idiag_validate(const epi_idiag_desc *d, char *err);
+/* bytes of device workspace epi_idiag_run_device needs (the per-block records of the two passes) */
+int epi_idiag_workspace_bytes(const epi_idiag_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; four kernels enqueued on `stream`: no host synchronisation, no allocation, no second stream.
+ * EPI_ERR_WORKSPACE for a workspace below epi_idiag_workspace_bytes */
+int epi_idiag_run_device(const epi_idiag_desc *d, const epi_idiag_inputs *in, const epi_idiag_outputs *out, void *ws,
+                         size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_idiag_run_host(const epi_idiag_desc *d, const epi_idiag_inputs *in, const epi_idiag_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

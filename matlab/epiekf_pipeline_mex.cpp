@@ -123,6 +123,13 @@
 //       peak_value, min_value, total, n_valid  B x rows';  peak_day, min_day  B x rows', ONE-based days;  first_cross (ONE-based,
 //       NaN: never), days_above, longest_run  B x rows' x n_thr;  n_paths  R x rows';  peak_day_hist  R x rows' x W (W = k_last -
 //       k_first + 1, at most 4096);  n_cross  R x rows' x n_thr;  cross_day_hist  R x rows' x n_thr x W.
+//   [stats, acf] = epiekf_pipeline_mex('idiag', e, S, n_lags, k_first, k_last, flip)
+//       Whiteness diagnostics of one chain's innovations (the statistics only -- p-values are left to the
+//       caller's chi2cdf).  e  1 x T innovations;  S  1 x T innovation variances by day (the 'loglik' command's S; NaN = the day
+//       does not count) or [] (e is taken as standardised);  n_lags  0 .. 64;  k_first, k_last ([] = 1, T)  the filter steps that
+//       count, ONE-based and inclusive;  flip  0, or 1 for a backward model (filter step k is day T+1-k).  stats  18 x 1 in the
+//       order of epi_idiag_outputs: mean, var, skew, kurt, jb, nis_sum, nis_mean, lb_q, het, cusumsq_max, max_abs, n, lb_lags,
+//       het_n1, het_n2, cusumsq_step, max_abs_step (both ONE-based; 0: none), status;  acf  n_lags x 1.
 //   [J0, J1, u] = epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days)
 //       :496-521.  sp  R x 48;  u_min  R x n_npi;  z ([] = noise-free)  (n_scen*R) x 3 x K;  J0, J1  R x n_scen;
 //       u  (n_scen*R) x n_npi x K (only when requested).  An optional 11th input `noise_seed` (see 'noise'; it may equal seed)
@@ -1051,6 +1058,48 @@ static void sdraw(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else if (o[k]) mxDestroyArray(o[k]);
 }
 
+static void idiag(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 7) mexErrMsgTxt("epiekf_pipeline_mex('idiag', e, S, n_lags, k_first, k_last, flip): 7 inputs expected");
+    if (mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1]) || mxIsEmpty(prhs[3]) || !mxGetPr(prhs[3]) || mxIsEmpty(prhs[6]) || !mxGetPr(prhs[6]))
+        mexErrMsgTxt("e, n_lags and flip must be non-empty double arrays");
+    const mwSize T = mxGetNumberOfElements(prhs[1]);
+    const bool hasS = !mxIsEmpty(prhs[2]);
+    if (hasS && (!mxGetPr(prhs[2]) || mxGetNumberOfElements(prhs[2]) != T)) mexErrMsgTxt("S must be 1 x T or []");
+    const double nl = mxGetScalar(prhs[3]), fl = mxGetScalar(prhs[6]);
+    if (nl != (double)(int32_t)nl) mexErrMsgTxt("n_lags must be an integer");
+    if (fl != 0.0 && fl != 1.0) mexErrMsgTxt("flip must be 0 or 1");
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[4])) kf = mxGetScalar(prhs[4]);
+    if (!mxIsEmpty(prhs[5])) kl = mxGetScalar(prhs[5]);
+    if (!(kf >= 1.0 && kl >= kf - 1.0 && kl <= (double)T) || kf != (double)(int32_t)kf || kl != (double)(int32_t)kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= k_last + 1 <= T + 1");
+    epi_idiag_desc d;
+    memset(&d, 0, sizeof d);
+    d.abi_version = EPIEKF_ABI_VERSION; d.B = 1; d.T = (int32_t)T; d.flip = (int32_t)fl; d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    d.n_lags = (int32_t)nl;
+    char err[256] = {0};
+    fail_if(epi_idiag_validate(&d, err), err);                 // before n_lags sizes anything
+    epi_idiag_inputs in;
+    memset(&in, 0, sizeof in);
+    in.e = mxGetPr(prhs[1]); in.S = hasS ? mxGetPr(prhs[2]) : nullptr;
+    mxArray *o[2] = {mxCreateDoubleMatrix(18, 1, mxREAL), mxCreateDoubleMatrix((mwSize)d.n_lags, 1, mxREAL)};
+    double *st = mxGetPr(o[0]);
+    int32_t iv[7] = {0, 0, 0, 0, 0, 0, 0};
+    epi_idiag_outputs out;
+    memset(&out, 0, sizeof out);
+    out.mean = st + 0; out.var = st + 1; out.skew = st + 2; out.kurt = st + 3; out.jb = st + 4; out.nis_sum = st + 5;
+    out.nis_mean = st + 6; out.lb_q = st + 7; out.het = st + 8; out.cusumsq_max = st + 9; out.max_abs = st + 10;
+    out.n = iv + 0; out.lb_lags = iv + 1; out.het_n1 = iv + 2; out.het_n2 = iv + 3; out.cusumsq_step = iv + 4;
+    out.max_abs_step = iv + 5; out.status = iv + 6;
+    out.acf = d.n_lags > 0 ? mxGetPr(o[1]) : nullptr;
+    const int rc = epi_idiag_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *a : o) mxDestroyArray(a); fail_if(rc, err); }
+    for (int k = 0; k < 7; k++) st[11 + k] = (double)(iv[k] + ((k == 4 || k == 5) ? 1 : 0));      // the two steps ONE-based
+    for (int k = 0; k < 2; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void mc(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 10 && nrhs != 11) mexErrMsgTxt("epiekf_pipeline_mex('mc', sp, u_min, n_scen, K, seed, z, J0_prefix, J1_prefix, prefix_days): 10 inputs expected (an 11th: noise_seed)");
@@ -1125,6 +1174,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "ar_forecast") == 0) ar_forecast(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "fuse") == 0) fuse(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "loglik") == 0) loglik(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "idiag") == 0) idiag(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "plan") == 0) plan(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "escore") == 0) escore(nlhs, plhs, nrhs, prhs);
