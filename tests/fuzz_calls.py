@@ -31,6 +31,7 @@ class Case:
     summary: str
     features: set
     flat: bool = False               # the ensemble calls: the example also goes through the batch entry with a 2-D src [T, B]
+    noise: tuple = None              # a seeded twin (seeded_twin): (seed, stream) the call under test draws from; kw["z"] is their array
 
 
 @dataclasses.dataclass
@@ -842,7 +843,7 @@ def make_npi_plan(seed):
 # R D (L + H): the simulated chain-days of an example; the C restatement needs microseconds for each, the cap keeps the arrays small
 ARFC_FUZZ_CAP = 200_000
 ARFC_FEATURES = ("B:<=64", "B:65-256", "B:>256", "rows:<=64", "rows:65-128", "rows:>128", "model:fit", "model:given", "nv_mode:0", "nv_mode:1",
-                 "drive:none", "drive:series", "drive:chain", "z:yes", "z:no", "region:constant", "region:nan", "p:1", "p:24", "host:yes",
+                 "drive:none", "drive:series", "drive:chain", "z:yes", "z:no", "z:seeded", "region:constant", "region:nan", "p:1", "p:24", "host:yes",
                  "host:no", "status:OK", "status:RANK_DEFICIENT", "status:BAD_INPUT")
 
 
@@ -958,7 +959,7 @@ SDRAW_WG = 256                                              # lanes of a workgro
 SDRAW_KINDS = ("cfg3", "adaptive", "total", "tail")
 SDRAW_FEATURES = (tuple(f"workload:{k}" for k in SDRAW_KINDS) + ("layout:classic", "layout:blocked-3", "layout:blocked-8", "layout:blocked-40",
                   "layout:ragged-last-block", "storage:f64", "storage:f32", "planted:yes", "planted:no", "D:<64", "D:64", "D:>64", "k0:0",
-                  "k0:>0", "k0:T-1", "clamp:0", "clamp:1", "z:none", "z:f64", "z:f32", "out_f32:0", "out_f32:1", "s_term:yes", "s_term:no",
+                  "k0:>0", "k0:T-1", "clamp:0", "clamp:1", "z:none", "z:f64", "z:f32", "z:seeded", "out_f32:0", "out_f32:1", "s_term:yes", "s_term:no",
                   "P_term:yes", "P_term:no", "launch-groups:library", "launch-groups:1-3", "launches:1", "launches:gain>1", "launches:paths>1", "host:yes", "host:no", "status:0",
                   "status:NONFINITE", "status:RANK_DEFICIENT"))
 
@@ -1276,9 +1277,47 @@ SENTINELS = {"mldivide": (-7, -7777.25), "svr": (-7, -7777.25), "rate_map": (-7,
 ONE_READING = ("ensemble_summary", "ar_forecast", "two_filter")      # calls with a single complete restatement
 
 
-def default_cases(call):
+# ---- seeded twins --------------------------------------------------------------------------------------
+# ar_forecast and smoother_draws also take seed= / noise_stream= in place of z: the draws are then made inside the kernel.  A twin
+# is DERIVED from a generated example that has a z -- the example itself, and every draw of its generator, stay what they were --
+# for the seeds that are a multiple of TWIN_EVERY: one example in three keeps the restatements' time of the two hunts within 1.5
+# times what it was without twins (profiles/fuzz_calls/README.md).
+SEEDED_CALLS = ("ar_forecast", "smoother_draws")
+TWIN_EVERY = 3
+
+
+def seeded_twin(refs, case):
+    """The seeded twin of an example of SEEDED_CALLS, or None (no z, or a seed that gets none).  The noise seed and stream come
+    from a generator of their own, keyed on the example's seed; the twin's kw["z"] is the array of that seed by the C restatement
+    tests/noise_ref.c, as double ([T - k0, 3, B D] for smoother_draws, t = 0 at day k0; [H, B] for ar_forecast: the single row,
+    squeezed), so `reference` and `second_reading` take the twin as they take any example; `noise` = (seed, stream) is what the
+    call under test receives in place of z."""
+    if case.call not in SEEDED_CALLS or case.noise is not None or case.kw["z"] is None or case.seed % TWIN_EVERY:
+        return None
+    rng = np.random.default_rng([case.seed, 0x5EED])
+    nseed, stream = int(rng.integers(0, 2 ** 64, dtype=np.uint64)), int(_pick(rng, (0, 1, 2 ** 30 - 1, int(rng.integers(0, 2 ** 30)))))
+    kw = dict(case.kw)
+    nt, lanes = case.kw["z"].shape[0], case.kw["z"].shape[-1]
+    if case.call == "ar_forecast":
+        kw["z"] = np.ascontiguousarray(refs.get("noise").fill(nseed, stream, 0, nt, 1, 0, lanes)[:, 0])
+    else:
+        kw["z"] = refs.get("noise").fill(nseed, stream, 0, nt, 3, 0, lanes)
+    f = {v for v in case.features if not v.startswith("z:")} | {"z:seeded"}
+    return dataclasses.replace(case, kw=kw, features=f, noise=(nseed, stream),
+                               summary=f"{case.summary} [seeded twin: seed={nseed:#x} stream={stream}]")
+
+
+def cases_of(refs, call, seed):
+    """the example of a seed, followed by its seeded twin where it has one"""
+    case = CALLS[call].make(seed)
+    twin = seeded_twin(refs, case) if refs is not None else None
+    return [case] if twin is None else [case, twin]
+
+
+def default_cases(call, refs=None):
+    """the examples of the call's default seeds; with refs (the noise restatement has to be built) also their seeded twins"""
     spec = CALLS[call]
-    return [spec.make(s) for s in range(spec.n)]
+    return [c for s in range(spec.n) for c in cases_of(refs, call, s)]
 
 
 # ======================================================================================================================
@@ -1314,6 +1353,8 @@ class Refs:
                 from tests.ar_forecast_ref import ArRef as Cls
             elif call == "smoother_draws":
                 from tests.sdraw_ref import SdrawRef as Cls
+            elif call == "noise":
+                from tests.noise_ref import NoiseRef as Cls
             elif call == "innovation_likelihood":
                 from tests.loglik_ref import LoglikRef as Cls
             else:

@@ -1,7 +1,8 @@
 """The random hunts of tests/test_gpu_fuzz_calls.py, as far as they go without a device: over every call's default seeds the
 generators of tests/fuzz_calls.py reach every entry of the call's declared feature list (and nothing outside it), the two
 restatements of a call agree bit for bit on every example -- a hunt of the references themselves -- and the restatement the
-GPU test compares with answers every item of every example: no example is left out."""
+GPU test compares with answers every item of every example: no example is left out.  ar_forecast and smoother_draws carry
+seeded twins (FZ.seeded_twin: the same example with its z made from a noise seed) among their default cases."""
 import numpy as np
 import pytest
 
@@ -17,9 +18,9 @@ _WANT = {}
 
 
 def want(refs, call):
-    """(case, the reference's outputs) of every default seed, computed once per call and shared (read-only)"""
+    """(case, the reference's outputs) of every default seed and of every seeded twin, computed once per call and shared (read-only)"""
     if call not in _WANT:
-        _WANT[call] = [(c, FZ.reference(refs, c)) for c in FZ.default_cases(call)]
+        _WANT[call] = [(c, FZ.reference(refs, c)) for c in FZ.default_cases(call, refs)]
     return _WANT[call]
 
 
@@ -71,3 +72,28 @@ def test_the_two_readings_agree_bit_for_bit(refs, call):
         assert other is not None
         for k in other:
             assert FZ.same_bits(w[k], other[k]), (case.summary, k)
+
+
+@pytest.mark.parametrize("call", list(FZ.SEEDED_CALLS))
+def test_seeded_twins(refs, call):
+    """a twin follows its example, leaves it as it was, differs from it in z alone, and its z is the array of its noise seed
+    under BOTH noise restatements, in the shape the call's z has"""
+    from tests import noise_ref as NR
+    plain, cases = FZ.default_cases(call), FZ.default_cases(call, refs)
+    assert [c.summary for c in cases if c.noise is None] == [c.summary for c in plain]
+    twins = [(cases[i - 1], c) for i, c in enumerate(cases) if c.noise is not None]
+    assert 0 < len(twins) <= len(plain) // 2 and any(t.host for _, t in twins) and any(not t.host for _, t in twins)
+    for case, twin in twins:
+        assert case.noise is None and case.seed == twin.seed and case.seed % FZ.TWIN_EVERY == 0 and case.kw["z"] is not None
+        assert "z:seeded" in twin.features and "z:seeded" not in case.features
+        assert {f for f in twin.features if f[:2] != "z:"} == {f for f in case.features if f[:2] != "z:"}
+        assert (twin.names, twin.cut, twin.host) == (case.names, case.cut, case.host)
+        assert _identical(FZ.CALLS[call].make(case.seed).kw, case.kw)                     # the example itself: untouched
+        assert _identical({k: v for k, v in twin.kw.items() if k != "z"}, {k: v for k, v in case.kw.items() if k != "z"})
+        seed, stream = twin.noise
+        assert 0 <= seed < 2 ** 64 and 0 <= stream < 2 ** 30 and twin.kw["z"].dtype == np.float64
+        assert twin.kw["z"].shape == case.kw["z"].shape
+        nt, lanes = twin.kw["z"].shape[0], twin.kw["z"].shape[-1]
+        z = NR.fill(seed, stream, 0, nt, 1 if call == "ar_forecast" else 3, 0, lanes)
+        assert NR.same_bits(twin.kw["z"], z[:, 0] if call == "ar_forecast" else z), twin.summary
+    assert FZ.seeded_twin(refs, twins[0][1]) is None                                      # a twin has no twin

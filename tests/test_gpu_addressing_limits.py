@@ -704,3 +704,80 @@ def test_lasso_across_the_2_and_4_gib_offsets(gpu_device, tmp_path_factory):
         assert np.array_equal(out[k].index_select(-1, sel).cpu().numpy(), want[k], equal_nan=True), k
     del out, X, y, fold
     torch.cuda.empty_cache()
+
+
+# ---------------------------------------------------------------- the seeded normal draws' fill kernel at its production bounds
+NOISE_GUARD = 64                                                     # poisoned words before and behind the output
+NOISE_CHUNK = 1 << 24                                                # lanes of one separate call of the every-word check
+
+
+def _noise_fill(out, guard, seed, stream, t0, rows, lane0, n, groups=0):
+    """epi_noise_fill_device of one day into the flat tensor `out` behind `guard` leading words; returns the call's seconds"""
+    import torch
+    from epidemicmodeling_amd import _lib
+    d, err = _lib.make_noise_desc(seed, stream), C.create_string_buffer(256)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    rc = _lib.lib().epi_noise_fill_device(C.byref(d), t0, 1, rows, lane0, n, int(out.dtype == torch.float32),
+                                          C.c_void_p(out.data_ptr() + guard * out.element_size()), groups,
+                                          C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream), err)
+    _lib.check(rc, err)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t
+
+
+@pytest.mark.parametrize("case", ["N1", "N2"])
+def test_noise_fill_at_its_production_bounds(gpu_device, tmp_path_factory, case):
+    """epi_noise_fill_device with test_launch_groups = 0: the real cut kNoiseLaunchGroups = 2^22 workgroups.
+    N1: float, rows = 3, one day, 2^30 + 2^29 + 300 lanes: 2 n = 3.2e9 items go out in FOUR launches (wg0 = k 2^22), the 3 n =
+    4.8e9 output words pass element 2^32 (row 2) and byte 2^32 (row 0, lane 2^30: the first launch boundary as well), 18 GiB.
+    N2: double, rows = 1, 2^29 + 300 lanes: one launch whose double stores pass byte 2^32.
+    The output is poisoned with guard words either side: no poison left, the guards intact; 130-lane windows of all rows at the
+    first and the last lanes, either side of every launch boundary (items k 2^30) and of word and byte 2^32 equal
+    tests/noise_ref.c, rounded to float for N1; and EVERY word equals the same array made by separate calls of 2^24 lanes at
+    lane0 + j 2^24 -- a window is a window, so that is an identity.  Measured on one MI355X: N1 the call 0.05 s, the case 0.6 s, peak 18.3 GiB; N2 0.01 s, 0.1 s, 4.3 GiB.
+
+    That it bites (scratch builds, never committed; noise_fill / noise_fill_lane of csrc/noise.hpp): `wg0` dropped from the item
+    index -- N1 fails (poison left: launches 2 .. 4 rewrite the first 2^30 items); `o` taken through uint32_t -- N1 fails (poison
+    left behind word 2^32, and the window behind it)."""
+    import torch
+    from tests import noise_ref as NR
+    ref = NR.NoiseRef(tmp_path_factory.mktemp("noise_ref_limits"))
+    t_case = time.perf_counter()
+    seed, stream, t0, lane0 = 0x9E3779B97F4A7C15, 3, 7, (1 << 33) + 5            # the high lane word is in use
+    if case == "N1":
+        dt, rows, n = torch.float32, 3, (1 << 30) + (1 << 29) + 300
+    else:
+        dt, rows, n = torch.float64, 1, (1 << 29) + 300
+    pairs, esz = (rows + 1) // 2, 4 if dt == torch.float32 else 8
+    items, words = pairs * n, rows * n
+    bounds = [k << 30 for k in range(1, 4) if (k << 30) < items]                # first items of the launches 2 ..
+    assert len(bounds) == (3 if case == "N1" else 0) and words * esz > (1 << 32) and (words > (1 << 32)) == (case == "N1")
+    # the lanes at which something wraps if it wraps: item -> lane (item % n), word and byte 2^32 -> lane (word % n)
+    marks = [0, n] + [b % n for b in bounds] + [w % n for w in ((1 << 32), (1 << 32) // esz) if w < words]
+    starts = sorted({min(max(m - 65, 0), n - 130) for m in marks})
+    assert len(starts) == (6 if case == "N1" else 3), starts                     # N1: byte 2^32 IS the first launch boundary
+    _need_free(gpu_device, words * esz + 3 * rows * NOISE_CHUNK * esz + (2 << 30))
+    flat = _poisoned((words + 2 * NOISE_GUARD,), dt, gpu_device)
+    t_call = _noise_fill(flat, NOISE_GUARD, seed, stream, t0, rows, lane0, n)
+    head, body, tail = flat[:NOISE_GUARD], flat[NOISE_GUARD:NOISE_GUARD + words].view(rows, n), flat[NOISE_GUARD + words:]
+    poison = _poisoned((NOISE_GUARD,), dt, gpu_device)
+    as_int = lambda t: t.view(torch.int32 if dt == torch.float32 else torch.int64)
+    assert torch.equal(as_int(head), as_int(poison)) and torch.equal(as_int(tail), as_int(poison)), "guard words overwritten"
+    for r in range(rows):
+        for lo in range(0, n, 1 << 28):
+            assert not _holds_poison(body[r, lo:lo + (1 << 28)]), ("poison left", r, lo)
+    for s in starts:
+        want = ref.fill(seed, stream, t0, 1, rows, lane0 + s, 130)[0]
+        got = body[:, s:s + 130].cpu().numpy()
+        assert NR.same_bits(got, want.astype(got.dtype)), ("window at lane", s)
+    # every word: the same array in pieces
+    piece = _poisoned((rows * NOISE_CHUNK,), dt, gpu_device)
+    for j in range(0, n, NOISE_CHUNK):
+        m = min(NOISE_CHUNK, n - j)
+        _noise_fill(piece, 0, seed, stream, t0, rows, lane0 + j, m)
+        assert torch.equal(as_int(piece[:rows * m].view(rows, m)), as_int(body[:, j:j + m])), ("lanes from", j)
+    H.report_limits(f"noise_fill {case}: {rows} x {n} {'float' if esz == 4 else 'double'}, {len(bounds) + 1} launches", t_call, t_case,
+                    gpu_device)
+    del flat, head, body, tail, piece
+    torch.cuda.empty_cache()

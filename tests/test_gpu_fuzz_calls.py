@@ -2,7 +2,9 @@
 tests/fuzz_calls.py -- sizes, options, layouts, output subsets, launch cuts and data drawn together from one seed -- go through
 the call's own device helper (sentinel-filled outputs with guard elements) and must equal the restatement bit for bit, every NaN
 one value; an output not asked for stays untouched; about one example in four also goes through the hostapi entry, and the
-one-row ensembles through the batch entry as a 2-D src, with the same bits.
+one-row ensembles through the batch entry as a 2-D src, with the same bits.  An example of ar_forecast or smoother_draws may be
+followed by its seeded twin (FZ.seeded_twin): the call under test gets a noise seed in place of z, the restatement the z of that
+seed by tests/noise_ref.c.
 
 The default run takes the seeds 0 .. N - 1 of the call (tests/test_fuzz_calls.py asserts without a device what they cover).
 EPI_FUZZ_EXAMPLES=n runs n seeds from EPI_FUZZ_SEED on (default: a fresh start, printed), a longer hunt."""
@@ -49,8 +51,7 @@ def _equal(got, want, names, what, flat=False):
 
 
 def _hunt(call, refs, device_run, host_run=None, flat_run=None):
-    for seed in _seeds(call):
-        case = FZ.CALLS[call].make(seed)
+    for case in (c for seed in _seeds(call) for c in FZ.cases_of(refs, call, seed)):         # an example, then its seeded twin if any
         want = FZ.reference(refs, case)
         try:
             device_run(case, want)
@@ -242,30 +243,65 @@ def test_random_npi_plan_matches_the_restatement(gpu_device, refs):
 
 def test_random_ar_forecast_matches_the_restatement(gpu_device, refs):
     """That it bites (a scratch build, never committed): ar_forecast.hpp, the recursion: `fma(-coef[k], ring, acc)` made
-    `acc - coef[k] * ring` (a rounding moved); the default seeds fail at seed 0 (S)."""
-    from epidemicmodeling_amd import hostapi
+    `acc - coef[k] * ring` (a rounding moved); the default seeds fail at seed 0 (S).  The seeded twins (FZ.seeded_twin) go
+    through batch.ar_forecast(seed=, noise_stream=) and, where the example says so, hostapi's."""
+    from epidemicmodeling_amd import batch, hostapi
     from tests import test_gpu_ar_forecast as G
+
+    def seeded_kw(case):
+        """a twin's arguments for the call under test: the noise seed and stream in place of z"""
+        return dict({k: v for k, v in case.kw.items() if k != "z"}, seed=case.noise[0], noise_stream=case.noise[1])
 
     def dev(case, want):
         kw = case.kw
+        if case.noise is not None:                                # a seeded twin: `want` is ArRef on the noise restatement's z
+            G._same({k: v.cpu().numpy() for k, v in batch.ar_forecast(device=gpu_device, **seeded_kw(case)).items()}, want)
+            return
         G._same(G._run_device(kw, kw["p"], A=kw["A"], noise_var=kw["noise_var"], nv_mode=kw["nv_mode"], device=gpu_device), want)
 
-    _hunt("ar_forecast", refs, dev, lambda case: hostapi.ar_forecast(**case.kw))
+    _hunt("ar_forecast", refs, dev, lambda case: hostapi.ar_forecast(**(case.kw if case.noise is None else seeded_kw(case))))
 
 
 def test_random_smoother_draws_matches_the_restatement(gpu_device, refs):
     """That it bites (a scratch build, never committed): smoother_draws.hpp, J (x - s-): `fma(w, dv, acc)` made `acc + w *
-    dv` (a rounding moved); the default seeds fail at seed 1 (X)."""
-    from epidemicmodeling_amd import hostapi
+    dv` (a rounding moved); the default seeds fail at seed 1 (X).  The seeded twins (FZ.seeded_twin) go through
+    epi_sdraw_run_device_seeded, batch.smoother_draws(seed=, noise_stream=) and, where the example says so, hostapi's."""
+    import torch
+    from epidemicmodeling_amd import _lib, batch, hostapi
+    from tests import loglik_ref as LR
     from tests import sdraw_ref as SR
+    from tests import test_gpu_noise as N
     from tests import test_gpu_sdraw as G
 
     def dev(case, want):
+        if case.noise is not None:
+            # a seeded twin: `want` is the C restatement on the noise restatement's z.  The device entry with the example's layout
+            # and launch cut (sentinel-filled outputs, guard words checked), then batch.smoother_draws on the same arrays
+            kw = {k: v for k, v in case.kw.items() if k != "z"}
+            got = N._sdraw_raw(kw.pop("case"), kw.pop("D"), noise=_lib.make_noise_desc(*case.noise), device=gpu_device, **case.cut, **kw)
+            for k in got:
+                assert SR.same_bits(got[k], want[k]), f"seeded device entry: {k} differs from the restatement"
+            c = SR.stored(case.kw["case"], kw["storage"])
+            ndt = np.float32 if kw["storage"] == "f32" else np.float64
+            with np.errstate(over="ignore", invalid="ignore"):
+                big = [c[k].astype(ndt) for k in SR.BIG]
+            blk = case.cut["blk"] if case.cut["blk"] < c["B"] else 0      # batch takes one block of all chains as classic arrays
+            if blk:
+                big = [LR.to_blocked(a, blk, np.nan) for a in big]
+            dev_t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=gpu_device)
+            res = batch.smoother_draws(*[dev_t(a) for a in big], dev_t(c["prm"]), case.kw["D"], s_term=dev_t(kw["s_term"]), P_term=dev_t(kw["P_term"]),
+                                       k0=kw["k0"], clamp=kw["clamp"], lane_block=blk, B=c["B"],
+                                       out_dtype=torch.float32 if kw["out_f32"] else torch.float64, outputs=case.names, seed=case.noise[0],
+                                       noise_stream=case.noise[1])
+            _equal({k: v.cpu().numpy() for k, v in res.items()}, want, case.names, "batch, seeded")
+            return
         got, clean = G._run_device(device=gpu_device, **case.cut, **case.kw)
         G._assert_equal(got, clean, want, "device entry")
 
     def host(case):
         kw = dict(case.kw)
+        if case.noise is not None:
+            kw.update(z=None, seed=case.noise[0], noise_stream=case.noise[1])
         c, storage, out_f32 = SR.stored(kw.pop("case"), kw["storage"]), kw.pop("storage"), kw.pop("out_f32")
         ndt = np.float32 if storage == "f32" else np.float64
         with np.errstate(over="ignore", invalid="ignore"):

@@ -3,7 +3,11 @@ for bit, as double and as float, on windows that reach the high counter words an
 outputs with guard words.  Each of the four consumers, called with a seed, equals on every output word the existing call given
 z = normal_draws(...) of the same seed and stream -- at the smallest shapes at which the kernels can go wrong.  The same seed
 twice gives the same bits, another stream or seed other bits; pipeline.smoothed_fan(rng="device") returns the summary of
-smoothed_fan(z=normal_draws(...)); the hostapi twins agree with batch."""
+smoothed_fan(z=normal_draws(...)); the hostapi twins agree with batch.
+
+Where chance never goes (tests/noise_place.py): the fill kernel at uniforms CHOSEN by inverting Philox -- the far tail, both
+branch boundaries, the extremes -- and each of the five seeded consumer kernels at a recorded seed whose first draws hold a
+far-tail uniform, against z made by the C restatement (not by the library's fill)."""
 import ctypes as C
 import functools
 
@@ -12,6 +16,7 @@ import pytest
 
 from tests import helpers as H
 from tests import loglik_ref as LR
+from tests import noise_place as NP
 from tests import noise_ref as NR
 from tests import sdraw_ref as SR
 
@@ -91,7 +96,8 @@ SD_NAMES = ("X", "rank", "status", "J", "L")
 SD_I32 = ("rank", "status")
 
 
-def _sdraw_raw(case, D, z=None, noise=None, k0=0, clamp=True, storage="f64", out_f32=False, blk=0, groups=0, device="cuda:0"):
+def _sdraw_raw(case, D, z=None, noise=None, k0=0, clamp=True, storage="f64", out_f32=False, blk=0, groups=0, device="cuda:0", s_term=None,
+               P_term=None):
     """epi_sdraw_run_device (z) or epi_sdraw_run_device_seeded (noise) on sentinel-filled outputs with GUARD words behind each
     and a sentinel-filled workspace; returns the dict of NumPy arrays after checking the guards"""
     import torch
@@ -104,7 +110,7 @@ def _sdraw_raw(case, D, z=None, noise=None, k0=0, clamp=True, storage="f64", out
         big = [case[k].astype(ndt) for k in SR.BIG]
     if blk:
         big = [LR.to_blocked(a, blk, np.nan) for a in big]
-    tens = [up(a, ndt) for a in big] + [up(case["prm"]), z, None, None]
+    tens = [up(a, ndt) for a in big] + [up(case["prm"]), z, up(s_term), up(P_term)]
     shapes = _lib.sdraw_shapes(B, T, D, k0)
     d = _lib.make_sdraw_desc(B, T, D, k0, clamp, blk, int(storage == "f32"), 0, int(out_f32), test_launch_groups=groups)
     ins = _lib.SdrawInputs()
@@ -332,3 +338,203 @@ def test_smoothed_fan_device_rng(gpu_device):
         pipeline.smoothed_fan(w, 70, z=zz, rng="device")
     with pytest.raises(ValueError, match="rng must be"):
         pipeline.smoothed_fan(w, 70, rng="numpy")
+
+
+# ---- where chance never goes: chosen uniforms under the fill kernel, recorded far-tail seeds under the consumers ----
+def _placed_windows():
+    """(n, stream, row, t0, lane0, t - t0, lane - lane0) of every target of tests/noise_place.py in either slot and as a row-0
+    placement, with its 3-day, 5-lane window"""
+    rng = np.random.default_rng([SEED & 0xFFFFFFFF, SEED >> 32])
+    for n in NP.targets():
+        for slot, row0 in ((0, False), (1, False), (0, True)):
+            stream, t, row, lane = NP.place(SEED, n, slot, rng, row0_only=row0)
+            t0, lane0 = NP.window(t, lane)
+            yield n, stream, row, t0, lane0, t - t0, lane - lane0
+
+
+def test_fill_at_placed_uniforms(gpu_device, ref):
+    """The far-tail branch (min(u, 1 - u) < e^-25), both branch boundaries with their neighbours, the two u next to 1/2, every
+    power of two and the extremes u = 2^-53, 1 - 2^-53, each put under the fill kernel by inverting Philox (tests/noise_place.py):
+    a 3 x 3 x 5 window around the placed counter -- and a 3 x 1 x 5 one where the placement is row 0 -- equals the C restatement
+    bit for bit, as double and as float, and the placed element itself is icdf(u) of the target.
+
+    That it bites (scratch builds, never committed; epi_normal_icdf of csrc/noise.hpp): `far = rt > 6.0` fails here at n = 1
+    (-8.076571004127453 for -8.076571004130123; n = 0 has rt = 6.06); NE[2] and NE[5] swapped (-8.4256 for -8.2095) and the far
+    branch's `rt - 5.0` made `rt - 1.6` (-13.12) fail at the first target, n = 0; every older test of this file passes.  `<= 0.425`
+    made `< 0.425` passes, as it must: no lattice point lies on |u - 1/2| = 0.425 (tests/test_noise_place.py asserts it), so the
+    two spellings are one function of the 2^52 uniforms; the neighbours either side are what pins the boundary."""
+    far = 0
+    z_ext = {}
+    for n, stream, row, t0, lane0, dt, dl in _placed_windows():
+        u = NP.u_of(n)
+        zt = ref.icdf([u])[0]
+        far += NP.classify(u) == "far"
+        for rows in ((3, 1) if row == 0 else (3,)):
+            want = ref.fill(SEED, stream, t0, 3, rows, lane0, 5)
+            assert want[dt, row, dl] == zt, (n, row, "the window misses the target")
+            got = _fill_raw(SEED, stream, t0, 3, rows, lane0, 5)
+            assert NR.same_bits(got, want), (n, row, rows, got[dt, row, dl], zt)
+            assert NR.same_bits(_fill_raw(SEED, stream, t0, 3, rows, lane0, 5, f32=True), want.astype(np.float32)), (n, row, rows)
+            assert got[dt, row, dl] == zt and np.abs(got).max() < 8.2096
+            if n in (0, NP.TOP):
+                z_ext.setdefault(n, set()).add(float(got[dt, row, dl]))
+    assert far >= 3 * 40
+    assert len(z_ext[0]) == len(z_ext[NP.TOP]) == 1 and z_ext[0].pop() == -z_ext[NP.TOP].pop()      # equal and opposite
+
+
+def _far_entries(box):
+    """every recorded seed of a box: both tails, and in 'rows3' each of the rows 0 .. 2.  All of them, because a mutation that
+    moves a far-tail draw by a few ulp (`far = rt > 6.0`: the near-tail polynomial is still good to 1 .. 8 ulp at these rt = 5.01
+    .. 5.18, and at three of the entries to the bit) reaches an output word only where the draw's scale lets it"""
+    entries = NP.recorded_seeds()[box]
+    assert {e["tail"] for e in entries} == {"lower", "upper"} and {e["row"] for e in entries} == ({0, 1, 2} if box == "rows3" else {0})
+    return entries
+
+
+def _z_with_far_draw(ref, e, nt, rows, lanes):
+    """the window [0, nt) x rows x [0, lanes) of the entry's seed by the C restatement, after checking that it holds the recorded
+    far-tail draw; and the same array with that one element set to 0"""
+    z = ref.fill(e["seed"], 0, 0, nt, rows, 0, lanes)
+    assert e["t"] < nt and e["row"] < rows and e["lane"] < lanes
+    zt = z[e["t"], e["row"], e["lane"]]
+    assert zt == ref.icdf([NP.u_of(e["n"])])[0] and NP.classify(NP.u_of(e["n"])) == "far" and abs(zt) > 6.5, e
+    z0 = z.copy()
+    z0[e["t"], e["row"], e["lane"]] = 0.0
+    return z, z0
+
+
+@pytest.mark.parametrize("out_f32", [False, True])                 # sdraw_paths_seeded<0> and <1>
+def test_sdraw_seeded_far_tail_draw(gpu_device, ref, out_f32):
+    """A recorded far-tail draw inside sdraw_paths_seeded: the seeded call equals the z call given the C restatement's array on
+    every output word, that array holds the draw, and the draw enters X at its path.
+
+    That it bites (scratch builds, never committed): NE[2] / NE[5] swapped and `rt - 1.6` in the far branch
+    (test_fill_at_placed_uniforms) fail here in both instantiations (X, at the first entry), with every older test of this file
+    passing; `far = rt > 6.0` fails <0> (X, the row-2 entry n = 13 597) and passes <1>: it moves these draws by at most 8 ulp, which
+    the float rounding of X absorbs; sd_ldz taking row 0's draw for row 2 fails both."""
+    import torch
+    from epidemicmodeling_amd import _lib
+    B, D, T = 3, 70, 6
+    w, case = _case(B, T)
+    for e in _far_entries("rows3"):
+        z, z0 = _z_with_far_draw(ref, e, T, 3, B * D)
+        for clamp in (False, True):
+            kw = dict(clamp=clamp, out_f32=out_f32)
+            want = _sdraw_raw(case, D, z=torch.as_tensor(z, device=gpu_device), **kw)
+            got = _sdraw_raw(case, D, noise=_lib.make_noise_desc(e["seed"], 0), **kw)
+            for k in SD_NAMES:
+                assert NR.same_bits(got[k], want[k]), (k, kw, e)
+            if not clamp:                                                             # unclamped: a draw cannot be cut away
+                without = _sdraw_raw(case, D, z=torch.as_tensor(z0, device=gpu_device), **kw)
+                differs = without["X"] != got["X"]
+        assert differs[:, :, e["lane"]].any(), e                                  # the draw enters its own path
+        assert not np.delete(differs, e["lane"], axis=2).any(), e                 # and no other
+
+
+def test_ar_forecast_seeded_far_tail_draw(gpu_device, ref):
+    """A recorded far-tail draw of row 0 inside ar_simulate_seeded (the single row of epi_arfc_*), as in
+    test_sdraw_seeded_far_tail_draw.  That it bites: the three far-branch mutations each fail here (S, at n = 10 855)."""
+    import torch
+    from epidemicmodeling_amd import batch, hostapi
+    rng = np.random.default_rng(5)
+    R, D, L, p, Hh = 2, 35, 20, 3, 5
+    B = R * D                                                      # 70 chains: the box's 64 lanes, and a second 64-lane workgroup
+    seg = 0.3 + 0.05 * np.cumsum(rng.standard_normal((L, R)), axis=0) * 0.2
+    beta, s0 = np.full(R, 0.2), np.full(R, 0.95)
+    args = (seg, beta, s0, 1 - s0, 0.5, p, Hh, D)
+    for e in _far_entries("row0"):
+        z, z0 = _z_with_far_draw(ref, e, Hh, 1, B)
+        a = batch.ar_forecast(*args, z=torch.as_tensor(z[:, 0].copy(), device=gpu_device), device=gpu_device)
+        a0 = batch.ar_forecast(*args, z=torch.as_tensor(z0[:, 0].copy(), device=gpu_device), device=gpu_device)
+        b = batch.ar_forecast(*args, seed=e["seed"], device=gpu_device)
+        h = hostapi.ar_forecast(*args, seed=e["seed"])
+        torch.cuda.synchronize()
+        for k in a:
+            assert NR.same_bits(a[k].cpu().numpy(), b[k].cpu().numpy()) and NR.same_bits(h[k], b[k].cpu().numpy()), (k, e)
+        assert (b["status"].cpu().numpy() == 0).all()
+        differs = (a0["S"] != b["S"]).cpu().numpy()
+        assert differs[:, :, e["lane"]].any() and not np.delete(differs, e["lane"], axis=2).any(), e
+
+
+def _score_raw(d, u, sp, us, j0p, j1p, z=None, noise=None, device="cuda:0"):
+    """epi_sialpha_score_device (z) or epi_sialpha_score_device_seeded (noise) on sentinel-filled outputs with guard words"""
+    import torch
+    from epidemicmodeling_amd import _lib
+    dev = torch.device(device)
+    K, B = d.K, d.B
+    t = lambda v, dt=torch.float64: None if v is None else torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    p = lambda v: None if v is None else C.c_void_p(v.data_ptr())
+    tens = [t(us, torch.int32), t(u), t(sp), t(z), t(j0p), t(j1p)]
+    o = {k: torch.full((cnt + GUARD,), FILL, dtype=torch.float64, device=dev) for k, cnt in (("s", K * B), ("i", K * B), ("alpha", K * B), ("J0", B), ("J1", B))}
+    err = C.create_string_buffer(256)
+    tail = (*[p(v) for v in tens], p(o["s"]), p(o["i"]), p(o["alpha"]), p(o["J0"]), p(o["J1"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), err)
+    rc = _lib.lib().epi_sialpha_score_device(C.byref(d), *tail) if noise is None else \
+        _lib.lib().epi_sialpha_score_device_seeded(C.byref(d), C.byref(noise), *tail)
+    _lib.check(rc, err)
+    torch.cuda.synchronize()
+    res = {k: v.cpu().numpy() for k, v in o.items()}
+    for k, v in res.items():
+        assert (v[-GUARD:] == FILL).all() and not (v[:-GUARD] == FILL).any(), k
+    return {k: v[:-GUARD] for k, v in res.items()}
+
+
+def test_sialpha_sim_and_score_seeded_far_tail_draw(gpu_device, ref):
+    """A recorded far-tail draw inside sialpha_sim_seeded, through epi_sialpha_sim_device_seeded (batch.sialpha_sim) and through
+    the scoring tail, as in test_sdraw_seeded_far_tail_draw.  That it bites: the three far-branch mutations each fail here
+    (`far = rt > 6.0` at the row-1 entry n = 31 146, i; the other two at the first entry, s)."""
+    import torch
+    from epidemicmodeling_amd import _lib, batch
+    rng = np.random.default_rng(8)
+    B, K, n, Su = 70, 5, 12, 4
+    sp = _sim_inputs(B, n, rng)
+    u = np.floor(rng.random((K, n, Su)) * 3)
+    us = rng.integers(0, Su, B).astype(np.int32)
+    j0p, j1p = rng.random(B), rng.random(B)
+    d = _lib.SimDesc()
+    d.abi_version, d.B, d.K, d.Su, d.n_npi, d.noise, d.with_cost, d.prefix_days = _lib.ABI_VERSION, B, K, Su, n, 1, 1, 33
+    for e in _far_entries("rows3"):
+        z, z0 = _z_with_far_draw(ref, e, K, 3, B)
+        tz, tz0 = (torch.as_tensor(v, device=gpu_device) for v in (z, z0))
+        a = batch.sialpha_sim(u, sp, z=tz, u_series=us, with_cost=True, device=gpu_device)
+        a0 = batch.sialpha_sim(u, sp, z=tz0, u_series=us, with_cost=True, device=gpu_device)
+        b = batch.sialpha_sim(u, sp, seed=e["seed"], u_series=us, with_cost=True, device=gpu_device)
+        torch.cuda.synchronize()
+        a, a0, b = ({k: v.cpu().numpy() for k, v in r.items()} for r in (a, a0, b))
+        sa = _score_raw(d, u, sp, us, j0p, j1p, z=z)
+        sa0 = _score_raw(d, u, sp, us, j0p, j1p, z=z0)
+        sb = _score_raw(d, u, sp, us, j0p, j1p, noise=_lib.make_noise_desc(e["seed"], 0))
+        for x, x0, y in ((a, a0, b), (sa, sa0, sb)):
+            assert list(x) == ["s", "i", "alpha", "J0", "J1"]
+            for k in x:
+                assert NR.same_bits(x[k], y[k]), (k, e)
+            name = ("s", "i", "alpha")[e["row"]]
+            differs = (x0[name] != y[name]).reshape(K, B)
+            assert differs[:, e["lane"]].any() and not np.delete(differs, e["lane"], axis=1).any(), e
+            for k in ("s", "i", "alpha", "J0", "J1"):                              # nothing of another chain moves
+                dk = (x0[k] != y[k]).reshape(-1, B)
+                assert not np.delete(dk, e["lane"], axis=1).any(), (k, e)
+            assert np.isfinite(y["alpha"]).all()
+
+
+def test_random_npi_mc_seeded_far_tail_draw(gpu_device, ref):
+    """A recorded far-tail draw inside random_npi_mc_seeded, as in test_sdraw_seeded_far_tail_draw.  That it bites: the three
+    far-branch mutations each fail here (J0; `far = rt > 6.0` at the row-2 entry of the upper tail)."""
+    import torch
+    from epidemicmodeling_amd import batch, hostapi
+    rng = np.random.default_rng(13)
+    R, n_scen, K, n = 3, 30, 5, 12                                  # 90 chains, chain = scenario * R + region
+    sp = _sim_inputs(R, n, rng)
+    u_min = np.zeros((n, R)); u_min[3] = 1.0
+    for e in _far_entries("rows3"):
+        z, z0 = _z_with_far_draw(ref, e, K, 3, n_scen * R)
+        kw = dict(seed=0x1234567890, store_u=True)
+        a = batch.random_npi_mc(sp, u_min, n_scen, K, z=torch.as_tensor(z, device=gpu_device), device=gpu_device, **kw)
+        a0 = batch.random_npi_mc(sp, u_min, n_scen, K, z=torch.as_tensor(z0, device=gpu_device), device=gpu_device, **kw)
+        b = batch.random_npi_mc(sp, u_min, n_scen, K, noise_seed=e["seed"], device=gpu_device, **kw)
+        h = hostapi.random_npi_mc(sp, u_min, n_scen, K, noise_seed=e["seed"], **kw)
+        torch.cuda.synchronize()
+        for k in ("u", "J0", "J1"):
+            assert NR.same_bits(a[k].cpu().numpy(), b[k].cpu().numpy()) and NR.same_bits(h[k], b[k].cpu().numpy()), (k, e)
+        j, r = divmod(e["lane"], R)
+        differs = (a0["J0"] != b["J0"]).cpu().numpy() | (a0["J1"] != b["J1"]).cpu().numpy()
+        assert differs[j, r] and differs.sum() == 1, e
