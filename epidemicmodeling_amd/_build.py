@@ -8,8 +8,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "epiekf.hip")
 DEPS = [SRC, os.path.join(HERE, "csrc", "launch_plan.hpp"), os.path.join(HERE, "csrc", "ekf_device.hpp"), os.path.join(HERE, "csrc", "ekf_sym.hpp"), os.path.join(HERE, "csrc", "ekf_quad.hpp"), os.path.join(HERE, "csrc", "ekf_wave.hpp"), os.path.join(HERE, "csrc", "ekf_hex.hpp"), os.path.join(HERE, "csrc", "ekf_lane6.hpp"),
-        os.path.join(HERE, "csrc", "scenario_kernels.hpp"), os.path.join(HERE, "csrc", "rt_expfit.hpp"), os.path.join(HERE, "csrc", "preprocess.hpp"), os.path.join(HERE, "csrc", "nnls.hpp"), os.path.join(HERE, "csrc", "lookahead.hpp"), os.path.join(HERE, "csrc", "rt_window.hpp"), os.path.join(HERE, "csrc", "lasso.hpp"), os.path.join(HERE, "csrc", "ens_summary.hpp"), os.path.join(HERE, "csrc", "ens_score.hpp"), os.path.join(HERE, "csrc", "ens_joint.hpp"), os.path.join(HERE, "csrc", "path_functionals.hpp"), os.path.join(HERE, "csrc", "ar_forecast.hpp"), os.path.join(HERE, "csrc", "two_filter.hpp"), os.path.join(HERE, "csrc", "robust_fit.hpp"), os.path.join(HERE, "csrc", "rate_map.hpp"), os.path.join(HERE, "csrc", "mldivide.hpp"), os.path.join(HERE, "csrc", "svr.hpp"), os.path.join(HERE, "csrc", "loglik.hpp"), os.path.join(HERE, "csrc", "innov_diag.hpp"), os.path.join(HERE, "csrc", "npi_plan.hpp"), os.path.join(HERE, "csrc", "smoother_draws.hpp"), os.path.join(HERE, "csrc", "noise.hpp"), os.path.join(HERE, "csrc", "host_stage.hpp"),
-        os.path.join(HERE, "..", "include", "epiekf.h"), os.path.join(HERE, "..", "include", "epiekf_layout.h"), os.path.join(HERE, "..", "include", "epiekf_idiag.h")]
+        os.path.join(HERE, "csrc", "scenario_kernels.hpp"), os.path.join(HERE, "csrc", "rt_expfit.hpp"), os.path.join(HERE, "csrc", "preprocess.hpp"), os.path.join(HERE, "csrc", "nnls.hpp"), os.path.join(HERE, "csrc", "lookahead.hpp"), os.path.join(HERE, "csrc", "rt_window.hpp"), os.path.join(HERE, "csrc", "lasso.hpp"), os.path.join(HERE, "csrc", "ens_summary.hpp"), os.path.join(HERE, "csrc", "ens_score.hpp"), os.path.join(HERE, "csrc", "ens_joint.hpp"), os.path.join(HERE, "csrc", "path_functionals.hpp"), os.path.join(HERE, "csrc", "curve_depth.hpp"), os.path.join(HERE, "csrc", "ar_forecast.hpp"), os.path.join(HERE, "csrc", "two_filter.hpp"), os.path.join(HERE, "csrc", "robust_fit.hpp"), os.path.join(HERE, "csrc", "rate_map.hpp"), os.path.join(HERE, "csrc", "mldivide.hpp"), os.path.join(HERE, "csrc", "svr.hpp"), os.path.join(HERE, "csrc", "loglik.hpp"), os.path.join(HERE, "csrc", "innov_diag.hpp"), os.path.join(HERE, "csrc", "npi_plan.hpp"), os.path.join(HERE, "csrc", "smoother_draws.hpp"), os.path.join(HERE, "csrc", "noise.hpp"), os.path.join(HERE, "csrc", "host_stage.hpp"),
+        os.path.join(HERE, "..", "include", "epiekf.h"), os.path.join(HERE, "..", "include", "epiekf_layout.h"), os.path.join(HERE, "..", "include", "epiekf_idiag.h"), os.path.join(HERE, "..", "include", "epiekf_cdepth.h")]
 LIB = os.path.join(HERE, "libepiekf.so")
 
 # -ffp-contract=off: the kernels' arithmetic contract is one IEEE rounding per written operation

@@ -484,6 +484,41 @@ def path_functionals(be, src, R, D, thresholds, population, first_day, k0, k1, o
     return out
 
 
+def curve_statistics(be, src, R, D, alpha, fence_factor, fence_frac, population, first_day, k0, k1, outputs, test_segments=0,
+                     test_launch_groups=0):
+    """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
+    if src.ndim not in (2, 3):
+        raise ValueError("src must be [T, rows, B] or [T, B]")
+    R, D = int(R), int(D)
+    if src.shape[-1] != R * D:
+        raise ValueError(f"src holds {src.shape[-1]} chains, R * D = {R * D}")
+    T, rows = int(src.shape[0]), (1 if src.ndim == 2 else int(src.shape[1]))
+    pop = be.f64(population)
+    if pop is not None and tuple(pop.shape) != (R,):
+        raise ValueError("population must be [R]")
+    fd = be.i32(first_day)
+    if fd is not None and tuple(fd.shape) != (R,):
+        raise ValueError("first_day must be [R]")
+    fence_factor = 0.0 if fence_factor is None else float(fence_factor)
+    d = _lib.make_cdepth_desc(T, rows, R, D, alpha, fence_factor, fence_frac if fence_factor > 0.0 else 0.0, storage=int(_is_f32(src)),
+                              derive_newcases=int(pop is not None), k0=k0, k1=k1, test_segments=test_segments,
+                              test_launch_groups=test_launch_groups)
+    names = _lib.cdepth_out_names(outputs, d.n_alpha, fence_factor)
+    ins = _lib.CdepthInputs()
+    for k, v in zip(_lib.CDEPTH_IN_NAMES, (src, pop, fd)):
+        setattr(ins, k, be.ptr(v))
+    probe = _lib.CdepthOutputs()
+    for k in names:
+        setattr(probe, k, 1)                            # validate looks only at which outputs are asked for
+    err = C.create_string_buffer(256)
+    _lib.check(_lib.lib().epi_cdepth_validate(C.byref(d), C.byref(ins), C.byref(probe), err), err)   # before anything is allocated
+    out = run_with_workspace("cdepth", be, d, ins, _lib.CdepthOutputs(), _lib.CDEPTH_OUT_NAMES, _lib.CDEPTH_OUT_I32,
+                             _lib.cdepth_shapes(T, rows, R, D, d.n_alpha, d.derive_newcases), names)
+    if src.ndim == 2:
+        out = {k: v.reshape(tuple(v.shape[:-2]) + tuple(v.shape[-1:])) for k, v in out.items()}
+    return out
+
+
 def ensemble_joint_score(be, src, truth, R, D, vs_p, max_lag, population, truth_series, first_day, k0, k1, outputs, test_launch_tiles=0):
     """src: contiguous [T, rows, R * D] or [T, R * D], float32 or float64, where the call reads it"""
     R, D, T, rows, Rt, pop, truth, ts, fd = _scored_inputs(be, src, truth, R, D, population, truth_series, first_day)

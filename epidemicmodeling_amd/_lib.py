@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "epi_svr_validate", "epi_svr_run_device", "epi_svr_run_host",
     "epi_loglik_validate", "epi_loglik_workspace_bytes", "epi_loglik_run_device", "epi_loglik_run_host",
     "epi_idiag_validate", "epi_idiag_workspace_bytes", "epi_idiag_run_device", "epi_idiag_run_host",
+    "epi_cdepth_validate", "epi_cdepth_workspace_bytes", "epi_cdepth_run_device", "epi_cdepth_run_host",
     "epi_plan_validate", "epi_plan_workspace_bytes", "epi_plan_run_device", "epi_plan_run_host",
     "epi_sdraw_validate", "epi_sdraw_workspace_bytes", "epi_sdraw_run_device", "epi_sdraw_run_host",
     "epi_escore_validate", "epi_escore_workspace_bytes", "epi_escore_run_device", "epi_escore_run_host",
@@ -880,6 +881,70 @@ def make_idiag_desc(B, T, n_lags=10, k0=0, k1=None, flip=0, lane_block=0, storag
     return d
 
 
+class CdepthDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "T", "rows", "R", "D", "n_alpha", "storage", "derive_newcases", "k0", "k1",
+                                         "test_segments", "test_launch_groups")] + [
+        ("alpha", C.c_double * 8), ("fence_factor", C.c_double), ("fence_frac", C.c_double)]
+
+
+CDEPTH_IN_NAMES = ("src", "population", "first_day")
+CDEPTH_PATH_F64 = ("depth", "mhi", "band_count", "pair_total")
+CDEPTH_PATH_I32 = ("n_valid", "depth_rank", "out_days")
+CDEPTH_REGION_I32 = ("n_ranked", "median_path", "n_outliers")
+CDEPTH_ENV_NAMES = ("env_lo", "env_hi")
+CDEPTH_DAY_NAMES = ("median_curve", "whisk_lo", "whisk_hi")
+CDEPTH_OUT_NAMES = CDEPTH_PATH_F64 + CDEPTH_PATH_I32 + CDEPTH_REGION_I32 + CDEPTH_ENV_NAMES + CDEPTH_DAY_NAMES
+CDEPTH_OUT_I32 = CDEPTH_PATH_I32 + CDEPTH_REGION_I32
+CDEPTH_NEED_FENCE = ("out_days", "n_outliers", "whisk_lo", "whisk_hi")
+CDEPTH_DEFAULT_ALPHA, CDEPTH_DEFAULT_FENCE_FACTOR, CDEPTH_DEFAULT_FENCE_FRAC = (0.5, 0.9), 1.5, 0.5
+
+
+class CdepthInputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in CDEPTH_IN_NAMES]
+
+
+class CdepthOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in CDEPTH_OUT_NAMES]
+
+
+def cdepth_shapes(T, rows, R, D, n_alpha, derive_newcases=0):
+    """shape of every output of epi_cdepth_run_* (rows' = rows + derive_newcases)"""
+    ro, N, T, na, R = int(rows) + int(derive_newcases), int(R) * int(D), int(T), int(n_alpha), int(R)
+    sh = {k: (ro, N) for k in CDEPTH_PATH_F64 + CDEPTH_PATH_I32}
+    sh.update({k: (ro, R) for k in CDEPTH_REGION_I32})
+    sh.update({k: (T, na, ro, R) for k in CDEPTH_ENV_NAMES})
+    sh.update({k: (T, ro, R) for k in CDEPTH_DAY_NAMES})
+    return sh
+
+
+def cdepth_out_names(outputs, n_alpha, fence_factor):
+    """None -> every output (the envelopes only with n_alpha > 0, the boxplot's only with fence_factor > 0); else the names asked
+    for, in the ABI's order"""
+    default = [k for k in CDEPTH_OUT_NAMES if (k not in CDEPTH_ENV_NAMES or int(n_alpha) > 0)
+               and (k not in CDEPTH_NEED_FENCE or float(fence_factor) > 0.0)]
+    names = out_names(CDEPTH_OUT_NAMES, outputs, default)
+    return [k for k in CDEPTH_OUT_NAMES if k in names]
+
+
+def make_cdepth_desc(T, rows, R, D, alpha=(), fence_factor=0.0, fence_frac=0.0, storage=0, derive_newcases=0, k0=0, k1=None,
+                     test_segments=0, test_launch_groups=0) -> CdepthDesc:
+    """storage: 0 / "f64" = double source, 1 / "f32" = float source.  k1 = None: T.  alpha: up to 8 fractions (more: ValueError)."""
+    alpha = [float(a) for a in (() if alpha is None else np.atleast_1d(np.asarray(alpha, dtype=np.float64)))]
+    if len(alpha) > 8:
+        raise ValueError("at most 8 central regions (alpha)")
+    d = CdepthDesc()
+    d.abi_version = ABI_VERSION
+    d.T, d.rows, d.R, d.D, d.n_alpha = int(T), int(rows), int(R), int(D), len(alpha)
+    d.storage = {"f64": 0, "f32": 1}.get(storage, storage)
+    d.derive_newcases = int(derive_newcases)
+    d.k0, d.k1 = int(k0), int(T) if k1 is None else int(k1)
+    d.test_segments, d.test_launch_groups = int(test_segments), int(test_launch_groups)
+    for k, a in enumerate(alpha):
+        d.alpha[k] = a
+    d.fence_factor, d.fence_frac = float(fence_factor), float(fence_frac)
+    return d
+
+
 # A family: a batched device call with the three entry points epi_<prefix>_validate / _run_device / _run_host, which take
 # (const desc *, args..., tail).  args: the argument types between the descriptor and the tail, the outputs structure last.
 Family = namedtuple("Family", "prefix desc args out_names out_i32")
@@ -1018,6 +1083,11 @@ def lib():
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
         h.epi_idiag_run_host.argtypes = [C.POINTER(IdiagDesc), C.POINTER(IdiagInputs), C.POINTER(IdiagOutputs),
                                          C.c_int, C.c_char_p]
+        h.epi_cdepth_validate.argtypes = [C.POINTER(CdepthDesc), C.POINTER(CdepthInputs), C.POINTER(CdepthOutputs), C.c_char_p]
+        h.epi_cdepth_workspace_bytes.argtypes = [C.POINTER(CdepthDesc), C.POINTER(C.c_size_t), C.c_char_p]
+        h.epi_cdepth_run_device.argtypes = [C.POINTER(CdepthDesc), C.POINTER(CdepthInputs), C.POINTER(CdepthOutputs),
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+        h.epi_cdepth_run_host.argtypes = [C.POINTER(CdepthDesc), C.POINTER(CdepthInputs), C.POINTER(CdepthOutputs), C.c_int, C.c_char_p]
         for f in FAMILIES.values():
             for kind, tail in FAMILY_TAILS.items():
                 getattr(h, f"epi_{f.prefix}_{kind}").argtypes = [C.POINTER(f.desc)] + f.args + tail

@@ -1217,6 +1217,42 @@ def path_functionals(src, R, D, thresholds=None, population=None, first_day=None
                                       outputs, test_segments, test_launch_groups)
 
 
+def curve_statistics(src, R, D, alpha=_lib.CDEPTH_DEFAULT_ALPHA, fence_factor=_lib.CDEPTH_DEFAULT_FENCE_FACTOR,
+                     fence_frac=_lib.CDEPTH_DEFAULT_FENCE_FRAC, population=None, first_day=None, k0=0, k1=None, outputs=None, stream=None,
+                     test_segments=0, test_launch_groups=0):
+    """Statistics of the CURVES of a Monte-Carlo ensemble in one device call (epi_cdepth_run_device): which path
+    is the typical one, and what band the central fraction of the paths covers -- what a per-day quantile cannot say, since a
+    per-day band is made of no curve and flattens a peak that the members reach on different days.  src [T, rows, B] or [T, B]
+    (float32 or float64, on the device) is what ensemble_summary takes: B = R * D paths, region-major; population [R] appends
+    the derived new-case row.  The window is the days k0 <= t < k1 (k1 = None: T), for region r from first_day[r] on (first_day
+    [R] int32); a NaN value is no day of its path.
+    Per path [rows', B]: depth, the modified band depth with bands of two curves (the share of (pair of members, day) whose band
+    holds the path; NaN for a path without a day that has two members), mhi (the modified hypograph index: the share of
+    (member, day) at or below the path), band_count and pair_total (depth's exact integer numerator and denominator), float64
+    and each itself an ensemble_summary source; n_valid, depth_rank (0 the deepest of its region, the lower draw wins a tie, -1
+    unranked), out_days (the days outside the fences), int32.  Per (row, region) [rows', R] int32: n_ranked, median_path (the
+    draw of rank 0, -1: none), n_outliers (ranked paths with out_days > 0).  Per day: env_lo, env_hi [T, n_alpha, rows', R], the
+    envelope of the ceil(alpha n_ranked) deepest paths (alpha: up to 8 fractions in (0, 1], strictly ascending); median_curve [T,
+    rows', R], the deepest path; whisk_lo, whisk_hi [T, rows', R], the envelope of the ranked paths that stay inside the fences
+    (the envelope of the fence_frac deepest, widened by fence_factor times its width on either side: the functional boxplot).
+    Days outside the window are NaN.  fence_factor = 0 or None: no boxplot.
+    outputs: any of these names (default: all).  Returns a dict of device tensors.  Enqueued on `stream` (default: the current
+    stream) without a host synchronisation.  A chain-blocked output (EkfRunner(lane_block=...)) is not accepted.
+    test_segments, test_launch_groups: the tests' time segments and launch cut (0 in production)."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a torch tensor (NumPy arrays: hostapi.curve_statistics)")
+    if src.dim() == 4:
+        raise ValueError("src is a chain-blocked tensor [T, nblk, rows, blk]; ensemble_summary takes the classic layout "
+                         "[T, rows, B]: pass EkfRunner.unblocked(name).contiguous(), or run with lane_block=0")
+    if src.dtype not in (torch.float32, torch.float64):
+        raise TypeError("src must be float32 or float64")
+    dev = src.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.stream(st):                         # the workspace and the outputs belong to the stream of the call
+        return _call.curve_statistics(DeviceBackend(dev, st), src.contiguous(), R, D, alpha, fence_factor, fence_frac, population,
+                                      first_day, k0, k1, outputs, test_segments, test_launch_groups)
+
+
 def ensemble_joint_score(src, truth, R, D, vs_p=None, max_lag=0, population=None, truth_series=None, first_day=None, k0=0, k1=None,
                          outputs=None, stream=None, test_launch_tiles=0):
     """Joint (multivariate) scores of a Monte-Carlo ensemble's paths against a truth in one device call (epi_ejoint_run_device,

@@ -820,6 +820,7 @@ __global__ __launch_bounds__(256) void sialpha_sim_seeded(const epi_sim_desc d, 
 #include "ens_summary.hpp"
 #include "ens_score.hpp"
 #include "path_functionals.hpp"
+#include "curve_depth.hpp"
 #include "ens_joint.hpp"
 #include "ar_forecast.hpp"
 // ar_simulate with the draw of (forecast day t, chain c) generated: draw (t, 0, c) of noise.hpp.  A body of its own: ar_forecast.hpp
@@ -4794,6 +4795,205 @@ int epi_idiag_run_host(const epi_idiag_desc *d, const epi_idiag_inputs *in, cons
         HostIO::bind_opt(dout, i32, o_i, base);
         dout.acf = only_empty_acf ? (double *)(base + o_ws) : HostIO::at<double>(base, o_acf);   // H = 0: nothing is written
         return epi_idiag_run_device(d, &din, &dout, base + o_ws, wsb, st, err);
+    };
+    return run_host(device, io, err, enqueue);
+}
+
+// ---- curve statistics of the ensembles: cdepth_days, cdepth_combine, cdepth_rank, cdepth_envelope, cdepth_fence, cdepth_outliers
+// (curve_depth.hpp) ----
+// One wavefront per 32-day block unless test_segments asks for fewer, longer segments: the depth pass is compute-bound on the
+// sort, so more wavefronts are only more parallelism.
+static void cdepth_geometry(const epi_cdepth_desc *d, int *nseg, int *seg_days, int *nblk)
+{
+    const int W = d->k1 - d->k0, nb = (W + kCdBlock - 1) / kCdBlock;
+    long long want = d->test_segments > 0 ? d->test_segments : kCdMaxSeg;
+    if (want > nb) want = nb;
+    const int per = (int)((nb + want - 1) / want);                    // blocks of a segment
+    *nseg = (nb + per - 1) / per;                                     // no empty segment
+    *seg_days = per * kCdBlock;
+    *nblk = nb;
+}
+
+static int cdepth_check_desc(const epi_cdepth_desc *d, char *err)
+{
+    if (!d) { set_err(err, "NULL descriptor"); return EPI_ERR_BAD_ARG; }
+    if (d->abi_version != EPIEKF_ABI_VERSION) { set_err(err, "ABI version mismatch"); return EPI_ERR_BAD_ARG; }
+    if (d->T < 1) { set_err(err, "T must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->rows < 1 || d->rows > 4096) { set_err(err, "rows must lie in 1 .. 4096"); return EPI_ERR_BAD_ARG; }
+    if (d->R < 1) { set_err(err, "R must be >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->D < 1 || d->D > kCdMaxD) { set_err(err, "D must lie in 1 .. 4096 (a wavefront holds the draws of an item in registers)"); return EPI_ERR_BAD_ARG; }
+    if ((int64_t)d->R * d->D > (int64_t)0x7fffffff) { set_err(err, "R * D is limited to 2^31 - 1"); return EPI_ERR_BAD_ARG; }
+    if (d->k0 < 0 || d->k1 <= d->k0 || d->k1 > d->T) { set_err(err, "k0, k1 must satisfy 0 <= k0 < k1 <= T"); return EPI_ERR_BAD_ARG; }
+    if (d->storage != 0 && d->storage != 1) { set_err(err, "storage must be 0 (double) or 1 (float)"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases != 0 && d->derive_newcases != 1) { set_err(err, "derive_newcases must be 0 or 1"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && d->rows < 3) { set_err(err, "derive_newcases needs at least 3 rows"); return EPI_ERR_BAD_ARG; }
+    if (d->n_alpha < 0 || d->n_alpha > kCdMaxAlpha) { set_err(err, "n_alpha must lie in 0 .. 8"); return EPI_ERR_BAD_ARG; }
+    for (int k = 0; k < d->n_alpha; k++) {
+        if (!(d->alpha[k] > 0.0 && d->alpha[k] <= 1.0)) { set_err(err, "every alpha must lie in (0, 1]"); return EPI_ERR_BAD_ARG; }
+        if (k > 0 && !(d->alpha[k] > d->alpha[k - 1])) { set_err(err, "alpha must be strictly ascending"); return EPI_ERR_BAD_ARG; }
+    }
+    if (!(d->fence_factor >= 0.0)) { set_err(err, "fence_factor must be >= 0 (0: no boxplot)"); return EPI_ERR_BAD_ARG; }
+    if (d->fence_factor > 0.0 && !(d->fence_frac > 0.0 && d->fence_frac <= 1.0)) { set_err(err, "fence_frac must lie in (0, 1]"); return EPI_ERR_BAD_ARG; }
+    const int nb = (d->k1 - d->k0 + kCdBlock - 1) / kCdBlock;
+    if (d->test_segments < 0 || d->test_segments > (nb < kCdMaxSeg ? nb : kCdMaxSeg)) {
+        set_err(err, "test_segments must lie in 0 .. min(ceil((k1 - k0) / 32), 1024): a segment is whole 32-day blocks");
+        return EPI_ERR_BAD_ARG;
+    }
+    if (d->test_launch_groups < 0) { set_err(err, "test_launch_groups must be >= 0"); return EPI_ERR_BAD_ARG; }
+    return EPI_OK;
+}
+
+static bool cdepth_wants_fence(const epi_cdepth_outputs *o) { return o->out_days || o->n_outliers || o->whisk_lo || o->whisk_hi; }
+static bool cdepth_wants_env(const epi_cdepth_outputs *o) { return o->env_lo || o->env_hi || o->median_curve || cdepth_wants_fence(o); }
+static bool cdepth_wants_rank(const epi_cdepth_outputs *o) { return o->depth_rank || o->n_ranked || o->median_path || cdepth_wants_env(o); }
+
+int epi_cdepth_validate(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, char *err)
+{
+    int rc = cdepth_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!in || !out) { set_err(err, "NULL inputs / outputs"); return EPI_ERR_BAD_ARG; }
+    if (!in->src) { set_err(err, "NULL src"); return EPI_ERR_BAD_ARG; }
+    if (d->derive_newcases && !in->population) { set_err(err, "NULL population (derive_newcases)"); return EPI_ERR_BAD_ARG; }
+    if (d->n_alpha == 0 && (out->env_lo || out->env_hi)) { set_err(err, "env_lo and env_hi need n_alpha >= 1"); return EPI_ERR_BAD_ARG; }
+    if (d->fence_factor == 0.0 && cdepth_wants_fence(out)) {
+        set_err(err, "out_days, n_outliers, whisk_lo and whisk_hi need fence_factor > 0");
+        return EPI_ERR_BAD_ARG;
+    }
+    if (!(out->depth || out->mhi || out->band_count || out->pair_total || out->n_valid || cdepth_wants_rank(out))) {
+        set_err(err, "no output requested");
+        return EPI_ERR_BAD_ARG;
+    }
+    return EPI_OK;
+}
+
+// the workspace: doubles depth [M], fence_lo, fence_hi [T][plane]; then 32-bit rec [nblk][4][M], depth_rank, out_days [M], n_ranked,
+// median_path [plane]
+static size_t cdepth_ws_bytes(const epi_cdepth_desc *d)
+{
+    int nseg, seg_days, nblk;
+    cdepth_geometry(d, &nseg, &seg_days, &nblk);
+    const size_t ro = (size_t)(d->rows + d->derive_newcases), M = ro * (size_t)d->R * (size_t)d->D, plane = ro * (size_t)d->R;
+    return (M + 2 * (size_t)d->T * plane) * sizeof(double) + ((size_t)nblk * 4 * M + 2 * M + 2 * plane) * sizeof(int32_t);
+}
+
+int epi_cdepth_workspace_bytes(const epi_cdepth_desc *d, size_t *bytes, char *err)
+{
+    int rc = cdepth_check_desc(d, err);
+    if (rc != EPI_OK) return rc;
+    if (!bytes) { set_err(err, "NULL bytes"); return EPI_ERR_BAD_ARG; }
+    *bytes = cdepth_ws_bytes(d);
+    return EPI_OK;
+}
+
+int epi_cdepth_run_device(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err)
+{
+    int rc = epi_cdepth_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    if (!ws || ws_bytes < cdepth_ws_bytes(d)) { set_err(err, "workspace too small (epi_cdepth_workspace_bytes)"); return EPI_ERR_WORKSPACE; }
+    CdArgs g{};
+    cdepth_geometry(d, &g.nseg, &g.seg_days, &g.nblk);
+    g.T = d->T; g.rows = d->rows; g.rows_out = d->rows + d->derive_newcases; g.R = d->R; g.D = d->D; g.derive = d->derive_newcases;
+    g.k0 = d->k0; g.k1 = d->k1; g.n_alpha = d->n_alpha; g.fence_factor = d->fence_factor;
+    g.src = in->src; g.population = in->population; g.first_day = in->first_day;
+    const bool rank = cdepth_wants_rank(out), env = cdepth_wants_env(out), fence = cdepth_wants_fence(out);
+    for (int k = 0; k < d->n_alpha; k++) g.frac[k] = d->alpha[k];
+    g.nk = d->n_alpha;
+    if (fence) g.frac[g.nk++] = d->fence_frac;
+    const size_t N = (size_t)d->R * (size_t)d->D, M = (size_t)g.rows_out * N, plane = (size_t)g.rows_out * (size_t)d->R;
+    double *wd = (double *)ws;
+    g.depth = out->depth ? out->depth : wd;                           // what a later pass reads and the caller did not ask for
+    g.fence_lo = wd + M;
+    g.fence_hi = g.fence_lo + (size_t)d->T * plane;
+    g.rec = (uint32_t *)(g.fence_hi + (size_t)d->T * plane);
+    int32_t *wi = (int32_t *)(g.rec + (size_t)g.nblk * 4 * M);
+    g.depth_rank = out->depth_rank ? out->depth_rank : wi;
+    g.out_days = out->out_days ? out->out_days : wi + M;
+    g.n_ranked = out->n_ranked ? out->n_ranked : wi + 2 * M;
+    g.median_path = out->median_path ? out->median_path : wi + 2 * M + plane;
+    g.mhi = out->mhi; g.band_count = out->band_count; g.pair_total = out->pair_total; g.n_valid = out->n_valid;
+    g.n_outliers = out->n_outliers; g.env_lo = out->env_lo; g.env_hi = out->env_hi; g.median_curve = out->median_curve;
+    g.whisk_lo = out->whisk_lo; g.whisk_hi = out->whisk_hi;
+    const hipStream_t st = (hipStream_t)stream;
+    const long long cap = d->test_launch_groups > 0 ? (long long)d->test_launch_groups : kCdLaunchGroups;
+    using Kernel = void (*)(const CdArgs);
+    hipError_t e = hipSuccess;
+    // a grid of `groups` workgroups in x and ny in y, in launches of at most `cap` workgroups
+    auto launch = [&](Kernel kern, long long groups, int ny, int wg) {
+        const long long per = cap / ny > 0 ? cap / ny : 1;
+        for (long long w0 = 0; w0 < groups && e == hipSuccess; w0 = w0 + per) {
+            g.group0 = w0;
+            const unsigned nb = (unsigned)(groups - w0 < per ? groups - w0 : per);
+            hipLaunchKernelGGL(kern, dim3(nb, (unsigned)ny), dim3(wg), 0, st, g);
+            e = hipGetLastError();
+        }
+    };
+    // NV: registers per lane of the item, P / 64, P the power of two >= max(D, 64), as epi_ens_run_device's
+#define EPI_CD_DAYS(NV) {cdepth_days<0, NV>, cdepth_days<1, NV>}
+    static const Kernel days[7][2] = {EPI_CD_DAYS(1), EPI_CD_DAYS(2), EPI_CD_DAYS(4), EPI_CD_DAYS(8), EPI_CD_DAYS(16), EPI_CD_DAYS(32),
+                                      EPI_CD_DAYS(64)};
+#undef EPI_CD_DAYS
+    int nv = 0;
+    while ((64 << nv) < d->D) nv++;
+    const long long lanes = (long long)((N + kCdLaneWg - 1) / kCdLaneWg);
+    launch(days[nv][d->storage], (long long)plane, g.nseg, 64);
+    if (e != hipSuccess) return hip_fail(err, e, "cdepth_days launch");
+    launch(cdepth_combine, lanes, g.rows_out, kCdLaneWg);
+    if (e != hipSuccess) return hip_fail(err, e, "cdepth_combine launch");
+    if (!rank) return EPI_OK;
+    launch(cdepth_rank, lanes, g.rows_out, kCdLaneWg);
+    if (e != hipSuccess) return hip_fail(err, e, "cdepth_rank launch");
+    if (!env) return EPI_OK;
+    g.mode = 0;
+    launch(d->storage ? cdepth_envelope<1> : cdepth_envelope<0>, (long long)d->T * (long long)plane, 1, 64);
+    if (e != hipSuccess) return hip_fail(err, e, "cdepth_envelope launch");
+    if (!fence) return EPI_OK;
+    launch(d->storage ? cdepth_fence<1> : cdepth_fence<0>, lanes, g.rows_out, kCdLaneWg);
+    if (e != hipSuccess) return hip_fail(err, e, "cdepth_fence launch");
+    if (out->n_outliers) {
+        launch(cdepth_outliers, (long long)((plane + kCdLaneWg - 1) / kCdLaneWg), 1, kCdLaneWg);
+        if (e != hipSuccess) return hip_fail(err, e, "cdepth_outliers launch");
+    }
+    if (out->whisk_lo || out->whisk_hi) {
+        g.mode = 1;
+        launch(d->storage ? cdepth_envelope<1> : cdepth_envelope<0>, (long long)d->T * (long long)plane, 1, 64);
+        if (e != hipSuccess) return hip_fail(err, e, "cdepth_envelope (whiskers) launch");
+    }
+    return EPI_OK;
+}
+
+int epi_cdepth_run_host(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, int device, char *err)
+{
+    int rc = epi_cdepth_validate(d, in, out, err);
+    if (rc != EPI_OK) return rc;
+    const size_t R = (size_t)d->R, N = R * (size_t)d->D, T = (size_t)d->T, ro = (size_t)(d->rows + d->derive_newcases);
+    const size_t na = (size_t)d->n_alpha, none = HostIO::kAbsent;
+    HostIO io;
+    const size_t o_src = io.add_in(in->src, T * (size_t)d->rows, d->storage ? 4 : 8, N, 0, N);
+    const size_t o_pop = d->derive_newcases ? io.add_in(in->population, 1, 8, R, 0, R) : none;
+    const size_t o_fd = in->first_day ? io.add_in(in->first_day, 1, 4, R, 0, R) : none;
+    using CO = epi_cdepth_outputs;
+    const HostIO::Opt<CO, double> f64p[4] = {{&CO::depth, ro}, {&CO::mhi, ro}, {&CO::band_count, ro}, {&CO::pair_total, ro}};
+    const HostIO::Opt<CO, int32_t> i32p[3] = {{&CO::n_valid, ro}, {&CO::depth_rank, ro}, {&CO::out_days, ro}};
+    const HostIO::Opt<CO, int32_t> i32r[3] = {{&CO::n_ranked, ro}, {&CO::median_path, ro}, {&CO::n_outliers, ro}};
+    const HostIO::Opt<CO, double> f64r[5] = {{&CO::env_lo, T * na * ro}, {&CO::env_hi, T * na * ro}, {&CO::median_curve, T * ro},
+                                             {&CO::whisk_lo, T * ro}, {&CO::whisk_hi, T * ro}};
+    size_t o_dp[4], o_ip[3], o_ir[3], o_dr[5];
+    io.add_opt(*out, f64p, o_dp, N);
+    io.add_opt(*out, i32p, o_ip, N);
+    io.add_opt(*out, i32r, o_ir, R);
+    io.add_opt(*out, f64r, o_dr, R);
+    const size_t wsb = cdepth_ws_bytes(d);
+    const size_t o_ws = io.reserve(wsb);
+    auto enqueue = [&](char *base, hipStream_t st) -> int {
+        epi_cdepth_inputs din{};
+        din.src = base + o_src; din.population = HostIO::at<const double>(base, o_pop); din.first_day = HostIO::at<const int32_t>(base, o_fd);
+        epi_cdepth_outputs dout{};
+        HostIO::bind_opt(dout, f64p, o_dp, base);
+        HostIO::bind_opt(dout, i32p, o_ip, base);
+        HostIO::bind_opt(dout, i32r, o_ir, base);
+        HostIO::bind_opt(dout, f64r, o_dr, base);
+        return epi_cdepth_run_device(d, &din, &dout, HostIO::at<char>(base, o_ws), wsb, st, err);
     };
     return run_host(device, io, err, enqueue);
 }

@@ -385,6 +385,19 @@ def path_functionals(src, R, D, thresholds=None, population=None, first_day=None
                                   test_segments, test_launch_groups)
 
 
+def curve_statistics(src, R, D, alpha=_lib.CDEPTH_DEFAULT_ALPHA, fence_factor=_lib.CDEPTH_DEFAULT_FENCE_FACTOR,
+                     fence_frac=_lib.CDEPTH_DEFAULT_FENCE_FRAC, population=None, first_day=None, k0=0, k1=None, outputs=None, device=0,
+                     test_segments=0, test_launch_groups=0):
+    """epi_cdepth_run_host: batch.curve_statistics on NumPy arrays (synchronous): the same arguments, and the same keys, order,
+    dtypes and bits.  A float32 src = float storage, anything else is taken as float64."""
+    src = np.asarray(src)
+    if src.ndim == 4:
+        raise ValueError("src is a chain-blocked array [T, nblk, rows, blk]; ensemble_summary takes the classic layout [T, rows, B]")
+    src = np.ascontiguousarray(src, dtype=np.float32 if src.dtype == np.float32 else np.float64)
+    return _call.curve_statistics(HostBackend(device), src, R, D, alpha, fence_factor, fence_frac, population, first_day, k0, k1,
+                                  outputs, test_segments, test_launch_groups)
+
+
 def ensemble_joint_score(src, truth, R, D, vs_p=None, max_lag=0, population=None, truth_series=None, first_day=None, k0=0, k1=None,
                          outputs=None, device=0, test_launch_tiles=0):
     """epi_ejoint_run_host: batch.ensemble_joint_score on NumPy arrays (synchronous): the same arguments, and the same keys, order,

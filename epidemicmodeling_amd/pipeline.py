@@ -730,7 +730,7 @@ def _check_rng(rng, z=None):
 
 
 def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None, seed=0, k0=0, storage="f64", clamp=True,
-                 device="cuda:0", lane_block="auto", z=None, rng="torch", noise_stream=0):
+                 device="cuda:0", lane_block="auto", z=None, rng="torch", noise_stream=0, curves=None):
     """The fan chart of the EKF/EKS itself: run the smoother of `w` (a synth.Workload of SIAlphaModelEKF), draw n_draws joint
     posterior paths per chain by backward simulation (batch.smoother_draws on the runner's arrays as they lie; the terminal law is
     the smoothed last day, so s_final / Ps_final of the workload are honoured) and summarise them over the draws of each chain
@@ -740,6 +740,8 @@ def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None,
     rng="device": the noise is generated inside the draw kernel from (`seed`, noise_stream) and no z array
     exists -- the fan's memory halves; the returned z is None, and batch.normal_draws(T - k0, 3, B * n_draws, seed, noise_stream)
     is the array that, passed as z, gives the same bits.  Another generator than torch's: other draws of the same law.
+    curves: None (the default: nothing below runs), True or a dict of curve_boxplot's keywords: summary["curves"] is then
+    curve_boxplot of the drawn paths (the deepest path, the envelopes of the deepest fractions of the paths, the whiskers).
     Returns (runner, X [T - k0, 3, B * n_draws], the summary dict, z).  No host synchronisation."""
     if w.model != "SIAlphaModelEKF":
         raise ValueError("smoothed_fan needs a workload of the 3-state SIAlphaModelEKF")
@@ -763,18 +765,20 @@ def smoothed_fan(w, n_draws, q=(0.025, 0.25, 0.5, 0.75, 0.975), population=None,
                                seed=int(seed) if seeded else None, noise_stream=noise_stream if seeded else 0)
     summary = batch.ensemble_summary(res["X"], w.B, n_draws, q=q, population=population)
     summary["rank"], summary["status"] = res["rank"], res["status"]
+    if curves is not None and curves is not False:
+        summary["curves"] = curve_boxplot(res["X"], w.B, n_draws, population=population, **(curves if isinstance(curves, dict) else {}))
     return r, res["X"], summary, z
 
 
 def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975), seed=0, k0=None,
                  storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0, device="cuda:0",
-                 rng="torch"):
+                 rng="torch", curves=None):
     """The forecast of Tools/TrainPredictPrescribeNPI.m:356-377 as a fan chart of the smoother's own joint law: the front half
     (preprocessing, EKF round 1, regression, round 2, regression), then the forecast filter -- the observations padded with NaN
     over `horizon` days, R_v padded with its mean (:360), the NPIs of `plan` [horizon, n, S] or, with plan = None, the last day's
     held (the reference's "fixed" forecast, :373-375) -- and smoothed_fan on it.  k0: the first day returned (default: the start
     of the horizon).  rng: smoothed_fan's ("device": no z array, z is None).  Returns the front half's intermediates, `workload` (the forecast filter's), `runner`, X [T + horizon - k0,
-    3, S * n_draws], `summary` (rows s, i, alpha, new cases) and z."""
+    3, S * n_draws], `summary` (rows s, i, alpha, new cases) and z.  curves: smoothed_fan's (None: nothing changes)."""
     T, S = cases.shape
     n = ip.shape[1]
     horizon = int(horizon)
@@ -795,7 +799,7 @@ def forecast_fan(cases, deaths, population, ip, horizon, n_draws=256, plan=None,
     uf = np.concatenate([u, tail])
     wf = workload3(xf, Rf, uf, N, pre["I0"], fit2["a"], fit2["b"])
     r, X, summary, z = smoothed_fan(wf, n_draws, q=q, population=N, seed=seed, k0=T if k0 is None else int(k0), storage=storage,
-                                    clamp=clamp, device=device, rng=rng)
+                                    clamp=clamp, device=device, rng=rng, curves=curves)
     out.update(workload=wf, runner=r, X=X, summary=summary, z=z)
     return out
 
@@ -908,16 +912,35 @@ def path_outlook(X, R, D, thresholds=None, population=None, q=(0.025, 0.25, 0.5,
     return out
 
 
+def curve_boxplot(X, R, D, alpha=(0.5, 0.9), fence_factor=1.5, fence_frac=0.5, population=None, q=(0.025, 0.25, 0.5, 0.75, 0.975), k0=0,
+                  k1=None, first_day=None):
+    """The functional boxplot of joint paths where they lie: which path is the typical one and what band the central fractions of
+    the PATHS cover -- a band made of curves, which keeps a peak that the members reach on different days, where the per-day
+    quantiles of ensemble_summary flatten it.  X [T, rows, R * D] (smoothed_fan's or forecast_fan's X, monte_carlo_eks',
+    ar_forecast's); batch.curve_statistics (DESIGN.md §4.23) ranks the paths of every (row, region) by modified band depth;
+    population [R] appends the new-case row; the window is k0 <= t < k1 from first_day[r] on.
+    Returns `statistics` (the dict of batch.curve_statistics), median_curve [T, rows', R] (the deepest path), env_lo, env_hi [T,
+    n_alpha, rows', R] (the envelope of the alpha deepest paths), whisk_lo, whisk_hi [T, rows', R] (the envelope of the paths that
+    stay inside the fences), n_outliers, n_ranked [rows', R], and `depth`: the dict of batch.ensemble_summary of the depths over
+    the draws of every region (quantiles at q [rows', n_q, R]).  Nothing is copied back."""
+    st = batch.curve_statistics(X, R, D, alpha=alpha, fence_factor=fence_factor, fence_frac=fence_frac, population=population,
+                                first_day=first_day, k0=k0, k1=k1)
+    out = {"statistics": st}
+    out.update({k: st[k] for k in ("median_curve", "env_lo", "env_hi", "whisk_lo", "whisk_hi", "n_outliers", "n_ranked") if k in st})
+    out["depth"] = batch.ensemble_summary(st["depth"] if st["depth"].dim() > 1 else st["depth"].unsqueeze(0), R, D, q=q)
+    return out
+
+
 def forecast_outlook(cases, deaths, population, ip, horizon, thresholds=None, n_draws=256, plan=None, q=(0.025, 0.25, 0.5, 0.75, 0.975),
                      seed=0, storage="f64", clamp=True, regression="nonnegls", num_regression_days=60, W=7, cv_folds=50, cv_seed=0,
-                     device="cuda:0", rng="torch"):
+                     device="cuda:0", rng="torch", curves=None):
     """forecast_fan, then path_outlook over the horizon: per region the law of the peak day and height of the forecast, of the
     cases over the horizon, and of the days above `thresholds` [n_thr, 4, S] (rows s, i, alpha, new cases; NaN: not asked).
-    rng: smoothed_fan's.  Returns forecast_fan's dict with `outlook` (path_outlook's; day 0 of its histograms is the first day of the
+    rng, curves: smoothed_fan's (curves = None: nothing changes).  Returns forecast_fan's dict with `outlook` (path_outlook's; day 0 of its histograms is the first day of the
     horizon)."""
     out = forecast_fan(cases, deaths, population, ip, horizon, n_draws=n_draws, plan=plan, q=q, seed=seed, storage=storage, clamp=clamp,
                        regression=regression, num_regression_days=num_regression_days, W=W, cv_folds=cv_folds, cv_seed=cv_seed,
-                       device=device, rng=rng)
+                       device=device, rng=rng, curves=curves)
     S = cases.shape[1]
     out["outlook"] = path_outlook(out["X"], S, int(n_draws), thresholds, population=np.asarray(population, dtype=np.float64), q=q)
     return out

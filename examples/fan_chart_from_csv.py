@@ -2,7 +2,7 @@
 joint posterior draws of the smoother's paths (epidemicmodeling_amd/pipeline.py: forecast_fan), for all regions of
 the file at once.
 
-    python examples/fan_chart_from_csv.py [--rng device] [--score-last N [--joint]] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
+    python examples/fan_chart_from_csv.py [--rng device] [--curves] [--score-last N [--joint]] [--threshold C] OxCGRT_latest.csv populations.csv 2020-03-01 2020-12-31 fan.csv [horizon [draws]]
 
 The front half of Tools/TrainPredictPrescribeNPI.m (preprocessing, two EKF rounds, two regressions), then its forecast filter
 (:356-377: NaN observations over the horizon, the last day's NPIs held), then 256 backward-simulated paths per region and their
@@ -21,6 +21,11 @@ joint draws from draws with the same bands and no dependence between days.
 DESIGN.md 4.18): per region the median and the 95 % band of the day of the peak of the daily new cases and of its height, the median
 of the cases summed over the horizon, and with a threshold the probability that the daily new cases reach C per 100 000 inhabitants
 within the horizon, the median first day they do, and the median longest run of days at or above it.
+
+--curves adds the bands made of curves (pipeline.curve_boxplot): the drawn paths of every region are ranked by
+modified band depth, and the output gains the deepest path (curve_median) and the envelopes of the deepest 50 % and 90 % of the
+paths (curve_lo50 .. curve_hi90).  Unlike the per-day quantiles these keep the height of a peak that the paths reach on different
+days.  The number of paths outside the functional boxplot's fences is printed per region.
 
 --rng device draws the noise inside the kernel from the seed instead of filling an array with torch.randn first:
 other draws of the same law, and half the memory."""
@@ -95,6 +100,9 @@ def main():
         i = sys.argv.index("--threshold")
         outlook, per_100k = True, float(sys.argv[i + 1])
         del sys.argv[i:i + 2]
+    curves = "--curves" in sys.argv
+    if curves:
+        sys.argv.remove("--curves")
     joint = "--joint" in sys.argv
     if joint:
         sys.argv.remove("--joint")
@@ -113,7 +121,8 @@ def main():
     d = dataio.read_oxcgrt(data, start, end)
     N = dataio.read_populations(pops, d["geo_ids"])
     keep = np.flatnonzero(np.isfinite(N) & np.isfinite(d["cases"]).any(axis=0))
-    out = pipeline.forecast_fan(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon, n_draws=draws, q=Q, rng=rng)
+    out = pipeline.forecast_fan(d["cases"][:, keep], d["deaths"][:, keep], N[keep], d["ip"][:, :, keep], horizon, n_draws=draws, q=Q, rng=rng,
+                                curves=True if curves else None)
     qs = out["summary"]["quantiles"].cpu().numpy()[:, :, 3]       # [horizon, n_q, S]: row 3 is the new cases
     mean = out["summary"]["mean"].cpu().numpy()[:, 3]
     status = out["summary"]["status"].cpu().numpy()
@@ -122,9 +131,18 @@ def main():
         for t in range(horizon):
             rows.append([d["geo_ids"][r], t + 1] + [qs[t, k, j] for k in range(len(Q))] + [mean[t, j], int(status[j])])
     table = pd.DataFrame(rows, columns=["region", "day_ahead"] + [f"q{100 * v:g}" for v in Q] + ["mean", "status"])
+    if curves:                                                    # [horizon, rows', S] and [horizon, n_alpha, rows', S]: row 3, alpha = (0.5, 0.9)
+        cv = {k: out["summary"]["curves"][k].cpu().numpy() for k in ("median_curve", "env_lo", "env_hi", "n_outliers", "n_ranked")}
+        cols = {"curve_median": cv["median_curve"][:, 3], "curve_lo50": cv["env_lo"][:, 0, 3], "curve_hi50": cv["env_hi"][:, 0, 3],
+                "curve_lo90": cv["env_lo"][:, 1, 3], "curve_hi90": cv["env_hi"][:, 1, 3]}
+        for name, v in cols.items():
+            table[name] = v.T.reshape(-1)                         # the rows run region by region, day by day
     table.to_csv(dst, index=False)
     print(f"{len(keep)} regions x {draws} draws x {horizon} days -> {dst}")
     print(table.head(12).to_string(index=False))
+    if curves:
+        print("paths outside the functional boxplot's fences (of the ranked paths), per region:")
+        print(" ".join(f"{d['geo_ids'][r]}: {cv['n_outliers'][3, j]}/{cv['n_ranked'][3, j]}" for j, r in enumerate(keep)))
     if outlook:
         print(f"the outlook over the {horizon} days (day 1 is the first forecast day):")
         print(outlook_table(out, d, N, keep, draws, per_100k).to_string(index=False))

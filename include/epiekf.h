@@ -1601,6 +1601,31 @@ int epi_idiag_run_device(const epi_idiag_desc *d, const epi_idiag_inputs *in, co
 /* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
 int epi_idiag_run_host(const epi_idiag_desc *d, const epi_idiag_inputs *in, const epi_idiag_outputs *out, int device, char *err);
 
+/* ---- Curve statistics of the Monte-Carlo ensembles: modified band depth, central envelopes, functional boxplot ----
+ * The definition and the structures epi_cdepth_desc / _inputs / _outputs are in epiekf_cdepth.h. */
+#ifdef __cplusplus
+}
+#endif
+#include "epiekf_cdepth.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* no GPU needed: EPI_ERR_BAD_ARG for what epi_pathfn_validate refuses of T, rows, R, D, k0 / k1, storage, derive_newcases,
+ * test_segments and test_launch_groups, and for D > 4096, n_alpha outside 0 .. 8, an alpha outside (0, 1] or not strictly
+ * ascending, a negative or NaN fence_factor, with fence_factor > 0 a fence_frac outside (0, 1], env_lo / env_hi with n_alpha = 0,
+ * out_days / n_outliers / whisk_lo / whisk_hi with fence_factor = 0, a NULL src, no output at all */
+int epi_cdepth_validate(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, char *err);
+/* bytes of device workspace epi_cdepth_run_device needs: the 32-day block records of every path and whatever a later pass reads
+ * (depth, ranks, fence envelope, out_days), whether the caller asks for it or not */
+int epi_cdepth_workspace_bytes(const epi_cdepth_desc *d, size_t *bytes, char *err);
+/* DEVICE pointers; the depth pass (one wavefront per (row, region, 32-day block)), its combining pass, and as far as the
+ * outputs asked for need them the rank, envelope, fence, outlier and whisker passes, enqueued on `stream` in launches of at most
+ * 2^22 workgroups: no host synchronisation, no allocation.  EPI_ERR_WORKSPACE for a workspace below epi_cdepth_workspace_bytes */
+int epi_cdepth_run_device(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, void *ws,
+                          size_t ws_bytes, void *stream, char *err);
+/* HOST pointers, on a pooled context of `device` (the workspace lives in its arena) */
+int epi_cdepth_run_host(const epi_cdepth_desc *d, const epi_cdepth_inputs *in, const epi_cdepth_outputs *out, int device, char *err);
+
 /* Measurement utility (not part of the reference's interface): copies n doubles src -> dst with the filter
  * kernels' access shape (8 B per lane); used to calibrate the HBM traffic counters on a known byte count. */
 int epi_calib_copy_f64_device(const double *src, double *dst, size_t n, void *stream, char *err);

@@ -116,6 +116,14 @@
 //       'escore' takes them;  vs_p ([] or 0 = no variogram score)  0.5 or 1;  max_lag ([] = 0: every pair of days)  the largest
 //       distance in days of a pair in the variogram score.  es, vs (NaN without vs_p), truth_term, spread_term, n_members,
 //       n_days  R x rows';  member_dist  B x rows' (NaN: an absent member).
+//   [depth, mhi, depth_rank, median_path, median_curve, env_lo, env_hi, whisk_lo, whisk_hi, out_days, n_outliers, n_ranked, band_count, pair_total, n_valid] = epiekf_pipeline_mex('cdepth', src, D, alpha, fence_factor, fence_frac, population, first_day, k_first, k_last)
+//       Curve statistics of a Monte-Carlo ensemble: modified band depth, central envelopes, functional boxplot.
+//       src, D, population, first_day, k_first, k_last  as 'pathfn' takes them;  alpha ([] = [0.5 0.9])  up to 8 fractions in (0, 1],
+//       ascending;  fence_factor ([] = 1.5; 0 = no boxplot), fence_frac ([] = 0.5).  depth, mhi, band_count, pair_total, n_valid,
+//       out_days  B x rows';  depth_rank  B x rows', ONE-based (1 = the deepest path of its region, 0 = unranked);  median_path,
+//       n_outliers, n_ranked  R x rows' (median_path ONE-based within the region, 0 = none);  median_curve, whisk_lo, whisk_hi
+//       R x rows' x T;  env_lo, env_hi  R x rows' x n_alpha x T.  Days outside the window are NaN; without a boxplot out_days,
+//       n_outliers are 0 and the whiskers NaN.
 //   [peak_value, peak_day, min_value, min_day, total, first_cross, days_above, longest_run, n_valid, n_paths, peak_day_hist, n_cross, cross_day_hist] = epiekf_pipeline_mex('pathfn', src, D, thr, population, first_day, k_first, k_last)
 //       Functionals of every joint path of a Monte-Carlo ensemble.  src, D, population  as 'ens_summary' takes
 //       them;  thr ([] = none)  R x rows' x n_thr (R x n_thr for a B x T src), at most 8 thresholds, NaN = not asked;  first_day
@@ -802,6 +810,87 @@ static void pathfn(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
 }
 
+static void cdepth(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs != 10) mexErrMsgTxt("epiekf_pipeline_mex('cdepth', src, D, alpha, fence_factor, fence_frac, population, first_day, k_first, k_last): 10 inputs expected");
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    if (nd > 3 || mxIsEmpty(prhs[1]) || !mxGetPr(prhs[1])) mexErrMsgTxt("src must be a double array B x rows x T (or B x T)");
+    const mwSize *ds = mxGetDimensions(prhs[1]);
+    const mwSize B = ds[0], rows = nd == 3 ? ds[1] : 1, T = nd == 3 ? ds[2] : ds[1];
+    const double Dd = mxGetScalar(prhs[2]);
+    if (!(Dd >= 1.0 && Dd <= 2147483647.0) || (double)(mwSize)Dd != Dd || B % (mwSize)Dd != 0) mexErrMsgTxt("D must be a positive integer that divides the number of chains");
+    const mwSize D = (mwSize)Dd, R = B / D;
+    const bool derive = !mxIsEmpty(prhs[6]);
+    if (derive && mxGetNumberOfElements(prhs[6]) != R) mexErrMsgTxt("population must have one entry per region");
+    const mwSize ro = rows + (derive ? 1 : 0);
+    epi_cdepth_desc d;
+    memset(&d, 0, sizeof d);
+    mwSize na = 2;
+    d.alpha[0] = 0.5; d.alpha[1] = 0.9;
+    if (!mxIsEmpty(prhs[3])) {
+        na = mxGetNumberOfElements(prhs[3]);
+        if (!mxGetPr(prhs[3]) || na > 8) mexErrMsgTxt("alpha must hold at most 8 fractions");
+        for (mwSize k = 0; k < na; k++) d.alpha[k] = mxGetPr(prhs[3])[k];
+    }
+    d.fence_factor = mxIsEmpty(prhs[4]) ? 1.5 : mxGetScalar(prhs[4]);
+    d.fence_frac = mxIsEmpty(prhs[5]) ? 0.5 : mxGetScalar(prhs[5]);
+    const bool fence = d.fence_factor > 0.0;
+    std::vector<int32_t> fd;
+    if (!mxIsEmpty(prhs[7])) {
+        if (mxGetNumberOfElements(prhs[7]) != R) mexErrMsgTxt("first_day must have one entry per region");
+        fd.resize((size_t)R);
+        for (mwSize r = 0; r < R; r++) {
+            const double v = mxGetPr(prhs[7])[r];
+            if (!(v >= 1.0 && v <= 2147483647.0) || (double)(mwSize)v != v) mexErrMsgTxt("first_day must hold ONE-based days");
+            fd[(size_t)r] = (int32_t)v - 1;
+        }
+    }
+    double kf = 1.0, kl = (double)T;
+    if (!mxIsEmpty(prhs[8])) kf = mxGetScalar(prhs[8]);
+    if (!mxIsEmpty(prhs[9])) kl = mxGetScalar(prhs[9]);
+    if (!(kf >= 1.0 && kf <= (double)T && kl >= kf && kl <= (double)T) || (double)(mwSize)kf != kf || (double)(mwSize)kl != kl)
+        mexErrMsgTxt("k_first, k_last must be integers with 1 <= k_first <= k_last <= T");
+    d.abi_version = EPIEKF_ABI_VERSION; d.T = (int32_t)T; d.rows = (int32_t)rows; d.R = (int32_t)R; d.D = (int32_t)D; d.n_alpha = (int32_t)na;
+    d.storage = 0; d.derive_newcases = derive ? 1 : 0; d.k0 = (int32_t)kf - 1; d.k1 = (int32_t)kl;
+    epi_cdepth_inputs in;
+    memset(&in, 0, sizeof in);
+    in.src = mxGetPr(prhs[1]); in.population = derive ? mxGetPr(prhs[6]) : NULL; in.first_day = fd.empty() ? NULL : fd.data();
+    // the ABI's [rows'][N], [rows'][R], [T][rows'][R], [T][n_alpha][rows'][R] are MATLAB's B x rows', R x rows', R x rows' x T,
+    // R x rows' x n_alpha x T: no transposition
+    const mwSize d4[4] = {R, ro, na, T};
+    mxArray *o[15] = {mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL),
+                      mxCreateDoubleMatrix(R, ro, mxREAL), dbl3(R, ro, T), mxCreateNumericArray(4, d4, mxDOUBLE_CLASS, mxREAL),
+                      mxCreateNumericArray(4, d4, mxDOUBLE_CLASS, mxREAL), dbl3(R, ro, T), dbl3(R, ro, T), mxCreateDoubleMatrix(B, ro, mxREAL),
+                      mxCreateDoubleMatrix(R, ro, mxREAL), mxCreateDoubleMatrix(R, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL),
+                      mxCreateDoubleMatrix(B, ro, mxREAL), mxCreateDoubleMatrix(B, ro, mxREAL)};
+    const size_t M = (size_t)(B * ro), cols = (size_t)(R * ro);
+    std::vector<int32_t> ibuf(3 * M + 3 * cols + 1, 0);
+    int32_t *rank = ibuf.data(), *od = rank + M, *nv = od + M, *mp = nv + M, *no = mp + cols, *nr = no + cols;
+    epi_cdepth_outputs out;
+    memset(&out, 0, sizeof out);
+    out.depth = mxGetPr(o[0]); out.mhi = mxGetPr(o[1]); out.depth_rank = rank; out.median_path = mp; out.median_curve = mxGetPr(o[4]);
+    if (na) { out.env_lo = mxGetPr(o[5]); out.env_hi = mxGetPr(o[6]); }
+    if (fence) { out.whisk_lo = mxGetPr(o[7]); out.whisk_hi = mxGetPr(o[8]); out.out_days = od; out.n_outliers = no; }
+    out.n_ranked = nr; out.band_count = mxGetPr(o[12]); out.pair_total = mxGetPr(o[13]); out.n_valid = nv;
+    char err[256] = {0};
+    const int rc = epi_cdepth_run_host(&d, &in, &out, /*device=*/0, err);
+    if (rc != EPI_OK) { for (mxArray *m : o) mxDestroyArray(m); fail_if(rc, err); }
+    for (size_t k = 0; k < M; k++) {
+        mxGetPr(o[2])[k] = (double)rank[k] + 1.0;                               // ONE-based, 0 = unranked
+        mxGetPr(o[9])[k] = (double)od[k];
+        mxGetPr(o[14])[k] = (double)nv[k];
+    }
+    for (size_t k = 0; k < cols; k++) {
+        mxGetPr(o[3])[k] = (double)mp[k] + 1.0;                                 // ONE-based, 0 = none
+        mxGetPr(o[10])[k] = (double)no[k];
+        mxGetPr(o[11])[k] = (double)nr[k];
+    }
+    if (!fence)
+        for (size_t k = 0; k < cols * (size_t)T; k++) mxGetPr(o[7])[k] = mxGetPr(o[8])[k] = std::numeric_limits<double>::quiet_NaN();
+    for (int k = 0; k < 15; k++)
+        if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]);
+}
+
 static void ar_forecast(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs != 13 && nrhs != 14) mexErrMsgTxt("epiekf_pipeline_mex('ar_forecast', seg, prm, dt, p, H, D, z, drive, drive_series, A, noise_var, nv_mode): 13 inputs expected (a 14th: seed)");
@@ -1179,6 +1268,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     else if (strcmp(cmd, "sdraw") == 0) sdraw(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "escore") == 0) escore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "pathfn") == 0) pathfn(nlhs, plhs, nrhs, prhs);
+    else if (strcmp(cmd, "cdepth") == 0) cdepth(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "jscore") == 0) jscore(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "mc") == 0) mc(nlhs, plhs, nrhs, prhs);
     else if (strcmp(cmd, "noise") == 0) noise(nlhs, plhs, nrhs, prhs);
